@@ -14,9 +14,19 @@ summed between neighbouring ranks over RCCL inside the timed region.
 that N devices are visible, starts N fresh rank processes (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set,
 127.0.0.1 rendezvous) and relays rank 0's line.  Under torchrun it is a rank.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernels, measured with events on the
-launch stream) and `cpu_baseline` (the restated reference CPU path = oracle, timed on this
+Prints ONE JSON line (rank 0) with `ms_per_step` and `roofline` (dominant kernels, measured
+with events on the launch stream in the timed steps).  A plain run does only that: set-up,
+warm-up, the timed steps, the line.  `--full` adds what takes runs of its own: per-phase kernel
+times and the binding resources, the residual-only assembly and the Newton-iteration figure,
+the state commit of the J2 family, BASELINE configuration 3 after the north-star
+(`other_configs`) and `cpu_baseline` (the restated reference CPU path = oracle, timed on this
 box's host cores on a bounded sample; rank 0, N = 1 only).
+
+`--dump-outputs DIR` writes, after the timed steps, what they computed (rank 0's arrays):
+DIR/residual.npy and DIR/tangent.npy (float64), r and the matrix values as the last timed step
+leaves them.  The step adds into r and A, so they hold the sum of the warm-up and the timed
+assemblies.  An array longer than its cap in DUMP_CAP is a seeded sample of its entries: the
+same positions for the same length in every run, so two builds compare output for output.
 """
 import argparse
 import hashlib
@@ -203,6 +213,23 @@ def synthetic_u(patch, scale=0.05, seed=20241008):
     u = scale * rng.standard_normal(patch.n_vdofs)
     u.reshape(-1, patch.dim)[patch.boundary_nodes(0, 0)] = 0.0
     return u
+
+
+# --dump-outputs: entries written per array at most (16 + 32 MiB of float64)
+DUMP_CAP = {"residual": 1 << 21, "tangent": 1 << 22}
+
+
+def dump_outputs(outdir, arrays, seed=20241008):
+    """DIR/<name>.npy (float64) of each device array; of one longer than DUMP_CAP[name], its entries at seeded positions in
+    ascending order (the positions depend on the array's length only)"""
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in arrays.items():
+        n, cap = t.numel(), DUMP_CAP[name]
+        if n > cap:
+            idx = np.unique(np.random.default_rng(seed).integers(0, n, size=cap))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(outdir, name + ".npy"), t.double().cpu().numpy())
 
 
 def kernel_description(p, material, path):
@@ -457,8 +484,9 @@ def supervise(procs, poll_s=0.2, grace_s=5.0):
 # ------------------------------------------------------------------------------------------------
 # one rank
 # ------------------------------------------------------------------------------------------------
-def measure(args, workload, rank, world, local_rank, backend, with_extras, loopback=False):
-    """time `args.steps` assemblies of one workload on this rank's slab; returns the result dict (rank 0) or None"""
+def measure(args, workload, rank, world, local_rank, backend, with_extras, loopback=False, dump_dir=None):
+    """time `args.steps` assemblies of one workload on this rank's slab; returns the result dict (rank 0) or None.
+    dump_dir: rank 0 writes what the timed steps computed there (dump_outputs)"""
     import torch
     import torch.distributed as dist
     import mimi_amd
@@ -627,6 +655,9 @@ def measure(args, workload, rank, world, local_rank, backend, with_extras, loopb
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kernel_ms = float(np.mean([ev[k].elapsed_time(ev[k + 1]) for k in range(steps)]))
+    # before anything below adds into r and A again (or zeroes them: the N > 1 check)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, {"residual": r} if args.residual_only else {"residual": r, "tangent": A})
 
     # N > 1 (unless --no-check): after the timed region, the rows this rank owns after the exchange against a whole-patch
     # assembly on this rank's own GPU -- the evidence that what travelled over RCCL is right
@@ -900,9 +931,9 @@ def run_rank(args):
         dist.destroy_process_group()
         return
 
-    main = measure(args, args.workload, rank, world, local_rank, backend, with_extras=True)
+    main = measure(args, args.workload, rank, world, local_rank, backend, with_extras=args.full, dump_dir=args.dump_outputs)
     other = {}
-    if world == 1 and not args.residual_only and not args.no_other_configs and args.workload == "northstar":
+    if args.full and world == 1 and not args.residual_only and not args.no_other_configs and args.workload == "northstar":
         # BASELINE configuration 3 in the same run (fewer steps: 45 ms each), so that its figure is measured, not copied
         saved = (args.steps, args.warmup)
         args.steps, args.warmup = min(args.steps, 5), min(args.warmup, 2)
@@ -931,7 +962,7 @@ def run_rank(args):
                 out[k] = main[k]
         if other:
             out["other_configs"] = other
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # a slow or failing host baseline must not throw the finished GPU measurement away
             try:
                 out["cpu_baseline"] = cpu_baseline_child(args.workload, sweep=args.cpu_sweep)
@@ -970,12 +1001,20 @@ def main():
     ap.add_argument("--rehearse-rccl", type=int, default=0, metavar="N",
                     help="time the step of the middle rank of an N-rank job on this one GPU, exchange over RCCL to itself")
     ap.add_argument("--workload", default=os.environ.get("MIMI_BENCH_WORKLOAD", "northstar"), choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the phases, the residual-only assembly, the state commit, cfg3 "
+                         "(north-star, N = 1) and the CPU baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed steps computed as DIR/residual.npy and DIR/tangent.npy (float64, at most "
+                         "48 MiB: a seeded sample of a longer array)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-baseline-only", action="store_true",
                     help="print the CPU baseline of the workload as one JSON line and exit (no GPU, no torch: what "
                          "cpu_baseline_child runs under OMP_PROC_BIND=close)")
-    ap.add_argument("--cpu-sweep", action="store_true", help="add a 1/32/64/128-thread sweep of the CPU baseline (minutes)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the cfg3 measurement that follows the north-star one at N = 1")
+    ap.add_argument("--cpu-sweep", action="store_true",
+                    help="--full: add a 1/32/64/128-thread sweep of the CPU baseline (minutes)")
+    ap.add_argument("--no-other-configs", action="store_true",
+                    help="--full without the cfg3 measurement that follows the north-star one at N = 1")
     ap.add_argument("--scheme", default="gather", choices=["gather", "boundary", "none"],
                     help="N > 1: how the exchange is overlapped with the assembly (see measure()); none = no overlap")
     ap.add_argument("--no-check", action="store_true",
@@ -985,6 +1024,10 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.rehearse_rccl:
+        raise SystemExit("--dump-outputs: not with --rehearse-rccl (its arrays are one slab's, exchanged with itself)")
     if args.cpu_baseline_only:
         _, p, material = WORKLOADS[args.workload]
         print(json.dumps(cpu_baseline(p, material, sweep=args.cpu_sweep)), flush=True)

@@ -10,7 +10,7 @@ mkdir -p $O
 for W in northstar cfg3; do
   for M in grad residual; do
     X=""; [ $M = residual ] && X="--residual-only"
-    B="python bench.py --workload $W --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 $X"
+    B="python bench.py --workload $W --full --no-cpu-baseline --no-other-configs --steps 3 --warmup 1 $X"
     T=${W}_${M}
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_stats -- $B > $O/${T}_stats.log 2>&1
     timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA GRBM_GUI_ACTIVE --output-format csv -d $O/${T}_pipe -- $B > $O/${T}_pipe.log 2>&1

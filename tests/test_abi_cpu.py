@@ -33,6 +33,9 @@ def test_library_builds_loads_and_exports_every_declared_symbol():
     from mimi_amd import build, _capi
     path = build.build()
     assert os.path.exists(path)
+    # torch first, as _capi.lib() does: loaded ahead of it, the library would bring the system's HIP runtime into this pytest
+    # process and torch would start a second one of its own, which finds no GPU for the tests that follow
+    import torch  # noqa: F401
     lib = ctypes.CDLL(path)
     missing = [n for n in declared_functions() if not hasattr(lib, n)]
     assert not missing, missing

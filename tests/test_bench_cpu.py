@@ -96,3 +96,24 @@ def test_algorithmic_counts_of_survey_8d():
     assert bench.b_alg(3, 3, grad=True) == 308240 and bench.b_alg(3, 3, grad=False) == 13328
     assert bench.b_alg(3, 3, grad=True, stateful=True) == 319240
     assert bench.useful_flop(2) == 513216.0 and bench.useful_flop(3) == 2835360.0
+
+
+def test_dump_outputs_writes_float64_and_samples_long_arrays_at_fixed_positions(tmp_path, monkeypatch):
+    """--dump-outputs: an array within its cap is written whole; a longer one as its entries at seeded positions, the same
+    positions in every run (two builds compare output for output)"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert sum(bench.DUMP_CAP.values()) * 8 <= 64 * 10 ** 6           # the shipped caps: 64 MB in all at most
+    monkeypatch.setattr(bench, "DUMP_CAP", {"residual": 100, "tangent": 1000})
+    r = torch.arange(50, dtype=torch.float64)
+    A = torch.arange(10 ** 5, dtype=torch.float64) * 0.5
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"residual": r, "tangent": A})
+    ra, ta = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("residual", "tangent"))
+    assert ra.dtype == np.float64 and np.array_equal(ra, r.numpy())
+    assert ta.dtype == np.float64 and 900 < ta.size <= 1000
+    pos = ta / 0.5                                       # (A's entries are their own positions)
+    assert np.all(np.diff(pos) > 0) and pos[-1] < 10 ** 5
+    assert np.array_equal(ta, np.load(tmp_path / "b" / "tangent.npy"))

@@ -41,13 +41,13 @@ def test_degree3_contraction_kernel_is_hazard_free_and_spill_free(need):
     print("tp3_contract_kernel", stats)
 
 
-def test_the_lint_turns_red_on_the_shipped_kernel_without_its_results_guard(need):
+def test_the_lint_turns_red_on_the_shipped_kernel_without_its_results_guard(need, tmp_path):
     """tensor_p3.hip's t3_results_guard (one `s_nop 15` behind the S3 matrix instructions of the plane tiles) is what keeps
     the stores of those tiles 18 wait states behind their producers: compiled away (-DT3_LINT_DROP_RESULTS_GUARD, a switch
     that exists for this test) the first stores follow after 3, and the lint must say so.  (The `s_nop` pair rounds 2-3 had
     behind S1 protected nothing -- the lint showed 42 wait states to the first reader with or without it -- and is gone;
     the pair behind S3 was 32 wait states where 16 are needed.)"""
-    asm = L.assembly("tensor_p3.hip", out=os.path.join(tempfile.gettempdir(), "tensor_p3.noguard.lint.s"),
+    asm = L.assembly("tensor_p3.hip", out=str(tmp_path / "tensor_p3.noguard.lint.s"),
                      extra_flags=["-DT3_LINT_DROP_RESULTS_GUARD"])
     bad, stats = L.lint_kernel(L.parse_kernel(asm, "tp3_contract_kernel"), need, asm_only=True)
     assert len(bad) > 20 and stats["nearest_mem"] < need["mem_read"]

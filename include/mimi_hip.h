@@ -320,6 +320,52 @@ int mimi_hip_contact_nodal(mimi_hip_contact_t h, int set, double* area, double* 
 int mimi_hip_contact_add_residual_from_nodal(mimi_hip_contact_t h, const double* u, double grad_factor, double* r,
                                              double* A_values);
 
+/* ---- follower-pressure boundary integrator (integrators::FollowerPressure) ---------------------------------------
+ * The reference stores BCMarker::Pressure(bid, value) (utils/boundary_conditions.cpp:43-50) and never applies it; here it
+ * is the follower load t = -p n da on the CURRENT surface x = X + u of a set of faces of one patch:
+ *   r(a,i)    += sum_q w_q p_q N_a m_i                         (m: the non-normalised outward normal, a_1 x a_2 in 3-D,
+ *   A(ai, bj) += grad_factor sum_q w_q p_q N_a dm_i/dx_bj        (a_y, -a_x) in 2-D, as in the contact integrator)
+ * p_q = the uniform value, or sum_a N_a p_a of values at the faces' nodes.  The tangent is exact and not symmetric.
+ * Tables: the same layout rules as mimi_hip_contact_tables (face orientation such that m points out of the body); the
+ * contributions are summed per CSR row in a fixed order (no atomics: bitwise reproducible). */
+typedef struct mimi_hip_pressure_s* mimi_hip_pressure_t;
+typedef struct mimi_hip_pressure_tables {
+  int32_t dim;
+  int32_t n_faces;
+  int32_t n_dof;        /* per face, <= 16 */
+  int32_t n_quad;       /* <= 25 */
+  int64_t n_nodes;
+  const int32_t* dofs;  /* [n_faces][n_dof] global node ids (QuadData of the boundary elements, as for contact) */
+  const double* N;      /* [n_faces][n_quad][n_dof]          QuadData::N */
+  const double* dN_dxi; /* [n_faces][n_quad][dim-1][n_dof]   QuadData::dN_dxi */
+  const double* weight; /* [n_faces][n_quad]                 QuadData::integration_weight */
+  const double* x_ref;  /* [n_nodes][dim] reference coordinates of the control points (byVDIM) */
+  const int64_t* csr_rowptr;
+  const int32_t* csr_col;
+} mimi_hip_pressure_tables;
+
+int mimi_hip_pressure_create(const mimi_hip_pressure_tables* tables, int device, mimi_hip_pressure_t* out);
+int mimi_hip_pressure_destroy(mimi_hip_pressure_t h);
+/* NULL = the handle's own stream; MIMI_HIP_STREAM_NULL = the device's null stream */
+int mimi_hip_pressure_set_stream(mimi_hip_pressure_t h, void* stream);
+int mimi_hip_pressure_synchronize(mimi_hip_pressure_t h);
+/* BCMarker::pressure_[bid] (boundary_conditions.cpp:43-50): a uniform pressure, used from the next assembly on (also
+ * after set_nodal); 0 at create time.  A face whose pressure is zero everywhere adds nothing to r / A_values. */
+int mimi_hip_pressure_set_value(mimi_hip_pressure_t h, double p);
+/* the sorted global node ids of the faces, the order of set_nodal's values (out == NULL: count only) */
+int mimi_hip_pressure_face_nodes(mimi_hip_pressure_t h, int32_t* out, int64_t capacity, int64_t* n);
+/* pressure values at the face nodes [n], host or device; p == NULL: back to the uniform value */
+int mimi_hip_pressure_set_nodal(mimi_hip_pressure_t h, const double* p, int64_t n);
+/* AddBoundaryResidual: r += R(u) (stands in for the dead-load VectorBoundaryLFIntegrator of py_nonlinear_solid.cpp:243-283,
+ * which the reference applies for traction only) */
+int mimi_hip_pressure_add_residual(mimi_hip_pressure_t h, const double* u, double* r);
+/* AddBoundaryResidualAndGrad: r += R(u); A_values += grad_factor dR/du */
+int mimi_hip_pressure_add_residual_and_grad(mimi_hip_pressure_t h, const double* u, double grad_factor, double* r,
+                                            double* A_values);
+/* of the latest Add* call (as mimi_hip_contact_last_history for last_area_ / last_force_, mortar_contact.hpp:33-35):
+ * out[0] = current area of the faces, out[1..1+dim) = external force -sum p m w; unused entries 0 */
+int mimi_hip_pressure_last_history(mimi_hip_pressure_t h, double* out4);
+
 /* ---- the callers' steps around the assembly, device-resident ---------------------------
  * One handle per CSR pattern (rowptr / col host or device; device arrays are used in place and must outlive the
  * handle) and list of essential dofs (forms::Nonlinear's zero_dofs). */

@@ -8,8 +8,9 @@ from .materials import (CompressibleOgdenNeoHookean, J2, StVenantKirchhoff, J2Li
                         JohnsonCookConstantTemperatureHardening)
 from .splines import BSplinePatch
 from . import integrators
-from .integrators import RigidSphere, RigidPlane, RigidSpline, NearestDistanceToSplines
+from .integrators import RigidSphere, RigidPlane, RigidSpline, NearestDistanceToSplines, FollowerPressure
 from .solid import NonlinearSolid, Solid, BoundaryConditions, RuntimeCommunication
 
 __all__ = ["CompressibleOgdenNeoHookean", "J2", "Material", "BSplinePatch", "integrators", "NonlinearSolid",
-           "Solid", "BoundaryConditions", "RuntimeCommunication", "RigidSphere", "RigidPlane"]
+           "Solid", "BoundaryConditions", "RuntimeCommunication", "RigidSphere", "RigidPlane",
+           "FollowerPressure"]

@@ -51,6 +51,14 @@ class ContactTables(C.Structure):
                 ("csr_rowptr", C.c_void_p), ("csr_col", C.c_void_p), ("spline", C.c_void_p)]
 
 
+class PressureTables(C.Structure):
+    """mimi_hip_pressure_tables"""
+    _fields_ = [("dim", C.c_int32), ("n_faces", C.c_int32), ("n_dof", C.c_int32), ("n_quad", C.c_int32),
+                ("n_nodes", C.c_int64),
+                ("dofs", C.c_void_p), ("N", C.c_void_p), ("dN_dxi", C.c_void_p), ("weight", C.c_void_p),
+                ("x_ref", C.c_void_p), ("csr_rowptr", C.c_void_p), ("csr_col", C.c_void_p)]
+
+
 class SplineBody(C.Structure):
     """mimi_hip_spline_body"""
     _fields_ = [("para_dim", C.c_int32), ("degree", C.c_int32 * 2), ("n_knots", C.c_int32 * 2),
@@ -75,6 +83,9 @@ EXPORTS = [
     "mimi_hip_contact_last_history", "mimi_hip_contact_get_pressure",
     "mimi_hip_contact_update_body", "mimi_hip_contact_gap_area", "mimi_hip_contact_marked_nodes", "mimi_hip_contact_nodal",
     "mimi_hip_contact_add_residual_from_nodal",
+    "mimi_hip_pressure_create", "mimi_hip_pressure_destroy", "mimi_hip_pressure_set_stream", "mimi_hip_pressure_synchronize",
+    "mimi_hip_pressure_set_value", "mimi_hip_pressure_face_nodes", "mimi_hip_pressure_set_nodal",
+    "mimi_hip_pressure_add_residual", "mimi_hip_pressure_add_residual_and_grad", "mimi_hip_pressure_last_history",
     "mimi_hip_linear_create", "mimi_hip_linear_destroy", "mimi_hip_linear_set_stream", "mimi_hip_linear_info", "mimi_hip_linear_eliminate",
     "mimi_hip_linear_add_mult",
     "mimi_hip_linear_gmres", "mimi_hip_linear_cg",
@@ -173,6 +184,16 @@ def lib():
     L.mimi_hip_contact_marked_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.mimi_hip_contact_nodal.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.mimi_hip_contact_add_residual_from_nodal.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    L.mimi_hip_pressure_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mimi_hip_pressure_destroy.argtypes = [C.c_void_p]
+    L.mimi_hip_pressure_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_pressure_synchronize.argtypes = [C.c_void_p]
+    L.mimi_hip_pressure_set_value.argtypes = [C.c_void_p, C.c_double]
+    L.mimi_hip_pressure_face_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.mimi_hip_pressure_set_nodal.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.mimi_hip_pressure_add_residual.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mimi_hip_pressure_add_residual_and_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    L.mimi_hip_pressure_last_history.argtypes = [C.c_void_p, C.c_void_p]
     L.mimi_hip_linear_create.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
     L.mimi_hip_linear_destroy.argtypes = [C.c_void_p]
     L.mimi_hip_linear_set_stream.argtypes = [C.c_void_p, C.c_void_p]

@@ -545,3 +545,119 @@ class MortarContact(NonlinearBase):
                 self._h = None
         except Exception:
             pass
+
+
+class FollowerPressure(NonlinearBase):
+    """Follower pressure t = -p n da on the CURRENT surface of one face of a B-spline patch (include/mimi_hip.h:
+    mimi_hip_pressure_*).  The reference's BCMarker::Pressure (utils/boundary_conditions.cpp:43-50) stores the value and
+    never applies it; the boundary-integrator surface is MortarContact's (integrators/mortar_contact.hpp:23-172).
+
+    Residual r(a,i) += sum_q w p_q N_a m_i (m: the non-normalised outward normal of the deformed face), tangent with
+    dm/dx -- exact, not symmetric.  element_box = (begin, end): only the faces of the elements in that box (element slabs:
+    every contribution lands in rows of the slab's own elements, no exchange of nodal values is needed)."""
+
+    def __init__(self, name, pattern, patch, axis, side, device=0, quadrature_order=-1, element_box=None):
+        super().__init__(name)
+        self.pattern_, self.patch_ = pattern, patch
+        self.axis_, self.side_ = axis, side
+        self.device_, self.quadrature_order_ = device, quadrature_order
+        self.element_box_ = element_box
+        self._h = None
+        self.last_area_ = 0.0
+        self.last_force_ = np.zeros(patch.dim)
+
+    def Prepare(self):
+        from . import splines
+        L = _capi.lib()
+        p = self.patch_
+        # (a rational patch raises here: face_tables builds B-spline tables only)
+        dofs, N, dN, weight = splines.face_tables(p, self.axis_, self.side_, self.quadrature_order_, self.element_box_)
+        if len(dofs) == 0:
+            raise RuntimeError("no loaded boundary faces in this element box")
+        t = _capi.PressureTables()
+        t.dim = p.dim
+        t.n_faces, t.n_dof = dofs.shape
+        t.n_quad = weight.shape[1]
+        t.n_nodes = p.n_nodes
+        x_ref = np.ascontiguousarray(p.control_points, dtype=np.float64)
+        self._keep = [dofs, N, dN, weight, x_ref]
+        t.dofs, t.N, t.dN_dxi, t.weight = dofs.ctypes.data, N.ctypes.data, dN.ctypes.data, weight.ctypes.data
+        t.x_ref = x_ref.ctypes.data
+        t.csr_rowptr = ptr(self.pattern_.rowptr, "int64").value
+        t.csr_col = ptr(self.pattern_.col, "int32").value
+        h = C.c_void_p()
+        check(L.mimi_hip_pressure_create(C.byref(t), self.device_, C.byref(h)))
+        self._h = h
+        self.n_faces_ = int(t.n_faces)
+        return self
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("Prepare() has not been called")
+        return self._h
+
+    def Synchronize(self):
+        check(_capi.lib().mimi_hip_pressure_synchronize(self._handle()))
+
+    def FaceNodes(self):
+        """sorted global node ids of the loaded faces: the order of a nodal pressure array"""
+        n = C.c_int64(0)
+        check(_capi.lib().mimi_hip_pressure_face_nodes(self._handle(), None, 0, C.byref(n)))
+        out = np.empty(n.value, dtype=np.int32)
+        check(_capi.lib().mimi_hip_pressure_face_nodes(self._handle(), ptr(out), out.size, C.byref(n)))
+        return out
+
+    def SetPressure(self, value):
+        """a float (uniform pressure) or an array of values at FaceNodes() (host array or device tensor); applies from the
+        next assembly on"""
+        if np.isscalar(value):
+            check(_capi.lib().mimi_hip_pressure_set_value(self._handle(), float(value)))
+            return
+        if isinstance(value, np.ndarray) or not hasattr(value, "data_ptr"):
+            value = np.ascontiguousarray(value, dtype=np.float64)
+        else:
+            self._follow_torch(value)
+        n = value.shape[0] if value.ndim == 1 else -1
+        check(_capi.lib().mimi_hip_pressure_set_nodal(self._handle(), fptr(value), n))
+
+    def SetStream(self, stream):
+        self._user_stream = bool(stream)
+        check(_capi.lib().mimi_hip_pressure_set_stream(self._handle(), C.c_void_p(stream) if stream else None))
+
+    def _follow_torch(self, *buffers):
+        if getattr(self, "_user_stream", False):
+            return
+        s = _capi.torch_stream_of(*buffers)
+        if s is not None or getattr(self, "_followed", None):
+            check(_capi.lib().mimi_hip_pressure_set_stream(self._handle(), C.c_void_p(s) if s else None))
+            self._followed = s
+
+    def AddBoundaryResidual(self, current_u, residual):
+        self._follow_torch(current_u, residual)
+        check(_capi.lib().mimi_hip_pressure_add_residual(self._handle(), fptr(current_u), fptr(residual)))
+
+    def AddBoundaryResidualAndGrad(self, current_u, grad_factor, residual, grad_values):
+        self._follow_torch(current_u, residual, grad_values)
+        check(_capi.lib().mimi_hip_pressure_add_residual_and_grad(self._handle(), fptr(current_u), float(grad_factor),
+                                                                  fptr(residual), fptr(grad_values)))
+
+    def _history(self):
+        out = np.zeros(4)
+        check(_capi.lib().mimi_hip_pressure_last_history(self._handle(), ptr(out)))
+        self.last_area_ = float(out[0])
+        self.last_force_ = out[1:1 + self.patch_.dim].copy()
+
+    # as MortarContact::BoundaryPostTimeAdvance (mortar_contact.cpp:469-488): area and force of the latest Add* call
+    def BoundaryPostTimeAdvance(self, converged_u):
+        self._history()
+
+    def AddBoundaryGrad(self, current_u, grad):
+        raise RuntimeError("Currently not implemented, use AddBoundaryResidualAndGrad")
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                _capi.lib().mimi_hip_pressure_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass

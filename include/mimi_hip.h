@@ -366,6 +366,30 @@ int mimi_hip_pressure_add_residual_and_grad(mimi_hip_pressure_t h, const double*
  * out[0] = current area of the faces, out[1..1+dim) = external force -sum p m w; unused entries 0 */
 int mimi_hip_pressure_last_history(mimi_hip_pressure_t h, double* out4);
 
+/* ---- periodic fold (BCMarker::PeriodicBoundary, boundary_conditions.cpp:152-159) ---------------------------------
+ * The integrators assemble into the patch's unwrapped structured CSR (rowptr_u / col_u); P is the 0/1 map from the
+ * folded (periodic) dofs to the unwrapped ones, given per node: node_map[n_nodes_u] -> folded node, onto [0, n_nodes_f)
+ * (vdof n dim + c -> node_map[n] dim + c).  The folded pattern is that of P^T A P, columns sorted.  No atomics: the same
+ * bits every run.  Host or device pointers; the work runs on the handle's stream. */
+typedef struct mimi_hip_fold_s* mimi_hip_fold_t;
+int mimi_hip_fold_create(int32_t dim, int64_t n_nodes_u, const int64_t* node_map, const int64_t* rowptr_u,
+                         const int32_t* col_u, int device, mimi_hip_fold_t* out);
+int mimi_hip_fold_destroy(mimi_hip_fold_t h);
+/* what: 0 n_nodes_f, 1 nnz_f, 2 nnz_u, 3 longest folded row (rounded up to 8), 4 folded rows added by one lane (a source
+ * row whose window wraps onto itself).  -1: bad argument. */
+int64_t mimi_hip_fold_info(mimi_hip_fold_t h, int what);
+/* the folded pattern: rowptr_f[n_nodes_f dim + 1], col_f[nnz_f] (col_f NULL: rowptr only) */
+int mimi_hip_fold_pattern(mimi_hip_fold_t h, int64_t* rowptr_f, int32_t* col_f);
+/* NULL = the handle's own stream; MIMI_HIP_STREAM_NULL = the device's null stream */
+int mimi_hip_fold_set_stream(mimi_hip_fold_t h, void* stream);
+int mimi_hip_fold_synchronize(mimi_hip_fold_t h);
+/* u_u = P u_f */
+int mimi_hip_fold_expand(mimi_hip_fold_t h, const double* u_f, double* u_u);
+/* r_f += P^T r_u (r_u == r_f == NULL: matrix only);  A_f = A_base + P^T A_u P (A_base == A_f: "+="; A_base == NULL:
+ * A_f = P^T A_u P; A_u == NULL: residual only) */
+int mimi_hip_fold_add(mimi_hip_fold_t h, const double* r_u, double* r_f, const double* A_u, const double* A_base,
+                      double* A_f);
+
 /* ---- the callers' steps around the assembly, device-resident ---------------------------
  * One handle per CSR pattern (rowptr / col host or device; device arrays are used in place and must outlive the
  * handle) and list of essential dofs (forms::Nonlinear's zero_dofs). */

@@ -661,3 +661,110 @@ class FollowerPressure(NonlinearBase):
                 self._h = None
         except Exception:
             pass
+
+
+def periodic_node_map(n_ctrl, axes):
+    """Node map of a lexicographically numbered patch (n_ctrl nodes per direction, direction 0 fastest) made periodic along
+    `axes`: the last node plane along a periodic axis is the first one.  Folded nodes are numbered lexicographically on the
+    grid without those last planes, so a merged node has the index of its lowest copy (what the reference's DofMap returns
+    for a space whose boundaries were joined by NURBSExtension::ConnectBoundaries, py/py_nonlinear_solid.cpp:34-62).
+    Returns node_map[n_nodes] (int64)."""
+    dim = len(n_ctrl)
+    axes = sorted(set(int(a) for a in axes))
+    if any(a < 0 or a >= dim for a in axes):
+        raise RuntimeError(f"periodic axes {axes} out of range for a {dim}-D patch")
+    idx = np.indices(tuple(reversed([int(n) for n in n_ctrl])))[::-1]         # idx[d][z, y, x] = coordinate along d
+    out = np.zeros(idx[0].shape, dtype=np.int64)
+    stride = 1
+    for d in range(dim):
+        n_d = int(n_ctrl[d])
+        if d in axes:
+            if n_d < 2:
+                raise RuntimeError(f"a periodic direction needs at least two nodes (direction {d} has {n_d})")
+            out += (idx[d] % (n_d - 1)) * stride
+            stride *= n_d - 1
+        else:
+            out += idx[d] * stride
+            stride *= n_d
+    return out.reshape(-1)
+
+
+class PeriodicFold:
+    """The periodic fold of include/mimi_hip.h (mimi_hip_fold_*) on one device: P is the 0/1 map from the folded dofs to
+    the unwrapped dofs of `pattern` (an integrator's structured pattern), given per node by node_map.
+    Expand(u_f, u_u): u_u = P u_f.  Add(r_u, r_f, A_u, A_base, A_f): r_f += P^T r_u, A_f = A_base + P^T A_u P (A_base is
+    A_f: "+="; None: A_f = P^T A_u P; A_u None: residual only; r_u / r_f None: matrix only).  Host arrays or device
+    tensors."""
+
+    def __init__(self, pattern, node_map, dim, device=0):
+        self.pattern_u_ = pattern
+        self.node_map_ = np.ascontiguousarray(node_map, dtype=np.int64)
+        self.dim_, self.device_ = int(dim), device
+        self._h = None
+
+    def Prepare(self):
+        L = _capi.lib()
+        h = C.c_void_p()
+        check(L.mimi_hip_fold_create(self.dim_, len(self.node_map_), ptr(self.node_map_, "int64"),
+                                     ptr(self.pattern_u_.rowptr, "int64"), ptr(self.pattern_u_.col, "int32"), self.device_,
+                                     C.byref(h)))
+        self._h = h
+        self.n_nodes_f_ = int(L.mimi_hip_fold_info(h, 0))
+        self.nnz_f_ = int(L.mimi_hip_fold_info(h, 1))
+        self.nnz_u_ = int(L.mimi_hip_fold_info(h, 2))
+        self.n_f_ = self.n_nodes_f_ * self.dim_
+        self.n_u_ = len(self.node_map_) * self.dim_
+        return self
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("Prepare() has not been called")
+        return self._h
+
+    def Info(self, what):
+        return int(_capi.lib().mimi_hip_fold_info(self._handle(), what))
+
+    def Pattern(self, on_device=False):
+        """the folded CSRPattern (the pattern of P^T A P, columns sorted)"""
+        if on_device:
+            import torch
+            dev = torch.device("cuda", self.device_)
+            rowptr = torch.empty(self.n_f_ + 1, dtype=torch.int64, device=dev)
+            col = torch.empty(self.nnz_f_, dtype=torch.int32, device=dev)
+        else:
+            rowptr = np.empty(self.n_f_ + 1, dtype=np.int64)
+            col = np.empty(self.nnz_f_, dtype=np.int32)
+        check(_capi.lib().mimi_hip_fold_pattern(self._handle(), ptr(rowptr), ptr(col)))
+        return CSRPattern(rowptr, col, self.nnz_f_)
+
+    def SetStream(self, stream):
+        self._user_stream = bool(stream)
+        check(_capi.lib().mimi_hip_fold_set_stream(self._handle(), C.c_void_p(stream) if stream else None))
+
+    def _follow_torch(self, *buffers):
+        if getattr(self, "_user_stream", False):
+            return
+        s = _capi.torch_stream_of(*buffers)
+        if s is not None or getattr(self, "_followed", None):
+            check(_capi.lib().mimi_hip_fold_set_stream(self._handle(), C.c_void_p(s) if s else None))
+            self._followed = s
+
+    def Synchronize(self):
+        check(_capi.lib().mimi_hip_fold_synchronize(self._handle()))
+
+    def Expand(self, u_f, u_u):
+        self._follow_torch(u_f, u_u)
+        check(_capi.lib().mimi_hip_fold_expand(self._handle(), fptr(u_f), fptr(u_u)))
+        return u_u
+
+    def Add(self, r_u, r_f, A_u=None, A_base=None, A_f=None):
+        self._follow_torch(r_u, r_f, A_u, A_base, A_f)
+        check(_capi.lib().mimi_hip_fold_add(self._handle(), fptr(r_u), fptr(r_f), fptr(A_u), fptr(A_base), fptr(A_f)))
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                _capi.lib().mimi_hip_fold_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass

@@ -28,7 +28,8 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import nurbs_mesh, splines
-from .integrators import CSRPattern, FollowerPressure, MortarContact, NonlinearSolid as NonlinearSolidIntegrator
+from .integrators import (CSRPattern, FollowerPressure, MortarContact, NonlinearSolid as NonlinearSolidIntegrator,
+                          PeriodicFold, periodic_node_map)
 from .linear import LinearSolver
 from .splines import BSplinePatch
 
@@ -115,6 +116,7 @@ class BoundaryMarker:
     def __init__(self, initial_config=True):
         self.dirichlet_, self.body_force_, self.contact_ = [], {}, {}
         self.traction_, self.pressure_ = {}, {}
+        self.constant_velocity_, self.periodic_boundaries_ = {}, {}
         self.initial_config_ = bool(initial_config)
 
     def _only_for_initial_config(self, b_name):        # BCMarker::OnlyForInitialConfig (boundary_conditions.cpp:5-11)
@@ -145,6 +147,23 @@ class BoundaryMarker:
         (py_nonlinear_solid.cpp:243-283)"""
         self._only_for_initial_config("Traction")
         self.traction_.setdefault(int(bid), {})[int(dim)] = float(value)
+        return self
+
+    def constant_velocity(self, bid, dim, value):
+        """boundary_conditions.cpp:127-138: component `dim` of boundary `bid` moves with velocity `value` (the dofs are
+        essential through the implied dirichlet(bid, dim)); applied around every generalized-alpha solve as
+        TimeDependentDirichletBoundaryCondition::Apply / Restore (boundary_conditions.cpp:209-291)"""
+        self._only_for_initial_config("ConstantVelocity")
+        self.dirichlet(bid, dim)
+        self.constant_velocity_.setdefault(int(bid), {})[int(dim)] = float(value)
+        return self
+
+    def periodic(self, bid0, bid1):
+        """boundary_conditions.cpp:150-159: join the faces of boundary ATTRIBUTES bid0 and bid1 -- 1-based ("fortran
+        numbering", unlike every other marker's bid, which is attribute bid + 1).  The two faces must be the opposite faces
+        of one parametric axis; the joined faces become interior (no load or contact marker may name them)."""
+        self._only_for_initial_config("PeriodicBoundary")
+        self.periodic_boundaries_[int(bid0)] = int(bid1)
         return self
 
 
@@ -205,6 +224,44 @@ class Solid:
     def patch(self):
         nb = self._nurbs
         return BSplinePatch(nb.degrees, nb.knots, nb.ctrl, nb.weights if nb.is_rational() else None)
+
+    def _periodic_axes(self, bc):
+        """the parametric axes joined by bc.initial.periodic_boundaries_ (attributes, 1-based), checked"""
+        pairs = bc.initial.periodic_boundaries_ if bc is not None else {}
+        axes, seen = [], {}
+        for b0, b1 in sorted(pairs.items()):
+            for b in (b0, b1):
+                if b not in self._faces:
+                    raise RuntimeError(f"periodic boundary: the mesh has no boundary attribute {b} (attributes: "
+                                       f"{sorted(self._faces)}; periodic(bid0, bid1) takes 1-based attributes)")
+                if b in seen:
+                    raise RuntimeError(f"periodic boundary: attribute {b} appears in two pairs ({seen[b]} and {(b0, b1)})")
+                seen[b] = (b0, b1)
+            (a0, s0), (a1, s1) = self._faces[b0], self._faces[b1]
+            if a0 != a1 or s0 == s1:
+                raise RuntimeError(f"periodic boundary: attributes {b0} and {b1} are not the two opposite faces of one "
+                                   f"parametric axis (axis {a0} side {s0}, axis {a1} side {s1})")
+            axes.append(a0)
+        # a joined face is interior: a load or contact on it has no surface to act on (bid -> attribute bid + 1)
+        for what, marks in (("pressure", bc.initial.pressure_ if pairs else {}), ("traction", bc.initial.traction_ if pairs else {}),
+                            ("contact", {**bc.initial.contact_, **bc.current.contact_} if pairs else {})):
+            for bid in marks:
+                if bid + 1 in seen:
+                    raise RuntimeError(f"periodic boundary: {what} marker on boundary {bid} (attribute {bid + 1}), "
+                                       "which the periodic pair makes interior")
+        return sorted(axes)
+
+    def dof_map(self, key):
+        """PySolid::DofMap (py_solid.cpp:320-331): the (folded) node of every node of the patch, in this facade's
+        lexicographic numbering -- the identity without periodic boundaries"""
+        if key != "displacement":
+            raise KeyError(key)
+        patch = self.patch()
+        nm = getattr(self, "node_map_", None)
+        if nm is None:
+            axes = self._periodic_axes(self.boundary_condition)
+            nm = periodic_node_map(patch.n_ctrl, axes) if axes else np.arange(patch.n_nodes, dtype=np.int64)
+        return np.asarray(nm, dtype=np.int32).copy()
 
 
 def _element_tables(patch, quadrature_order=-1, with_gradients=False, elements=None):
@@ -291,9 +348,22 @@ class NonlinearSolid(Solid):
     # -- Setup (py_nonlinear_solid.cpp:15-387) -------------------------------------------------
     def setup(self, nthreads=-1):
         dim = self._dim
+        bc = self.boundary_condition or BoundaryConditions()
+        axes = self._periodic_axes(bc)                               # refusals come before any device work
         self.patch_ = patch = self.patch()
         n = patch.n_vdofs
-        self.pattern_ = CSRPattern.of_bspline_patch(patch, device=self.device)
+        # the integrators' pattern: the patch's unwrapped structured one (the tensor kernels' own) -- with periodic
+        # boundaries the solver's vectors and matrices live on the folded pattern, and one device pass (PeriodicFold) folds
+        # what the integrators assemble
+        self.pattern_u_ = CSRPattern.of_bspline_patch(patch, device=self.device)
+        self.fold_, self.node_map_ = None, None
+        if axes:
+            self.node_map_ = periodic_node_map(patch.n_ctrl, axes)
+            self.fold_ = PeriodicFold(self.pattern_u_, self.node_map_, dim, device=self.device).Prepare()
+            self.pattern_ = self.fold_.Pattern()
+            n = self.fold_.n_f_
+        else:
+            self.pattern_ = self.pattern_u_
         rowptr, col = self.pattern_.rowptr, self.pattern_.col
         self.x = np.zeros(n)        # displacement (py_nonlinear_solid.cpp:119)
         self.x_dot = np.zeros(n)
@@ -301,30 +371,51 @@ class NonlinearSolid(Solid):
             self.runtime_communication = RuntimeCommunication()
         rc = self.runtime_communication
         rc.initialize_time_step()                                    # py_solid.cpp:360
-        bc = self.boundary_condition or BoundaryConditions()
         # Dirichlet dofs (FindBoundaryDofIds, py_solid.cpp:185-235): bid -> attribute bid+1
         dofs = []
         for bid, comp in bc.initial.dirichlet_:
             axis, side = self._faces[bid + 1]
-            dofs.append(patch.boundary_nodes(axis, side) * dim + comp)
+            dofs.append(self._folded_dofs(patch.boundary_nodes(axis, side), comp))
         self.dirichlet_ = np.unique(np.concatenate(dofs)) if dofs else np.zeros(0, dtype=np.int64)
+        # constant velocity (py_nonlinear_solid.cpp:372-380): dof -> value, later markers over earlier ones (std::map order)
+        cv = {}
+        for bid, dim_value in sorted(bc.initial.constant_velocity_.items()):
+            axis, side = self._faces[bid + 1]
+            for comp, value in sorted(dim_value.items()):
+                for d in self._folded_dofs(patch.boundary_nodes(axis, side), comp):
+                    cv[int(d)] = value
+        self.constant_velocity_dofs_ = np.array(sorted(cv), dtype=np.int64)
+        self.constant_velocity_values_ = np.array([cv[d] for d in sorted(cv)], dtype=np.float64)
         # mass (VectorMassIntegrator(rho), FormSystemMatrix(zero_dofs); :155-173), damping (:176-192:
         # VectorDiffusionIntegrator(viscosity): C_(a,i),(b,j) = d_ij nu int grad N_a . grad N_b, integrated with the same
         # rule as the mass matrix -- exact on affine patches; mfem's own default rule for this integrator cannot be read
         # here and no reference fixture sets a viscosity: parity unpinned) and rhs (:221-283), in chunks of elements
         viscosity = getattr(self.material, "viscosity", -1.0)
-        mass, visc, rhs = _assemble_mass_viscosity_rhs(patch, rowptr, self.material.density, viscosity,
+        mass, visc, rhs = _assemble_mass_viscosity_rhs(patch, self.pattern_u_.rowptr, self.material.density, viscosity,
                                                        bc.initial.body_force_)
+        if self.fold_ is not None:
+            # assembled on the unwrapped pattern as without periodicity, folded once by the device pass
+            rhs = _load_vector(patch, self._faces, bc.initial.traction_, rhs, np.zeros(0, dtype=np.int64))
+            rhs_f = np.zeros(n)
+            self.fold_.Add(rhs, rhs_f)
+            rhs = rhs_f
+            mass_f = np.empty(self.pattern_.nnz)
+            self.fold_.Add(None, None, mass, None, mass_f)
+            mass = mass_f
+            if visc is not None:
+                visc_f = np.empty(self.pattern_.nnz)
+                self.fold_.Add(None, None, visc, None, visc_f)
+                visc = visc_f
         self.mass_ = mass
         _eliminate_row_col(rowptr, col, self.mass_, self.dirichlet_)
         self.visc_ = visc
         if visc is not None:
             _eliminate_row_col(rowptr, col, self.visc_, self.dirichlet_)
-        self.rhs_ = _load_vector(patch, self._faces, bc.initial.traction_, rhs, self.dirichlet_)
+        self.rhs_ = _load_vector(patch, self._faces, bc.initial.traction_ if self.fold_ is None else {}, rhs, self.dirichlet_)
         # integrators (py_nonlinear_solid.cpp:197-218, 286-326)
         q_order = rc.get_int("nonlinear_solid_quadrature_order", -1)
         try:
-            self.domain_ = NonlinearSolidIntegrator("nonlinear_solid", self.material, self.pattern_, patch=patch,
+            self.domain_ = NonlinearSolidIntegrator("nonlinear_solid", self.material, self.pattern_u_, patch=patch,
                                                     device=self.device, quadrature_order=q_order).Prepare()
         except RuntimeError as exc:
             if "not a tensor product" not in str(exc):
@@ -333,19 +424,19 @@ class NonlinearSolid(Solid):
             _, wd_t, conn_t, dN_dX = _element_tables(patch, q_order, with_gradients=True)
             tables = dict(dim=dim, n_nodes=patch.n_nodes, dofs=conn_t.astype(np.int32), dN_dX=np.ascontiguousarray(dN_dX),
                           weight_det=np.ascontiguousarray(wd_t))
-            self.domain_ = NonlinearSolidIntegrator("nonlinear_solid", self.material, self.pattern_, tables=tables,
+            self.domain_ = NonlinearSolidIntegrator("nonlinear_solid", self.material, self.pattern_u_, tables=tables,
                                                     device=self.device).Prepare()
         self.domain_.SetTangentMode(self.tangent_mode)
         self.contacts_ = []
         for bid, body in bc.current.contact_.items():
             axis, side = self._faces[bid + 1]
-            self.contacts_.append(MortarContact(body, "contact", self.pattern_, patch, axis, side, device=self.device,
+            self.contacts_.append(MortarContact(body, "contact", self.pattern_u_, patch, axis, side, device=self.device,
                                                 quadrature_order=rc.get_int("contact_quadrature_order", -1)).Prepare())
         # follower pressure (the reference stores BCMarker::pressure_ and never applies it): one device integrator per bid
         self.pressures_, self._pressure_by_bid = [], {}
         for bid, value in bc.initial.pressure_.items():
             axis, side = self._faces[bid + 1]
-            fp = FollowerPressure("pressure", self.pattern_, patch, axis, side, device=self.device).Prepare()
+            fp = FollowerPressure("pressure", self.pattern_u_, patch, axis, side, device=self.device).Prepare()
             fp.SetPressure(value)
             self.pressures_.append(fp)
             self._pressure_by_bid[bid] = fp
@@ -364,6 +455,13 @@ class NonlinearSolid(Solid):
         self.use_iterative_solver_ = bool(rc.get_int("use_iterative_solver", 0))
         self._to_device()
 
+    def _folded_dofs(self, nodes, comp):
+        """dofs (node, comp) of unwrapped nodes in the solver's numbering (through the periodic node map), unique"""
+        nodes = np.asarray(nodes, dtype=np.int64)
+        if self.node_map_ is not None:
+            nodes = np.unique(self.node_map_[nodes])
+        return nodes * self._dim + comp
+
     def configure_newton(self, name, rel_tol, abs_tol, max_iter, iterative_mode):   # py_solid.cpp:334-346
         self._newton = dict(rel_tol=rel_tol, abs_tol=abs_tol, max_iter=int(max_iter), iterative_mode=bool(iterative_mode))
 
@@ -379,7 +477,12 @@ class NonlinearSolid(Solid):
         """"x" (the displacement), "x_dot", "x_ref" (the nodes' reference positions, py_nonlinear_solid.cpp:91-114): host
         arrays in this facade's node order, the solver's own storage for the first two (write prescribed values in place)"""
         if component == "x_ref":
-            return np.ascontiguousarray(self.patch_.control_points, dtype=np.float64).reshape(-1).copy()
+            x_ref = np.ascontiguousarray(self.patch_.control_points, dtype=np.float64)
+            if self.node_map_ is not None:
+                # the lowest copy of every folded node (the node map is ascending in it)
+                _, first = np.unique(self.node_map_, return_index=True)
+                x_ref = x_ref.reshape(-1, self._dim)[first]
+            return x_ref.reshape(-1).copy()
         return {"x": self.x, "x_dot": self.x_dot}[component]
 
     # -- operators::NonlinearSolid ----------------------------------------------------------------
@@ -399,6 +502,14 @@ class NonlinearSolid(Solid):
         self.d_jac_ = torch.zeros_like(self.d_mass_)
         self.d_dirichlet_ = torch.from_numpy(np.asarray(self.dirichlet_, dtype=np.int64)).to(dev)
         self.d_x_, self.d_v_ = f(self.x), f(self.x_dot)
+        if self.fold_ is not None:
+            # the integrators' side of the fold: expanded x, unwrapped residual and values
+            self.d_xu_ = torch.zeros(self.fold_.n_u_, dtype=torch.float64, device=dev)
+            self.d_ru_ = torch.zeros_like(self.d_xu_)
+            self.d_Au_ = torch.zeros(self.fold_.nnz_u_, dtype=torch.float64, device=dev)
+        if len(self.constant_velocity_dofs_):
+            self.d_cv_dofs_ = torch.from_numpy(self.constant_velocity_dofs_).to(dev)
+            self.d_cv_values_ = f(self.constant_velocity_values_)
         self.pcie_csr_bytes_ = 0          # CSR values that crossed PCIe since setup (direct-solve route only)
 
     def _csr(self, vals):
@@ -408,7 +519,24 @@ class NonlinearSolid(Solid):
     def _push(self, integ):
         integ.dt_, integ.first_effective_dt_, integ.second_effective_dt_ = self.time_step_size, self._fac0, self._fac1
 
+    def _expand(self, x):
+        """the unwrapped vector the integrators read (periodic route)"""
+        return self.fold_.Expand(x, self.d_xu_)
+
     def _add_mult(self, xt, y):                       # forms/nonlinear.hpp:53-81
+        if self.fold_ is not None:
+            # expand, every integrator into the unwrapped residual, one fold into y
+            xu, ru = self._expand(xt), self.d_ru_
+            ru.zero_()
+            self._push(self.domain_)
+            self.domain_.AddDomainResidual(xu, ru)
+            for c in self.contacts_:
+                c.AddBoundaryResidual(xu, ru)
+            for c in self.pressures_:
+                c.AddBoundaryResidual(xu, ru)
+            self.fold_.Add(ru, y)
+            self.linear_.Eliminate(y, None)
+            return
         self._push(self.domain_)
         self.domain_.AddDomainResidual(xt, y)
         for c in self.contacts_:
@@ -441,11 +569,24 @@ class NonlinearSolid(Solid):
         # where "+=" would read J (mimi_hip_domain_add_residual_and_grad_from) -- no 2 x nnz copy, and the domain
         # integrator of a single-patch solid touches every row
         self._push(self.domain_)
-        self.domain_.AddDomainResidualAndGradFrom(xt, self._fac0, y, self.d_mass_, self.d_jac_)
-        for c in self.contacts_:
-            c.AddBoundaryResidualAndGrad(xt, self._fac0, y, self.d_jac_)
-        for c in self.pressures_:
-            c.AddBoundaryResidualAndGrad(xt, self._fac0, y, self.d_jac_)
+        if self.fold_ is not None:
+            # periodic route: expand x_t, every integrator into the zeroed unwrapped r_u / A_u, then ONE fold
+            # y += P^T r_u, J = M + P^T A_u P in place of the from-base pass
+            xu, ru, Au = self._expand(xt), self.d_ru_, self.d_Au_
+            ru.zero_()
+            Au.zero_()
+            self.domain_.AddDomainResidualAndGrad(xu, self._fac0, ru, Au)
+            for c in self.contacts_:
+                c.AddBoundaryResidualAndGrad(xu, self._fac0, ru, Au)
+            for c in self.pressures_:
+                c.AddBoundaryResidualAndGrad(xu, self._fac0, ru, Au)
+            self.fold_.Add(ru, y, Au, self.d_mass_, self.d_jac_)
+        else:
+            self.domain_.AddDomainResidualAndGradFrom(xt, self._fac0, y, self.d_mass_, self.d_jac_)
+            for c in self.contacts_:
+                c.AddBoundaryResidualAndGrad(xt, self._fac0, y, self.d_jac_)
+            for c in self.pressures_:
+                c.AddBoundaryResidualAndGrad(xt, self._fac0, y, self.d_jac_)
         self.linear_.Eliminate(y, self.d_jac_)        # forms/nonlinear.hpp:76-80,112-115
         if self.d_visc_ is not None:
             self.d_jac_.add_(self.d_visc_, alpha=self._fac1)     # jacobian_->Add(fac1_, viscosity_->SpMat())
@@ -536,6 +677,14 @@ class NonlinearSolid(Solid):
         a = self._a
         self._xa = x + (v + f0 * dt * a) * (f1 * dt)
         self._va = v + f2 * dt * a
+        cv = len(self.constant_velocity_dofs_) > 0
+        if cv:
+            # TimeDependentDirichletBoundaryCondition::Apply (boundary_conditions.cpp:209-259, ode.cpp:56-58)
+            idx, val = self.d_cv_dofs_, self.d_cv_values_
+            self._aa[idx] = 0.0
+            self._va[idx] = val
+            self._xa[idx] = x[idx] + val * dt
+            saved_x = self._xa[idx].clone()
         self._aa = self._newton_solve(self._aa)
         aa = self._aa
         xa = self._xa + self._fac0 * aa
@@ -544,13 +693,19 @@ class NonlinearSolid(Solid):
         x.mul_(prev).add_(xa, alpha=1.0 / f1)
         v.mul_(prev).add_(va, alpha=1.0 / f1)
         self._a = a * prev + aa / f5
+        if cv:
+            # ... Restore (boundary_conditions.cpp:261-291, ode.cpp:73-75)
+            x[idx] = saved_x
+            v[idx] = val
+            self._a[idx] = 0.0
         # PostTimeAdvance (operators/nonlinear_solid.cpp:285-292)
+        xp = self._expand(x) if self.fold_ is not None else x
         self._push(self.domain_)
-        self.domain_.DomainPostTimeAdvance(x)
+        self.domain_.DomainPostTimeAdvance(xp)
         for c in self.contacts_:
-            c.BoundaryPostTimeAdvance(x)
+            c.BoundaryPostTimeAdvance(xp)
         for c in self.pressures_:
-            c.BoundaryPostTimeAdvance(x)
+            c.BoundaryPostTimeAdvance(xp)
         self.current_time += dt
         # the arrays solution_view handed out (zero-copy views of the reference: py_solid.cpp:379-388)
         self.x[:] = x.cpu().numpy()
@@ -566,14 +721,24 @@ class NonlinearSolid(Solid):
             rc.next_time_step(dt)
 
     def in_reference_numbering(self, vec):
-        """byVDIM vector of this facade (lexicographic nodes) -> the reference's dof order (MFEM's NURBS numbering)"""
+        """byVDIM vector of this facade (lexicographic nodes) -> the reference's dof order (MFEM's NURBS numbering).
+
+        With periodic boundaries the vector is expanded first (every copy of a joined node gets its value) and written
+        in the NON-periodic reference numbering: MFEM's numbering of a periodic space cannot be restated without MFEM."""
         order = self._nurbs.mfem_order()
-        return np.ascontiguousarray(np.asarray(vec).reshape(-1, self._dim)[order]).reshape(-1)
+        v = np.asarray(vec).reshape(-1, self._dim)
+        if getattr(self, "node_map_", None) is not None and len(v) != len(order):
+            v = v[self.node_map_]
+        return np.ascontiguousarray(v[order]).reshape(-1)
 
     def from_reference_numbering(self, vec):
+        """inverse of in_reference_numbering (periodic: the value of a joined node is its lowest copy's)"""
         order = self._nurbs.mfem_order()
         out = np.zeros(len(order) * self._dim)
         out.reshape(-1, self._dim)[order] = np.asarray(vec).reshape(-1, self._dim)
+        if getattr(self, "node_map_", None) is not None:
+            _, first = np.unique(self.node_map_, return_index=True)
+            out = np.ascontiguousarray(out.reshape(-1, self._dim)[first]).reshape(-1)
         return out
 
 

@@ -366,6 +366,29 @@ int mimi_hip_pressure_add_residual_and_grad(mimi_hip_pressure_t h, const double*
  * out[0] = current area of the faces, out[1..1+dim) = external force -sum p m w; unused entries 0 */
 int mimi_hip_pressure_last_history(mimi_hip_pressure_t h, double* out4);
 
+/* ---- coupling surface (partitioned fluid-structure coupling) ---------------------------------------------------------
+ * What a fluid partner exchanges with the solid every coupling iteration of the reference's fixed-point loop
+ * (fixed_point_solve2 / fixed_point_advance2 / advance_time2: py/py_solid.cpp:443-511, solvers/ode.cpp:81-186), on the
+ * faces of a mimi_hip_pressure_tables (the same tables, rule and outward normal m as the pressure integrator; csr_rowptr /
+ * csr_col are not read), for the configuration x = X + u (u == NULL: the reference configuration):
+ *   points    x_q = sum_a N_a x_a,  normal n_q = m_q / |m_q|,  area weight w_q |m_q|  -- face-major, point-minor
+ *   add_load  f(a,i) += sum_q w_q |m_q| N_a(xi_q) t(q,i): the consistent nodal forces of a traction t per unit area of x
+ *             (Cauchy for the current configuration, nominal for the reference one); a dead load, no tangent
+ * u, t, the outputs and f: host or device pointers, as for the integrators' add calls.  No atomics: the same bits every
+ * run. */
+typedef struct mimi_hip_surface_s* mimi_hip_surface_t;
+int mimi_hip_surface_create(const mimi_hip_pressure_tables* tables, int device, mimi_hip_surface_t* out);
+int mimi_hip_surface_destroy(mimi_hip_surface_t h);
+/* NULL = the handle's own stream; MIMI_HIP_STREAM_NULL = the device's null stream */
+int mimi_hip_surface_set_stream(mimi_hip_surface_t h, void* stream);
+int mimi_hip_surface_synchronize(mimi_hip_surface_t h);
+/* n_faces * n_quad (-1: null handle) */
+int64_t mimi_hip_surface_n_points(mimi_hip_surface_t h);
+/* x[n_points][dim], normal[n_points][dim], weight[n_points]: each output may be NULL */
+int mimi_hip_surface_points(mimi_hip_surface_t h, const double* u, double* x, double* normal, double* weight);
+/* t[n_points][dim]: f[n_vdofs] += the nodal forces */
+int mimi_hip_surface_add_load(mimi_hip_surface_t h, const double* u, const double* t, double* f);
+
 /* ---- periodic fold (BCMarker::PeriodicBoundary, boundary_conditions.cpp:152-159) ---------------------------------
  * The integrators assemble into the patch's unwrapped structured CSR (rowptr_u / col_u); P is the 0/1 map from the
  * folded (periodic) dofs to the unwrapped ones, given per node: node_map[n_nodes_u] -> folded node, onto [0, n_nodes_f)

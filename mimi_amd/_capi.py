@@ -86,6 +86,8 @@ EXPORTS = [
     "mimi_hip_pressure_create", "mimi_hip_pressure_destroy", "mimi_hip_pressure_set_stream", "mimi_hip_pressure_synchronize",
     "mimi_hip_pressure_set_value", "mimi_hip_pressure_face_nodes", "mimi_hip_pressure_set_nodal",
     "mimi_hip_pressure_add_residual", "mimi_hip_pressure_add_residual_and_grad", "mimi_hip_pressure_last_history",
+    "mimi_hip_surface_create", "mimi_hip_surface_destroy", "mimi_hip_surface_set_stream", "mimi_hip_surface_synchronize",
+    "mimi_hip_surface_n_points", "mimi_hip_surface_points", "mimi_hip_surface_add_load",
     "mimi_hip_fold_create", "mimi_hip_fold_destroy", "mimi_hip_fold_info", "mimi_hip_fold_pattern", "mimi_hip_fold_set_stream",
     "mimi_hip_fold_synchronize", "mimi_hip_fold_expand", "mimi_hip_fold_add",
     "mimi_hip_linear_create", "mimi_hip_linear_destroy", "mimi_hip_linear_set_stream", "mimi_hip_linear_info", "mimi_hip_linear_eliminate",
@@ -196,6 +198,14 @@ def lib():
     L.mimi_hip_pressure_add_residual.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mimi_hip_pressure_add_residual_and_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
     L.mimi_hip_pressure_last_history.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_surface_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mimi_hip_surface_destroy.argtypes = [C.c_void_p]
+    L.mimi_hip_surface_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_surface_synchronize.argtypes = [C.c_void_p]
+    L.mimi_hip_surface_n_points.argtypes = [C.c_void_p]
+    L.mimi_hip_surface_n_points.restype = C.c_int64
+    L.mimi_hip_surface_points.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mimi_hip_surface_add_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mimi_hip_fold_create.argtypes = [C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.mimi_hip_fold_destroy.argtypes = [C.c_void_p]
     L.mimi_hip_fold_info.argtypes = [C.c_void_p, C.c_int]

@@ -21,10 +21,7 @@
 #include <vector>
 
 #include "common.hpp"
-
-#ifndef MH_DEV
-#define MH_DEV __device__ __forceinline__
-#endif
+#include "face_common.hpp"
 
 namespace mimi_hip {
 
@@ -49,29 +46,6 @@ struct PressureArgs {
   double* face_scal;         // [n_faces][1 + dim]  current area, external force
   unsigned char* face_active;   // some pressure on the face is not zero
 };
-
-constexpr int kPressureMaxDof = 16;
-constexpr int kPressureMaxQuad = 25;
-
-MH_DEV double pressure_lane_read(double v, int l) {   // the value lane l holds, in every lane (l wave-uniform)
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)u, l), hi = __builtin_amdgcn_readlane((unsigned)(u >> 32), l);
-  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
-
-// the non-normalised outward normal from the surface tangents t = [a_1 | a_2] (contact.hip surface_normal; the orientation
-// is the one splines.face_tables builds the face parametrisation for)
-template<int DIM>
-MH_DEV void pressure_normal(const double* t /*[DIM-1][DIM]*/, double* m) {
-  if constexpr (DIM == 2) {
-    m[0] = t[1];
-    m[1] = -t[0];
-  } else {
-    m[0] = t[1] * t[5] - t[2] * t[4];
-    m[1] = t[2] * t[3] - t[0] * t[5];
-    m[2] = t[0] * t[4] - t[1] * t[3];
-  }
-}
 
 // One WAVE per face.  Lane c < n_dof holds node c (position, nodal pressure); lane q < n_q forms the point's pressure,
 // tangents and normal from them by lane reads; lane k = i n_dof + a sums the residual entry over the points; lane 0 sums the
@@ -426,17 +400,15 @@ int mimi_hip_pressure_create(const mimi_hip_pressure_tables* t, int device, mimi
       std::copy(t->dofs, t->dofs + nfd, dofs.begin());
     for (int32_t d : dofs)
       if (d < 0 || d >= t->n_nodes) fail("face node id %d out of range [0,%lld)", d, (long long)t->n_nodes);
-    // the face nodes, sorted and unique: the order of the nodal pressure values and of the row gather
-    std::vector<int32_t> fnodes(dofs);
-    std::sort(fnodes.begin(), fnodes.end());
-    fnodes.erase(std::unique(fnodes.begin(), fnodes.end()), fnodes.end());
+    if (t->n_faces >= (1 << 25)) fail("too many boundary faces for the incidence encoding");
+    // the face nodes, sorted and unique (the order of the nodal pressure values and of the row gather), and their
+    // (face, local node) incidences, faces ascending: the summation order of the gather
+    const FaceIncidences inc = face_incidences(dofs, t->n_dof);
+    const std::vector<int32_t>& fnodes = inc.fnodes;
     h->n_fnodes = (int)fnodes.size();
     h->face_nodes = fnodes;
-    std::vector<int32_t> local(nfd);
-    for (size_t k = 0; k < nfd; ++k)
-      local[k] = (int32_t)(std::lower_bound(fnodes.begin(), fnodes.end(), dofs[k]) - fnodes.begin());
     h->dofs.assign(dofs.data(), nfd, h->stream);
-    h->local.assign(local.data(), nfd, h->stream);
+    h->local.assign(inc.local.data(), nfd, h->stream);
     const size_t npts = (size_t)t->n_faces * t->n_quad;
     h->N.assign(t->N, npts * t->n_dof, h->stream);
     h->dN.assign(t->dN_dxi, npts * t->n_dof * (t->dim - 1), h->stream);
@@ -445,18 +417,9 @@ int mimi_hip_pressure_create(const mimi_hip_pressure_tables* t, int device, mimi
     h->nodal.resize(h->n_fnodes);
     h->scalars.resize(4);
     MH_HIP(hipMemsetAsync(h->scalars.ptr, 0, 4 * sizeof(double), h->stream));
-    {
-      // face node -> its (face, local node) incidences, faces in ascending order: the summation order of the gather
-      if (t->n_faces >= (1 << 25)) fail("too many boundary faces for the incidence encoding");
-      std::vector<int32_t> ptr(fnodes.size() + 1, 0), adj(nfd);
-      for (size_t k = 0; k < nfd; ++k) ++ptr[local[k] + 1];
-      for (size_t l = 0; l < fnodes.size(); ++l) ptr[l + 1] += ptr[l];
-      std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-      for (size_t k = 0; k < nfd; ++k) adj[fill[local[k]]++] = (int32_t)(((k / t->n_dof) << 6) | (k % t->n_dof));
-      h->adj_ptr.assign(ptr.data(), ptr.size(), h->stream);
-      h->adj.assign(adj.data(), adj.size(), h->stream);
-      h->fnodes_dev.assign(fnodes.data(), fnodes.size(), h->stream);
-    }
+    h->adj_ptr.assign(inc.adj_ptr.data(), inc.adj_ptr.size(), h->stream);
+    h->adj.assign(inc.adj.data(), inc.adj.size(), h->stream);
+    h->fnodes_dev.assign(fnodes.data(), fnodes.size(), h->stream);
     h->face_r.resize(nfd * t->dim);
     h->face_scal.resize((size_t)t->n_faces * (1 + t->dim));
     h->face_active.resize((size_t)t->n_faces);

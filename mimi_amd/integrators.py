@@ -663,6 +663,141 @@ class FollowerPressure(NonlinearBase):
             pass
 
 
+class CouplingSurface:
+    """The coupling surface of one face of a B-spline patch (include/mimi_hip.h: mimi_hip_surface_*): what a fluid partner
+    exchanges with the solid every iteration of the reference's fixed-point loop (fixed_point_solve2 / fixed_point_advance2
+    / advance_time2, py/py_solid.cpp:443-511), on the face tables, rule and outward normal of FollowerPressure
+    (splines.face_tables).  Points are face-major, point-minor: n_points_ = n_faces_ * n_q_.
+
+      points(u=None)          -> device tensors x [n_points, dim], unit outward normal [n_points, dim], area weight
+                                 w_q |m_q| [n_points] of the configuration X + u
+      set_traction(t, u=None) -> load_ = f(a,i) = sum_q w_q |m_q(X+u)| N_a t(q,i): the consistent nodal forces of t
+                                 [n_points, dim], a traction per unit area of X + u (Cauchy for the current or advanced
+                                 configuration, nominal for u = None); None removes the load
+
+    u and load_ are in the solver's numbering: with `fold` (a PeriodicFold) u is expanded by fold.Expand and the load folded
+    by fold.Add.  The load is dead within a solve and has no tangent: the coupling iteration carries its dependence on the
+    geometry (the follower load with an exact tangent is FollowerPressure's).  Points / AddLoad are the C ABI as it stands
+    (u in the patch's numbering, host arrays or device tensors, AddLoad adds into f)."""
+
+    def __init__(self, patch, axis, side, device=0, quadrature_order=-1, fold=None):
+        self.patch_, self.axis_, self.side_ = patch, axis, side
+        self.device_, self.quadrature_order_, self.fold_ = device, quadrature_order, fold
+        self._h = None
+        self.load_ = None
+
+    def Prepare(self):
+        from . import splines
+        L = _capi.lib()
+        p = self.patch_
+        # (a rational patch raises here: face_tables builds B-spline tables only)
+        dofs, N, dN, weight = splines.face_tables(p, self.axis_, self.side_, self.quadrature_order_)
+        t = _capi.PressureTables()
+        t.dim = p.dim
+        t.n_faces, t.n_dof = dofs.shape
+        t.n_quad = weight.shape[1]
+        t.n_nodes = p.n_nodes
+        x_ref = np.ascontiguousarray(p.control_points, dtype=np.float64)
+        t.dofs, t.N, t.dN_dxi, t.weight = dofs.ctypes.data, N.ctypes.data, dN.ctypes.data, weight.ctypes.data
+        t.x_ref = x_ref.ctypes.data
+        h = C.c_void_p()
+        check(L.mimi_hip_surface_create(C.byref(t), self.device_, C.byref(h)))
+        self._h = h
+        self.n_faces_, self.n_q_ = int(t.n_faces), int(t.n_quad)
+        self.n_points_ = int(L.mimi_hip_surface_n_points(h))
+        return self
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("Prepare() has not been called")
+        return self._h
+
+    def SetStream(self, stream):
+        self._user_stream = bool(stream)
+        check(_capi.lib().mimi_hip_surface_set_stream(self._handle(), C.c_void_p(stream) if stream else None))
+
+    def _follow_torch(self, *buffers):
+        if getattr(self, "_user_stream", False):
+            return
+        s = _capi.torch_stream_of(*buffers)
+        if s is not None or getattr(self, "_followed", None):
+            check(_capi.lib().mimi_hip_surface_set_stream(self._handle(), C.c_void_p(s) if s else None))
+            self._followed = s
+
+    def Synchronize(self):
+        check(_capi.lib().mimi_hip_surface_synchronize(self._handle()))
+
+    def Points(self, u, x, normal, weight):
+        self._follow_torch(u, x, normal, weight)
+        check(_capi.lib().mimi_hip_surface_points(self._handle(), fptr(u), fptr(x), fptr(normal), fptr(weight)))
+
+    def AddLoad(self, u, t, f):
+        self._follow_torch(u, t, f)
+        check(_capi.lib().mimi_hip_surface_add_load(self._handle(), fptr(u), fptr(t), fptr(f)))
+
+    def _on_device(self, a):
+        import torch
+        if not hasattr(a, "data_ptr"):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))
+        return a.to(device=torch.device("cuda", self.device_), dtype=torch.float64).contiguous()
+
+    def _unwrapped(self, u):
+        """u in the solver's numbering -> the device vector of the patch's nodes the kernels read (None stays None)"""
+        if u is None:
+            return None
+        import torch
+        u = self._on_device(u).reshape(-1)
+        n = self.fold_.n_f_ if self.fold_ is not None else self.patch_.n_vdofs
+        if u.numel() != n:
+            raise ValueError(f"displacement of {u.numel()} entries, the solver has {n}")
+        if self.fold_ is None:
+            return u
+        return self.fold_.Expand(u, torch.empty(self.fold_.n_u_, dtype=torch.float64, device=u.device))
+
+    def points(self, u=None):
+        """device tensors (x [n_points, dim], unit outward normal [n_points, dim], area weight w_q |m_q| [n_points]) of
+        the configuration X + u (u = None: the reference configuration)"""
+        import torch
+        uu = self._unwrapped(u)
+        dev = torch.device("cuda", self.device_)
+        x = torch.empty((self.n_points_, self.patch_.dim), dtype=torch.float64, device=dev)
+        n = torch.empty_like(x)
+        w = torch.empty(self.n_points_, dtype=torch.float64, device=dev)
+        self.Points(uu, x, n, w)
+        return x, n, w
+
+    def set_traction(self, t, u=None):
+        """load_ = the consistent nodal forces f(a,i) = sum_q w_q |m_q(X+u)| N_a t(q,i) of t [n_points, dim] (or flat),
+        a traction per unit area of X + u: Cauchy traction for the current or advanced displacement, nominal traction for
+        u = None.  t = None removes the load.  The load is dead within a solve and has no tangent: the coupling iteration
+        carries its dependence on the geometry (a follower load with an exact tangent is FollowerPressure's)."""
+        if t is None:
+            self.load_ = None
+            return
+        import torch
+        t = self._on_device(t)
+        shape = (self.n_points_, self.patch_.dim)
+        if tuple(t.shape) not in (shape, (shape[0] * shape[1],)):
+            raise ValueError(f"traction of shape {tuple(t.shape)}: expected {shape} (points by components) or that many "
+                             "values flat")
+        uu = self._unwrapped(u)
+        f = torch.zeros(self.patch_.n_vdofs, dtype=torch.float64, device=t.device)
+        self.AddLoad(uu, t, f)
+        if self.fold_ is not None:
+            f_f = torch.zeros(self.fold_.n_f_, dtype=torch.float64, device=t.device)
+            self.fold_.Add(f, f_f)
+            f = f_f
+        self.load_ = f
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                _capi.lib().mimi_hip_surface_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
 def periodic_node_map(n_ctrl, axes):
     """Node map of a lexicographically numbered patch (n_ctrl nodes per direction, direction 0 fastest) made periodic along
     `axes`: the last node plane along a periodic axis is the first one.  Folded nodes are numbered lexicographically on the

@@ -28,8 +28,8 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import nurbs_mesh, splines
-from .integrators import (CSRPattern, FollowerPressure, MortarContact, NonlinearSolid as NonlinearSolidIntegrator,
-                          PeriodicFold, periodic_node_map)
+from .integrators import (CouplingSurface, CSRPattern, FollowerPressure, MortarContact,
+                          NonlinearSolid as NonlinearSolidIntegrator, PeriodicFold, periodic_node_map)
 from .linear import LinearSolver
 from .splines import BSplinePatch
 
@@ -367,6 +367,14 @@ class NonlinearSolid(Solid):
         rowptr, col = self.pattern_.rowptr, self.pattern_.col
         self.x = np.zeros(n)        # displacement (py_nonlinear_solid.cpp:119)
         self.x_dot = np.zeros(n)
+        # the fixed-point entries' state: a step predicted and not yet advanced, the arrays fixed_point_advance2 fills
+        self._fp_open = False
+        self._fp_x_, self._fp_v_ = np.zeros((n // dim, dim)), np.zeros((n // dim, dim))
+        self.bc_ = bc
+        self.surfaces_ = {}
+        self._rhs_view_ = None
+        # the reference makes the "rhs" linear form only for a body force or a traction (py_nonlinear_solid.cpp:221-283)
+        self.has_rhs_ = bool(bc.initial.body_force_) or bool(bc.initial.traction_)
         if self.runtime_communication is None:                       # PySolid::RuntimeCommunication(): created on demand
             self.runtime_communication = RuntimeCommunication()
         rc = self.runtime_communication
@@ -498,6 +506,7 @@ class NonlinearSolid(Solid):
         dev = torch.device("cuda", self.device)
         f = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
         self.d_mass_, self.d_rhs_ = f(self.mass_), f(self.rhs_)
+        self._rhs = self.d_rhs_           # what the residual subtracts (_update_rhs)
         self.d_visc_ = f(self.visc_) if self.visc_ is not None else None
         self.d_jac_ = torch.zeros_like(self.d_mass_)
         self.d_dirichlet_ = torch.from_numpy(np.asarray(self.dirichlet_, dtype=np.int64)).to(dev)
@@ -557,7 +566,7 @@ class NonlinearSolid(Solid):
         y = self._torch.empty_like(a)
         self._linear_part(a, y)
         self._add_mult(xt, y)
-        y -= self.d_rhs_
+        y -= self._rhs
         self.linear_.Eliminate(y, None)
         return y
 
@@ -590,7 +599,7 @@ class NonlinearSolid(Solid):
         self.linear_.Eliminate(y, self.d_jac_)        # forms/nonlinear.hpp:76-80,112-115
         if self.d_visc_ is not None:
             self.d_jac_.add_(self.d_visc_, alpha=self._fac1)     # jacobian_->Add(fac1_, viscosity_->SpMat())
-        y -= self.d_rhs_
+        y -= self._rhs
         self.linear_.Eliminate(y, None)
         return y, self.d_jac_
 
@@ -651,8 +660,29 @@ class NonlinearSolid(Solid):
         self.newton_history.append(dict(converged=converged, iterations=it, norm=norm, norm0=norm0))
         return x
 
-    # -- GeneralizedAlpha2::StepTime2 (solvers/ode.cpp:16-79) -------------------------------------
-    def step_time2(self):
+    # -- GeneralizedAlpha2::StepTime2 / FixedPointSolve2 / FixedPointAdvance2 / AdvanceTime2 (solvers/ode.cpp:16-187) ----
+    # A step is: predict (once per step), the Newton solve of aa, commit.  step_time2 runs the three in a row; the
+    # fixed-point entries run them apart, so `fixed_point_solve2(); advance_time2()` performs the same operations in the same
+    # order as `step_time2()` and gives the same bits.
+    def _update_rhs(self):
+        """the right-hand side of the next solve, pushed before every solve: the host view linear_form_view2 handed out (if
+        one was requested) into d_rhs_, plus the loads of the coupling surfaces with the Dirichlet rows zeroed -- one
+        vector, so still one subtraction per residual evaluation.  A solid with neither subtracts d_rhs_ as it is."""
+        torch = self._torch
+        if self._rhs_view_ is not None:
+            self.d_rhs_.copy_(torch.from_numpy(self._rhs_view_))
+        loads = [s.load_ for _, s in sorted(self.surfaces_.items()) if s.load_ is not None]
+        if not loads:
+            self._rhs = self.d_rhs_
+            return
+        rhs = self.d_rhs_.clone()
+        for f in loads:
+            rhs += f
+        self.linear_.Eliminate(rhs, None)
+        self._rhs = rhs
+
+    def _predict(self):
+        """StepTime2 up to the solve (ode.cpp:38-58; FixedPointSolve2's predictor, :87-103)"""
         torch = self._torch
         dt = self.time_step_size
         f0, f1, f2, f3, f4, f5 = self._fac
@@ -661,12 +691,13 @@ class NonlinearSolid(Solid):
         self.d_v_.copy_(torch.from_numpy(self.x_dot))
         x, v = self.d_x_, self.d_v_
         self._fac0, self._fac1 = f3 * dt * dt, f4 * dt
+        self._update_rhs()
         if self._nstate == 0:
             z = torch.zeros_like(x)                    # operators/nonlinear_solid.cpp:124-156
             self._add_mult(x, z)
             if self.d_visc_ is not None:
                 self.linear_.AddMult(self.d_visc_, v, z)
-            z = self.d_rhs_ - z
+            z = self._rhs - z
             if self.use_iterative_solver_:
                 # mass_inv_: mfem::CGSolver + DSmoother (operators/nonlinear_solid.cpp:39-50,155)
                 self._a = self.linear_.MultCG(self.d_mass_, z, torch.zeros_like(z))
@@ -677,27 +708,38 @@ class NonlinearSolid(Solid):
         a = self._a
         self._xa = x + (v + f0 * dt * a) * (f1 * dt)
         self._va = v + f2 * dt * a
-        cv = len(self.constant_velocity_dofs_) > 0
-        if cv:
+        self._saved_x = None
+        if len(self.constant_velocity_dofs_):
             # TimeDependentDirichletBoundaryCondition::Apply (boundary_conditions.cpp:209-259, ode.cpp:56-58)
             idx, val = self.d_cv_dofs_, self.d_cv_values_
             self._aa[idx] = 0.0
             self._va[idx] = val
             self._xa[idx] = x[idx] + val * dt
-            saved_x = self._xa[idx].clone()
-        self._aa = self._newton_solve(self._aa)
+            self._saved_x = self._xa[idx].clone()
+
+    def _extrapolate(self, x, v):
+        """x, v <- the end-of-step vectors of the current aa, in place (ode.cpp:61-68, and the Restore of x and v, :73-75)"""
         aa = self._aa
+        f1 = self._fac[1]
         xa = self._xa + self._fac0 * aa
         va = self._va + self._fac1 * aa
         prev = 1.0 - 1.0 / f1
         x.mul_(prev).add_(xa, alpha=1.0 / f1)
         v.mul_(prev).add_(va, alpha=1.0 / f1)
-        self._a = a * prev + aa / f5
-        if cv:
-            # ... Restore (boundary_conditions.cpp:261-291, ode.cpp:73-75)
-            x[idx] = saved_x
-            v[idx] = val
-            self._a[idx] = 0.0
+        if self._saved_x is not None:
+            # ... Restore (boundary_conditions.cpp:261-291)
+            x[self.d_cv_dofs_] = self._saved_x
+            v[self.d_cv_dofs_] = self.d_cv_values_
+
+    def _commit(self):
+        """AdvanceTime2 (ode.cpp:148-187) and PySolid's save cadence (py_solid.cpp:494-510)"""
+        dt = self.time_step_size
+        f1, f5 = self._fac[1], self._fac[5]
+        x, v = self.d_x_, self.d_v_
+        self._extrapolate(x, v)
+        self._a = self._a * (1.0 - 1.0 / f1) + self._aa / f5
+        if self._saved_x is not None:
+            self._a[self.d_cv_dofs_] = 0.0
         # PostTimeAdvance (operators/nonlinear_solid.cpp:285-292)
         xp = self._expand(x) if self.fold_ is not None else x
         self._push(self.domain_)
@@ -719,6 +761,130 @@ class NonlinearSolid(Solid):
             if rc.should_save("v"):
                 rc.save_dynamic_vector("v_", self.in_reference_numbering(v))
             rc.next_time_step(dt)
+
+    def step_time2(self):
+        """PySolid::StepTime2 (py_solid.cpp:425-441).
+
+        Difference from the reference: refused (RuntimeError) while a fixed-point step is open, i.e. after a
+        fixed_point_solve2() that no advance_time2() has committed yet; the reference would silently commit that step's
+        stale alpha levels."""
+        if self._fp_open:
+            raise RuntimeError("step_time2() while a fixed-point step is open: finish it with advance_time2() first")
+        self._predict()
+        self._aa = self._newton_solve(self._aa)
+        self._commit()
+
+    # -- partitioned coupling: PySolid::FixedPointSolve2 / FixedPointAdvance2 / AdvanceTime2 (py_solid.cpp:443-511) -----
+    def fixed_point_solve2(self):
+        """Solve the current step with the current loads and commit nothing (GeneralizedAlpha2::FixedPointSolve2,
+        ode.cpp:81-111): the first call of a step takes x / x_dot from the host arrays, forms the initial acceleration on the
+        first step, predicts the alpha levels and applies constant velocity; every call then runs the Newton solve of aa.
+        x, x_dot, the acceleration, the material state and the contact history stay untouched, so calling it again (after
+        set_traction / a write to linear_form_view2) re-solves the same step.  `fixed_point_solve2(); advance_time2()` gives
+        the same bits as `step_time2()`.
+
+        Differences from the reference, both RuntimeError where the reference silently commits stale alpha levels:
+        advance_time2() without a fixed_point_solve2() in the step, and step_time2() while a fixed-point step is open."""
+        if not self._fp_open:
+            self._predict()
+            self._fp_open = True
+        else:
+            self._update_rhs()
+        self._aa = self._newton_solve(self._aa)
+
+    def fixed_point_advance2(self):
+        """(x, v), each (n // dim, dim): the end-of-step vectors the current aa gives, after the constant-velocity Restore
+        (GeneralizedAlpha2::FixedPointAdvance2, ode.cpp:113-146).  The same two host arrays on every call, updated in place;
+        no solver state changes."""
+        if not self._fp_open:
+            raise RuntimeError("FixedPointAdvance2() should be called after FixedPointSolve2()")
+        x, v = self.d_x_.clone(), self.d_v_.clone()
+        self._extrapolate(x, v)
+        self._fp_x_.reshape(-1)[:] = x.cpu().numpy()
+        self._fp_v_.reshape(-1)[:] = v.cpu().numpy()
+        return self.fixed_point_advanced_vector_views()
+
+    def fixed_point_advanced_vector_views(self):
+        """the arrays of the latest fixed_point_advance2, not recomputed (py_solid.cpp:482-492)"""
+        return self._fp_x_, self._fp_v_
+
+    def advance_time2(self):
+        """Commit the step of the latest fixed_point_solve2 (GeneralizedAlpha2::AdvanceTime2, ode.cpp:148-187): x / v / a,
+        the constant-velocity Restore, DomainPostTimeAdvance and the boundary integrators' post-advance, current_time, the
+        host arrays, the RuntimeCommunication save cadence and next_time_step; the predictor is re-armed.
+
+        Difference from the reference: refused (RuntimeError) without a fixed_point_solve2() in the step; the reference
+        would silently commit stale alpha levels."""
+        if not self._fp_open:
+            raise RuntimeError("advance_time2() without a fixed_point_solve2() in this step: there is no solved step to "
+                               "commit")
+        self._commit()
+        self._fp_open = False
+
+    # -- the accessors a coupling reads (py_solid.cpp:363-407, py_solid.hpp:213-218) ------------------------------------
+    def linear_form_view2(self, lf_name):
+        """PySolid::LinearFormView2: the writable host view of the right-hand side "rhs" (body force plus traction,
+        Dirichlet rows zero).  What the caller writes there is used from the next step_time2 / fixed_point_solve2 on (pushed
+        to the device before every solve).  As in the reference it exists only when a body force or traction marker made
+        it (py_nonlinear_solid.cpp:221-283); otherwise, and for any other name, KeyError."""
+        if lf_name != "rhs" or not getattr(self, "has_rhs_", False):
+            raise KeyError(f"Requested linear form -{lf_name}- does not exist.")
+        self._rhs_view_ = self.rhs_
+        return self.rhs_
+
+    def boundary_dof_ids(self, fe_space, bid, dim):
+        """PySolid::BoundaryDofIds: the dofs of component `dim` on boundary `bid` (attribute bid + 1, as the markers), in
+        this facade's numbering (folded on periodic solids), sorted"""
+        if fe_space != "displacement":
+            raise KeyError(fe_space)
+        axis, side = self._faces[int(bid) + 1]
+        return np.sort(self._folded_dofs(self.patch_.boundary_nodes(axis, side), int(dim))).astype(np.int32)
+
+    def zero_dof_ids(self, fe_space):
+        """PySolid::ZeroDofIds: the sorted unique Dirichlet dofs (constant-velocity dofs included: that marker implies
+        dirichlet)"""
+        if fe_space != "displacement":
+            raise KeyError(fe_space)
+        return np.asarray(self.dirichlet_, dtype=np.int32).copy()
+
+    def newton_final_norms(self, name):
+        """PySolid::NewtonFinalNorms: (final / initial, final) residual norm of the latest Newton solve, of step_time2 or
+        fixed_point_solve2"""
+        if name != "nonlinear_solid":
+            raise KeyError(name)
+        if not self.newton_history:
+            return 0.0, 0.0
+        h = self.newton_history[-1]
+        return (h["norm"] / h["norm0"] if h["norm0"] else 0.0), h["norm"]
+
+    def coupling_surface(self, bid, quadrature_order=-1):
+        """integrators.CouplingSurface of boundary `bid` (attribute bid + 1, as the markers), in this facade's numbering:
+        points(u) hands a fluid partner the wet surface, set_traction(t, u) takes its traction back as nodal forces that are
+        subtracted with the right-hand side from the next solve on (step_time2 and fixed_point_solve2).  The load is dead
+        within a solve and has no tangent: the coupling iteration carries its dependence on the geometry (a follower load
+        with an exact tangent is bc.initial.pressure's).  One object per bid (a second call with another quadrature_order is
+        refused); call after setup()."""
+        if getattr(self, "surfaces_", None) is None:
+            raise RuntimeError("coupling_surface() needs setup() first")
+        bid = int(bid)
+        if bid in self.surfaces_:
+            s = self.surfaces_[bid]
+            if s.quadrature_order_ != quadrature_order:
+                raise RuntimeError(f"coupling surface of boundary {bid} exists with quadrature_order "
+                                   f"{s.quadrature_order_}, not {quadrature_order}")
+            return s
+        if bid + 1 not in self._faces:
+            raise RuntimeError(f"coupling surface: the mesh has no boundary {bid} (attribute {bid + 1}; attributes: "
+                               f"{sorted(self._faces)})")
+        joined = {b for pair in self.bc_.initial.periodic_boundaries_.items() for b in pair}
+        if bid + 1 in joined:
+            raise RuntimeError(f"coupling surface on boundary {bid} (attribute {bid + 1}), which the periodic pair makes "
+                               "interior")
+        axis, side = self._faces[bid + 1]
+        s = CouplingSurface(self.patch_, axis, side, device=self.device, quadrature_order=quadrature_order,
+                            fold=self.fold_).Prepare()
+        self.surfaces_[bid] = s
+        return s
 
     def in_reference_numbering(self, vec):
         """byVDIM vector of this facade (lexicographic nodes) -> the reference's dof order (MFEM's NURBS numbering).

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -136,6 +137,32 @@ struct MaterialDev {
   double sigma_y_ref;                     // HardeningBase::SigmaY()
 };
 
-MaterialDev make_material_dev(const mimi_hip_material& m);
+// What the kernels read next to the C struct, with the reference's checks; needs no HIP runtime, so the host build of the
+// device routines (tests/host_materials.hip) calls the same function as the library.
+inline MaterialDev make_material_dev(const mimi_hip_material& m) {
+  MaterialDev d{};
+  d.m = m;
+  d.const_temperature_contribution = 1.0;
+  if (m.kind == MIMI_HIP_MAT_J2 || m.kind == MIMI_HIP_MAT_J2SIMO || m.kind == MIMI_HIP_MAT_J2LOG) {
+    if (m.hardening < MIMI_HIP_HARD_POWERLAW || m.hardening > MIMI_HIP_HARD_JC_CONST_TEMP)
+      fail("hardening missing for J2 / J2Simo / J2Log");  // materials.cpp:139-148,177-183,217-223
+    d.sigma_y_ref = (m.hardening == MIMI_HIP_HARD_POWERLAW || m.hardening == MIMI_HIP_HARD_VOCE) ? m.sigma_y : m.A;
+    if (m.hardening >= MIMI_HIP_HARD_JC_TEMP_RATE && m.reference_temperature > m.melting_temperature)
+      fail("reference temperature, %g ,can't be bigger than melting temperature, %g .",
+           m.reference_temperature, m.melting_temperature);  // material_hardening.hpp:228-238
+    if (m.hardening == MIMI_HIP_HARD_JC_CONST_TEMP) {
+      d.const_temperature_contribution =
+          1.0 - std::pow((m.initial_temperature - m.reference_temperature)
+                             / (m.melting_temperature - m.reference_temperature), m.m);
+      if (d.const_temperature_contribution <= 0.0)
+        fail("Invalid temperature contribution %g", d.const_temperature_contribution);
+    }
+  } else if (m.kind == MIMI_HIP_MAT_J2LINEAR) {
+    d.sigma_y_ref = m.sigma_y;
+  } else if (m.kind != MIMI_HIP_MAT_NEOHOOKEAN && m.kind != MIMI_HIP_MAT_STVK) {
+    fail("unknown material kind %d", m.kind);
+  }
+  return d;
+}
 
 }  // namespace mimi_hip

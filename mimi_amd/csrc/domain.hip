@@ -25,32 +25,6 @@ namespace mimi_hip {
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& s) { g_last_error = s; }
 
-MaterialDev make_material_dev(const mimi_hip_material& m) {
-  MaterialDev d{};
-  d.m = m;
-  d.const_temperature_contribution = 1.0;
-  if (m.kind == MIMI_HIP_MAT_J2 || m.kind == MIMI_HIP_MAT_J2SIMO || m.kind == MIMI_HIP_MAT_J2LOG) {
-    if (m.hardening < MIMI_HIP_HARD_POWERLAW || m.hardening > MIMI_HIP_HARD_JC_CONST_TEMP)
-      fail("hardening missing for J2 / J2Simo / J2Log");  // materials.cpp:139-148,177-183,217-223
-    d.sigma_y_ref = (m.hardening == MIMI_HIP_HARD_POWERLAW || m.hardening == MIMI_HIP_HARD_VOCE) ? m.sigma_y : m.A;
-    if (m.hardening >= MIMI_HIP_HARD_JC_TEMP_RATE && m.reference_temperature > m.melting_temperature)
-      fail("reference temperature, %g ,can't be bigger than melting temperature, %g .",
-           m.reference_temperature, m.melting_temperature);  // material_hardening.hpp:228-238
-    if (m.hardening == MIMI_HIP_HARD_JC_CONST_TEMP) {
-      d.const_temperature_contribution =
-          1.0 - std::pow((m.initial_temperature - m.reference_temperature)
-                             / (m.melting_temperature - m.reference_temperature), m.m);
-      if (d.const_temperature_contribution <= 0.0)
-        fail("Invalid temperature contribution %g", d.const_temperature_contribution);
-    }
-  } else if (m.kind == MIMI_HIP_MAT_J2LINEAR) {
-    d.sigma_y_ref = m.sigma_y;
-  } else if (m.kind != MIMI_HIP_MAT_NEOHOOKEAN && m.kind != MIMI_HIP_MAT_STVK) {
-    fail("unknown material kind %d", m.kind);
-  }
-  return d;
-}
-
 template<typename F>
 static int guarded(F&& f) {
   try {

@@ -6,13 +6,25 @@
 
 using namespace mimi_hip;
 
+// the library's own make_material_dev (csrc/common.hpp): solver tolerance reference, constant-temperature factor, checks.
+// 0 and the two derived values, or 1 and the message the C ABI would hand to mimi_hip_last_error()
+extern "C" int host_make_material(const mimi_hip_material* m, double* sigma_y_ref, double* const_temperature_contribution,
+                                  char* message, int n_message) {
+  try {
+    const MaterialDev md = make_material_dev(*m);
+    *sigma_y_ref = md.sigma_y_ref;
+    *const_temperature_contribution = md.const_temperature_contribution;
+    return 0;
+  } catch (const std::exception& e) {
+    snprintf(message, n_message, "%s", e.what());
+    return 1;
+  }
+}
+
 // state arrays address ONE point (SoA with n_pts = 1 = plain column-major matrices)
-extern "C" int host_point(const mimi_hip_material* m, double sigma_y_ref, int dim, double dt, const double* F, double* m1,
+extern "C" int host_point(const mimi_hip_material* m, int dim, double dt, const double* F, double* m1,
                           double* m2, double eqps, double T, double* P, double* A) {
-  MaterialDev md{};
-  md.m = *m;
-  md.const_temperature_contribution = 1.0;
-  md.sigma_y_ref = sigma_y_ref;
+  const MaterialDev md = make_material_dev(*m);
   StateView sv{&eqps, &T, m1, 1, m2};
   if (m->kind == MIMI_HIP_MAT_NEOHOOKEAN || m->kind == MIMI_HIP_MAT_J2) {
     int status;
@@ -34,12 +46,9 @@ extern "C" int host_point(const mimi_hip_material* m, double sigma_y_ref, int di
 }
 
 // DomainPostTimeAdvance at one point; state updated in place
-extern "C" int host_accumulate(const mimi_hip_material* m, double sigma_y_ref, int dim, double dt, const double* F,
+extern "C" int host_accumulate(const mimi_hip_material* m, int dim, double dt, const double* F,
                                double* m1, double* m2, double* eqps, double* T) {
-  MaterialDev md{};
-  md.m = *m;
-  md.const_temperature_contribution = 1.0;
-  md.sigma_y_ref = sigma_y_ref;
+  const MaterialDev md = make_material_dev(*m);
   StateView sv{eqps, T, m1, 1, m2};
   if (m->kind == MIMI_HIP_MAT_NEOHOOKEAN || m->kind == MIMI_HIP_MAT_J2)
     return dim == 2 ? accumulate_state<2>(md, dt, sv, 0, F) : accumulate_state<3>(md, dt, sv, 0, F);

@@ -90,6 +90,16 @@ def test_material_surface_matches_reference_names():
     h = mimi_amd.JohnsonCookTemperatureAndRateDependentHardening()
     for attr in ("A", "B", "n", "C", "eps0_dot", "reference_temperature", "m"):
         assert hasattr(h, attr)
+    # every hardening class of py_hardening.cpp:25-82 with its attributes (tests/_cases.py HARDENING_LAWS)
+    from _cases import HARDENING_LAWS
+    assert len({cls for _, cls, _ in HARDENING_LAWS.values()}) == 6
+    for oracle, cls, attrs in HARDENING_LAWS.values():
+        h = getattr(mimi_amd, cls)()
+        assert h.name() == cls
+        for attr in attrs:
+            assert hasattr(h, attr), (cls, attr)
+        m.hardening = h
+        assert m._c_struct().hardening == h._kind
     m.set_young_poisson(2100, 0.3)
     assert abs(m.lambda_ - 2100 * 0.3 / (1.3 * 0.4)) < 1e-9 and abs(m.mu - 2100 / 2.6) < 1e-9
     m2 = mimi_amd.CompressibleOgdenNeoHookean()

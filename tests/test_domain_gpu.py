@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from _cases import JC_TEST, oracle_material, synthetic_u
+from _cases import JC_TEST, oracle_material, product_material, synthetic_u
 
 pytestmark = pytest.mark.gpu
 
@@ -16,37 +16,6 @@ pytestmark = pytest.mark.gpu
 CASES = [((2, 2), 3, [5.0, 1.0]), ((3, 4), 2, None), ((3, 2, 2), 2, None), ((2, 2, 1), 3, None),
          ((4, 3, 2), 1, None), ((8, 8, 2), 2, None), ((5, 6, 4), 2, [2.5, 3.0, 1.0]), ((5, 5, 5), 2, None),
          ((4, 5, 6), 2, None)]
-
-
-def product_material(name):
-    import mimi_amd
-    if name == "neohook":
-        m = mimi_amd.CompressibleOgdenNeoHookean()
-        m.density = 1.0
-        m.set_young_poisson(2100, 0.3)
-        return m
-    if name == "stvk":
-        m = mimi_amd.StVenantKirchhoff()
-        m.density = 1.0
-        m.set_young_poisson(2100, 0.3)
-        return m
-    if name == "j2linear":
-        m = mimi_amd.J2Linear()
-        m.density = 1.0
-        m.set_young_poisson(2100, 0.3)
-        m.isotropic_hardening, m.kinematic_hardening, m.sigma_y = 40.0, 25.0, 70.0
-        return m
-    m = {"j2": mimi_amd.J2, "j2simo": mimi_amd.J2Simo, "j2log": mimi_amd.J2Log}[name]()
-    m.density = 1.0
-    m.set_young_poisson(2100, 0.3)
-    m.heat_fraction, m.specific_heat = 0.9, 450
-    m.initial_temperature, m.melting_temperature = 20, 1500
-    h = mimi_amd.JohnsonCookTemperatureAndRateDependentHardening()
-    for k, v in JC_TEST.items():
-        if k != "kind":
-            setattr(h, k, v)
-    m.hardening = h
-    return m
 
 
 def make_pair(n_el, p, lengths, matname, creator):

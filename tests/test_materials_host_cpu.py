@@ -10,8 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from _cases import oracle_material
-from test_domain_gpu import product_material
+from _cases import oracle_material, product_material
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -63,7 +62,6 @@ def test_device_materials_on_host_vs_oracle(host_lib, name, dim):
     from oracle import ref_path as rp
     mo = oracle_material(name)
     mp = product_material(name)._c_struct()
-    sigma_y_ref = 70.0
     rng = np.random.default_rng(7 + dim)
     tol_A = 1e-11 if name in ("neohook", "j2") else 1e-10
     n_plastic = 0
@@ -75,7 +73,7 @@ def test_device_materials_on_host_vs_oracle(host_lib, name, dim):
         Fc = np.ascontiguousarray(F.T).ravel()
         P, A = np.zeros(dim * dim), np.zeros(dim ** 4)
         a1, a2 = np.ascontiguousarray(m1.T).ravel().copy(), np.ascontiguousarray(m2.T).ravel().copy()
-        st = host_lib.host_point(C.byref(mp), C.c_double(sigma_y_ref), dim, C.c_double(0.5), ptr(Fc), ptr(a1), ptr(a2),
+        st = host_lib.host_point(C.byref(mp), dim, C.c_double(0.5), ptr(Fc), ptr(a1), ptr(a2),
                                  C.c_double(eqps), C.c_double(20.0), ptr(P), ptr(A))
         assert st == 0
         Pg, Ag = P.reshape(dim, dim).T, A.reshape(dim, dim, dim, dim)
@@ -85,7 +83,7 @@ def test_device_materials_on_host_vs_oracle(host_lib, name, dim):
         if name in ("neohook", "stvk"):
             continue
         e, T = C.c_double(eqps), C.c_double(20.0)
-        st = host_lib.host_accumulate(C.byref(mp), C.c_double(sigma_y_ref), dim, C.c_double(0.5), ptr(Fc), ptr(a1), ptr(a2),
+        st = host_lib.host_accumulate(C.byref(mp), dim, C.c_double(0.5), ptr(Fc), ptr(a1), ptr(a2),
                                       C.byref(e), C.byref(T))
         assert st == 0
         n_plastic += e.value > eqps

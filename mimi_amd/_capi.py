@@ -275,3 +275,72 @@ def torch_stream_of(*buffers):
 
 
 STREAM_NULL = 2 ** 64 - 1        # MIMI_HIP_STREAM_NULL of include/mimi_hip.h
+
+
+class Handle:
+    """What the front-ends of the library's handles share: `_h` (None until the handle exists), the stream rules and the
+    release.  `_prefix` names the C entries: mimi_hip_<_prefix>_set_stream / _synchronize / _destroy."""
+    _prefix = None
+    _h = None
+
+    def _fn(self, name):
+        return getattr(lib(), f"mimi_hip_{self._prefix}_{name}")
+
+    def _handle(self):
+        if self._h is None:
+            raise RuntimeError("Prepare() has not been called")
+        return self._h
+
+    def SetStream(self, stream):
+        """launch on `stream` (a hipStream_t as an int); 0 / None: back to following torch's current stream for CUDA
+        tensors and the handle's own stream for host buffers"""
+        self._user_stream = bool(stream)
+        self._user_stream_value = int(stream) if stream else 0
+        check(self._fn("set_stream")(self._handle(), C.c_void_p(stream) if stream else None))
+
+    def _follow_torch(self, *buffers):
+        # ordering with the caller's torch work (zero fills of r / A, copies of u): see torch_stream_of.  A handle that
+        # was never given a stream launches on torch's current stream when it gets CUDA tensors
+        if getattr(self, "_user_stream", False):
+            return
+        s = torch_stream_of(*buffers)
+        if s is not None or getattr(self, "_followed", None):
+            check(self._fn("set_stream")(self._handle(), C.c_void_p(s) if s else None))
+            self._followed = s
+
+    def Synchronize(self):
+        check(self._fn("synchronize")(self._handle()))
+
+    def __del__(self):
+        try:
+            if self._h is not None:
+                self._fn("destroy")(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _sized_query(self, name, dtype):
+        """the C entries that list values (out == NULL: count only): ask for the size, allocate, ask again"""
+        n = C.c_int64(0)
+        check(self._fn(name)(self._handle(), None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=dtype)
+        check(self._fn(name)(self._handle(), ptr(out), out.size, C.byref(n)))
+        return out
+
+
+def fill_face_tables(t, patch, axis, side, quadrature_order, element_box=None, empty="no boundary faces in this element box"):
+    """the fields ContactTables and PressureTables share, from splines.face_tables; returns the arrays the caller keeps
+    alive while the C side reads them"""
+    from . import splines
+    # (a rational patch raises here: face_tables builds B-spline tables only)
+    dofs, N, dN, weight = splines.face_tables(patch, axis, side, quadrature_order, element_box)
+    if len(dofs) == 0:
+        raise RuntimeError(empty)
+    x_ref = np.ascontiguousarray(patch.control_points, dtype=np.float64)
+    t.dim = patch.dim
+    t.n_faces, t.n_dof = dofs.shape
+    t.n_quad = weight.shape[1]
+    t.n_nodes = patch.n_nodes
+    t.dofs, t.N, t.dN_dxi, t.weight = dofs.ctypes.data, N.ctypes.data, dN.ctypes.data, weight.ctypes.data
+    t.x_ref = x_ref.ctypes.data
+    return [dofs, N, dN, weight, x_ref]

@@ -1,9 +1,10 @@
-// Shared host-side plumbing of libmimi_hip: error reporting, device buffers, pointer
-// classification.  No kernels here.
+// Shared host-side plumbing of libmimi_hip: error reporting and the guard of the C entries, the stream-owning base of
+// the handles, device buffers, pointer classification.  No kernels here.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
@@ -60,6 +61,81 @@ inline void ensure_dynamic_lds(const void* kernel, int bytes) {
 
 void set_last_error(const std::string& s);
 
+// Every entry of the C ABI runs its body through this: an exception becomes the text of mimi_hip_last_error() and a
+// non-zero return.
+template<typename F>
+int guarded(F&& f) {
+  try {
+    f();
+    return 0;
+  } catch (const std::exception& e) {
+    set_last_error(e.what());
+    return 1;
+  } catch (...) {
+    set_last_error("unknown error");
+    return 1;
+  }
+}
+
+// the stream argument of the C ABI: MIMI_HIP_STREAM_NULL = the device's null stream, NULL = `fallback`
+inline hipStream_t pick_stream(void* stream, hipStream_t fallback) {
+  return stream == MIMI_HIP_STREAM_NULL ? nullptr : (stream ? reinterpret_cast<hipStream_t>(stream) : fallback);
+}
+
+// What every handle of the library starts with: its device, a non-blocking stream of its own and the stream it launches
+// on.  The handle structs derive from it; handle_set_stream / _synchronize / _destroy below are their C entries.
+struct StreamHandle {
+  int device = 0;
+  hipStream_t own_stream = nullptr, stream = nullptr;
+  StreamHandle() = default;
+  StreamHandle(const StreamHandle&) = delete;
+  StreamHandle& operator=(const StreamHandle&) = delete;
+  ~StreamHandle() {
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
+  void open(int dev) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
+      fail("libmimi_hip: no HIP device visible -- this library has no CPU fallback");
+    if (dev < 0 || dev >= count) fail("device %d out of range (%d visible)", dev, count);
+    device = dev;
+    MH_HIP(hipSetDevice(dev));
+    MH_HIP(hipStreamCreateWithFlags(&own_stream, hipStreamNonBlocking));
+    stream = own_stream;
+  }
+  void set_stream(void* s) { stream = pick_stream(s, own_stream); }
+  void synchronize() {
+    MH_HIP(hipSetDevice(device));
+    MH_HIP(hipStreamSynchronize(stream));
+  }
+};
+
+template<typename H>
+int handle_set_stream(H* h, void* stream) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    h->set_stream(stream);
+  });
+}
+
+template<typename H>
+int handle_synchronize(H* h) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    h->synchronize();
+  });
+}
+
+template<typename H>
+int handle_destroy(H* h) {
+  return guarded([&] {
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    (void)hipStreamSynchronize(h->stream);
+    delete h;
+  });
+}
+
 // true when p points to device memory of any kind
 inline bool is_device_pointer(const void* p) {
   if (!p) return false;
@@ -70,6 +146,16 @@ inline bool is_device_pointer(const void* p) {
     return false;
   }
   return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
+}
+
+// a host copy of n elements of a host or device source
+template<typename T>
+std::vector<T> to_host(const T* p, size_t n) {
+  std::vector<T> out(n);
+  if (n == 0) return out;
+  if (is_device_pointer(p)) MH_HIP(hipMemcpy(out.data(), p, n * sizeof(T), hipMemcpyDeviceToHost));
+  else std::copy(p, p + n, out.begin());
+  return out;
 }
 
 template<typename T>

@@ -15,7 +15,8 @@
 // Instead of per-thread copies + a mutex (mortar_contact.cpp:235-260,338-341,400-408) every contribution is stored
 // densely -- per quadrature point the nodal area / gap shares, per face the residual vector and the tangent block --
 // and summed afterwards in a fixed order through the marked nodes' (face, local node) incidences: no atomics, results
-// bitwise reproducible like the domain paths (round 3; rounds 1-2 used fp64 atomics here).
+// bitwise reproducible like the domain paths (round 3; rounds 1-2 used fp64 atomics here).  The face tables, the
+// incidences, the pair positions, the fixed-order sums and the row gather are face_common.hpp's, shared with pressure.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "face_common.hpp"
 #include "materials.hpp"
 #include "spline_body.hpp"
 
@@ -37,15 +39,10 @@ struct ContactArgs {
   const double* dN;          // [n_faces][n_q][dim-1][n_dof]
   const double* weight;      // [n_faces][n_q]
   const double* x_ref;       // [n_nodes][dim]
-  const int64_t* rowptr;
-  const int32_t* pair_pos;   // [n_faces][n_dof][n_dof]
   int body_kind;
   double body[8];
   double penalty;
   const double* u;
-  double* r;
-  double* A;
-  double grad_factor;
   double* area;              // [n_marked]
   double* gap;
   double* pressure;
@@ -61,8 +58,6 @@ struct ContactArgs {
   double* face_scal;         // [n_faces][1 + dim]     pressure integral, force
   unsigned char* face_active;   // IsPressureZero == false
 };
-
-constexpr int kMaxFaceDof = 16;
 
 // analytic stand-in for NearestDistance + ComputeNormal<true> + NormalGap
 // (nearest_distance.hpp:139-193): true gap and |x_rigid - x_query|
@@ -221,35 +216,9 @@ __global__ __launch_bounds__(256) void contact_nodal_kernel(int n_marked, int n_
   }
 }
 
-// out[k] = sum_i in[i * stride + k] (k < n_out), optionally over the rows with flag[i] != 0: ONE workgroup, every thread a
-// fixed subset of the rows, then a fixed-shape tree -- the same bits every run
-__global__ __launch_bounds__(1024) void contact_sum_kernel(int64_t n, int stride, int n_out, const double* __restrict__ in,
-                                                           const unsigned char* __restrict__ flag, double* __restrict__ out) {
-  __shared__ double part[1024];
-  for (int k = 0; k < n_out; ++k) {
-    double s = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 1024)
-      if (!flag || flag[i]) s += in[i * stride + k];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w >= 1; w >>= 1) {
-      if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out[k] = part[0];
-    __syncthreads();
-  }
-}
-
 __global__ void contact_pressure_kernel(int n, const double* area, const double* gap, double penalty, double* pressure) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) pressure[i] = gap[i] / area[i] * penalty;  // mortar_contact.cpp:253-257
-}
-
-MH_DEV double contact_lane_read(double v, int l) {   // the value lane l holds, in every lane (l wave-uniform)
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)u, l), hi = __builtin_amdgcn_readlane((unsigned)(u >> 32), l);
-  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
 }
 
 // element residual at given x_e (used by the FD mode too)
@@ -276,19 +245,19 @@ MH_DEV void face_residual(const ContactArgs& p, int f, const double* x_e, const 
 }
 
 // reference-FD mode of pass 2: one thread per face, the face tangent block by forward differences of the face residual
-// (stored densely: contact_gather_kernel)
+// (stored densely: face_row_gather_kernel)
 template<int DIM>
 __global__ void contact_residual_kernel(ContactArgs p, int with_grad) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= p.n_faces) return;
-  double p_e[kMaxFaceDof];
+  double p_e[kFaceMaxDof];
   bool any = false;
   for (int a = 0; a < p.n_dof; ++a) {
     p_e[a] = p.pressure[p.local[(int64_t)f * p.n_dof + a]];
     any = any || (p_e[a] != 0.0);
   }
   if (!any) return;  // IsPressureZero (integrator_utils.cpp:112-119)
-  double x_e[DIM * kMaxFaceDof], R_e[DIM * kMaxFaceDof];
+  double x_e[DIM * kFaceMaxDof], R_e[DIM * kFaceMaxDof];
   gather_x<DIM>(p, f, x_e);
   face_residual<DIM>(p, f, x_e, p_e, R_e, nullptr, nullptr);
   const int NT = p.n_dof * DIM;
@@ -297,7 +266,7 @@ __global__ void contact_residual_kernel(ContactArgs p, int with_grad) {
   if (!with_grad) return;
   double* Kf = p.face_k + (int64_t)f * NT * NT;     // row (a, i): [j][b]
   // mortar_contact.cpp:263-295: forward FD on the current POSITION, pressure frozen
-  double fwd[DIM * kMaxFaceDof];
+  double fwd[DIM * kFaceMaxDof];
   for (int c = 0; c < NT; ++c) {
     const double orig = x_e[c];
     const double step = (orig != 0.0) ? fabs(orig) * 1.0e-8 : 1.0e-10;
@@ -347,10 +316,10 @@ __global__ __launch_bounds__(256) void contact_residual_wave_kernel(ContactArgs 
 #pragma unroll
     for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = 0.0;
     for (int c = 0; c < n_dof; ++c) {
-      pq = __builtin_fma(N[c], contact_lane_read(pc, c), pq);
+      pq = __builtin_fma(N[c], face_lane_read(pc, c), pq);
 #pragma unroll
       for (int i = 0; i < DIM; ++i) {
-        const double x = contact_lane_read(xc[i], c);
+        const double x = face_lane_read(xc[i], c);
 #pragma unroll
         for (int k = 0; k < DIM - 1; ++k) t[k * DIM + i] = __builtin_fma(x, dN[k * n_dof + c], t[k * DIM + i]);
       }
@@ -375,11 +344,11 @@ __global__ __launch_bounds__(256) void contact_residual_wave_kernel(ContactArgs 
     const int k = lane < NT ? lane : 0, i = k / n_dof, a = k % n_dof;
     double R = 0.0;
     for (int q = 0; q < n_q; ++q) {
-      const double mf = -contact_lane_read(fac, q);
-      double aw = contact_lane_read(nq[0], q) * mf;
+      const double mf = -face_lane_read(fac, q);
+      double aw = face_lane_read(nq[0], q) * mf;
 #pragma unroll
       for (int ii = 1; ii < DIM; ++ii) {
-        const double v = contact_lane_read(nq[ii], q) * mf;
+        const double v = face_lane_read(nq[ii], q) * mf;
         aw = i == ii ? v : aw;
       }
       R += aw * p.N[((int64_t)f * n_q + q) * n_dof + a];
@@ -392,9 +361,9 @@ __global__ __launch_bounds__(256) void contact_residual_wave_kernel(ContactArgs 
 #pragma unroll
     for (int i = 0; i < DIM; ++i) force[i] = 0.0;
     for (int q = 0; q < n_q; ++q) {
-      const double fq = contact_lane_read(fac, q);
+      const double fq = face_lane_read(fac, q);
 #pragma unroll
-      for (int i = 0; i < DIM; ++i) force[i] += fq * contact_lane_read(nq[i], q);
+      for (int i = 0; i < DIM; ++i) force[i] += fq * face_lane_read(nq[i], q);
       pint += fq;
     }
     if (lane == 0) {
@@ -438,10 +407,10 @@ __global__ __launch_bounds__(256) void contact_tangent_kernel(ContactArgs p) {
     const double* dN = p.dN + pt * n_dof * (DIM - 1);
     double pq = 0.0;
     for (int c = 0; c < n_dof; ++c) {
-      pq = __builtin_fma(N[c], contact_lane_read(pc, c), pq);
+      pq = __builtin_fma(N[c], face_lane_read(pc, c), pq);
 #pragma unroll
       for (int i = 0; i < DIM; ++i) {
-        const double x = contact_lane_read(xc[i], c);
+        const double x = face_lane_read(xc[i], c);
 #pragma unroll
         for (int k = 0; k < DIM - 1; ++k) tq[k * DIM + i] = __builtin_fma(x, dN[k * n_dof + c], tq[k * DIM + i]);
       }
@@ -459,11 +428,11 @@ __global__ __launch_bounds__(256) void contact_tangent_kernel(ContactArgs p) {
     for (int k = 0; k < DIM * DIM; ++k) acc[k] = 0.0;
     for (int q = 0; q < n_q; ++q) {
       const int64_t pt = (int64_t)f * n_q + q;
-      const double wpn = contact_lane_read(wq, q) * p.N[pt * n_dof + a];
+      const double wpn = face_lane_read(wq, q) * p.N[pt * n_dof + a];
       const double* dN = p.dN + pt * n_dof * (DIM - 1);
       double t[(DIM - 1) * DIM];
 #pragma unroll
-      for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = contact_lane_read(tq[k], q);
+      for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = face_lane_read(tq[k], q);
 #pragma unroll
       for (int j = 0; j < DIM; ++j) {
         double dm[DIM];
@@ -493,109 +462,20 @@ __global__ __launch_bounds__(256) void contact_tangent_kernel(ContactArgs p) {
   }
 }
 
-// The sums the reference forms under a mutex (mortar_contact.cpp:338-341,400-408), without atomics: one wave per CSR row
-// (marked node, i); the wave walks the node's (face, local node) incidences in face order, adds row (a, i) of every ACTIVE
-// face block into an LDS image of the CSR row through the pair positions (lane = column node b: distinct positions within
-// an instruction), then adds the image to the caller's values in one coalesced pass; the residual entry likewise.
-// Rows none of whose faces is active are left untouched.
-constexpr int CG_WAVES = 4;
-constexpr int CG_MAX_ROW = 1056;   // (2 p + 1)^3 neighbours x 3 at p = 3 is 1029
-template<int DIM, int WITH_K>
-__global__ __launch_bounds__(64 * CG_WAVES) void contact_gather_kernel(ContactArgs p, int n_marked, const int32_t* __restrict__ marked,
-                                                                       const int32_t* __restrict__ adj_ptr, const int32_t* __restrict__ adj) {
-  __shared__ double img_all[WITH_K ? CG_WAVES : 1][CG_MAX_ROW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t R = (int64_t)blockIdx.x * CG_WAVES + wave;
-  if (R >= (int64_t)n_marked * DIM) return;
-  const int l = (int)(R / DIM), i = (int)(R % DIM);
-  const int a_beg = adj_ptr[l], a_end = adj_ptr[l + 1];
-  bool any = false;
-  for (int t = a_beg; t < a_end; ++t) any = any || p.face_active[adj[t] >> 6];
-  if (!any) return;
-  const int64_t row = (int64_t)marked[l] * DIM + i;
-  const int NT = p.n_dof * DIM;
-  if constexpr (WITH_K) {
-    double* img = img_all[wave];
-    const int64_t beg = p.rowptr[row];
-    const int len = (int)(p.rowptr[row + 1] - beg);
-    for (int k = lane; k < len; k += 64) img[k] = 0.0;
-    __builtin_amdgcn_wave_barrier();
-    for (int t = a_beg; t < a_end; ++t) {
-      const int64_t f = adj[t] >> 6;
-      const int a = adj[t] & 63;
-      if (!p.face_active[f]) continue;
-      const double* Kr = p.face_k + (f * NT + (a * DIM + i)) * (int64_t)NT;   // row (a, i): [j][b]
-      for (int b = lane; b < p.n_dof; b += 64) {
-        const int32_t off = p.pair_pos[(f * p.n_dof + a) * p.n_dof + b];
-#pragma unroll
-        for (int j = 0; j < DIM; ++j) img[off + j] += Kr[j * p.n_dof + b];
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-    __builtin_amdgcn_wave_barrier();
-    for (int k = lane; k < len; k += 64) p.A[beg + k] += p.grad_factor * img[k];
-  }
-  if (lane == 0) {
-    double rs = 0.0;
-    for (int t = a_beg; t < a_end; ++t) {
-      const int64_t f = adj[t] >> 6;
-      if (p.face_active[f]) rs += p.face_r[f * NT + i * p.n_dof + (adj[t] & 63)];
-    }
-    p.r[row] += rs;
-  }
-}
-
-__global__ void contact_pair_pos_kernel(int n_faces, int n_dof, int dim, const int32_t* dofs, const int64_t* rowptr,
-                                        const int32_t* col, int32_t* pair_pos, int* status) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)n_faces * n_dof * n_dof) return;
-  const int b = idx % n_dof, a = (idx / n_dof) % n_dof;
-  const int64_t f = idx / ((int64_t)n_dof * n_dof);
-  const int64_t row = (int64_t)dofs[f * n_dof + a] * dim;
-  const int32_t target = dofs[f * n_dof + b] * dim;
-  int64_t lo = rowptr[row], hi = rowptr[row + 1];
-  const int64_t base = lo;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (col[mid] < target) lo = mid + 1; else hi = mid;
-  }
-  if (lo >= rowptr[row + 1] || col[lo] != target) {
-    atomicOr(status, 4);
-    pair_pos[idx] = 0;
-    return;
-  }
-  pair_pos[idx] = (int32_t)(lo - base);
-}
-
 }  // namespace mimi_hip
 
 using namespace mimi_hip;
 
-struct mimi_hip_contact_s {
-  int device = 0, dim = 0, n_faces = 0, n_dof = 0, n_q = 0, n_marked = 0;
-  int64_t n_nodes = 0, n_vdofs = 0, nnz = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
+// (n_fnodes, fnodes, adj_ptr / adj of the FaceSet are the reference's marked nodes and their incidences)
+struct mimi_hip_contact_s : FaceAssembly {
   int mode = MIMI_HIP_TANGENT_ANALYTIC;
   int body_kind = 0;
   double body[8] = {0};
   double penalty = 1e4;
-  DeviceBuffer<int32_t> dofs, local, pair_pos;
-  DeviceBuffer<double> N, dN, weight, x_ref, area, gap, pressure, scalars;
-  DeviceBuffer<int64_t> rowptr_own;
-  const int64_t* rowptr = nullptr;
-  DeviceBuffer<double> stage_u, stage_r, stage_A;
-  DeviceBuffer<int> status;
-  // dense stores of the atomic-free assembly and the node -> (face, local node) incidences of the marked nodes
-  DeviceBuffer<double> pt_area, pt_gap, pt_scal, face_r, face_k, face_scal;
-  DeviceBuffer<unsigned char> face_active;
-  DeviceBuffer<int32_t> madj_ptr, madj, marked_dev;
-  std::vector<int32_t> marked_nodes;   // sorted global node ids of the marked dofs (local index -> node)
+  DeviceBuffer<double> area, gap, pressure, scalars;
+  DeviceBuffer<double> pt_area, pt_gap, pt_scal;   // per quadrature point: the dense stores of pass 1
   SplineBodyDev spline{};
   DeviceBuffer<double> sb_knots[2], sb_ctrl, sb_sample_xi, sb_sample_x;
-  double last[6] = {0};
-  ~mimi_hip_contact_s() {
-    if (own_stream) (void)hipStreamDestroy(own_stream);
-  }
 };
 
 // NearestDistanceToSplines::AddSpline / PlantKdTree (nearest_distance.hpp:223-255): (re)upload the rigid spline and the
@@ -663,18 +543,7 @@ static void upload_spline_body(mimi_hip_contact_s* h, const mimi_hip_spline_body
   h->spline.max_iterations = sp->max_iterations;
 }
 
-template<typename F>
-static int guarded_c(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    set_last_error(e.what());
-    return 1;
-  }
-}
-
-static ContactArgs contact_args(mimi_hip_contact_s* h, const double* u, double* r, double* A, double gf) {
+static ContactArgs contact_args(mimi_hip_contact_s* h, const double* u) {
   ContactArgs a{};
   a.dim = h->dim;
   a.n_faces = h->n_faces;
@@ -686,16 +555,11 @@ static ContactArgs contact_args(mimi_hip_contact_s* h, const double* u, double* 
   a.dN = h->dN.ptr;
   a.weight = h->weight.ptr;
   a.x_ref = h->x_ref.ptr;
-  a.rowptr = h->rowptr;
-  a.pair_pos = h->pair_pos.ptr;
   a.body_kind = h->body_kind;
   a.spline = h->spline;
   for (int i = 0; i < 8; ++i) a.body[i] = h->body[i];
   a.penalty = h->penalty;
   a.u = u;
-  a.r = r;
-  a.A = A;
-  a.grad_factor = gf;
   a.area = h->area.ptr;
   a.gap = h->gap.ptr;
   a.pressure = h->pressure.ptr;
@@ -713,7 +577,7 @@ static ContactArgs contact_args(mimi_hip_contact_s* h, const double* u, double* 
 
 // pass 1 (mortar_contact.cpp:148-193): nodal area / gap of this handle's faces; pressure not formed yet
 static void contact_pass1(mimi_hip_contact_s* h, const double* u_dev) {
-  ContactArgs a = contact_args(h, u_dev, nullptr, nullptr, 0.0);
+  ContactArgs a = contact_args(h, u_dev);
   // InitializeGapAreaPressure + last_* reset (mortar_contact.cpp:135-146,302-306)
   MH_HIP(hipMemsetAsync(h->scalars.ptr, 0, 6 * sizeof(double), h->stream));
   const int threads = 128;
@@ -721,26 +585,21 @@ static void contact_pass1(mimi_hip_contact_s* h, const double* u_dev) {
   const unsigned b1 = (unsigned)((npts + threads - 1) / threads);
   if (h->dim == 2) hipLaunchKernelGGL(contact_gap_area_kernel<2>, dim3(b1), dim3(threads), 0, h->stream, a, 0);
   else hipLaunchKernelGGL(contact_gap_area_kernel<3>, dim3(b1), dim3(threads), 0, h->stream, a, 0);
-  hipLaunchKernelGGL(contact_nodal_kernel, dim3((unsigned)((h->n_marked + 3) / 4)), dim3(256), 0, h->stream,
-                     h->n_marked, h->n_q, h->n_dof, h->madj_ptr.ptr, h->madj.ptr, h->pt_area.ptr, h->pt_gap.ptr, h->area.ptr, h->gap.ptr);
-  hipLaunchKernelGGL(contact_sum_kernel, dim3(1), dim3(1024), 0, h->stream, npts, 1, 1, h->pt_scal.ptr,
+  hipLaunchKernelGGL(contact_nodal_kernel, dim3((unsigned)((h->n_fnodes + 3) / 4)), dim3(256), 0, h->stream,
+                     h->n_fnodes, h->n_q, h->n_dof, h->adj_ptr.ptr, h->adj.ptr, h->pt_area.ptr, h->pt_gap.ptr, h->area.ptr, h->gap.ptr);
+  hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, npts, 1, 1, h->pt_scal.ptr,
                      (const unsigned char*)nullptr, h->scalars.ptr);
-  MH_HIP(hipGetLastError());
 }
 
 // pressure from the nodal area / gap (mortar_contact.cpp:195-261), then pass 2: face residual vectors (+ tangent blocks)
 // and their row gather
 static void contact_pass2(mimi_hip_contact_s* h, const double* u_dev, double* r_dev, double* A_dev, double gf, bool with_grad) {
-  ContactArgs a = contact_args(h, u_dev, r_dev, A_dev, gf);
+  if (with_grad) h->reserve_face_k();
+  ContactArgs a = contact_args(h, u_dev);
   const int threads = 128;
-  const unsigned b2 = (unsigned)((h->n_marked + threads - 1) / threads);
+  const unsigned b2 = (unsigned)((h->n_fnodes + threads - 1) / threads);
   const unsigned b3 = (unsigned)((h->n_faces + 63) / 64);
-  hipLaunchKernelGGL(contact_pressure_kernel, dim3(b2), dim3(threads), 0, h->stream, h->n_marked, h->area.ptr, h->gap.ptr, h->penalty, h->pressure.ptr);
-  if (with_grad && !h->face_k.ptr) {
-    const size_t nt = (size_t)h->n_dof * h->dim;
-    h->face_k.resize((size_t)h->n_faces * nt * nt);
-    a.face_k = h->face_k.ptr;
-  }
+  hipLaunchKernelGGL(contact_pressure_kernel, dim3(b2), dim3(threads), 0, h->stream, h->n_fnodes, h->area.ptr, h->gap.ptr, h->penalty, h->pressure.ptr);
   // analytic tangent: the residual by the face-per-thread kernel, the tangent by one wave per face
   const bool wave_tangent = with_grad && h->mode != MIMI_HIP_TANGENT_REFERENCE_FD;
   const int grad_flag = (with_grad && !wave_tangent) ? 1 : 0;
@@ -757,59 +616,29 @@ static void contact_pass2(mimi_hip_contact_s* h, const double* u_dev, double* r_
     else hipLaunchKernelGGL(contact_tangent_kernel<3>, dim3(b4), dim3(256), 0, h->stream, a);
   }
   // pressure integral and force of the active faces (last_pressure_ / last_force_), in a fixed order
-  hipLaunchKernelGGL(contact_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, 1 + h->dim, 1 + h->dim,
+  hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, 1 + h->dim, 1 + h->dim,
                      h->face_scal.ptr, h->face_active.ptr, h->scalars.ptr + 1);
-  const unsigned b5 = (unsigned)(((int64_t)h->n_marked * h->dim + CG_WAVES - 1) / CG_WAVES);
-  if (h->dim == 2) {
-    if (with_grad) hipLaunchKernelGGL((contact_gather_kernel<2, 1>), dim3(b5), dim3(64 * CG_WAVES), 0, h->stream, a, h->n_marked, h->marked_dev.ptr, h->madj_ptr.ptr, h->madj.ptr);
-    else hipLaunchKernelGGL((contact_gather_kernel<2, 0>), dim3(b5), dim3(64 * CG_WAVES), 0, h->stream, a, h->n_marked, h->marked_dev.ptr, h->madj_ptr.ptr, h->madj.ptr);
-  } else {
-    if (with_grad) hipLaunchKernelGGL((contact_gather_kernel<3, 1>), dim3(b5), dim3(64 * CG_WAVES), 0, h->stream, a, h->n_marked, h->marked_dev.ptr, h->madj_ptr.ptr, h->madj.ptr);
-    else hipLaunchKernelGGL((contact_gather_kernel<3, 0>), dim3(b5), dim3(64 * CG_WAVES), 0, h->stream, a, h->n_marked, h->marked_dev.ptr, h->madj_ptr.ptr, h->madj.ptr);
-  }
-  MH_HIP(hipGetLastError());
+  if (h->dim == 2) h->gather<2>(r_dev, A_dev, gf, with_grad);
+  else h->gather<3>(r_dev, A_dev, gf, with_grad);
 }
 
 // which: 1 = pass 1 only (u), 2 = pass 2 only (u, r, A), 3 = both (the single-process call)
 static void run_contact(mimi_hip_contact_s* h, const double* u, double* r, double* A, double gf, bool with_grad, int which = 3) {
-  MH_HIP(hipSetDevice(h->device));
-  if (!u || ((which & 2) && (!r || (with_grad && !A)))) fail("null vector argument");
-  Mirror<double> mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
-  Mirror<double> mr, mA;
-  if (which & 2) mr = Mirror<double>::inout(r, h->n_vdofs, h->stage_r, h->stream);
-  if ((which & 2) && with_grad) mA = Mirror<double>::inout(A, h->nnz, h->stage_A, h->stream);
-  if (which & 1) contact_pass1(h, mu.dev);
-  if (which & 2) {
-    contact_pass2(h, mu.dev, mr.dev, mA.dev, gf, with_grad);
-    mr.finish(h->stream);
-    if (with_grad) mA.finish(h->stream);
-  }
-  if (mu.host || mr.host || mA.host) MH_HIP(hipStreamSynchronize(h->stream));
+  if ((which & 2) && !r) fail("null vector argument");
+  h->run(u, r, A, with_grad, [&](const double* u_dev, double* r_dev, double* A_dev) {
+    if (which & 1) contact_pass1(h, u_dev);
+    if (which & 2) contact_pass2(h, u_dev, r_dev, A_dev, gf, with_grad);
+  });
 }
 
 extern "C" {
 
 int mimi_hip_contact_create(const mimi_hip_contact_tables* t, int device, mimi_hip_contact_t* out) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!t || !out) fail("null argument");
-    if (t->dim != 2 && t->dim != 3) fail("Unsupported Dim: %d", t->dim);
-    if (t->n_dof < 1 || t->n_dof > kMaxFaceDof) fail("face n_dof %d out of range [1,%d]", t->n_dof, kMaxFaceDof);
-    if (t->n_faces < 1) fail("no marked boundary faces");
-    if (t->n_quad < 1 || t->n_quad > 64) fail("face quadrature points %d out of range [1,64]", t->n_quad);   // (a lane per point)
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-      fail("libmimi_hip: no HIP device visible -- this library has no CPU fallback");
+    const FaceTables ft = face_tables_of(*t);
     auto h = std::make_unique<mimi_hip_contact_s>();
-    h->device = device;
-    MH_HIP(hipSetDevice(device));
-    MH_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    h->stream = h->own_stream;
-    h->dim = t->dim;
-    h->n_faces = t->n_faces;
-    h->n_dof = t->n_dof;
-    h->n_q = t->n_quad;
-    h->n_nodes = t->n_nodes;
-    h->n_vdofs = t->n_nodes * t->dim;
+    h->create(ft, device, 64, "marked boundary");
     h->body_kind = t->body_kind;
     for (int i = 0; i < 8; ++i) h->body[i] = t->body[i];
     h->penalty = t->penalty;
@@ -818,136 +647,35 @@ int mimi_hip_contact_create(const mimi_hip_contact_tables* t, int device, mimi_h
     } else if (t->body_kind != MIMI_HIP_BODY_SPHERE && t->body_kind != MIMI_HIP_BODY_PLANE) {
       fail("unknown rigid body kind %d", t->body_kind);
     }
-    const size_t nfd = (size_t)t->n_faces * t->n_dof;
-    // host copy of the connectivity for the dense local numbering of marked dofs
-    // (mortar_contact.cpp:41-76: sorted unique marked dofs -> 0..n_marked-1)
-    std::vector<int32_t> dofs(nfd);
-    if (is_device_pointer(t->dofs))
-      MH_HIP(hipMemcpy(dofs.data(), t->dofs, nfd * sizeof(int32_t), hipMemcpyDeviceToHost));
-    else
-      std::copy(t->dofs, t->dofs + nfd, dofs.begin());
-    std::vector<int32_t> marked(dofs);
-    std::sort(marked.begin(), marked.end());
-    marked.erase(std::unique(marked.begin(), marked.end()), marked.end());
-    h->n_marked = (int)marked.size();
-    h->marked_nodes = marked;
-    std::vector<int32_t> local(nfd);
-    for (size_t k = 0; k < nfd; ++k)
-      local[k] = (int32_t)(std::lower_bound(marked.begin(), marked.end(), dofs[k]) - marked.begin());
-    h->dofs.assign(dofs.data(), nfd, h->stream);
-    h->local.assign(local.data(), nfd, h->stream);
-    const size_t npts = (size_t)t->n_faces * t->n_quad;
-    h->N.assign(t->N, npts * t->n_dof, h->stream);
-    h->dN.assign(t->dN_dxi, npts * t->n_dof * (t->dim - 1), h->stream);
-    h->weight.assign(t->weight, npts, h->stream);
-    h->x_ref.assign(t->x_ref, (size_t)t->n_nodes * t->dim, h->stream);
-    h->area.resize(h->n_marked);
-    h->gap.resize(h->n_marked);
-    h->pressure.resize(h->n_marked);
+    h->area.resize(h->n_fnodes);
+    h->gap.resize(h->n_fnodes);
+    h->pressure.resize(h->n_fnodes);
     h->scalars.resize(6);
-    MH_HIP(hipMemsetAsync(h->pressure.ptr, 0, h->n_marked * sizeof(double), h->stream));
-    {
-      // marked node -> its (face, local node) incidences, faces in ascending order: the summation order of every gather
-      if (t->n_faces >= (1 << 25)) fail("too many boundary faces for the incidence encoding");
-      std::vector<int32_t> ptr(marked.size() + 1, 0), adj(nfd);
-      for (size_t k = 0; k < nfd; ++k) ++ptr[local[k] + 1];
-      for (size_t l = 0; l < marked.size(); ++l) ptr[l + 1] += ptr[l];
-      std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-      for (size_t k = 0; k < nfd; ++k) adj[fill[local[k]]++] = (int32_t)(((k / t->n_dof) << 6) | (k % t->n_dof));
-      h->madj_ptr.assign(ptr.data(), ptr.size(), h->stream);
-      h->madj.assign(adj.data(), adj.size(), h->stream);
-      h->marked_dev.assign(marked.data(), marked.size(), h->stream);
-      const size_t npts_ = (size_t)t->n_faces * t->n_quad;
-      h->pt_area.resize(npts_ * t->n_dof);
-      h->pt_gap.resize(npts_ * t->n_dof);
-      h->pt_scal.resize(npts_);
-      h->face_r.resize((size_t)t->n_faces * t->n_dof * t->dim);
-      h->face_scal.resize((size_t)t->n_faces * (1 + t->dim));
-      h->face_active.resize((size_t)t->n_faces);
-      MH_HIP(hipMemsetAsync(h->face_active.ptr, 0, (size_t)t->n_faces, h->stream));
-    }
-    h->status.resize(1);
-    MH_HIP(hipMemsetAsync(h->status.ptr, 0, sizeof(int), h->stream));
-    if (!t->csr_rowptr || !t->csr_col) fail("csr_rowptr / csr_col must be given");
-    if (is_device_pointer(t->csr_rowptr)) {
-      h->rowptr = t->csr_rowptr;
-    } else {
-      h->rowptr_own.assign(t->csr_rowptr, h->n_vdofs + 1, h->stream);
-      h->rowptr = h->rowptr_own.ptr;
-    }
-    MH_HIP(hipMemcpy(&h->nnz, h->rowptr + h->n_vdofs, sizeof(int64_t), hipMemcpyDeviceToHost));
-    {
-      // contact_gather_kernel keeps the CSR row of a marked dof in LDS (CG_MAX_ROW doubles): a caller's pattern with a
-      // longer marked row (multi-patch, degree >= 4) is refused here instead of overflowing the image at assembly time
-      std::vector<int64_t> rp_host;
-      const int64_t* rp = t->csr_rowptr;
-      if (is_device_pointer(t->csr_rowptr)) {
-        rp_host.resize((size_t)h->n_vdofs + 1);
-        MH_HIP(hipMemcpy(rp_host.data(), t->csr_rowptr, rp_host.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
-        rp = rp_host.data();
-      }
-      int64_t longest = 0;
-      for (int32_t node : marked)
-        for (int i = 0; i < t->dim; ++i) {
-          const int64_t row = (int64_t)node * t->dim + i;
-          longest = std::max(longest, rp[row + 1] - rp[row]);
-        }
-      if (longest > CG_MAX_ROW)
-        fail("a CSR row of a marked contact dof holds %lld entries; the contact gather supports at most %d", (long long)longest, CG_MAX_ROW);
-    }
-    DeviceBuffer<int32_t> col_tmp;
-    const int32_t* col_dev = t->csr_col;
-    if (!is_device_pointer(t->csr_col)) {
-      col_tmp.assign(t->csr_col, h->nnz, h->stream);
-      col_dev = col_tmp.ptr;
-    }
-    const int64_t total = (int64_t)nfd * t->n_dof;
-    h->pair_pos.resize(total);
-    hipLaunchKernelGGL(contact_pair_pos_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, t->n_faces,
-                       t->n_dof, t->dim, h->dofs.ptr, h->rowptr, col_dev, h->pair_pos.ptr, h->status.ptr);
-    MH_HIP(hipGetLastError());
-    int st = 0;
-    MH_HIP(hipMemcpyAsync(&st, h->status.ptr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    MH_HIP(hipStreamSynchronize(h->stream));
-    if (st) fail("CSR pattern does not contain a boundary element's dof block");
+    MH_HIP(hipMemsetAsync(h->pressure.ptr, 0, h->n_fnodes * sizeof(double), h->stream));
+    const size_t npts = (size_t)t->n_faces * t->n_quad;
+    h->pt_area.resize(npts * t->n_dof);
+    h->pt_gap.resize(npts * t->n_dof);
+    h->pt_scal.resize(npts);
+    h->attach_csr(ft, "marked contact", "contact");
     *out = h.release();
   });
 }
 
-int mimi_hip_contact_destroy(mimi_hip_contact_t h) {
-  return guarded_c([&] {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-  });
-}
+int mimi_hip_contact_destroy(mimi_hip_contact_t h) { return handle_destroy(h); }
 
 int mimi_hip_contact_set_tangent_mode(mimi_hip_contact_t h, int mode) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     if (mode != MIMI_HIP_TANGENT_ANALYTIC && mode != MIMI_HIP_TANGENT_REFERENCE_FD) fail("bad tangent mode %d", mode);
     h->mode = mode;
   });
 }
 
-int mimi_hip_contact_set_stream(mimi_hip_contact_t h, void* stream) {
-  return guarded_c([&] {
-    if (!h) fail("null handle");
-    h->stream = stream == MIMI_HIP_STREAM_NULL ? nullptr : (stream ? reinterpret_cast<hipStream_t>(stream) : h->own_stream);
-  });
-}
-
-int mimi_hip_contact_synchronize(mimi_hip_contact_t h) {
-  return guarded_c([&] {
-    if (!h) fail("null handle");
-    MH_HIP(hipSetDevice(h->device));
-    MH_HIP(hipStreamSynchronize(h->stream));
-  });
-}
+int mimi_hip_contact_set_stream(mimi_hip_contact_t h, void* stream) { return handle_set_stream(h, stream); }
+int mimi_hip_contact_synchronize(mimi_hip_contact_t h) { return handle_synchronize(h); }
 
 int mimi_hip_contact_add_residual(mimi_hip_contact_t h, const double* u, double* r) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     run_contact(h, u, r, nullptr, 0.0, false);
   });
@@ -955,18 +683,18 @@ int mimi_hip_contact_add_residual(mimi_hip_contact_t h, const double* u, double*
 
 int mimi_hip_contact_add_residual_and_grad(mimi_hip_contact_t h, const double* u, double grad_factor, double* r,
                                            double* A_values) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     run_contact(h, u, r, A_values, grad_factor, true);
   });
 }
 
 int mimi_hip_contact_gap_norm(mimi_hip_contact_t h, const double* u, double* out) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h || !out) fail("null argument");
     MH_HIP(hipSetDevice(h->device));
     Mirror<double> mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
-    ContactArgs a = contact_args(h, mu.dev, nullptr, nullptr, 0.0);
+    ContactArgs a = contact_args(h, mu.dev);
     const int threads = 128;
     const int64_t npts = (int64_t)h->n_faces * h->n_q;
     const unsigned b1 = (unsigned)((npts + threads - 1) / threads);
@@ -974,7 +702,7 @@ int mimi_hip_contact_gap_norm(mimi_hip_contact_t h, const double* u, double* out
       hipLaunchKernelGGL(contact_gap_area_kernel<2>, dim3(b1), dim3(threads), 0, h->stream, a, 1);
     else
       hipLaunchKernelGGL(contact_gap_area_kernel<3>, dim3(b1), dim3(threads), 0, h->stream, a, 1);
-    hipLaunchKernelGGL(contact_sum_kernel, dim3(1), dim3(1024), 0, h->stream, npts, 1, 1, h->pt_scal.ptr,
+    hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, npts, 1, 1, h->pt_scal.ptr,
                        (const unsigned char*)nullptr, h->scalars.ptr + 5);
     MH_HIP(hipGetLastError());
     double g2 = 0;
@@ -985,7 +713,7 @@ int mimi_hip_contact_gap_norm(mimi_hip_contact_t h, const double* u, double* out
 }
 
 int mimi_hip_contact_last_history(mimi_hip_contact_t h, double* out5) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h || !out5) fail("null argument");
     MH_HIP(hipSetDevice(h->device));
     MH_HIP(hipMemcpyAsync(out5, h->scalars.ptr, 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -994,7 +722,7 @@ int mimi_hip_contact_last_history(mimi_hip_contact_t h, double* out5) {
 }
 
 int mimi_hip_contact_update_body(mimi_hip_contact_t h, const mimi_hip_spline_body* spline, double penalty) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     MH_HIP(hipSetDevice(h->device));
     MH_HIP(hipStreamSynchronize(h->stream));
@@ -1008,27 +736,24 @@ int mimi_hip_contact_update_body(mimi_hip_contact_t h, const mimi_hip_spline_bod
 }
 
 int mimi_hip_contact_gap_area(mimi_hip_contact_t h, const double* u) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     run_contact(h, u, nullptr, nullptr, 0.0, false, 1);
   });
 }
 
 int mimi_hip_contact_marked_nodes(mimi_hip_contact_t h, int32_t* out, int64_t capacity, int64_t* n) {
-  return guarded_c([&] {
-    if (!h || !n) fail("null argument");
-    *n = h->n_marked;
-    if (!out) return;
-    if (capacity < h->n_marked) fail("node buffer too small");
-    std::copy(h->marked_nodes.begin(), h->marked_nodes.end(), out);
+  return guarded([&] {
+    if (!h) fail("null argument");
+    h->copy_fnodes(out, capacity, n);
   });
 }
 
 int mimi_hip_contact_nodal(mimi_hip_contact_t h, int set, double* area, double* gap) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h || !area || !gap) fail("null argument");
     MH_HIP(hipSetDevice(h->device));
-    const size_t bytes = (size_t)h->n_marked * sizeof(double);
+    const size_t bytes = (size_t)h->n_fnodes * sizeof(double);
     if (set) {
       MH_HIP(hipMemcpyAsync(h->area.ptr, area, bytes, hipMemcpyDefault, h->stream));
       MH_HIP(hipMemcpyAsync(h->gap.ptr, gap, bytes, hipMemcpyDefault, h->stream));
@@ -1042,20 +767,20 @@ int mimi_hip_contact_nodal(mimi_hip_contact_t h, int set, double* area, double* 
 
 int mimi_hip_contact_add_residual_from_nodal(mimi_hip_contact_t h, const double* u, double grad_factor, double* r,
                                              double* A_values) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     run_contact(h, u, r, A_values, grad_factor, A_values != nullptr, 2);
   });
 }
 
 int mimi_hip_contact_get_pressure(mimi_hip_contact_t h, double* out, int64_t capacity, int64_t* n) {
-  return guarded_c([&] {
+  return guarded([&] {
     if (!h || !n) fail("null argument");
-    *n = h->n_marked;
+    *n = h->n_fnodes;
     if (!out) return;
-    if (capacity < h->n_marked) fail("pressure buffer too small");
+    if (capacity < h->n_fnodes) fail("pressure buffer too small");
     MH_HIP(hipSetDevice(h->device));
-    MH_HIP(hipMemcpyAsync(out, h->pressure.ptr, h->n_marked * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MH_HIP(hipMemcpyAsync(out, h->pressure.ptr, h->n_fnodes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     MH_HIP(hipStreamSynchronize(h->stream));
   });
 }

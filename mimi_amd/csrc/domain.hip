@@ -25,20 +25,6 @@ namespace mimi_hip {
 static thread_local std::string g_last_error;
 void set_last_error(const std::string& s) { g_last_error = s; }
 
-template<typename F>
-static int guarded(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    set_last_error(e.what());
-    return 1;
-  } catch (...) {
-    set_last_error("unknown error");
-    return 1;
-  }
-}
-
 static void check_status(mimi_hip_domain_s* h) {
   MH_HIP(hipMemcpyAsync(h->status_host, h->status_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   MH_HIP(hipStreamSynchronize(h->stream));
@@ -54,14 +40,7 @@ static void check_status(mimi_hip_domain_s* h) {
 }
 
 static void init_common(mimi_hip_domain_s* h, int device, const mimi_hip_material* material) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-    fail("libmimi_hip: no HIP device visible -- this library has no CPU fallback");
-  if (device < 0 || device >= count) fail("device %d out of range (%d visible)", device, count);
-  h->device = device;
-  MH_HIP(hipSetDevice(device));
-  MH_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-  h->stream = h->own_stream;
+  h->open(device);
   h->mat = make_material_dev(*material);
   MH_HIP(hipMalloc(reinterpret_cast<void**>(&h->status_dev), sizeof(int)));
   MH_HIP(hipMemsetAsync(h->status_dev, 0, sizeof(int), h->stream));
@@ -516,7 +495,6 @@ mimi_hip_domain_s::~mimi_hip_domain_s() {
     if (ev) (void)hipEventDestroy(ev);
   if (status_dev) (void)hipFree(status_dev);
   if (status_host) (void)hipHostFree(status_host);
-  if (own_stream) (void)hipStreamDestroy(own_stream);
 }
 
 extern "C" {
@@ -789,14 +767,7 @@ int mimi_hip_domain_create_bspline(const mimi_hip_bspline_patch* p, const mimi_h
   });
 }
 
-int mimi_hip_domain_destroy(mimi_hip_domain_t h) {
-  return guarded([&] {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-  });
-}
+int mimi_hip_domain_destroy(mimi_hip_domain_t h) { return handle_destroy(h); }
 
 int mimi_hip_domain_set_dt(mimi_hip_domain_t h, double dt, double first_effective_dt, double second_effective_dt) {
   return guarded([&] {
@@ -815,12 +786,7 @@ int mimi_hip_domain_set_tangent_mode(mimi_hip_domain_t h, int mode) {
   });
 }
 
-int mimi_hip_domain_set_stream(mimi_hip_domain_t h, void* stream) {
-  return guarded([&] {
-    if (!h) fail("null handle");
-    h->stream = stream == MIMI_HIP_STREAM_NULL ? nullptr : (stream ? reinterpret_cast<hipStream_t>(stream) : h->own_stream);
-  });
-}
+int mimi_hip_domain_set_stream(mimi_hip_domain_t h, void* stream) { return handle_set_stream(h, stream); }
 
 // the two-step form of a tangent assembly: phase 1 of the whole handle, then phase 2 over parts of its nodes
 static void require_two_phase(mimi_hip_domain_s* h) {

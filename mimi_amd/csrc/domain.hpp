@@ -5,12 +5,10 @@
 #include "bspline_host.hpp"
 #include "common.hpp"
 
-struct mimi_hip_domain_s {
-  int device = 0;
+struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   int dim = 0, n_el = 0, n_dof = 0, n_q = 0;
   int64_t n_nodes = 0, n_vdofs = 0, nnz = 0, n_pts = 0;
   int path = 0;  // 0 general tables, 1 tensor-product (sum factorisation)
-  hipStream_t own_stream = nullptr, stream = nullptr;
 
   mimi_hip::MaterialDev mat{};
   double dt = 0.0, first_effective_dt = 0.0, second_effective_dt = 0.0;

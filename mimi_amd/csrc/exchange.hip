@@ -69,20 +69,6 @@ __global__ __launch_bounds__(256) void entries_kernel(const int64_t* __restrict_
   }
 }
 
-template<typename F>
-int guarded_x(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    set_last_error(e.what());
-    return 1;
-  } catch (...) {
-    set_last_error("unknown error");
-    return 1;
-  }
-}
-
 template<int MODE>
 void launch_rows(void* stream, const int64_t* rowptr, const int64_t* rows, const int64_t* offsets, int64_t n_rows,
                  double* r, double* A, double* msg) {
@@ -90,7 +76,7 @@ void launch_rows(void* stream, const int64_t* rowptr, const int64_t* rows, const
   if (n_rows < 0 || !rowptr || !rows || !r) fail("rows exchange: null argument");
   if (MODE != 0 && !msg) fail("rows exchange: no message buffer");
   if (MODE != 0 && A && !offsets) fail("rows exchange: offsets must be given with A");
-  hipStream_t s = stream == MIMI_HIP_STREAM_NULL ? nullptr : (hipStream_t)stream;
+  hipStream_t s = pick_stream(stream, nullptr);
   const int64_t blocks = (n_rows + XW - 1) / XW;
   hipLaunchKernelGGL(rows_kernel<MODE>, dim3((unsigned)blocks), dim3(64 * XW), 0, s, rowptr, rows, offsets, n_rows, r, A, msg);
   MH_HIP(hipGetLastError());
@@ -104,7 +90,7 @@ void launch_entries(void* stream, const int64_t* rows, int64_t n_rows, const int
   if (n == 0) return;
   if (!msg || (n_rows && (!rows || !r))) fail("entries exchange: null argument");
   if (A && n_positions && !positions) fail("entries exchange: positions must be given with A");
-  hipStream_t s = stream == MIMI_HIP_STREAM_NULL ? nullptr : (hipStream_t)stream;
+  hipStream_t s = pick_stream(stream, nullptr);
   const int64_t blocks = std::min<int64_t>((n + 255) / 256, 1 << 16);
   hipLaunchKernelGGL(entries_kernel<MODE>, dim3((unsigned)blocks), dim3(256), 0, s, rows, n_rows, positions, n_positions, r, A, msg);
   MH_HIP(hipGetLastError());
@@ -118,31 +104,31 @@ using namespace mimi_hip;
 extern "C" {
 
 int mimi_hip_rows_zero(void* stream, const int64_t* rowptr, const int64_t* rows, int64_t n_rows, double* r, double* A_values) {
-  return guarded_x([&] { launch_rows<0>(stream, rowptr, rows, nullptr, n_rows, r, A_values, nullptr); });
+  return guarded([&] { launch_rows<0>(stream, rowptr, rows, nullptr, n_rows, r, A_values, nullptr); });
 }
 
 int mimi_hip_rows_pack(void* stream, const int64_t* rowptr, const int64_t* rows, const int64_t* offsets, int64_t n_rows,
                        const double* r, const double* A_values, double* message) {
-  return guarded_x([&] {
+  return guarded([&] {
     launch_rows<1>(stream, rowptr, rows, offsets, n_rows, const_cast<double*>(r), const_cast<double*>(A_values), message);
   });
 }
 
 int mimi_hip_rows_unpack_add(void* stream, const int64_t* rowptr, const int64_t* rows, const int64_t* offsets, int64_t n_rows,
                              const double* message, double* r, double* A_values) {
-  return guarded_x([&] { launch_rows<2>(stream, rowptr, rows, offsets, n_rows, r, A_values, const_cast<double*>(message)); });
+  return guarded([&] { launch_rows<2>(stream, rowptr, rows, offsets, n_rows, r, A_values, const_cast<double*>(message)); });
 }
 
 int mimi_hip_entries_pack(void* stream, const int64_t* rows, int64_t n_rows, const int64_t* positions, int64_t n_positions,
                           const double* r, const double* A_values, double* message) {
-  return guarded_x([&] {
+  return guarded([&] {
     launch_entries<1>(stream, rows, n_rows, positions, n_positions, const_cast<double*>(r), const_cast<double*>(A_values), message);
   });
 }
 
 int mimi_hip_entries_unpack_add(void* stream, const int64_t* rows, int64_t n_rows, const int64_t* positions, int64_t n_positions,
                                 const double* message, double* r, double* A_values) {
-  return guarded_x([&] {
+  return guarded([&] {
     launch_entries<2>(stream, rows, n_rows, positions, n_positions, r, A_values, const_cast<double*>(message));
   });
 }

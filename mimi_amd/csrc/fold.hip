@@ -209,55 +209,25 @@ __global__ __launch_bounds__(256) void fold_expand_kernel(int dim, int64_t n_u, 
 
 using namespace mimi_hip;
 
-struct mimi_hip_fold_s {
-  int device = 0, dim = 0, row_cap = 0;
+struct mimi_hip_fold_s : StreamHandle {
+  int dim = 0, row_cap = 0;
   int64_t n_nodes_u = 0, n_nodes_f = 0, n_u = 0, n_f = 0, nnz_u = 0, nnz_f = 0, n_serial = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
   DeviceBuffer<int32_t> node_map, copy_ptr, copies, col_f, entry_pos;
   DeviceBuffer<int64_t> rowptr_u, rowptr_f;
   DeviceBuffer<unsigned char> serial;
   DeviceBuffer<double> stage_uf, stage_uu, stage_ru, stage_rf, stage_Au, stage_Ab, stage_Af;
-  ~mimi_hip_fold_s() {
-    if (own_stream) (void)hipStreamDestroy(own_stream);
-  }
 };
-
-template<typename F>
-static int guarded_f(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    set_last_error(e.what());
-    return 1;
-  }
-}
-
-template<typename T>
-static std::vector<T> to_host(const T* p, size_t n) {
-  std::vector<T> out(n);
-  if (n == 0) return out;
-  if (is_device_pointer(p)) MH_HIP(hipMemcpy(out.data(), p, n * sizeof(T), hipMemcpyDeviceToHost));
-  else std::copy(p, p + n, out.begin());
-  return out;
-}
 
 extern "C" {
 
 int mimi_hip_fold_create(int32_t dim, int64_t n_nodes_u, const int64_t* node_map, const int64_t* rowptr_u,
                          const int32_t* col_u, int device, mimi_hip_fold_t* out) {
-  return guarded_f([&] {
+  return guarded([&] {
     if (!out || !node_map || !rowptr_u || !col_u) fail("null argument");
     if (dim < 1 || dim > 3) fail("Unsupported Dim: %d", dim);
     if (n_nodes_u < 1 || n_nodes_u * dim >= ((int64_t)1 << 31)) fail("n_nodes_u %lld out of range", (long long)n_nodes_u);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-      fail("libmimi_hip: no HIP device visible -- this library has no CPU fallback");
     auto h = std::make_unique<mimi_hip_fold_s>();
-    h->device = device;
-    MH_HIP(hipSetDevice(device));
-    MH_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    h->stream = h->own_stream;
+    h->open(device);
     h->dim = dim;
     h->n_nodes_u = n_nodes_u;
     h->n_u = n_nodes_u * dim;
@@ -375,7 +345,7 @@ int64_t mimi_hip_fold_info(mimi_hip_fold_t h, int what) {
 }
 
 int mimi_hip_fold_pattern(mimi_hip_fold_t h, int64_t* rowptr_f, int32_t* col_f) {
-  return guarded_f([&] {
+  return guarded([&] {
     if (!h || !rowptr_f) fail("null argument");
     MH_HIP(hipSetDevice(h->device));
     MH_HIP(hipMemcpyAsync(rowptr_f, h->rowptr_f.ptr, ((size_t)h->n_f + 1) * sizeof(int64_t), hipMemcpyDefault, h->stream));
@@ -385,32 +355,12 @@ int mimi_hip_fold_pattern(mimi_hip_fold_t h, int64_t* rowptr_f, int32_t* col_f) 
   });
 }
 
-int mimi_hip_fold_set_stream(mimi_hip_fold_t h, void* stream) {
-  return guarded_f([&] {
-    if (!h) fail("null handle");
-    h->stream = stream == MIMI_HIP_STREAM_NULL ? nullptr : (stream ? reinterpret_cast<hipStream_t>(stream) : h->own_stream);
-  });
-}
-
-int mimi_hip_fold_synchronize(mimi_hip_fold_t h) {
-  return guarded_f([&] {
-    if (!h) fail("null handle");
-    MH_HIP(hipSetDevice(h->device));
-    MH_HIP(hipStreamSynchronize(h->stream));
-  });
-}
-
-int mimi_hip_fold_destroy(mimi_hip_fold_t h) {
-  return guarded_f([&] {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-  });
-}
+int mimi_hip_fold_set_stream(mimi_hip_fold_t h, void* stream) { return handle_set_stream(h, stream); }
+int mimi_hip_fold_synchronize(mimi_hip_fold_t h) { return handle_synchronize(h); }
+int mimi_hip_fold_destroy(mimi_hip_fold_t h) { return handle_destroy(h); }
 
 int mimi_hip_fold_expand(mimi_hip_fold_t h, const double* u_f, double* u_u) {
-  return guarded_f([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     if (!u_f || !u_u) fail("null vector argument");
     MH_HIP(hipSetDevice(h->device));
@@ -426,7 +376,7 @@ int mimi_hip_fold_expand(mimi_hip_fold_t h, const double* u_f, double* u_u) {
 
 int mimi_hip_fold_add(mimi_hip_fold_t h, const double* r_u, double* r_f, const double* A_u, const double* A_base,
                       double* A_f) {
-  return guarded_f([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     if (!r_u != !r_f) fail("r_u and r_f must both be given or both be NULL");
     if (A_u && !A_f) fail("A_f must be given with A_u");

@@ -332,11 +332,9 @@ __global__ void kr_mark_kernel(int64_t n_ess, const int64_t* __restrict__ ess, u
 
 using namespace mimi_hip;
 
-struct mimi_hip_linear_s {
-  int device = 0;
+struct mimi_hip_linear_s : StreamHandle {
   int64_t n = 0, nnz = 0;
   int kdim = 50;
-  hipStream_t stream = nullptr, own_stream = nullptr;
   DeviceBuffer<int64_t> rowptr_own, diag_pos, ess;
   DeviceBuffer<int32_t> col_own;
   const int64_t* rowptr = nullptr;
@@ -367,25 +365,10 @@ struct mimi_hip_linear_s {
       if (column_ready[k]) (void)hipEventDestroy(column_ready[k]);
     }
     if (status_dev) (void)hipFree(status_dev);
-    if (own_stream) (void)hipStreamDestroy(own_stream);
   }
 };
 
 namespace {
-
-template<typename F>
-int guarded_k(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    set_last_error(e.what());
-    return 1;
-  } catch (...) {
-    set_last_error("unknown error");
-    return 1;
-  }
-}
 
 void spmv(mimi_hip_linear_s* h, const double* val, const double* x, const double* b, const double* dinv, double* y) {
   if (h->nodecol)
@@ -409,18 +392,11 @@ extern "C" {
 
 int mimi_hip_linear_create(int64_t n, const int64_t* csr_rowptr, const int32_t* csr_col, const int64_t* ess_dofs,
                            int64_t n_ess, int device, mimi_hip_linear_t* out) {
-  return guarded_k([&] {
+  return guarded([&] {
     if (!out || !csr_rowptr || !csr_col || n < 1) fail("null / empty argument");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-      fail("libmimi_hip: no HIP device visible -- this library has no CPU fallback");
-    if (device < 0 || device >= count) fail("device %d out of range (%d visible)", device, count);
     auto h = std::make_unique<mimi_hip_linear_s>();
-    h->device = device;
+    h->open(device);
     h->n = n;
-    MH_HIP(hipSetDevice(device));
-    MH_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    h->stream = h->own_stream;
     if (is_device_pointer(csr_rowptr)) {
       h->rowptr = csr_rowptr;
     } else {
@@ -484,21 +460,8 @@ int mimi_hip_linear_create(int64_t n, const int64_t* csr_rowptr, const int32_t* 
   });
 }
 
-int mimi_hip_linear_destroy(mimi_hip_linear_t h) {
-  return guarded_k([&] {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-  });
-}
-
-int mimi_hip_linear_set_stream(mimi_hip_linear_t h, void* stream) {
-  return guarded_k([&] {
-    if (!h) fail("null handle");
-    h->stream = stream == MIMI_HIP_STREAM_NULL ? nullptr : (stream ? reinterpret_cast<hipStream_t>(stream) : h->own_stream);
-  });
-}
+int mimi_hip_linear_destroy(mimi_hip_linear_t h) { return handle_destroy(h); }
+int mimi_hip_linear_set_stream(mimi_hip_linear_t h, void* stream) { return handle_set_stream(h, stream); }
 
 int64_t mimi_hip_linear_info(mimi_hip_linear_t h, int what) {
   if (!h) return -1;
@@ -512,7 +475,7 @@ int64_t mimi_hip_linear_info(mimi_hip_linear_t h, int what) {
 }
 
 int mimi_hip_linear_eliminate(mimi_hip_linear_t h, double* r, double* A_values) {
-  return guarded_k([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     MH_HIP(hipSetDevice(h->device));
     if (h->n_ess == 0) return;
@@ -536,7 +499,7 @@ int mimi_hip_linear_eliminate(mimi_hip_linear_t h, double* r, double* A_values) 
 }
 
 int mimi_hip_linear_add_mult(mimi_hip_linear_t h, const double* A_values, const double* x, double alpha, double* y) {
-  return guarded_k([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     if (!A_values || !x || !y) fail("null vector argument");
     MH_HIP(hipSetDevice(h->device));
@@ -563,7 +526,7 @@ int mimi_hip_linear_add_mult(mimi_hip_linear_t h, const double* A_values, const 
 
 int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol, double abs_tol,
                           int max_iter, int kdim, int use_jacobi, int32_t* iterations, double* final_norm, int32_t* converged) {
-  return guarded_k([&] {
+  return guarded([&] {
     if (!h || !A_values || !b || !x) fail("null argument");
     if (kdim < 1) kdim = 50;   // mfem::GMRESSolver default m
     MH_HIP(hipSetDevice(h->device));
@@ -721,7 +684,7 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
  * stops when (r, M r) <= max(rel_tol^2 (r0, M r0), abs_tol^2)  (mfem linalg/solvers.cpp, CGSolver::Mult) */
 int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol, double abs_tol,
                        int max_iter, int use_jacobi, int32_t* iterations, double* final_norm, int32_t* converged) {
-  return guarded_k([&] {
+  return guarded([&] {
     if (!h || !A_values || !b || !x) fail("null argument");
     MH_HIP(hipSetDevice(h->device));
     const int64_t n = h->n;

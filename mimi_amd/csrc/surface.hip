@@ -89,14 +89,14 @@ __global__ __launch_bounds__(256) void surface_face_kernel(SurfaceArgs p) {
       const double Nc = N[c];
 #pragma unroll
       for (int i = 0; i < DIM; ++i) {
-        const double x = pressure_lane_read(xc[i], c);
+        const double x = face_lane_read(xc[i], c);
         xq[i] = __builtin_fma(Nc, x, xq[i]);
 #pragma unroll
         for (int k = 0; k < DIM - 1; ++k) tq[k * DIM + i] = __builtin_fma(x, dN[k * n_dof + c], tq[k * DIM + i]);
       }
     }
   }
-  pressure_normal<DIM>(tq, mq);
+  face_normal<DIM>(tq, mq);
   double mm = 0.0;
 #pragma unroll
   for (int i = 0; i < DIM; ++i) mm += mq[i] * mq[i];
@@ -128,10 +128,10 @@ __global__ __launch_bounds__(256) void surface_face_kernel(SurfaceArgs p) {
     const int k = lane < NT ? lane : 0, a = k / DIM, i = k - a * DIM;
     double F = 0.0;
     for (int qq = 0; qq < n_q; ++qq) {
-      double v = pressure_lane_read(wt[0], qq);
+      double v = face_lane_read(wt[0], qq);
 #pragma unroll
       for (int ii = 1; ii < DIM; ++ii) {
-        const double w = pressure_lane_read(wt[ii], qq);
+        const double w = face_lane_read(wt[ii], qq);
         v = i == ii ? w : v;
       }
       F = __builtin_fma(v, p.N[((int64_t)f * n_q + qq) * n_dof + a], F);
@@ -160,28 +160,11 @@ __global__ __launch_bounds__(256) void surface_gather_kernel(int dim, int n_dof,
 
 using namespace mimi_hip;
 
-struct mimi_hip_surface_s {
-  int device = 0, dim = 0, n_faces = 0, n_dof = 0, n_q = 0, n_fnodes = 0;
-  int64_t n_nodes = 0, n_vdofs = 0, n_points = 0;
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  DeviceBuffer<int32_t> dofs, adj_ptr, adj, fnodes;
-  DeviceBuffer<double> N, dN, weight, x_ref, face_f;
-  DeviceBuffer<double> stage_u, stage_t, stage_f, stage_x, stage_n, stage_w;
-  ~mimi_hip_surface_s() {
-    if (own_stream) (void)hipStreamDestroy(own_stream);
-  }
+struct mimi_hip_surface_s : FaceSet {
+  int64_t n_points = 0;
+  DeviceBuffer<double> face_f;
+  DeviceBuffer<double> stage_t, stage_f, stage_x, stage_n, stage_w;
 };
-
-template<typename F>
-static int guarded_s(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    set_last_error(e.what());
-    return 1;
-  }
-}
 
 static SurfaceArgs surface_args(const mimi_hip_surface_s* h, const double* u) {
   SurfaceArgs a{};
@@ -205,82 +188,25 @@ static void launch_surface_face(const mimi_hip_surface_s* h, const SurfaceArgs& 
 extern "C" {
 
 int mimi_hip_surface_create(const mimi_hip_pressure_tables* t, int device, mimi_hip_surface_t* out) {
-  return guarded_s([&] {
+  return guarded([&] {
     if (!t || !out) fail("null argument");
-    if (t->dim != 2 && t->dim != 3) fail("Unsupported Dim: %d", t->dim);
-    if (t->n_dof < 1 || t->n_dof > kPressureMaxDof) fail("face n_dof %d out of range [1,%d]", t->n_dof, kPressureMaxDof);
-    if (t->n_faces < 1) fail("no coupling faces");
-    if (t->n_faces >= (1 << 25)) fail("too many coupling faces for the incidence encoding");
-    if (t->n_quad < 1 || t->n_quad > kPressureMaxQuad) fail("face quadrature points %d out of range [1,%d]", t->n_quad, kPressureMaxQuad);
-    if (!t->dofs || !t->N || !t->dN_dxi || !t->weight || !t->x_ref) fail("null table");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count == 0)
-      fail("libmimi_hip: no HIP device visible -- this library has no CPU fallback");
     auto h = std::make_unique<mimi_hip_surface_s>();
-    h->device = device;
-    MH_HIP(hipSetDevice(device));
-    MH_HIP(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
-    h->stream = h->own_stream;
-    h->dim = t->dim;
-    h->n_faces = t->n_faces;
-    h->n_dof = t->n_dof;
-    h->n_q = t->n_quad;
-    h->n_nodes = t->n_nodes;
-    h->n_vdofs = t->n_nodes * t->dim;
+    h->create(face_tables_of(*t), device, kFaceMaxQuad, "coupling");
     h->n_points = (int64_t)t->n_faces * t->n_quad;
-    const size_t nfd = (size_t)t->n_faces * t->n_dof;
-    std::vector<int32_t> dofs(nfd);
-    if (is_device_pointer(t->dofs))
-      MH_HIP(hipMemcpy(dofs.data(), t->dofs, nfd * sizeof(int32_t), hipMemcpyDeviceToHost));
-    else
-      std::copy(t->dofs, t->dofs + nfd, dofs.begin());
-    for (int32_t d : dofs)
-      if (d < 0 || d >= t->n_nodes) fail("face node id %d out of range [0,%lld)", d, (long long)t->n_nodes);
-    const FaceIncidences inc = face_incidences(dofs, t->n_dof);
-    h->n_fnodes = (int)inc.fnodes.size();
-    h->dofs.assign(dofs.data(), nfd, h->stream);
-    const size_t npts = (size_t)h->n_points;
-    h->N.assign(t->N, npts * t->n_dof, h->stream);
-    h->dN.assign(t->dN_dxi, npts * t->n_dof * (t->dim - 1), h->stream);
-    h->weight.assign(t->weight, npts, h->stream);
-    h->x_ref.assign(t->x_ref, (size_t)t->n_nodes * t->dim, h->stream);
-    h->adj_ptr.assign(inc.adj_ptr.data(), inc.adj_ptr.size(), h->stream);
-    h->adj.assign(inc.adj.data(), inc.adj.size(), h->stream);
-    h->fnodes.assign(inc.fnodes.data(), inc.fnodes.size(), h->stream);
-    h->face_f.resize(nfd * t->dim);
+    h->face_f.resize((size_t)t->n_faces * t->n_dof * t->dim);
     MH_HIP(hipStreamSynchronize(h->stream));
     *out = h.release();
   });
 }
 
-int mimi_hip_surface_destroy(mimi_hip_surface_t h) {
-  return guarded_s([&] {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipStreamSynchronize(h->stream);
-    delete h;
-  });
-}
-
-int mimi_hip_surface_set_stream(mimi_hip_surface_t h, void* stream) {
-  return guarded_s([&] {
-    if (!h) fail("null handle");
-    h->stream = stream == MIMI_HIP_STREAM_NULL ? nullptr : (stream ? reinterpret_cast<hipStream_t>(stream) : h->own_stream);
-  });
-}
-
-int mimi_hip_surface_synchronize(mimi_hip_surface_t h) {
-  return guarded_s([&] {
-    if (!h) fail("null handle");
-    MH_HIP(hipSetDevice(h->device));
-    MH_HIP(hipStreamSynchronize(h->stream));
-  });
-}
+int mimi_hip_surface_destroy(mimi_hip_surface_t h) { return handle_destroy(h); }
+int mimi_hip_surface_set_stream(mimi_hip_surface_t h, void* stream) { return handle_set_stream(h, stream); }
+int mimi_hip_surface_synchronize(mimi_hip_surface_t h) { return handle_synchronize(h); }
 
 int64_t mimi_hip_surface_n_points(mimi_hip_surface_t h) { return h ? h->n_points : -1; }
 
 int mimi_hip_surface_points(mimi_hip_surface_t h, const double* u, double* x, double* normal, double* weight) {
-  return guarded_s([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     MH_HIP(hipSetDevice(h->device));
     const size_t nv = (size_t)h->n_points * h->dim;
@@ -304,7 +230,7 @@ int mimi_hip_surface_points(mimi_hip_surface_t h, const double* u, double* x, do
 }
 
 int mimi_hip_surface_add_load(mimi_hip_surface_t h, const double* u, const double* t, double* f) {
-  return guarded_s([&] {
+  return guarded([&] {
     if (!h) fail("null handle");
     if (!t || !f) fail("null vector argument");
     MH_HIP(hipSetDevice(h->device));
@@ -319,7 +245,7 @@ int mimi_hip_surface_add_load(mimi_hip_surface_t h, const double* u, const doubl
     else launch_surface_face<3, 1>(h, a);
     const int64_t rows = (int64_t)h->n_fnodes * h->dim;
     hipLaunchKernelGGL(surface_gather_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, h->dim, h->n_dof,
-                       rows, h->fnodes.ptr, h->adj_ptr.ptr, h->adj.ptr, h->face_f.ptr, mf.dev);
+                       rows, h->fnodes_dev.ptr, h->adj_ptr.ptr, h->adj.ptr, h->face_f.ptr, mf.dev);
     MH_HIP(hipGetLastError());
     mf.finish(h->stream);
     if (mu.host || mt.host || mf.host) MH_HIP(hipStreamSynchronize(h->stream));

@@ -62,7 +62,7 @@ class CSRPattern:
         return cls(rowptr, col, nnz.value)
 
 
-class NonlinearBase:
+class NonlinearBase(_capi.Handle):
     """integrators/nonlinear_base.hpp:14-154"""
     dt_ = 0.0
     first_effective_dt_ = 0.0
@@ -82,6 +82,7 @@ class NonlinearSolid(NonlinearBase):
     tensor-product kernels are used) or `tables` (dict with the reference's flattened
     PrecomputedData: dim, n_nodes, dofs[e,a], dN_dX[e,q,J,a], weight_det[e,q]) must be given.
     """
+    _prefix = "domain"
 
     def __init__(self, name, material, pattern, patch=None, tables=None, device=0, quadrature_order=-1,
                  element_box=None, node_ids=None):
@@ -93,7 +94,6 @@ class NonlinearSolid(NonlinearBase):
         self.quadrature_order_ = quadrature_order
         self.element_box_ = element_box
         self.node_ids_ = node_ids
-        self._h = None
         self._keep = []
 
     # -- NonlinearSolid::Prepare (nonlinear_solid.cpp:31-46) --------------------------
@@ -151,11 +151,6 @@ class NonlinearSolid(NonlinearBase):
         self.has_states_ = self.material_._kind == 1
         return self
 
-    def _handle(self):
-        if self._h is None:
-            raise RuntimeError("Prepare() has not been called")
-        return self._h
-
     def _push_dt(self):
         # forms::Nonlinear pushes these public members before each call (forms/nonlinear.hpp:63-65)
         check(_capi.lib().mimi_hip_domain_set_dt(self._handle(), self.dt_, self.first_effective_dt_,
@@ -163,12 +158,6 @@ class NonlinearSolid(NonlinearBase):
 
     def SetTangentMode(self, mode):
         check(_capi.lib().mimi_hip_domain_set_tangent_mode(self._handle(), mode))
-
-    def SetStream(self, stream):
-        """launch on `stream` (a hipStream_t as an int); 0 / None: back to following torch's current stream for CUDA
-        tensors and the handle's own stream for host buffers"""
-        self._user_stream = bool(stream)
-        check(_capi.lib().mimi_hip_domain_set_stream(self._handle(), C.c_void_p(stream) if stream else None))
 
     def Integrate(self, current_u):
         """phase 1 of a tangent assembly on its own (mimi_hip.h: mimi_hip_domain_integrate): the element pieces stay in the
@@ -184,18 +173,6 @@ class NonlinearSolid(NonlinearBase):
         lo = (C.c_int32 * 3)(*[int(v) for v in node_begin])
         hi = (C.c_int32 * 3)(*[int(v) for v in node_end])
         check(_capi.lib().mimi_hip_domain_gather(self._handle(), float(grad_factor), fptr(residual), fptr(grad), lo, hi))
-
-    def _follow_torch(self, *buffers):
-        # ordering with the caller's torch work (zero fills of r / A, copies of u): see _capi.torch_stream_of
-        if getattr(self, "_user_stream", False):
-            return
-        s = _capi.torch_stream_of(*buffers)
-        if s is not None or getattr(self, "_followed", None):
-            check(_capi.lib().mimi_hip_domain_set_stream(self._handle(), C.c_void_p(s) if s else None))
-            self._followed = s
-
-    def Synchronize(self):
-        check(_capi.lib().mimi_hip_domain_synchronize(self._handle()))
 
     # -- nonlinear_solid.cpp:151-160 ---------------------------------------------------
     def AddDomainResidual(self, current_u, residual):
@@ -264,14 +241,6 @@ class NonlinearSolid(NonlinearBase):
 
     def ResetState(self):
         check(_capi.lib().mimi_hip_domain_reset_state(self._handle()))
-
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _capi.lib().mimi_hip_domain_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     # snake_case aliases
     prepare = Prepare
@@ -394,6 +363,7 @@ class NearestDistanceToSplines:
 class MortarContact(NonlinearBase):
     """integrators::MortarContact (integrators/mortar_contact.hpp:23-172) against an analytic
     rigid body, on one face of a B-spline patch."""
+    _prefix = "contact"
 
     def __init__(self, nearest_distance_coeff, name, pattern, patch, axis, side, device=0, quadrature_order=-1,
                  element_box=None):
@@ -403,26 +373,16 @@ class MortarContact(NonlinearBase):
         self.pattern_, self.patch_ = pattern, patch
         self.axis_, self.side_ = axis, side
         self.device_, self.quadrature_order_ = device, quadrature_order
-        self._h = None
         self.last_area_ = 0.0
         self.last_pressure_ = 0.0
         self.last_force_ = np.zeros(patch.dim)
 
     def Prepare(self):
-        from . import splines
         L = _capi.lib()
         p = self.patch_
-        dofs, N, dN, weight = splines.face_tables(p, self.axis_, self.side_, self.quadrature_order_, self.element_box_)
-        if len(dofs) == 0:
-            raise RuntimeError("no marked boundary faces in this element box")
         t = _capi.ContactTables()
-        t.dim = p.dim
-        t.n_faces, t.n_dof = dofs.shape
-        t.n_quad = weight.shape[1]
-        t.n_nodes = p.n_nodes
-        self._keep = [dofs, N, dN, weight, p.control_points]
-        t.dofs, t.N, t.dN_dxi, t.weight = dofs.ctypes.data, N.ctypes.data, dN.ctypes.data, weight.ctypes.data
-        t.x_ref = p.control_points.ctypes.data
+        self._keep = _capi.fill_face_tables(t, p, self.axis_, self.side_, self.quadrature_order_, self.element_box_,
+                                            "no marked boundary faces in this element box")
         body = self.nearest_distance_coeff_
         t.body_kind = body.kind
         for i, v in enumerate(body.params(p.dim)):
@@ -442,14 +402,6 @@ class MortarContact(NonlinearBase):
         self.n_marked_boundaries_ = int(t.n_faces)
         return self
 
-    def _handle(self):
-        if self._h is None:
-            raise RuntimeError("Prepare() has not been called")
-        return self._h
-
-    def Synchronize(self):
-        check(_capi.lib().mimi_hip_contact_synchronize(self._handle()))
-
     def UpdateBody(self, spline=False, penalty=-1.0):
         """the rigid body moved (spline=True: re-read it from nearest_distance_coeff_) and / or the penalty changed"""
         sp = None
@@ -465,11 +417,7 @@ class MortarContact(NonlinearBase):
         check(_capi.lib().mimi_hip_contact_gap_area(self._handle(), fptr(current_u)))
 
     def MarkedNodes(self):
-        n = C.c_int64(0)
-        check(_capi.lib().mimi_hip_contact_marked_nodes(self._handle(), None, 0, C.byref(n)))
-        out = np.empty(n.value, dtype=np.int32)
-        check(_capi.lib().mimi_hip_contact_marked_nodes(self._handle(), ptr(out), out.size, C.byref(n)))
-        return out
+        return self._sized_query("marked_nodes", np.int32)
 
     def GetNodal(self, area, gap):
         self._follow_torch(area, gap)
@@ -487,19 +435,6 @@ class MortarContact(NonlinearBase):
 
     def SetTangentMode(self, mode):
         check(_capi.lib().mimi_hip_contact_set_tangent_mode(self._handle(), mode))
-
-    def SetStream(self, stream):
-        self._user_stream = bool(stream)
-        self._user_stream_value = int(stream) if stream else 0
-        check(_capi.lib().mimi_hip_contact_set_stream(self._handle(), C.c_void_p(stream) if stream else None))
-
-    def _follow_torch(self, *buffers):
-        if getattr(self, "_user_stream", False):
-            return
-        s = _capi.torch_stream_of(*buffers)
-        if s is not None or getattr(self, "_followed", None):
-            check(_capi.lib().mimi_hip_contact_set_stream(self._handle(), C.c_void_p(s) if s else None))
-            self._followed = s
 
     def _history(self):
         out = np.zeros(5)
@@ -529,22 +464,10 @@ class MortarContact(NonlinearBase):
         self._history()
 
     def AveragePressure(self):
-        n = C.c_int64(0)
-        check(_capi.lib().mimi_hip_contact_get_pressure(self._handle(), None, 0, C.byref(n)))
-        out = np.zeros(n.value)
-        check(_capi.lib().mimi_hip_contact_get_pressure(self._handle(), ptr(out), out.size, C.byref(n)))
-        return out
+        return self._sized_query("get_pressure", np.float64)
 
     def AddBoundaryGrad(self, current_u, grad):
         raise RuntimeError("Currently not implemented, use AddDomainResidualAndGrad")  # mortar_contact.hpp:142-149
-
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _capi.lib().mimi_hip_contact_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
 
 class FollowerPressure(NonlinearBase):
@@ -555,6 +478,7 @@ class FollowerPressure(NonlinearBase):
     Residual r(a,i) += sum_q w p_q N_a m_i (m: the non-normalised outward normal of the deformed face), tangent with
     dm/dx -- exact, not symmetric.  element_box = (begin, end): only the faces of the elements in that box (element slabs:
     every contribution lands in rows of the slab's own elements, no exchange of nodal values is needed)."""
+    _prefix = "pressure"
 
     def __init__(self, name, pattern, patch, axis, side, device=0, quadrature_order=-1, element_box=None):
         super().__init__(name)
@@ -562,27 +486,14 @@ class FollowerPressure(NonlinearBase):
         self.axis_, self.side_ = axis, side
         self.device_, self.quadrature_order_ = device, quadrature_order
         self.element_box_ = element_box
-        self._h = None
         self.last_area_ = 0.0
         self.last_force_ = np.zeros(patch.dim)
 
     def Prepare(self):
-        from . import splines
         L = _capi.lib()
-        p = self.patch_
-        # (a rational patch raises here: face_tables builds B-spline tables only)
-        dofs, N, dN, weight = splines.face_tables(p, self.axis_, self.side_, self.quadrature_order_, self.element_box_)
-        if len(dofs) == 0:
-            raise RuntimeError("no loaded boundary faces in this element box")
         t = _capi.PressureTables()
-        t.dim = p.dim
-        t.n_faces, t.n_dof = dofs.shape
-        t.n_quad = weight.shape[1]
-        t.n_nodes = p.n_nodes
-        x_ref = np.ascontiguousarray(p.control_points, dtype=np.float64)
-        self._keep = [dofs, N, dN, weight, x_ref]
-        t.dofs, t.N, t.dN_dxi, t.weight = dofs.ctypes.data, N.ctypes.data, dN.ctypes.data, weight.ctypes.data
-        t.x_ref = x_ref.ctypes.data
+        self._keep = _capi.fill_face_tables(t, self.patch_, self.axis_, self.side_, self.quadrature_order_, self.element_box_,
+                                            "no loaded boundary faces in this element box")
         t.csr_rowptr = ptr(self.pattern_.rowptr, "int64").value
         t.csr_col = ptr(self.pattern_.col, "int32").value
         h = C.c_void_p()
@@ -591,21 +502,9 @@ class FollowerPressure(NonlinearBase):
         self.n_faces_ = int(t.n_faces)
         return self
 
-    def _handle(self):
-        if self._h is None:
-            raise RuntimeError("Prepare() has not been called")
-        return self._h
-
-    def Synchronize(self):
-        check(_capi.lib().mimi_hip_pressure_synchronize(self._handle()))
-
     def FaceNodes(self):
         """sorted global node ids of the loaded faces: the order of a nodal pressure array"""
-        n = C.c_int64(0)
-        check(_capi.lib().mimi_hip_pressure_face_nodes(self._handle(), None, 0, C.byref(n)))
-        out = np.empty(n.value, dtype=np.int32)
-        check(_capi.lib().mimi_hip_pressure_face_nodes(self._handle(), ptr(out), out.size, C.byref(n)))
-        return out
+        return self._sized_query("face_nodes", np.int32)
 
     def SetPressure(self, value):
         """a float (uniform pressure) or an array of values at FaceNodes() (host array or device tensor); applies from the
@@ -619,18 +518,6 @@ class FollowerPressure(NonlinearBase):
             self._follow_torch(value)
         n = value.shape[0] if value.ndim == 1 else -1
         check(_capi.lib().mimi_hip_pressure_set_nodal(self._handle(), fptr(value), n))
-
-    def SetStream(self, stream):
-        self._user_stream = bool(stream)
-        check(_capi.lib().mimi_hip_pressure_set_stream(self._handle(), C.c_void_p(stream) if stream else None))
-
-    def _follow_torch(self, *buffers):
-        if getattr(self, "_user_stream", False):
-            return
-        s = _capi.torch_stream_of(*buffers)
-        if s is not None or getattr(self, "_followed", None):
-            check(_capi.lib().mimi_hip_pressure_set_stream(self._handle(), C.c_void_p(s) if s else None))
-            self._followed = s
 
     def AddBoundaryResidual(self, current_u, residual):
         self._follow_torch(current_u, residual)
@@ -654,16 +541,8 @@ class FollowerPressure(NonlinearBase):
     def AddBoundaryGrad(self, current_u, grad):
         raise RuntimeError("Currently not implemented, use AddBoundaryResidualAndGrad")
 
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _capi.lib().mimi_hip_pressure_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
-
-class CouplingSurface:
+class CouplingSurface(_capi.Handle):
     """The coupling surface of one face of a B-spline patch (include/mimi_hip.h: mimi_hip_surface_*): what a fluid partner
     exchanges with the solid every iteration of the reference's fixed-point loop (fixed_point_solve2 / fixed_point_advance2
     / advance_time2, py/py_solid.cpp:443-511), on the face tables, rule and outward normal of FollowerPressure
@@ -679,53 +558,23 @@ class CouplingSurface:
     by fold.Add.  The load is dead within a solve and has no tangent: the coupling iteration carries its dependence on the
     geometry (the follower load with an exact tangent is FollowerPressure's).  Points / AddLoad are the C ABI as it stands
     (u in the patch's numbering, host arrays or device tensors, AddLoad adds into f)."""
+    _prefix = "surface"
 
     def __init__(self, patch, axis, side, device=0, quadrature_order=-1, fold=None):
         self.patch_, self.axis_, self.side_ = patch, axis, side
         self.device_, self.quadrature_order_, self.fold_ = device, quadrature_order, fold
-        self._h = None
         self.load_ = None
 
     def Prepare(self):
-        from . import splines
         L = _capi.lib()
-        p = self.patch_
-        # (a rational patch raises here: face_tables builds B-spline tables only)
-        dofs, N, dN, weight = splines.face_tables(p, self.axis_, self.side_, self.quadrature_order_)
         t = _capi.PressureTables()
-        t.dim = p.dim
-        t.n_faces, t.n_dof = dofs.shape
-        t.n_quad = weight.shape[1]
-        t.n_nodes = p.n_nodes
-        x_ref = np.ascontiguousarray(p.control_points, dtype=np.float64)
-        t.dofs, t.N, t.dN_dxi, t.weight = dofs.ctypes.data, N.ctypes.data, dN.ctypes.data, weight.ctypes.data
-        t.x_ref = x_ref.ctypes.data
+        keep = _capi.fill_face_tables(t, self.patch_, self.axis_, self.side_, self.quadrature_order_)   # (copied at create)
         h = C.c_void_p()
         check(L.mimi_hip_surface_create(C.byref(t), self.device_, C.byref(h)))
         self._h = h
         self.n_faces_, self.n_q_ = int(t.n_faces), int(t.n_quad)
         self.n_points_ = int(L.mimi_hip_surface_n_points(h))
         return self
-
-    def _handle(self):
-        if self._h is None:
-            raise RuntimeError("Prepare() has not been called")
-        return self._h
-
-    def SetStream(self, stream):
-        self._user_stream = bool(stream)
-        check(_capi.lib().mimi_hip_surface_set_stream(self._handle(), C.c_void_p(stream) if stream else None))
-
-    def _follow_torch(self, *buffers):
-        if getattr(self, "_user_stream", False):
-            return
-        s = _capi.torch_stream_of(*buffers)
-        if s is not None or getattr(self, "_followed", None):
-            check(_capi.lib().mimi_hip_surface_set_stream(self._handle(), C.c_void_p(s) if s else None))
-            self._followed = s
-
-    def Synchronize(self):
-        check(_capi.lib().mimi_hip_surface_synchronize(self._handle()))
 
     def Points(self, u, x, normal, weight):
         self._follow_torch(u, x, normal, weight)
@@ -789,14 +638,6 @@ class CouplingSurface:
             f = f_f
         self.load_ = f
 
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _capi.lib().mimi_hip_surface_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
 
 def periodic_node_map(n_ctrl, axes):
     """Node map of a lexicographically numbered patch (n_ctrl nodes per direction, direction 0 fastest) made periodic along
@@ -824,18 +665,18 @@ def periodic_node_map(n_ctrl, axes):
     return out.reshape(-1)
 
 
-class PeriodicFold:
+class PeriodicFold(_capi.Handle):
     """The periodic fold of include/mimi_hip.h (mimi_hip_fold_*) on one device: P is the 0/1 map from the folded dofs to
     the unwrapped dofs of `pattern` (an integrator's structured pattern), given per node by node_map.
     Expand(u_f, u_u): u_u = P u_f.  Add(r_u, r_f, A_u, A_base, A_f): r_f += P^T r_u, A_f = A_base + P^T A_u P (A_base is
     A_f: "+="; None: A_f = P^T A_u P; A_u None: residual only; r_u / r_f None: matrix only).  Host arrays or device
     tensors."""
+    _prefix = "fold"
 
     def __init__(self, pattern, node_map, dim, device=0):
         self.pattern_u_ = pattern
         self.node_map_ = np.ascontiguousarray(node_map, dtype=np.int64)
         self.dim_, self.device_ = int(dim), device
-        self._h = None
 
     def Prepare(self):
         L = _capi.lib()
@@ -850,11 +691,6 @@ class PeriodicFold:
         self.n_f_ = self.n_nodes_f_ * self.dim_
         self.n_u_ = len(self.node_map_) * self.dim_
         return self
-
-    def _handle(self):
-        if self._h is None:
-            raise RuntimeError("Prepare() has not been called")
-        return self._h
 
     def Info(self, what):
         return int(_capi.lib().mimi_hip_fold_info(self._handle(), what))
@@ -872,21 +708,6 @@ class PeriodicFold:
         check(_capi.lib().mimi_hip_fold_pattern(self._handle(), ptr(rowptr), ptr(col)))
         return CSRPattern(rowptr, col, self.nnz_f_)
 
-    def SetStream(self, stream):
-        self._user_stream = bool(stream)
-        check(_capi.lib().mimi_hip_fold_set_stream(self._handle(), C.c_void_p(stream) if stream else None))
-
-    def _follow_torch(self, *buffers):
-        if getattr(self, "_user_stream", False):
-            return
-        s = _capi.torch_stream_of(*buffers)
-        if s is not None or getattr(self, "_followed", None):
-            check(_capi.lib().mimi_hip_fold_set_stream(self._handle(), C.c_void_p(s) if s else None))
-            self._followed = s
-
-    def Synchronize(self):
-        check(_capi.lib().mimi_hip_fold_synchronize(self._handle()))
-
     def Expand(self, u_f, u_u):
         self._follow_torch(u_f, u_u)
         check(_capi.lib().mimi_hip_fold_expand(self._handle(), fptr(u_f), fptr(u_u)))
@@ -895,11 +716,3 @@ class PeriodicFold:
     def Add(self, r_u, r_f, A_u=None, A_base=None, A_f=None):
         self._follow_torch(r_u, r_f, A_u, A_base, A_f)
         check(_capi.lib().mimi_hip_fold_add(self._handle(), fptr(r_u), fptr(r_f), fptr(A_u), fptr(A_base), fptr(A_f)))
-
-    def __del__(self):
-        try:
-            if self._h is not None:
-                _capi.lib().mimi_hip_fold_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass

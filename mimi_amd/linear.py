@@ -9,9 +9,10 @@ from . import _capi
 from ._capi import check, fptr, ptr
 
 
-class LinearSolver:
+class LinearSolver(_capi.Handle):
     """One per CSR pattern and list of essential dofs.  Vectors / CSR values may be numpy arrays (staged) or torch
     device tensors (in place)."""
+    _prefix = "linear"
 
     # mfem::GMRESSolver as configured by the reference (py_nonlinear_solid.cpp:331-336); kdim: mfem's default m
     rel_tol = 1e-8
@@ -31,19 +32,6 @@ class LinearSolver:
                                                  ess.size, device, C.byref(h)))
         self._h = h
         self.final_iter_, self.final_norm_, self.converged_ = 0, 0.0, False
-
-    def SetStream(self, stream):
-        self._user_stream = bool(stream)
-        check(_capi.lib().mimi_hip_linear_set_stream(self._h, C.c_void_p(stream) if stream else None))
-
-    def _follow_torch(self, *buffers):
-        # a handle that was never given a stream launches on torch's current stream when it gets CUDA tensors
-        if getattr(self, "_user_stream", False):
-            return
-        s = _capi.torch_stream_of(*buffers)
-        if s is not None or getattr(self, "_followed", None):
-            check(_capi.lib().mimi_hip_linear_set_stream(self._h, C.c_void_p(s) if s else None))
-            self._followed = s
 
     def RowGroup(self):
         """consecutive rows sharing one column list that the products read once (3, 2 or 1)"""
@@ -83,11 +71,3 @@ class LinearSolver:
                                              1 if self.use_jacobi else 0, C.byref(it), C.byref(nrm), C.byref(conv)))
         self.final_iter_, self.final_norm_, self.converged_ = it.value, nrm.value, bool(conv.value)
         return x
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                _capi.lib().mimi_hip_linear_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass

@@ -1,16 +1,23 @@
 #!/bin/bash
-# usage: scratch/ab_lib.sh NAME [GIT_REV|-] [extra hipcc flags...]  ->  scratch/lib_NAME.so: domain.hip of the working tree (or of
-# GIT_REV) compiled beside the other objects of mimi_amd/lib/obj, for same-box A/B timing
-# (MIMI_HIP_LIBRARY=scratch/lib_NAME.so python bench.py ...)
+# usage: scratch/ab_lib.sh NAME [GIT_REV|-] [extra hipcc flags...]  ->  scratch/lib_NAME.so: every source of
+# mimi_amd.build.SOURCES, of the working tree (no revision, or "-") or of GIT_REV, compiled with the build's flags plus the
+# extra ones, for same-box A/B runs (MIMI_HIP_LIBRARY=scratch/lib_NAME.so python bench.py ...).  The library of a revision
+# is built where the git history is and travels as the git-ignored scratch/lib_NAME.so.
 set -e
 name=$1; rev=$2; shift; shift || true
-src=/root/repo/mimi_amd/csrc
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
+work=$(mktemp -d); trap 'rm -rf "$work"' EXIT
+tree=$root
 if [ -n "$rev" ] && [ "$rev" != "-" ]; then
-  rm -rf /tmp/ab_$name && mkdir -p /tmp/ab_$name
-  (git archive $rev mimi_amd/csrc include) | tar -x -C /tmp/ab_$name
-  src=/tmp/ab_$name/mimi_amd/csrc
+  git -C "$root" archive "$rev" mimi_amd/build.py mimi_amd/csrc include | tar -x -C "$work"
+  tree=$work
 fi
-obj=/root/repo/mimi_amd/lib/obj
-(cd $src && hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result "$@" -c domain.hip -o /tmp/domain_$name.o)
-hipcc --offload-arch=gfx950 -shared -fPIC -o /root/repo/scratch/lib_$name.so /tmp/domain_$name.o $obj/tensor_p3.o $obj/contact.o $obj/krylov.o $obj/exchange.o
+sources=$(python3 -c "import runpy, sys; print(' '.join(runpy.run_path(sys.argv[1])['SOURCES']))" "$tree/mimi_amd/build.py")
+cd "$tree/mimi_amd/csrc"
+pids=()
+for s in $sources; do
+  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wno-unused-result "$@" -c "$s" -o "$work/${s%.hip}.o" & pids+=($!)
+done
+for p in "${pids[@]}"; do wait "$p"; done
+hipcc --offload-arch=gfx950 -shared -fPIC -o "$root/scratch/lib_$name.so" $(for s in $sources; do echo "$work/${s%.hip}.o"; done)
 echo scratch/lib_$name.so

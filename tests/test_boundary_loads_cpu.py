@@ -126,7 +126,8 @@ def test_traction_refuses_a_rational_patch():
                     reason="no hipcc: nothing to compile")
 def test_pressure_kernels_spill_no_register():
     from mimi_amd import isa_lint as L
-    spills = {n: c for n, c in L.spill_counts(L.assembly("pressure.hip")).items() if "pressure" in n}
-    # face and gather kernels for DIM 2 / 3 with and without the tangent, the fixed-order sum, the pair positions
+    spills = {n: c for n, c in L.spill_counts(L.assembly("pressure.hip")).items() if "pressure" in n or "face_" in n}
+    # face kernels and the shared row gather (face_common.hpp) for DIM 2 / 3 with and without the tangent, the shared
+    # fixed-order sum and pair positions
     assert len(spills) == 10, sorted(spills)
     assert all(c == 0 for c in spills.values()), spills

@@ -153,4 +153,27 @@ inline Tables1D make_tables_1d(const double* knots, int n_knots, int p, int nq, 
   return t;
 }
 
+// NURBS weights of a patch with nc[d] control points per direction (nc[d] = 1 beyond dim): accepted when they are a tensor
+// product of 1-D weights (then the rational basis factorises); w1d[d] = the weights along the line through node 0
+inline void factorise_nurbs_weights(const double* weights, int dim, const int64_t nc[3], std::vector<double> w1d[3]) {
+  const int64_t stride[3] = {1, nc[0], nc[0] * nc[1]};
+  const double c = weights[0];
+  if (!(c > 0.0)) fail("NURBS weights must be positive");
+  for (int d = 0; d < dim; ++d) {
+    w1d[d].resize(nc[d]);
+    for (int64_t a = 0; a < nc[d]; ++a) w1d[d][a] = weights[a * stride[d]];
+  }
+  const double cpow = dim == 3 ? c * c : c;
+  for (int64_t a2 = 0; a2 < nc[2]; ++a2)
+    for (int64_t a1 = 0; a1 < nc[1]; ++a1)
+      for (int64_t a0 = 0; a0 < nc[0]; ++a0) {
+        const double w = weights[a0 + a1 * stride[1] + a2 * stride[2]];
+        const double prod = w1d[0][a0] * w1d[1][a1] * (dim == 3 ? w1d[2][a2] : 1.0);
+        if (!(w > 0.0)) fail("NURBS weights must be positive");
+        if (std::fabs(w * cpow - prod) > 1e-12 * std::fabs(prod))
+          fail("NURBS weights are not a tensor product of 1-D weights (node %lld): pass this patch as flat tables "
+               "(mimi_hip_domain_create)", (long long)(a0 + a1 * stride[1] + a2 * stride[2]));
+      }
+}
+
 }  // namespace mimi_hip

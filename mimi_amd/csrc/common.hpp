@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -58,6 +59,38 @@ inline void ensure_dynamic_lds(const void* kernel, int bytes) {
   }
 }
 
+// Every kernel launch of the converted sources: above the 64 KB every kernel may use unasked, the dynamic-LDS limit is raised
+// first (the nine-block and symmetric-half kernels ask for 69-76 KB, so this is the rule their launchers applied
+// unconditionally); kernels under the limit get no attribute call.
+template<typename... Params, typename... Args>
+void launch(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+  if (lds_bytes > 64 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)lds_bytes);
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, args...);
+  MH_HIP(hipGetLastError());
+}
+
+// The environment switches of the library: the only getenv of csrc, one accessor per switch.
+// WHEN a switch is read is part of its behaviour -- the tests flip the per-create and per-launch ones inside one process.
+inline const char* env_text(const char* name) { return getenv(name); }
+inline bool env_starts(const char* name, char c) {
+  const char* v = env_text(name);
+  return v && v[0] == c;
+}
+// once per process, at first use
+inline bool env_general_no_two_phase() { static const bool on = env_starts("MIMI_HIP_GENERAL_NO_TWO_PHASE", '1'); return on; }
+inline bool env_general_no_wpe() { static const bool on = env_starts("MIMI_HIP_GENERAL_NO_WPE", '1'); return on; }
+inline bool env_general_no_mfma() { static const bool on = env_starts("MIMI_HIP_GENERAL_NO_MFMA", '1'); return on; }
+inline bool env_tensor_variant_full() { static const bool on = env_starts("MIMI_HIP_TENSOR_VARIANT", 'w'); return on; }
+inline bool env_residual_variant_element() { static const bool on = env_starts("MIMI_HIP_RESIDUAL_VARIANT", 'e'); return on; }
+// at every create
+inline bool env_force_general() { return env_starts("MIMI_HIP_FORCE_GENERAL", '1'); }
+inline bool env_keep_general() { return env_starts("MIMI_HIP_KEEP_GENERAL", '1'); }
+inline bool env_no_structured() { return env_starts("MIMI_HIP_NO_STRUCTURED", '1'); }
+// at every launch of the degree-3 contraction
+inline bool env_p3_contract_cxx() {
+  const char* v = env_text("MIMI_HIP_P3_CONTRACT");
+  return v && !strcmp(v, "cxx");
+}
 
 void set_last_error(const std::string& s);
 

@@ -54,15 +54,9 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   hipEvent_t phase_ev[4] = {nullptr, nullptr, nullptr, nullptr};   // [3]: end of the material pre-pass, when there is one
   bool phase_has_prepass = false;
 
-  // mimi_hip_domain_integrate / _gather: 0 = an assembly runs both phases, 1 = phase 1 only, 2 = phase 2 only, over the
-  // node window [gather_begin, gather_end)
-  int phase_select = 0;
-  int gather_begin[3] = {0, 0, 0}, gather_end[3] = {0, 0, 0};
+  // mimi_hip_domain_integrate has stored the element pieces mimi_hip_domain_gather reads (what one call runs, and over
+  // which nodes, is the call's own: DomainCall, domain_call.hpp)
   bool integrated = false;
-  // mimi_hip_domain_add_residual_and_grad_from: the array the row gathers read the old values from during this call
-  // (device; nullptr = the output array itself, the plain "+=").  Paths without a row gather take it by a copy
-  // (consume_base below).
-  const double* A_base = nullptr;
   // kernel family of the last assembly / state commit on this handle (mimi_hip_domain_info(h, 7)): 0 none yet,
   // 1 two-phase tensor degree 2, 2 two-phase tensor degree 3, 3 small-element tensor kernel, 4 general kernels
   int last_family = 0;
@@ -72,12 +66,3 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
 
   ~mimi_hip_domain_s();
 };
-
-namespace mimi_hip {
-// for an assembly route that adds into the value array in place (colour kernel, atomics): A <- A_base first, then "+="
-inline void consume_base(mimi_hip_domain_s* h, double* A) {
-  if (h->A_base && A && h->A_base != A)
-    MH_HIP(hipMemcpyAsync(A, h->A_base, (size_t)h->nnz * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-  h->A_base = nullptr;
-}
-}  // namespace mimi_hip

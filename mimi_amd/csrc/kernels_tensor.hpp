@@ -23,7 +23,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "domain.hpp"
+#include "domain_call.hpp"
 #include "materials.hpp"
 #include "materials_other.hpp"
 
@@ -83,7 +83,7 @@ inline bool tensor_supported(int dim, const int* degree, int nq) {
   return dim == 2 && degree[0] >= 1 && degree[0] <= 3;
 }
 
-inline TensorArgs tensor_args(mimi_hip_domain_s* h, const double* u, double* r, double* A, double gf) {
+inline TensorArgs tensor_args(mimi_hip_domain_s* h, const DomainCall& c) {
   TensorArgs a{};
   for (int d = 0; d < 3; ++d) {
     a.box_begin[d] = h->el_begin[d];
@@ -92,9 +92,9 @@ inline TensorArgs tensor_args(mimi_hip_domain_s* h, const double* u, double* r, 
     a.tabD[d] = h->tab1d.ptr + h->tab_off_D[d];
   }
   for (int d = 0; d < 3; ++d) {
-    if (h->phase_select == 2) {
-      a.win_begin[d] = h->gather_begin[d];
-      a.win_n[d] = h->gather_end[d] - h->gather_begin[d];
+    if (c.phases == DomainCall::GATHER_ONLY) {
+      a.win_begin[d] = c.gather_begin[d];
+      a.win_n[d] = c.gather_end[d] - c.gather_begin[d];
     } else {
       a.win_begin[d] = a.box_begin[d];
       a.win_n[d] = a.box_n[d] + h->degree[d];
@@ -117,11 +117,11 @@ inline TensorArgs tensor_args(mimi_hip_domain_s* h, const double* u, double* r, 
     a.first[d] = h->first1d.ptr + h->first_off[d];
   }
   a.rowptr = h->rowptr;
-  a.u = u;
-  a.r = r;
-  a.A = A;
-  a.A_base = (h->A_base && A) ? h->A_base : A;
-  a.grad_factor = gf;
+  a.u = c.u;
+  a.r = c.r;
+  a.A = c.A;
+  a.A_base = c.A_old();
+  a.grad_factor = c.grad_factor;
   a.dt = h->dt;
   a.mat = h->mat;
   a.state = StateView{h->eqps.ptr, h->temperature.ptr, h->plastic_strain.ptr, h->n_pts, h->state2.ptr};

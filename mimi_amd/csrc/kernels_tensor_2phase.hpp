@@ -228,8 +228,7 @@ inline bool two_phase_supported(const mimi_hip_domain_s* h) {
 
 inline void launch_tensor_p2(mimi_hip_domain_s* h, const TensorArgs& a) {
   const int64_t n_nodes = (int64_t)a.win_n[0] * a.win_n[1] * a.win_n[2];   // nodes of the shard (or of the gather window)
-  hipLaunchKernelGGL(tensor_p2_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, h->stream, a, n_nodes);
-  MH_HIP(hipGetLastError());
+  launch(tensor_p2_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, h->stream, a, n_nodes);
 }
 
 }  // namespace mimi_hip

@@ -553,35 +553,29 @@ __global__ __launch_bounds__(256) void tensor_residual_col_gather_kernel(TensorA
 }
 
 inline void launch_tensor_residual(mimi_hip_domain_s* h, TensorArgs a) {
+  const int kind = h->mat.m.kind;
   // MIMI_HIP_RESIDUAL_VARIANT=element: one wave per element (rounds 1-3; kept for A/B timing)
-  static const bool per_element = getenv("MIMI_HIP_RESIDUAL_VARIANT") && getenv("MIMI_HIP_RESIDUAL_VARIANT")[0] == 'e';
-  if (!per_element && h->mat.m.kind == MIMI_HIP_MAT_NEOHOOKEAN) {
+  if (!env_residual_variant_element() && kind == MIMI_HIP_MAT_NEOHOOKEAN) {
     const int n_cols = a.box_n[0] * a.box_n[1];
     h->scratch_r.resize(std::max((size_t)h->n_el * 3 * 27, (size_t)n_cols * (a.box_n[2] + 2) * 27));
     a.scratch_r = h->scratch_r.ptr;
     const unsigned blocks = (unsigned)((n_cols + 3) / 4);
     const size_t lds = (size_t)4 * ResidualColLds::per_wave * sizeof(double);
-    if (lds > 64 * 1024) ensure_dynamic_lds(reinterpret_cast<const void*>(tensor_residual_col_kernel<MIMI_HIP_MAT_NEOHOOKEAN>), (int)lds);
-    hipLaunchKernelGGL(tensor_residual_col_kernel<MIMI_HIP_MAT_NEOHOOKEAN>, dim3(blocks), dim3(256), lds, h->stream, a, n_cols);
-    MH_HIP(hipGetLastError());
+    launch(tensor_residual_col_kernel<MIMI_HIP_MAT_NEOHOOKEAN>, dim3(blocks), dim3(256), lds, h->stream, a, n_cols);
     const int64_t n_nodes = (int64_t)(a.box_n[0] + 2) * (a.box_n[1] + 2) * (a.box_n[2] + 2);   // nodes of the shard
-    hipLaunchKernelGGL(tensor_residual_col_gather_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, h->stream, a, n_nodes);
-    MH_HIP(hipGetLastError());
+    launch(tensor_residual_col_gather_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, h->stream, a, n_nodes);
     return;
   }
   h->scratch_r.resize((size_t)h->n_el * 3 * 27);
   a.scratch_r = h->scratch_r.ptr;
   const unsigned blocks = (unsigned)((h->n_el + 3) / 4);
-  if (h->mat.m.kind != MIMI_HIP_MAT_NEOHOOKEAN && h->mat.m.kind != MIMI_HIP_MAT_J2)
-    hipLaunchKernelGGL(tensor_residual_kernel<WGS_KIND_RECORD>, dim3(blocks), dim3(256), 0, h->stream, a, (int)h->n_el);
-  else if (h->mat.m.kind == MIMI_HIP_MAT_NEOHOOKEAN)
-    hipLaunchKernelGGL(tensor_residual_kernel<MIMI_HIP_MAT_NEOHOOKEAN>, dim3(blocks), dim3(256), 0, h->stream, a, (int)h->n_el);
-  else
-    hipLaunchKernelGGL(tensor_residual_kernel<MIMI_HIP_MAT_J2>, dim3(blocks), dim3(256), 0, h->stream, a, (int)h->n_el);
-  MH_HIP(hipGetLastError());
+  by_material_family(kind, [&](auto K) {
+    auto kernel = decltype(K)::value != 0 ? tensor_residual_kernel<WGS_KIND_RECORD>
+                  : kind == MIMI_HIP_MAT_NEOHOOKEAN ? tensor_residual_kernel<MIMI_HIP_MAT_NEOHOOKEAN> : tensor_residual_kernel<MIMI_HIP_MAT_J2>;
+    launch(kernel, dim3(blocks), dim3(256), 0, h->stream, a, (int)h->n_el);
+  });
   const int64_t n_nodes = (int64_t)(a.box_n[0] + 2) * (a.box_n[1] + 2) * (a.box_n[2] + 2);   // nodes of the shard
-  hipLaunchKernelGGL(tensor_residual_gather_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, h->stream, a, n_nodes);
-  MH_HIP(hipGetLastError());
+  launch(tensor_residual_gather_kernel, dim3((unsigned)((n_nodes + 3) / 4)), dim3(256), 0, h->stream, a, n_nodes);
 }
 
 }  // namespace mimi_hip

@@ -998,7 +998,7 @@ __global__ __launch_bounds__(256, 2) void tensor_wgs_kernel(TensorArgs p) {
   }
 }
 
-inline void launch_tensor_wgs(mimi_hip_domain_s* h, TensorArgs a) {
+inline void launch_tensor_wgs(mimi_hip_domain_s* h, const DomainCall& c, TensorArgs a) {
   h->scratch_k.resize((size_t)h->n_el * P2Block::size);
   h->scratch_r.resize((size_t)h->n_el * 3 * 27);
   a.scratch_k = h->scratch_k.ptr;
@@ -1007,45 +1007,32 @@ inline void launch_tensor_wgs(mimi_hip_domain_s* h, TensorArgs a) {
   a.n_units_v = a.box_n[1];
   const size_t lds = WgsLds::total * sizeof(double);
   const int kind = h->mat.m.kind;
-  const bool record = kind != MIMI_HIP_MAT_NEOHOOKEAN && kind != MIMI_HIP_MAT_J2;
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[0], h->stream));   // phase 1 = material pre-pass + nine-block kernel
-  if (kind != MIMI_HIP_MAT_NEOHOOKEAN) {
-    h->scratch_pt.resize((size_t)h->n_el * (record ? WGS_REC_FIELDS : WGS_PT_FIELDS) * 64);
+  const bool has_prepass = kind != MIMI_HIP_MAT_NEOHOOKEAN;
+  if (has_prepass) {
+    h->scratch_pt.resize((size_t)h->n_el * (material_closed_form(kind) ? WGS_PT_FIELDS : WGS_REC_FIELDS) * 64);
     a.scratch_pt = h->scratch_pt.ptr;
-    if (h->phase_select != 2) {
-      void (*point_kernel)(TensorArgs, int) =
-          kind == MIMI_HIP_MAT_J2 ? tensor_point_kernel<0>
-          : kind == MIMI_HIP_MAT_STVK ? tensor_point_kernel<MIMI_HIP_MAT_STVK>
-          : kind == MIMI_HIP_MAT_J2LINEAR ? tensor_point_kernel<MIMI_HIP_MAT_J2LINEAR>
-          : kind == MIMI_HIP_MAT_J2SIMO ? tensor_point_kernel<MIMI_HIP_MAT_J2SIMO> : tensor_point_kernel<MIMI_HIP_MAT_J2LOG>;
-      hipLaunchKernelGGL(point_kernel, dim3((unsigned)((h->n_el + 3) / 4)), dim3(256), 0, h->stream, a, (int)h->n_el);
-      MH_HIP(hipGetLastError());
-    }
   }
-  h->phase_has_prepass = kind != MIMI_HIP_MAT_NEOHOOKEAN;
-  if (h->phase_timing && h->phase_has_prepass) MH_HIP(hipEventRecord(h->phase_ev[3], h->stream));
-  auto kernel = kind == MIMI_HIP_MAT_NEOHOOKEAN ? tensor_wgs_kernel<MIMI_HIP_MAT_NEOHOOKEAN>
-                : record ? tensor_wgs_kernel<WGS_KIND_RECORD> : tensor_wgs_kernel<MIMI_HIP_MAT_J2>;
-  ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)lds);
-  if (h->phase_select != 2) {
-    hipLaunchKernelGGL(kernel, dim3(a.box_n[0] * a.box_n[1]), dim3(256), lds, h->stream, a);
-    MH_HIP(hipGetLastError());
-  }
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[1], h->stream));
-  if (h->phase_select != 1) launch_tensor_p2(h, a);
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[2], h->stream));
+  // phase 1 = material pre-pass + nine-block kernel
+  by_material_family(kind, [&](auto K) {
+    constexpr int FK = decltype(K)::value;
+    run_two_phase(
+        h, c, has_prepass,
+        [&] { launch(tensor_point_kernel<FK>, dim3((unsigned)((h->n_el + 3) / 4)), dim3(256), 0, h->stream, a, (int)h->n_el); },
+        [&] {
+          // (the other four materials come to the nine-block kernel as the pre-pass's tangent record)
+          auto kernel = FK != 0 ? tensor_wgs_kernel<WGS_KIND_RECORD>
+                        : kind == MIMI_HIP_MAT_NEOHOOKEAN ? tensor_wgs_kernel<MIMI_HIP_MAT_NEOHOOKEAN> : tensor_wgs_kernel<MIMI_HIP_MAT_J2>;
+          launch(kernel, dim3(a.box_n[0] * a.box_n[1]), dim3(256), lds, h->stream, a);
+        },
+        [&] { launch_tensor_p2(h, a); });
+  });
 }
 
 // DomainPostTimeAdvance at degree 2: the pre-pass kernel in its commit mode
 inline void launch_tensor_p2_post(mimi_hip_domain_s* h, TensorArgs a) {
-  const int kind = h->mat.m.kind;
-  void (*kernel)(TensorArgs, int) =
-      (kind == MIMI_HIP_MAT_J2 || kind == MIMI_HIP_MAT_NEOHOOKEAN) ? tensor_point_kernel<0, 1>
-      : kind == MIMI_HIP_MAT_STVK ? tensor_point_kernel<MIMI_HIP_MAT_STVK, 1>
-      : kind == MIMI_HIP_MAT_J2LINEAR ? tensor_point_kernel<MIMI_HIP_MAT_J2LINEAR, 1>
-      : kind == MIMI_HIP_MAT_J2SIMO ? tensor_point_kernel<MIMI_HIP_MAT_J2SIMO, 1> : tensor_point_kernel<MIMI_HIP_MAT_J2LOG, 1>;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)((h->n_el + 3) / 4)), dim3(256), 0, h->stream, a, (int)h->n_el);
-  MH_HIP(hipGetLastError());
+  by_material_family(h->mat.m.kind, [&](auto K) {
+    launch(tensor_point_kernel<decltype(K)::value, 1>, dim3((unsigned)((h->n_el + 3) / 4)), dim3(256), 0, h->stream, a, (int)h->n_el);
+  });
 }
 
 }  // namespace mimi_hip

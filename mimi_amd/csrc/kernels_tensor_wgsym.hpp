@@ -448,7 +448,7 @@ __global__ __launch_bounds__(256, 2) void tensor_wgsym_kernel(TensorArgs p) {
   }
 }
 
-inline void launch_tensor_wgsym(mimi_hip_domain_s* h, TensorArgs a) {
+inline void launch_tensor_wgsym(mimi_hip_domain_s* h, const DomainCall& c, TensorArgs a) {
   h->scratch_k.resize((size_t)h->n_el * P2Block::size);
   h->scratch_r.resize((size_t)h->n_el * 3 * 27);
   a.scratch_k = h->scratch_k.ptr;
@@ -456,8 +456,6 @@ inline void launch_tensor_wgsym(mimi_hip_domain_s* h, TensorArgs a) {
   a.n_units_u = a.box_n[0];
   a.n_units_v = a.box_n[1];
   const size_t lds = WgsymLds::total * sizeof(double);
-  auto kernel = tensor_wgsym_kernel<MIMI_HIP_MAT_NEOHOOKEAN>;
-  ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), (int)lds);
   // several columns per workgroup (the pipeline of the four waves then runs through the column boundaries: one
   // prologue per workgroup instead of one per column) as long as the grid still fills the chip several times over
   // few columns (the boundary layers of a multi-GPU slab): each column is cut into segments with their own workgroup, so
@@ -467,15 +465,13 @@ inline void launch_tensor_wgsym(mimi_hip_domain_s* h, TensorArgs a) {
   a.seg_len = a.box_n[2] / nseg;
   const int n_cols_all = a.box_n[0] * a.box_n[1] * nseg;
   a.cols_per_wg = n_cols_all / WGSYM_MIN_WGS < 1 ? 1 : (n_cols_all / WGSYM_MIN_WGS > WGSYM_MAX_COLS ? WGSYM_MAX_COLS : n_cols_all / WGSYM_MIN_WGS);
-  h->phase_has_prepass = false;
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[0], h->stream));
-  if (h->phase_select != 2) {
-    hipLaunchKernelGGL(kernel, dim3((n_cols_all + a.cols_per_wg - 1) / a.cols_per_wg), dim3(256), lds, h->stream, a);
-    MH_HIP(hipGetLastError());
-  }
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[1], h->stream));
-  if (h->phase_select != 1) launch_tensor_p2(h, a);
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[2], h->stream));
+  run_two_phase(
+      h, c, false, [] {},
+      [&] {
+        launch(tensor_wgsym_kernel<MIMI_HIP_MAT_NEOHOOKEAN>, dim3((n_cols_all + a.cols_per_wg - 1) / a.cols_per_wg), dim3(256), lds,
+               h->stream, a);
+      },
+      [&] { launch_tensor_p2(h, a); });
 }
 
 }  // namespace mimi_hip

@@ -7,11 +7,11 @@
 
 namespace mimi_hip {
 
-inline bool two_phase_supported(const mimi_hip_domain_s* h);                     // kernels_tensor_2phase.hpp
-inline void launch_tensor_wgs(mimi_hip_domain_s* h, TensorArgs a);               // kernels_tensor_wgs.hpp
-inline void launch_tensor_wgsym(mimi_hip_domain_s* h, TensorArgs a);             // kernels_tensor_wgsym.hpp
-inline void launch_tensor_residual(mimi_hip_domain_s* h, TensorArgs a);          // kernels_tensor_residual.hpp
-inline void launch_tensor_p2_post(mimi_hip_domain_s* h, TensorArgs a);           // kernels_tensor_wgs.hpp
+inline bool two_phase_supported(const mimi_hip_domain_s* h);                                 // kernels_tensor_2phase.hpp
+inline void launch_tensor_wgs(mimi_hip_domain_s* h, const DomainCall& c, TensorArgs a);      // kernels_tensor_wgs.hpp
+inline void launch_tensor_wgsym(mimi_hip_domain_s* h, const DomainCall& c, TensorArgs a);    // kernels_tensor_wgsym.hpp
+inline void launch_tensor_residual(mimi_hip_domain_s* h, TensorArgs a);                      // kernels_tensor_residual.hpp
+inline void launch_tensor_p2_post(mimi_hip_domain_s* h, TensorArgs a);                       // kernels_tensor_wgs.hpp
 
 // can this handle's assembly run on the tensor kernels?  (3-D degree 2 and 3 have the two-phase kernels only: a patch
 // whose CSR is not the structured pattern, or with repeated interior knots, takes the general kernels)
@@ -22,31 +22,23 @@ inline bool tensor_usable(const mimi_hip_domain_s* h) {
 }
 
 // returns the kernel family that ran (mimi_hip_domain_s::last_family)
-inline int launch_tensor(mimi_hip_domain_s* h, int grad, const double* u, double* r, double* A, double gf) {
-  TensorArgs a = tensor_args(h, u, r, A, gf);
+inline int launch_tensor(mimi_hip_domain_s* h, const DomainCall& c) {
+  TensorArgs a = tensor_args(h, c);
   if (h->degree[0] == 3) {
-    launch_tensor_p3(h, grad, a);
+    launch_tensor_p3(h, c, a);
     return 2;
   }
   // MIMI_HIP_TENSOR_VARIANT=wgs: the full nine-block kernel also for hyperelastic materials (default: symmetric half)
-  static const char* variant = getenv("MIMI_HIP_TENSOR_VARIANT");
-  if (grad) {
-    const bool want_full = variant && variant[0] == 'w';
-    if (h->mat.m.kind == MIMI_HIP_MAT_NEOHOOKEAN && !want_full) launch_tensor_wgsym(h, a);
-    else launch_tensor_wgs(h, a);
-  } else {
-    launch_tensor_residual(h, a);
-  }
+  const bool want_full = env_tensor_variant_full();
+  if (!c.grad) launch_tensor_residual(h, a);
+  else if (h->mat.m.kind == MIMI_HIP_MAT_NEOHOOKEAN && !want_full) launch_tensor_wgsym(h, c, a);
+  else launch_tensor_wgs(h, c, a);
   return 1;
 }
 
-inline void launch_tensor_post(mimi_hip_domain_s* h, const double* u) {
-  TensorArgs a = tensor_args(h, u, nullptr, nullptr, 0.0);
-  if (h->degree[0] == 3) {
-    launch_tensor_p3_post(h, a);
-    return;
-  }
-  launch_tensor_p2_post(h, a);
+inline void launch_tensor_post(mimi_hip_domain_s* h, const DomainCall& c) {
+  if (h->degree[0] == 3) launch_tensor_p3_post(h, tensor_args(h, c));
+  else launch_tensor_p2_post(h, tensor_args(h, c));
 }
 
 }  // namespace mimi_hip

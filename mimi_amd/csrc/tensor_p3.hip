@@ -1333,21 +1333,17 @@ bool tensor_p3_ready(const mimi_hip_domain_s* h) {
          (h->structured_csr || h->structured_perm) && h->first_is_identity;
 }
 
-// the pre-pass kernel of a material kind (one instantiation per kind: see tp3_point_kernel)
-template<int GRAD>
-static auto t3_point_kernel_of(int kind) -> void (*)(TensorArgs) {
-  switch (kind) {
-  case MIMI_HIP_MAT_NEOHOOKEAN:
-  case MIMI_HIP_MAT_J2: return tp3_point_kernel<0, GRAD>;
-  case MIMI_HIP_MAT_STVK: return tp3_point_kernel<MIMI_HIP_MAT_STVK, GRAD>;
-  case MIMI_HIP_MAT_J2LINEAR: return tp3_point_kernel<MIMI_HIP_MAT_J2LINEAR, GRAD>;
-  case MIMI_HIP_MAT_J2SIMO: return tp3_point_kernel<MIMI_HIP_MAT_J2SIMO, GRAD>;
-  default: return tp3_point_kernel<MIMI_HIP_MAT_J2LOG, GRAD>;
-  }
+// the pre-pass kernel of the handle's material (one instantiation per family: see tp3_point_kernel); MODE 0 residual,
+// 1 tangent record, 2 state commit
+template<int MODE>
+static void launch_t3_point(mimi_hip_domain_s* h, const TensorArgs& a) {
+  by_material_family(h->mat.m.kind, [&](auto K) {
+    launch(tp3_point_kernel<decltype(K)::value, MODE>, dim3((unsigned)h->n_el), dim3(128), 0, h->stream, a);
+  });
 }
 
-void launch_tensor_p3(mimi_hip_domain_s* h, int grad, TensorArgs a) {
-  const int kind = h->mat.m.kind;
+void launch_tensor_p3(mimi_hip_domain_s* h, const DomainCall& c, TensorArgs a) {
+  const int grad = c.grad;
   h->scratch_r.resize((size_t)h->n_el * 3 * T3_ND);
   a.scratch_r = h->scratch_r.ptr;
   const int64_t n_cols = (int64_t)a.box_n[0] * a.box_n[1];
@@ -1360,43 +1356,29 @@ void launch_tensor_p3(mimi_hip_domain_s* h, int grad, TensorArgs a) {
     a.scratch_tail = h->scratch_tail.ptr;
     if (!h->t3_t2pack.ptr) {
       h->t3_t2pack.resize((size_t)h->el_total[2] * 64 * 8);
-      hipLaunchKernelGGL(tp3_t2pack_kernel, dim3((unsigned)h->el_total[2]), dim3(64), 0, h->stream, a.tabB[2], a.tabD[2], h->t3_t2pack.ptr);
-      MH_HIP(hipGetLastError());
+      launch(tp3_t2pack_kernel, dim3((unsigned)h->el_total[2]), dim3(64), 0, h->stream, a.tabB[2], a.tabD[2], h->t3_t2pack.ptr);
     }
     a.t2pack = h->t3_t2pack.ptr;
   }
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[0], h->stream));
-  if (h->phase_select != 2) {
-    hipLaunchKernelGGL(grad ? t3_point_kernel_of<1>(kind) : t3_point_kernel_of<0>(kind), dim3((unsigned)h->n_el), dim3(128), 0, h->stream, a);
-    MH_HIP(hipGetLastError());
-  }
-  h->phase_has_prepass = true;
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[3], h->stream));
-  if (grad && h->phase_select != 2) {
-    // MIMI_HIP_P3_CONTRACT=cxx: the compiler-scheduled form of the same arithmetic (the A/B reference of the bitwise test)
-    // (read per launch, so that one process can run both: tests/test_tensor_p3_gpu.py)
-    const char* variant = getenv("MIMI_HIP_P3_CONTRACT");
-    const bool cxx = variant && !strcmp(variant, "cxx");
-    hipLaunchKernelGGL(cxx ? tp3_contract_kernel : tp3_contract_asm_kernel, dim3((unsigned)(n_cols * 9)), dim3(64),
-                       (16 * 4 * 64 + 48) * sizeof(double), h->stream, a);
-    MH_HIP(hipGetLastError());
-  }
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[1], h->stream));
   const int64_t n_rows = (int64_t)a.win_n[0] * a.win_n[1] * a.win_n[2] * 3;   // (node window: the shard's nodes unless a gather asks for a part)
-  if (h->phase_select == 1) {
-    // integrate only
-  } else if (grad)
-    hipLaunchKernelGGL(tp3_gather_kernel<1>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, h->stream, a, n_rows);
-  else
-    hipLaunchKernelGGL(tp3_residual_gather_kernel, dim3((unsigned)((n_rows / 3 + 3) / 4)), dim3(256), 0, h->stream, a, n_rows / 3);
-  MH_HIP(hipGetLastError());
-  if (h->phase_timing) MH_HIP(hipEventRecord(h->phase_ev[2], h->stream));
+  run_two_phase(
+      h, c, true,
+      [&] {
+        if (grad) launch_t3_point<1>(h, a); else launch_t3_point<0>(h, a);
+      },
+      [&] {
+        if (!grad) return;   // (a residual is complete after the pre-pass)
+        // MIMI_HIP_P3_CONTRACT=cxx: the compiler-scheduled form of the same arithmetic (the A/B reference of the bitwise test)
+        // (read per launch, so that one process can run both: tests/test_tensor_p3_gpu.py)
+        launch(env_p3_contract_cxx() ? tp3_contract_kernel : tp3_contract_asm_kernel, dim3((unsigned)(n_cols * 9)), dim3(64),
+               (16 * 4 * 64 + 48) * sizeof(double), h->stream, a);
+      },
+      [&] {
+        if (grad) launch(tp3_gather_kernel<1>, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, h->stream, a, n_rows);
+        else launch(tp3_residual_gather_kernel, dim3((unsigned)((n_rows / 3 + 3) / 4)), dim3(256), 0, h->stream, a, n_rows / 3);
+      });
 }
 
-void launch_tensor_p3_post(mimi_hip_domain_s* h, TensorArgs a) {
-  const int kind = h->mat.m.kind;
-  hipLaunchKernelGGL(t3_point_kernel_of<2>(kind), dim3((unsigned)h->n_el), dim3(128), 0, h->stream, a);
-  MH_HIP(hipGetLastError());
-}
+void launch_tensor_p3_post(mimi_hip_domain_s* h, TensorArgs a) { launch_t3_point<2>(h, a); }
 
 }  // namespace mimi_hip

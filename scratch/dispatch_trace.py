@@ -1,0 +1,228 @@
+#!/usr/bin/env python3
+"""Same launches, same bits: a fixed, seeded list of cases through the C ABI of the domain integrator, for comparing two
+builds of the library (MIMI_HIP_LIBRARY=scratch/lib_parent.so, then the tree's own) across a refactor of its host side.
+
+  python scratch/dispatch_trace.py [--atomics] > hashes.txt       one line per result: case, what, SHA-256 of the bytes
+  rocprofv3 --kernel-trace --output-format csv -d DIR -- python scratch/dispatch_trace.py   (kernel trace alone, no counters)
+  python scratch/dispatch_trace.py --compare-hashes A.txt B.txt
+  python scratch/dispatch_trace.py --compare-traces DIR_A DIR_B   (kernel name, grid, workgroup, LDS) in dispatch order
+
+Entries reached: create from tables and from a B-spline, residual, residual + tangent, from-base in its three residences,
+post-time-advance, integrate + gather over partial windows, phase timing.  Kernel families: 2-D degree 1-3, 3-D degree 1,
+3-D degree 2 and 3 with neo-Hookean / J2 / a record material, 3-D degree 2 with node_ids, the general kernels
+(MIMI_HIP_FORCE_GENERAL) with a closed-form and a record material, the reference-FD tangent.  Switches:
+MIMI_HIP_P3_CONTRACT flipped between two calls, MIMI_HIP_NO_STRUCTURED set between two creates.  Every route sums in a
+fixed order, so every hash must agree; --atomics runs the general path's atomics route
+(MIMI_HIP_GENERAL_NO_TWO_PHASE=1, read once per process) instead, whose sums do not: trace it, do not compare its hashes."""
+import csv
+import glob
+import hashlib
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+
+def sha(a):
+    import numpy as np
+    import torch
+    if isinstance(a, torch.Tensor):
+        a = a.cpu().numpy()
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:24]
+
+
+def out(case, what, value):
+    print(f"{case:44s} {what:14s} {value}", flush=True)
+
+
+def run():
+    import numpy as np
+    import scipy.sparse as sp
+    import torch
+    import mimi_amd
+    from _cases import product_material
+    from mimi_amd.integrators import CSRPattern, NonlinearSolid
+    dev = torch.device("cuda", 0)
+
+    def seeded(n, seed, scale=1.0):
+        return scale * np.random.default_rng(seed).standard_normal(n)
+
+    def handle(n_el, p, mat, env=None, **kw):
+        patch = mimi_amd.BSplinePatch.block(n_el, p)
+        pattern = CSRPattern.of_bspline_patch(patch)
+        for k, v in (env or {}).items():
+            os.environ[k] = v
+        G = NonlinearSolid("trace", product_material(mat), pattern, patch=patch, **kw).Prepare()
+        for k in env or {}:
+            del os.environ[k]
+        G.dt_ = 0.5
+        return patch, pattern, G
+
+    def assemblies(case, G, n_vdofs, nnz, mat, fd=False):
+        """residual, residual + tangent, and for a material with state: commit, the state, the tangent again"""
+        u = seeded(n_vdofs, 1, 0.05 if mat == "neohook" else 0.02)
+        r = seeded(n_vdofs, 2)
+        G.AddDomainResidual(u, r)
+        out(case, "residual r", sha(r))
+        r, A = seeded(n_vdofs, 2), seeded(nnz, 3)
+        G.AddDomainResidualAndGrad(u, 0.37, r, A)
+        out(case, "tangent r", sha(r))
+        out(case, "tangent A", sha(A))
+        out(case, "family", G.LastKernelFamily())
+        if mat not in ("neohook", "stvk"):
+            G.DomainPostTimeAdvance(seeded(n_vdofs, 4, 0.03))
+            for what in ("accumulated_plastic_strain", "plastic_strain"):
+                out(case, "state " + what[:7], sha(G.State(what)))
+            r, A = seeded(n_vdofs, 2), seeded(nnz, 3)
+            G.AddDomainResidualAndGrad(u, 0.37, r, A)
+            out(case, "committed A", sha(A))
+        if fd:
+            G.SetTangentMode(1)
+            r, A = seeded(n_vdofs, 2), seeded(nnz, 3)
+            G.AddDomainResidualAndGrad(u, 0.37, r, A)
+            out(case, "fd A", sha(A))
+            out(case, "fd family", G.LastKernelFamily())
+            G.SetTangentMode(0)
+
+    def from_base(case, G, n_vdofs, nnz):
+        u, base = seeded(n_vdofs, 1, 0.05), seeded(nnz, 5, 50.0)
+        to = lambda a, on_dev: torch.from_numpy(a.copy()).to(dev) if on_dev else a.copy()
+        for name, (base_dev, out_dev) in {"device": (True, True), "host": (False, False), "host base": (False, True)}.items():
+            r, A = to(seeded(n_vdofs, 2), out_dev), to(np.full(nnz, 1e30), out_dev)
+            G.AddDomainResidualAndGradFrom(to(u, out_dev), 0.37, r, to(base, base_dev), A)
+            G.Synchronize()
+            out(case, "from " + name, sha(A))
+
+    if "--atomics" in sys.argv:
+        os.environ["MIMI_HIP_GENERAL_NO_TWO_PHASE"] = "1"
+        for n_el, p, mat in [((4, 3), 2, "neohook"), ((3, 2, 2), 2, "j2simo")]:
+            patch, pattern, G = handle(n_el, p, mat, env={"MIMI_HIP_FORCE_GENERAL": "1"})
+            case = f"atomics {'x'.join(map(str, n_el))} p{p} {mat}"
+            assemblies(case, G, patch.n_vdofs, pattern.nnz, mat)
+            from_base(case, G, patch.n_vdofs, pattern.nnz)
+        return
+
+    # every kernel family, from a B-spline
+    for n_el, p, mat in [((5, 4), 1, "neohook"), ((4, 3), 2, "neohook"), ((3, 3), 3, "neohook"), ((3, 3), 3, "j2"), ((4, 3), 2, "j2linear"),
+                         ((4, 3, 2), 1, "neohook"), ((3, 2, 2), 1, "j2log"),
+                         ((5, 4, 4), 2, "neohook"), ((4, 4, 5), 2, "j2"), ((3, 4, 4), 2, "stvk"), ((3, 3, 4), 2, "j2simo"),
+                         ((3, 2, 3), 3, "neohook"), ((2, 3, 5), 3, "j2"), ((2, 3, 2), 3, "stvk"), ((2, 2, 3), 3, "j2log")]:
+        patch, pattern, G = handle(n_el, p, mat)
+        assemblies(f"bspline {'x'.join(map(str, n_el))} p{p} {mat}", G, patch.n_vdofs, pattern.nnz, mat, fd=len(n_el) == 2 or p == 1)
+        if mat == "neohook":
+            from_base(f"bspline {'x'.join(map(str, n_el))} p{p} {mat}", G, patch.n_vdofs, pattern.nnz)
+    # the general kernels: closed-form and record materials, small and large elements
+    for n_el, p, mat in [((4, 3), 2, "neohook"), ((3, 3), 3, "j2"), ((3, 2, 2), 2, "neohook"), ((3, 2, 2), 2, "j2simo"),
+                         ((2, 2, 1), 3, "neohook"), ((2, 1, 2), 3, "stvk"), ((3, 2, 2), 1, "j2linear")]:
+        patch, pattern, G = handle(n_el, p, mat, env={"MIMI_HIP_FORCE_GENERAL": "1"})
+        case = f"general {'x'.join(map(str, n_el))} p{p} {mat}"
+        assemblies(case, G, patch.n_vdofs, pattern.nnz, mat, fd=True)
+        if mat == "neohook":
+            from_base(case, G, patch.n_vdofs, pattern.nnz)
+    # create from flat tables (the oracle's own tables)
+    from _cases import oracle_material
+    from oracle import iga, ref_path as rp
+    for n_el, p, mat in [((2, 2), 3, "j2"), ((3, 2, 2), 2, "neohook")]:
+        P = iga.Patch.block(n_el, p)
+        D = rp.DomainOracle(P, oracle_material(mat), n_threads=1)
+        pattern = CSRPattern(D.rowptr.astype(np.int64), D.col.astype(np.int32), D.nnz)
+        tables = dict(dim=P.dim, n_nodes=P.n_nodes, dofs=D.conn, dN_dX=D.dN_dX, weight_det=D.weight * D.det)
+        G = NonlinearSolid("trace", product_material(mat), pattern, tables=tables).Prepare()
+        G.dt_ = 0.5
+        case = f"tables {'x'.join(map(str, n_el))} p{p} {mat}"
+        assemblies(case, G, P.n_vdofs, D.nnz, mat, fd=True)
+        from_base(case, G, P.n_vdofs, D.nnz)
+    # permuted numbering (node_ids), 3-D degree 2 and 3: the caller's CSR is the lexicographic one renumbered
+    for n_el, p in [((5, 4, 4), 2), ((3, 3, 4), 3)]:
+        patch = mimi_amd.BSplinePatch.block(n_el, p)
+        lex = CSRPattern.of_bspline_patch(patch)
+        perm = np.random.default_rng(11).permutation(patch.n_nodes).astype(np.int64)
+        dofperm = (perm[:, None] * 3 + np.arange(3)[None, :]).ravel()
+        rows = np.repeat(np.arange(patch.n_vdofs), np.diff(lex.rowptr))
+        S = sp.coo_matrix((np.ones(lex.nnz), (dofperm[rows], dofperm[lex.col])), shape=(patch.n_vdofs,) * 2).tocsr()
+        S.sort_indices()
+        pattern = CSRPattern(S.indptr.astype(np.int64), S.indices.astype(np.int32), lex.nnz)
+        for mat in ("neohook", "j2"):
+            G = NonlinearSolid("trace", product_material(mat), pattern, patch=patch, node_ids=perm).Prepare()
+            G.dt_ = 0.5
+            assemblies(f"node_ids {'x'.join(map(str, n_el))} p{p} {mat}", G, patch.n_vdofs, pattern.nnz, mat)
+    # integrate + gather over partial windows, phase timing on (which event pairs exist is what is printed, not the times)
+    for n_el, p, mat in [((5, 7, 4), 2, "neohook"), ((4, 6, 5), 2, "j2"), ((3, 4, 4), 2, "stvk"), ((3, 5, 4), 3, "j2")]:
+        patch = mimi_amd.BSplinePatch.block(n_el, p)
+        pattern = CSRPattern.of_bspline_patch(patch, on_device=True)
+        G = NonlinearSolid("trace", product_material(mat), pattern, patch=patch).Prepare()
+        G.dt_ = 0.5
+        G.SetPhaseTiming(True)
+        case = f"two-step {'x'.join(map(str, n_el))} p{p} {mat}"
+        u = torch.from_numpy(seeded(patch.n_vdofs, 1, 0.02)).to(dev)
+        r, A = torch.zeros(patch.n_vdofs, dtype=torch.float64, device=dev), torch.zeros(pattern.nnz, dtype=torch.float64, device=dev)
+        G.AddDomainResidualAndGrad(u, 0.7, r, A)
+        G.Synchronize()
+        out(case, "one call A", sha(A))
+        out(case, "prepass timed", G.PhaseMsDetail()[0] > 0.0)
+        r2, A2 = torch.zeros_like(r), torch.zeros_like(A)
+        G.Integrate(u)
+        hi = [n_el[d] + p for d in range(3)]
+        cuts = [0, 1, 1 + hi[1] // 2, hi[1]]
+        for y0, y1 in zip(cuts[:-1], cuts[1:]):
+            G.Gather(0.7, r2, A2, [0, y0, 0], [hi[0], y1, hi[2]])
+            G.Synchronize()
+            out(case, f"gather y<{y1}", sha(A2))
+        out(case, "gather r", sha(r2))
+        out(case, "prepass timed", G.PhaseMsDetail()[0] > 0.0)
+        G.SetPhaseTiming(False)
+        r = torch.zeros_like(r)
+        G.AddDomainResidual(u, r)
+        G.Synchronize()
+        out(case, "residual r", sha(r))
+    # MIMI_HIP_P3_CONTRACT flipped between two calls of one handle
+    patch, pattern, G = handle((2, 3, 4), 3, "neohook")
+    u = seeded(patch.n_vdofs, 1, 0.05)
+    for variant in ("cxx", "asm", "cxx"):
+        os.environ["MIMI_HIP_P3_CONTRACT"] = variant
+        r, A = seeded(patch.n_vdofs, 2), seeded(pattern.nnz, 3)
+        G.AddDomainResidualAndGrad(u, 0.37, r, A)
+        out("p3 contract switch", variant + " A", sha(A))
+    del os.environ["MIMI_HIP_P3_CONTRACT"]
+    # MIMI_HIP_NO_STRUCTURED set between two creates
+    for env in (None, {"MIMI_HIP_NO_STRUCTURED": "1"}, None):
+        patch, pattern, G = handle((4, 3, 3), 2, "neohook", env=env)
+        assemblies("no-structured " + ("set" if env else "unset"), G, patch.n_vdofs, pattern.nnz, "neohook")
+
+
+def compare_hashes(a, b):
+    la, lb = open(a).read().splitlines(), open(b).read().splitlines()
+    la, lb = [l for l in la if not l.startswith("atomics")], [l for l in lb if not l.startswith("atomics")]
+    bad = [(x, y) for x, y in zip(la, lb) if x != y]
+    for x, y in bad[:20]:
+        print(f"- {x}\n+ {y}")
+    print(f"{len(la)} / {len(lb)} lines, {len(bad)} differ" + ("" if len(la) == len(lb) else ": DIFFERENT LENGTHS"))
+    return 1 if bad or len(la) != len(lb) or not la else 0
+
+
+def launches(directory):
+    files = glob.glob(os.path.join(directory, "**", "*kernel_trace.csv"), recursive=True)
+    if len(files) != 1:
+        sys.exit(f"{directory}: {len(files)} kernel traces")
+    rows = sorted(csv.DictReader(open(files[0])), key=lambda r: int(r["Dispatch_Id"]))
+    return [(r["Kernel_Name"], r["Grid_Size_X"], r["Grid_Size_Y"], r["Grid_Size_Z"], r["Workgroup_Size_X"], r["Workgroup_Size_Y"],
+             r["Workgroup_Size_Z"], r["LDS_Block_Size"]) for r in rows]
+
+
+def compare_traces(a, b):
+    la, lb = launches(a), launches(b)
+    bad = [(k, x, y) for k, (x, y) in enumerate(zip(la, lb)) if x != y]
+    for k, x, y in bad[:10]:
+        print(f"dispatch {k}:\n- {x}\n+ {y}")
+    print(f"{len(la)} / {len(lb)} launches, {len(set(x[0] for x in la))} distinct kernels, {len(bad)} differ"
+          + ("" if len(la) == len(lb) else ": DIFFERENT LENGTHS"))
+    return 1 if bad or len(la) != len(lb) or not la else 0
+
+
+if __name__ == "__main__":
+    if "--compare-hashes" in sys.argv:
+        sys.exit(compare_hashes(*sys.argv[-2:]))
+    if "--compare-traces" in sys.argv:
+        sys.exit(compare_traces(*sys.argv[-2:]))
+    run()

@@ -19,35 +19,38 @@ matrix instruction, where the compiler's hazard recogniser does pad, and reads t
 """
 import os
 import re
-import shutil
 import subprocess
 import tempfile
 from collections import deque
 
-# the compiler the library is built with (mimi_amd/build.py resolves it the same way: what is linted is what ships)
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-ASM_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-Wno-unused-result", "-S",
-             "--cuda-device-only"]
+from . import build
+
+# the compiler and the flags the library is built with (what is linted is what ships): the build's, compiled to device assembly
+HIPCC = build.HIPCC
+CSRC = build.CSRC
+ASM_FLAGS = [f for f in build.FLAGS if f not in ("-shared", "-fPIC")] + ["-S", "--cuda-device-only"]
 
 _REG = re.compile(r"\b([vas])(?:(\d+)|\[(\d+):(\d+)\])(?![\w.])")
 
 
 def assembly(source, out=None, extra_flags=()):
-    """hipcc -S --cuda-device-only of csrc/<source> (cached beside the library's objects by modification time)."""
-    src = source if os.path.isabs(source) else os.path.join(CSRC, source)
-    if out is None:
-        objdir = os.path.join(os.path.dirname(CSRC), "lib", "obj")
-        os.makedirs(objdir, exist_ok=True)
-        out = os.path.join(objdir, os.path.basename(src).rsplit(".", 1)[0] + ".lint.s")
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] if src.startswith(CSRC) else [src]
-    if extra_flags or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in deps):
+    """Device assembly of a source.  A source of the library (build.SOURCES), as the library has it: the assembly kept from
+    the compilation of its object in lib/obj, which is compiled first if it is not current -- the build writes that file and
+    nothing else does.  Anything else (another file, extra flags, an `out` of the caller's): hipcc -S --cuda-device-only with
+    the build's flags, into `out` or a temporary file."""
+    if out is None and not extra_flags and source in build.SOURCES:
+        obj = build.compile_object(source, os.path.join(build.LIBDIR, "obj"), gate=build.lint_gate(False))
+        with open(obj[:-len(".o")] + ".lint.s") as f:
+            return f.read()
+    src = source if os.path.isabs(source) else os.path.join(build.CSRC, source)
+    with tempfile.TemporaryDirectory() as tmp:
+        out = out or os.path.join(tmp, "out.s")
         run = subprocess.run([HIPCC] + ASM_FLAGS + list(extra_flags) + ["-o", out, src], cwd=os.path.dirname(src),
                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if run.returncode != 0:
             raise RuntimeError(f"{HIPCC} -S {src} failed ({run.returncode}):\n{run.stderr[-4000:]}")
-    with open(out) as f:
-        return f.read()
+        with open(out) as f:
+            return f.read()
 
 
 class Instr:
@@ -78,8 +81,9 @@ _NO_DST = ("global_store", "buffer_store", "flat_store", "scratch_store", "ds_wr
 
 
 def parse_kernel(asm, name):
-    """instructions of the kernel whose mangled name contains `name` (labels resolved to instruction indices)"""
-    m = re.search(r"^(\w*%s\w*):" % re.escape(name), asm, re.M)
+    """instructions of the kernel whose mangled name is `name` or, failing that, the first one whose name contains it
+    (labels resolved to instruction indices)"""
+    m = re.search(r"^%s:" % re.escape(name), asm, re.M) or re.search(r"^(\w*%s\w*):" % re.escape(name), asm, re.M)
     if not m:
         raise KeyError(name)
     a = m.end()

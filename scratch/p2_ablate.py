@@ -1,4 +1,4 @@
-"""phase times of the degree-2 two-phase path for the library named by MIMI_HIP_LIBRARY (timing experiments: scratch/ab_lib.sh)"""
+"""phase times of the degree-2 two-phase path for the library named by MIMI_HIP_LIBRARY (timing experiments: python -m mimi_amd.build --out)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -14,6 +14,7 @@ import tempfile
 import pytest
 
 from mimi_amd import isa_lint as L
+from _hazard import HAZARD as _HAZARD, PAD_STATEMENT, SAFE_STATEMENT
 
 # (a CPU box without ROCm: nothing to lint -- skip instead of erroring; with it, a failed compile shows the compiler's stderr)
 pytestmark = pytest.mark.skipif(not os.path.exists(L.HIPCC), reason="no hipcc: nothing to compile")
@@ -238,21 +239,6 @@ def test_the_generated_contraction_loop_is_current_and_waits_for_what_it_uses():
     assert len(gen.check_schedule(broken)) > 100
 
 
-_HAZARD = r"""
-#include <hip/hip_runtime.h>
-typedef double d4 __attribute__((ext_vector_type(4)));
-extern "C" __global__ void hazard_kernel(const double* a, const double* b, double* out) {
-  d4 c;
-  const double x = a[threadIdx.x], y = b[threadIdx.x];
-  asm volatile("s_nop 1\n\tv_mfma_f64_16x16x4_f64 %0, %1, %2, 0" : "=&v"(c) : "v"(x), "v"(y));
-  asm volatile("s_nop %0" :: "n"(PAD));
-  double s;
-  asm volatile("v_add_f64 %0, %1, %2" : "=v"(s) : "v"(c[0]), "v"(c[1]));
-  out[threadIdx.x] = s;
-}
-"""
-
-
 @pytest.mark.parametrize("pad", [15, 7, 0])
 def test_the_lint_turns_red_on_a_real_hazard(need, pad):
     """an asm matrix instruction whose result a vector instruction reads after pad + 1 < 19 wait states"""
@@ -269,7 +255,7 @@ def test_the_lint_turns_red_on_a_real_hazard(need, pad):
 def test_the_lint_stays_green_with_the_wait_states_in_place(need):
     with tempfile.TemporaryDirectory() as tmp:
         src = os.path.join(tmp, "hazard.hip")
-        open(src, "w").write(_HAZARD.replace('asm volatile("s_nop %0" :: "n"(PAD));', 'asm volatile("s_nop 15\\n\\ts_nop 2");'))
+        open(src, "w").write(_HAZARD.replace(PAD_STATEMENT, SAFE_STATEMENT))
         asm = L.assembly(src, out=os.path.join(tmp, "hazard.s"))
     bad, stats = L.lint_kernel(L.parse_kernel(asm, "hazard_kernel"), need, asm_only=True)
     assert not bad and stats["nearest_valu_read"] >= 19

@@ -105,13 +105,17 @@ def compile_object(src, objdir, csrc=None, extra_flags=(), force=False, gate=Non
     """<csrc>/<src> -> <objdir>/<stem>.o, beside it <stem>.d (what it was compiled from) and <stem>.lint.s: with
     -save-temps=obj the device assembly that IS assembled into the object stays -- what the hazard lint and the tests read
     is the shipped code, not a second compilation of it.  The object is current while it is newer than every file the
-    depfile names.  Otherwise everything is compiled under temporary names and `gate(src, assembly file)` runs before any
+    depfile names and this source is one of them.  Otherwise everything is compiled under temporary names and `gate(src, assembly file)` runs before any
     of it gets its name: a source the gate refuses leaves no object behind."""
     csrc = csrc or CSRC
     stem = os.path.join(objdir, src[:-len(".hip")])
     with contextlib.suppress(OSError):            # (a file that is missing: the object, its depfile, something it was compiled from)
         t = os.path.getmtime(stem + ".o")
-        if not force and os.path.exists(stem + ".lint.s") and all(os.path.getmtime(d) < t for d in read_depfile(stem + ".d", csrc)):
+        deps = read_depfile(stem + ".d", csrc)
+        # (a depfile that does not name this very source was written in another tree, of which this one is a copy: its
+        # files are not the ones this object has to follow)
+        own = os.path.realpath(os.path.join(csrc, src)) in {os.path.realpath(d) for d in deps}
+        if not force and own and os.path.exists(stem + ".lint.s") and all(os.path.getmtime(d) < t for d in deps):
             return stem + ".o"
     os.makedirs(objdir, exist_ok=True)
     with tempfile.TemporaryDirectory(prefix=src + ".", dir=objdir) as tmp:

@@ -484,46 +484,28 @@ static void upload_spline_body(mimi_hip_contact_s* h, const mimi_hip_spline_body
   // NearestDistanceToSplines::AddSpline / PlantKdTree (nearest_distance.hpp:223-255)
   if (!sp) fail("body_kind spline without a spline description");
   if (sp->para_dim + 1 != dim) fail("boundary para_dim should be one smaller than dim.");   // :121-124
-  SplineBodyDev host{};
-  host.para_dim = sp->para_dim;
-  host.dim = dim;
+  for (int k = 0; k < sp->para_dim; ++k) {
+    const int p = sp->degree[k], n_ctrl = sp->n_knots[k] - p - 1;
+    if (p < 0 || p > kMaxBodyDegree) fail("spline body degree %d unsupported (<= %d)", p, kMaxBodyDegree);
+    if (n_ctrl < p + 1) fail("spline body knot vector too short");
+  }
   size_t n_ctrl = 1;
-  for (int k = 0; k < 2; ++k) {
-    host.p[k] = k < sp->para_dim ? sp->degree[k] : 0;
-    host.n_knots[k] = k < sp->para_dim ? sp->n_knots[k] : 2;
-    host.n_ctrl[k] = host.n_knots[k] - host.p[k] - 1;
-    if (host.p[k] < 0 || host.p[k] > kMaxBodyDegree) fail("spline body degree %d unsupported (<= %d)", host.p[k], kMaxBodyDegree);
-    if (host.n_ctrl[k] < host.p[k] + 1) fail("spline body knot vector too short");
-    n_ctrl *= host.n_ctrl[k];
-  }
-  const int hd = dim + 1;
-  std::vector<double> ctrl_h(n_ctrl * hd);
-  for (size_t a = 0; a < n_ctrl; ++a) {
-    const double w = sp->weights ? sp->weights[a] : 1.0;
-    if (!(w > 0.0)) fail("spline body weights must be positive");
-    for (int i = 0; i < dim; ++i) ctrl_h[a * hd + i] = w * sp->control_points[a * dim + i];
-    ctrl_h[a * hd + dim] = w;
-  }
-  static const double unit_knots[2] = {0.0, 1.0};
-  host.knots[0] = sp->knots[0];
-  host.knots[1] = sp->para_dim == 2 ? sp->knots[1] : unit_knots;
-  host.ctrl_h = ctrl_h.data();
+  for (int k = 0; k < sp->para_dim; ++k) n_ctrl *= (size_t)(sp->n_knots[k] - sp->degree[k] - 1);
+  if (sp->weights)
+    for (size_t a = 0; a < n_ctrl; ++a)
+      if (!(sp->weights[a] > 0.0)) fail("spline body weights must be positive");
   int res = sp->kdtree_resolution > 1 ? sp->kdtree_resolution : 100;
   if (sp->para_dim == 2 && res > 1000) res = 1000;   // res^2 samples: the reference's kd-tree takes what it is given
   if (res > 1000000) res = 1000000;
-  const int n_s = sp->para_dim == 2 ? res * res : res;
-  std::vector<double> sxi((size_t)n_s * sp->para_dim), sx((size_t)n_s * dim);
-  for (int s_ = 0; s_ < n_s; ++s_) {
-    const int idx[2] = {s_ % res, s_ / res};
-    double xi[2] = {0, 0}, S[3], S1[6], S2[12];
-    for (int k = 0; k < sp->para_dim; ++k) {
-      const double lo = host.knots[k][host.p[k]], hi = host.knots[k][host.n_knots[k] - host.p[k] - 1];
-      xi[k] = lo + (hi - lo) * idx[k] / (res - 1);
-      sxi[(size_t)s_ * sp->para_dim + k] = xi[k];
-    }
-    sb_evaluate(host, xi, S, S1, S2);
-    for (int i = 0; i < dim; ++i) sx[(size_t)s_ * dim + i] = S[i];
-  }
+  // weighted control points, samples and closed directions: the one set-up the tests' host harness runs too
+  SplineBodyHost filled;
+  const int degree[2] = {sp->degree[0], sp->degree[1]}, n_knots[2] = {sp->n_knots[0], sp->n_knots[1]};
+  sb_fill_host(filled, sp->para_dim, dim, degree, n_knots, sp->knots, sp->control_points, sp->weights, res,
+               sp->max_iterations);
+  const SplineBodyDev& host = filled.dev;
+  const std::vector<double>&ctrl_h = filled.ctrl_h, &sxi = filled.sample_xi, &sx = filled.sample_x;
+  static const double unit_knots[2] = {0.0, 1.0};
+  const int n_s = host.n_samples;
   h->spline = host;
   for (int k = 0; k < sp->para_dim; ++k) {
     h->sb_knots[k].assign(sp->knots[k], (size_t)sp->n_knots[k], h->stream);
@@ -540,7 +522,6 @@ static void upload_spline_body(mimi_hip_contact_s* h, const mimi_hip_spline_body
   h->spline.sample_xi = h->sb_sample_xi.ptr;
   h->spline.sample_x = h->sb_sample_x.ptr;
   h->spline.n_samples = n_s;
-  h->spline.max_iterations = sp->max_iterations;
 }
 
 static ContactArgs contact_args(mimi_hip_contact_s* h, const double* u) {

@@ -4,14 +4,21 @@
 // splinepy (SplinepyPlantNewKdTreeForProximity for the initial guess, SplinepyVerboseProximity with aggressive bounds
 // for the search), an absent, un-pinned third-party library.  What is restated here is the published scheme: nearest
 // of res^para_dim sampled points as the initial guess, then Newton on the squared distance in the parametric
-// coordinates, clipped to the parametric bounds, with step halving when the distance does not decrease -- **parity
-// unpinned**, as all of contact.  Results as Results::{physical_, first_derivatives_} (nearest_distance.hpp:46-58);
-// ComputeNormal<true> / NormalGap (:139-193) are applied by the caller.
+// coordinates, clipped to the parametric bounds, with step halving when the distance does not decrease.  A direction in
+// which the body closes on itself (S(lo, .) == S(hi, .), found once at set-up: sb_fill_host) does not end at its seam: a
+// coordinate that would be pinned there continues from the opposite end, once.  Parity with splinepy itself cannot be
+// pinned; what IS pinned is the answer: sb_evaluate, sb_closest_point and sb_nearest against a long-double evaluation
+// and a brute-force global closest point that share nothing with this file (tests/_closest_point.py), on the host
+// (tests/host_spline_body.hip, tests/test_spline_body_cpu.py) and through the contact kernels
+// (tests/test_contact_spline_gpu.py), and against closed forms (circle, parabola, plane, cylinder, sphere).
+// Results as Results::{physical_, first_derivatives_} (nearest_distance.hpp:46-58); ComputeNormal<true> / NormalGap
+// (:139-193) are applied by the caller.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <vector>
 
 namespace mimi_hip {
 
@@ -27,6 +34,7 @@ struct SplineBodyDev {
   const double* sample_xi;   // [n_samples][para_dim]
   const double* sample_x;    // [n_samples][dim]
   int n_samples, max_iterations;
+  int closed[2];             // S(lo, .) == S(hi, .) in this direction (decided once, from the samples, by sb_fill_host)
 };
 
 // span index i with U[i] <= xi < U[i+1] (the last non-empty span at the upper end)
@@ -172,10 +180,29 @@ SB_HD void sb_closest_point(const SplineBodyDev& b, const double* xq, double* xi
   };
   double f = dist2(S);
   const int max_it = b.max_iterations > 0 ? b.max_iterations : 50;
+  bool wrapped[2] = {false, false};
   for (int it = 0; it < max_it; ++it) {
     double g[2] = {0, 0}, H[4] = {0, 0, 0, 0}, GN[4] = {0, 0, 0, 0};
     for (int k = 0; k < pd; ++k)
       for (int i = 0; i < dim; ++i) g[k] += S1[k * dim + i] * (S[i] - xq[i]);
+    // a direction in which the body closes on itself does not end at its seam: a coordinate that would be pinned there
+    // continues from the opposite end (the same point of the body), once per direction -- no ping-pong
+    bool wrap = false;
+    for (int k = 0; k < pd; ++k) {
+      if (!b.closed[k] || wrapped[k]) continue;
+      if (xi[k] <= lo[k] && g[k] > 0.0) {
+        xi[k] = hi[k];
+        wrapped[k] = wrap = true;
+      } else if (xi[k] >= hi[k] && g[k] < 0.0) {
+        xi[k] = lo[k];
+        wrapped[k] = wrap = true;
+      }
+    }
+    if (wrap) {
+      sb_evaluate(b, xi, S, S1, S2);
+      f = dist2(S);
+      continue;
+    }
     for (int k = 0; k < pd; ++k)
       for (int l = 0; l < pd; ++l) {
         double gn = 0.0, cv = 0.0;
@@ -274,6 +301,79 @@ SB_HD void sb_nearest(const SplineBodyDev& b, const double* xq, double& true_g, 
   }
   true_g = g;
   distance = sqrt(d2);
+}
+
+// ---- host only: what NearestDistanceToSplines::AddSpline / PlantKdTree (nearest_distance.hpp:223-255) prepare -----------
+// The weighted homogeneous control points, the res^para_dim sampled initial guesses at lo + (hi - lo) i / (res - 1), and
+// the closed directions.  `dev` points into the vectors and into the caller's knot vectors: the integrator
+// (csrc/contact.hip) re-points it to device copies, the host harness of the tests uses it as it is.
+struct SplineBodyHost {
+  SplineBodyDev dev{};
+  std::vector<double> ctrl_h, sample_xi, sample_x;
+};
+
+inline void sb_fill_host(SplineBodyHost& h, int para_dim, int dim, const int* degree, const int* n_knots,
+                         const double* const* knots, const double* control_points, const double* weights, int res,
+                         int max_iterations) {
+  static const double unit_knots[2] = {0.0, 1.0};
+  SplineBodyDev& d = h.dev;
+  d = SplineBodyDev{};
+  d.para_dim = para_dim;
+  d.dim = dim;
+  size_t n_ctrl = 1;
+  for (int k = 0; k < 2; ++k) {
+    d.p[k] = k < para_dim ? degree[k] : 0;
+    d.n_knots[k] = k < para_dim ? n_knots[k] : 2;
+    d.n_ctrl[k] = d.n_knots[k] - d.p[k] - 1;
+    d.knots[k] = k < para_dim ? knots[k] : unit_knots;
+    n_ctrl *= (size_t)d.n_ctrl[k];
+  }
+  const int hd = dim + 1;
+  h.ctrl_h.resize(n_ctrl * hd);
+  for (size_t a = 0; a < n_ctrl; ++a) {
+    const double w = weights ? weights[a] : 1.0;
+    for (int i = 0; i < dim; ++i) h.ctrl_h[a * hd + i] = w * control_points[a * dim + i];
+    h.ctrl_h[a * hd + dim] = w;
+  }
+  d.ctrl_h = h.ctrl_h.data();
+  const int n_s = para_dim == 2 ? res * res : res;
+  h.sample_xi.resize((size_t)n_s * para_dim);
+  h.sample_x.resize((size_t)n_s * dim);
+  double xmin[3] = {0, 0, 0}, xmax[3] = {0, 0, 0};
+  for (int s = 0; s < n_s; ++s) {
+    const int idx[2] = {s % res, s / res};
+    double xi[2] = {0, 0}, S[3], S1[6], S2[12];
+    for (int k = 0; k < para_dim; ++k) {
+      const double lo = d.knots[k][d.p[k]], hi = d.knots[k][d.n_knots[k] - d.p[k] - 1];
+      xi[k] = lo + (hi - lo) * idx[k] / (res - 1);
+      h.sample_xi[(size_t)s * para_dim + k] = xi[k];
+    }
+    sb_evaluate(d, xi, S, S1, S2);
+    for (int i = 0; i < dim; ++i) {
+      h.sample_x[(size_t)s * dim + i] = S[i];
+      xmin[i] = s == 0 || S[i] < xmin[i] ? S[i] : xmin[i];
+      xmax[i] = s == 0 || S[i] > xmax[i] ? S[i] : xmax[i];
+    }
+  }
+  d.sample_xi = h.sample_xi.data();
+  d.sample_x = h.sample_x.data();
+  d.n_samples = n_s;
+  d.max_iterations = max_iterations;
+  // closed in direction k: every sample of the first layer coincides with its partner of the last (to the rounding of
+  // the evaluation: 1e-12 of the body's extent)
+  double extent = 0.0;
+  for (int i = 0; i < dim; ++i) extent = xmax[i] - xmin[i] > extent ? xmax[i] - xmin[i] : extent;
+  for (int k = 0; k < para_dim; ++k) {
+    const int stride = k == 0 ? 1 : res, other = k == 0 ? res : 1, n_other = para_dim == 2 ? res : 1;
+    bool same = true;
+    for (int j = 0; j < n_other && same; ++j)
+      for (int i = 0; i < dim; ++i) {
+        const double a = h.sample_x[(size_t)(j * other) * dim + i];
+        const double c = h.sample_x[(size_t)(j * other + (res - 1) * stride) * dim + i];
+        if (!(fabs(a - c) <= 1e-12 * extent)) same = false;
+      }
+    d.closed[k] = same ? 1 : 0;
+  }
 }
 
 }  // namespace mimi_hip

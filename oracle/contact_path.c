@@ -44,6 +44,7 @@ typedef struct {
   const double* sp_ctrl;      /* [n_ctrl][dim] */
   const double* sp_weights;   /* [n_ctrl] or NULL */
   int sp_resolution, sp_max_iterations;
+  int sp_closed[2];           /* S(lo, .) == S(hi, .) in this direction: oracle_contact_spline_setup */
 } oracle_contact;
 
 /* analytic stand-in for NearestDistance + Results::ComputeNormal<true> + NormalGap
@@ -163,9 +164,12 @@ static void sp_eval(const oracle_contact* C, const double* xi, double* S, double
 
 /* the published scheme behind SplinepyVerboseProximity (nearest_distance.hpp:268-279; splinepy is absent): nearest of
  * resolution^para_dim samples, then Newton on the squared distance, clipped to the bounds, halved while it grows */
-static void sp_nearest(const oracle_contact* C, const double* xq, double* true_g, double* distance) {
+static void sp_nearest_at(const oracle_contact* C, const double* xq, double* true_g, double* distance, double* xi,
+                          double* S) {
   const int dim = C->dim, pd = C->sp_para_dim, res = C->sp_resolution;
-  double lo[2] = {0, 0}, hi[2] = {1, 1}, xi[2] = {0, 0}, S[3], S1[6], S2[12];
+  double lo[2] = {0, 0}, hi[2] = {1, 1}, S1[6], S2[12];
+  int wrapped[2] = {0, 0};
+  xi[0] = xi[1] = 0.0;
   for (int k = 0; k < pd; ++k) {
     lo[k] = C->sp_knots[k][C->sp_p[k]];
     hi[k] = C->sp_knots[k][C->sp_n_knots[k] - C->sp_p[k] - 1];
@@ -196,6 +200,25 @@ static void sp_nearest(const oracle_contact* C, const double* xq, double* true_g
     int fr[2] = {1, 1};
     for (int k = 0; k < pd; ++k)
       for (int i = 0; i < dim; ++i) g[k] += S1[k * dim + i] * (S[i] - xq[i]);
+    /* a closed direction does not end at its seam: a coordinate that would be pinned there continues from the opposite
+     * end (the same point of the body), once per direction */
+    int wrap = 0;
+    for (int k = 0; k < pd; ++k) {
+      if (!C->sp_closed[k] || wrapped[k]) continue;
+      if (xi[k] <= lo[k] && g[k] > 0.0) {
+        xi[k] = hi[k];
+        wrapped[k] = wrap = 1;
+      } else if (xi[k] >= hi[k] && g[k] < 0.0) {
+        xi[k] = lo[k];
+        wrapped[k] = wrap = 1;
+      }
+    }
+    if (wrap) {
+      sp_eval(C, xi, S, S1, S2);
+      f = 0;
+      for (int i = 0; i < dim; ++i) f += (S[i] - xq[i]) * (S[i] - xq[i]);
+      continue;
+    }
     for (int k = 0; k < pd; ++k)
       for (int l = 0; l < pd; ++l) {
         double gn = 0, cv = 0;
@@ -260,7 +283,7 @@ static void sp_nearest(const oracle_contact* C, const double* xq, double* true_g
       if (fabs(xn[k] - xi[k]) > step) step = fabs(xn[k] - xi[k]);
       xi[k] = xn[k];
     }
-    memcpy(S, Sn, sizeof(Sn));
+    memcpy(S, Sn, sizeof(double) * dim);
     memcpy(S1, S1n, sizeof(S1n));
     memcpy(S2, S2n, sizeof(S2n));
     f = fn;
@@ -286,6 +309,57 @@ static void sp_nearest(const oracle_contact* C, const double* xq, double* true_g
   }
   *true_g = g;
   *distance = sqrt(d2);
+}
+
+static void sp_nearest(const oracle_contact* C, const double* xq, double* true_g, double* distance) {
+  double xi[2], S[3];
+  sp_nearest_at(C, xq, true_g, distance, xi, S);
+}
+
+/* the closed directions of the spline body, decided once from the sampled points (first layer == last layer to 1e-12 of
+ * the body's extent); to be called after the sp_* fields are filled */
+void oracle_contact_spline_setup(oracle_contact* C) {
+  const int dim = C->dim, pd = C->sp_para_dim, res = C->sp_resolution;
+  double lo[2] = {0, 0}, hi[2] = {1, 1}, mn[3], mx[3], S[3], S1[6], S2[12];
+  for (int k = 0; k < pd; ++k) {
+    lo[k] = C->sp_knots[k][C->sp_p[k]];
+    hi[k] = C->sp_knots[k][C->sp_n_knots[k] - C->sp_p[k] - 1];
+  }
+  const int n_s = pd == 2 ? res * res : res;
+  double* x = (double*)malloc(sizeof(double) * n_s * dim);
+  for (int s = 0; s < n_s; ++s) {
+    const int idx[2] = {s % res, s / res};
+    double xi[2] = {0, 0};
+    for (int k = 0; k < pd; ++k) xi[k] = lo[k] + (hi[k] - lo[k]) * idx[k] / (res - 1);
+    sp_eval(C, xi, S, S1, S2);
+    for (int i = 0; i < dim; ++i) {
+      x[(long)s * dim + i] = S[i];
+      if (s == 0 || S[i] < mn[i]) mn[i] = S[i];
+      if (s == 0 || S[i] > mx[i]) mx[i] = S[i];
+    }
+  }
+  double extent = 0;
+  for (int i = 0; i < dim; ++i)
+    if (mx[i] - mn[i] > extent) extent = mx[i] - mn[i];
+  for (int k = 0; k < pd; ++k) {
+    const int stride = k == 0 ? 1 : res, other = k == 0 ? res : 1, n_other = pd == 2 ? res : 1;
+    int same = 1;
+    for (int j = 0; j < n_other; ++j)
+      for (int i = 0; i < dim; ++i)
+        if (!(fabs(x[(long)(j * other) * dim + i] - x[(long)(j * other + (res - 1) * stride) * dim + i]) <= 1e-12 * extent))
+          same = 0;
+    C->sp_closed[k] = same;
+  }
+  free(x);
+}
+
+/* one query of the spline body, for the pointwise tests: xi[para_dim], S[dim], true gap, distance */
+void oracle_spline_nearest(const oracle_contact* C, const double* xq, double* xi, double* S, double* true_g,
+                           double* distance) {
+  double xi2[2], S3[3];
+  sp_nearest_at(C, xq, true_g, distance, xi2, S3);
+  for (int k = 0; k < C->sp_para_dim; ++k) xi[k] = xi2[k];
+  for (int i = 0; i < C->dim; ++i) S[i] = S3[i];
 }
 
 static void nearest(const oracle_contact* C, const double* xq, double* true_g, double* distance) {

@@ -71,7 +71,7 @@ class _Contact(C.Structure):
                 ("last_force", C.c_double * 3),
                 ("sp_para_dim", C.c_int), ("sp_p", C.c_int * 2), ("sp_n_knots", C.c_int * 2),
                 ("sp_knots", C.c_void_p * 2), ("sp_ctrl", C.c_void_p), ("sp_weights", C.c_void_p),
-                ("sp_resolution", C.c_int), ("sp_max_iterations", C.c_int)]
+                ("sp_resolution", C.c_int), ("sp_max_iterations", C.c_int), ("sp_closed", C.c_int * 2)]
 
 
 _lib = None
@@ -302,6 +302,16 @@ class ContactOracle:
         c.penalty = penalty
         c.area, c.gap, c.pressure = map(_ptr, (self.area, self.gap, self.pressure))
         self.c = c
+        if c.body_kind == 2:
+            lib().oracle_contact_spline_setup(C.byref(c))
+
+    def spline_nearest(self, xq):
+        """one closest-point query of the spline body: (xi, S, true gap, distance)"""
+        xq = np.ascontiguousarray(xq, dtype=np.float64)
+        xi, S = np.zeros(self.c.sp_para_dim), np.zeros(self.patch.dim)
+        g, d = C.c_double(), C.c_double()
+        lib().oracle_spline_nearest(C.byref(self.c), _ptr(xq), _ptr(xi), _ptr(S), C.byref(g), C.byref(d))
+        return xi, S, g.value, d.value
 
     def add_boundary_residual(self, u, r):
         u = np.ascontiguousarray(u, dtype=np.float64)

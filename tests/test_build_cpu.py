@@ -157,6 +157,27 @@ def test_assembly_of_a_library_source_is_the_object_s_own_and_is_never_written_b
     assert after["a"] > before["a"] and os.stat(shipped).st_mtime_ns > stamp and after["b"] == before["b"]
 
 
+def test_a_copied_tree_follows_its_own_files_not_those_of_the_tree_it_was_copied_from(tree, tmp_path, monkeypatch):
+    """the depfiles hold the absolute names of the tree the objects were compiled in: in a copy of that tree (objects and
+    all) an object whose depfile names the ORIGINAL's files is compiled again, and then follows the copy's"""
+    build.build()
+    copy = str(tmp_path / "copy")
+    shutil.copytree(tree.csrc, os.path.join(copy, "csrc"), copy_function=shutil.copy2)
+    shutil.copytree(tree.libdir, os.path.join(copy, "lib"), copy_function=shutil.copy2)
+    csrc, obj = os.path.join(copy, "csrc"), os.path.join(copy, "lib", "obj")
+    before = os.stat(os.path.join(obj, "a.o")).st_mtime_ns
+    assert os.path.realpath(os.path.join(tree.csrc, "a.hip")) in {os.path.realpath(d) for d in build.read_depfile(os.path.join(obj, "a.d"), csrc)}
+    build.compile_object("a.hip", obj, csrc)
+    deps = {os.path.realpath(d) for d in build.read_depfile(os.path.join(obj, "a.d"), csrc)}
+    assert os.stat(os.path.join(obj, "a.o")).st_mtime_ns > before
+    assert {os.path.realpath(os.path.join(csrc, f)) for f in ("a.hip", "a.hpp", "shared.hpp", "a_loop.inc")} <= deps
+    assert not any(d.startswith(os.path.realpath(tree.csrc) + os.sep) for d in deps)
+    # and is current from then on
+    again = os.stat(os.path.join(obj, "a.o")).st_mtime_ns
+    build.compile_object("a.hip", obj, csrc)
+    assert os.stat(os.path.join(obj, "a.o")).st_mtime_ns == again
+
+
 def test_the_depfile_is_read_as_make_reads_it(tmp_path):
     d = tmp_path / "x.d"
     d.write_text("/tmp/o/x.o: /src/x.hip \\\n  common.hpp ../../include/mimi\\ hip.h \\\n  /opt/a$$b.h\n")

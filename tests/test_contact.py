@@ -1,8 +1,10 @@
 """Contact integrator: oracle self-checks (CPU) and HIP-vs-oracle parity (GPU).
 
-PARITY UNPINNED for contact: no reference test exercises MortarContact and its closest-point
-query (splinepy) is absent; the oracle follows the reference's arithmetic downstream of an
-analytic rigid body (see oracle/contact_path.c)."""
+No reference test exercises MortarContact and its closest-point query (splinepy) is absent, so parity with the
+reference's own numbers cannot be pinned.  What is pinned: the arithmetic downstream of the query by the oracle
+(oracle/contact_path.c) and by the closed forms below (uniform and tilted penetration, objectivity of the tangent); the
+closest-point search of a rigid SPLINE body, in the kernels and in the oracle alike, by the long-double brute-force
+reference of tests/_closest_point.py (tests/test_spline_body_cpu.py, tests/test_contact_spline_gpu.py)."""
 import numpy as np
 import pytest
 

@@ -178,6 +178,44 @@ int mimi_hip_domain_post_time_advance(mimi_hip_domain_t h, const double* u);
  *        3 its second one: beta (J2Linear, materials.hpp:158), F_old (J2Simo, materials.hpp:434) */
 int mimi_hip_domain_get_state(mimi_hip_domain_t h, int what, double* out, int64_t capacity);
 int mimi_hip_domain_reset_state(mimi_hip_domain_t h);
+
+/* ---- field output -----------------------------------------------------------------
+ * Beyond the reference (its only outputs are the x_ / v_ vectors), from its own quantities.  All fields are fp64.  At a
+ * quadrature point, with F = I + grad u and P the first Piola-Kirchhoff stress mimi_hip_domain_add_residual would integrate
+ * at this u (committed state, the dt of mimi_hip_domain_set_dt; no state is changed):
+ *   CAUCHY       dim*dim components, column-major [i + j*dim]: sigma = P F^T / det F.  For the materials that go through the
+ *                reference's pk1 conversion this is their sigma, for St. Venant-Kirchhoff F S F^T / J, for J2Simo the stress
+ *                the reference actually uses.
+ *   VON_MISES    sqrt(3/2) * || sigma - tr(sigma)/dim I ||_F.  The deviator takes the trace over dim, as the reference's
+ *                own Dev does (material_utils.hpp:33,44): for J2 this is the q of its yield function, and in 3-D the usual
+ *                von Mises stress; in 2-D it is NOT the plane-strain von Mises stress of the 3-D tensor.
+ *   DET_F        det(I + grad u)
+ *   EQPS         the committed accumulated plastic strain, the values of mimi_hip_domain_get_state(what = 0)
+ *   TEMPERATURE  the committed temperature, the values of mimi_hip_domain_get_state(what = 1)
+ * EQPS and TEMPERATURE need no u (NULL allowed) and, like mimi_hip_domain_get_state, fail for a material without state. */
+enum mimi_hip_field {
+  MIMI_HIP_FIELD_CAUCHY = 0,
+  MIMI_HIP_FIELD_VON_MISES = 1,
+  MIMI_HIP_FIELD_DET_F = 2,
+  MIMI_HIP_FIELD_EQPS = 3,
+  MIMI_HIP_FIELD_TEMPERATURE = 4
+};
+/* components of a field in `dim` dimensions; -1: unknown field */
+int mimi_hip_field_components(int field, int dim);
+/* out[e][q][c] over the handle's elements, overwritten (capacity: doubles `out` holds, at least n_el * n_q * components).
+ * u and out host or device; synchronous when either is on the host, stream-ordered otherwise. */
+int mimi_hip_domain_point_field(mimi_hip_domain_t h, const double* u, int field, double* out, int64_t capacity);
+/* Lumped L2 projection onto the nodes, in accumulate form like every other output:
+ *   sum[A][c] += sum_e sum_q w_q det_q N_A(q) f_c(q),    weight[A] += sum_e sum_q w_q det_q N_A(q)      (weight may be NULL)
+ * over the handle's elements, A the caller's global node id (node_ids honoured); the caller divides.  Since N_A >= 0 and the
+ * shape functions sum to one, the quotient reproduces constants and stays inside the range of the point values around the
+ * node; element boxes and ranks compose by adding sums and weights before the division.  No atomics: two calls on the same
+ * inputs give the same bytes.  sum [n_nodes][components], weight [n_nodes]. */
+int mimi_hip_domain_nodal_field(mimi_hip_domain_t h, const double* u, int field, double* sum, double* weight);
+/* flat-table handles only: QuadData::N [n_elements][n_quad][n_dof] (precomputed.hpp:58-71), copied; the flat tables carry
+ * no shape values, and the nodal projection needs them.  Without it mimi_hip_domain_nodal_field on such a handle reports
+ * an error that says so. */
+int mimi_hip_domain_set_shape_values(mimi_hip_domain_t h, const double* N);
 /* The two-step form of mimi_hip_domain_add_residual_and_grad, for a caller that needs some rows before the others (the
  * rows a neighbour rank is waiting for: mimi_amd/parallel.py, bench.py): integrate() runs the integration kernels of the
  * whole handle -- element row pieces and element residual pieces into the handle's scratch, nothing into r / A_values --
@@ -199,7 +237,8 @@ int mimi_hip_domain_phase_ms(mimi_hip_domain_t h, double* phase1_ms, double* pha
 int mimi_hip_domain_phase_ms_detail(mimi_hip_domain_t h, double* prepass_ms, double* integration_ms, double* gather_ms);
 /* sizes: what = 0 n_elements, 1 n_quad, 2 n_dof, 3 nnz, 4 n_vdofs, 5 path (0 general, 1 tensor), 6 CSR kind (0 any,
  * 1 structured lexicographic, 2 structured permuted), 7 kernel family of the last assembly on the handle (0 none yet,
- * 1 two-phase tensor degree 2, 2 two-phase tensor degree 3, 3 small-element tensor, 4 general) */
+ * 1 two-phase tensor degree 2, 2 two-phase tensor degree 3, 3 small-element tensor, 4 general), 8 whether the handle
+ * currently holds per-point gradient tables dN_dX (flat-table handles always; patch handles once a general kernel ran) */
 int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what);
 
 /* ---- structured sparsity: PrecomputedData::PrepareSparsity (precomputed.cpp:151-174) ----

@@ -96,6 +96,8 @@ EXPORTS = [
     "mimi_hip_domain_integrate", "mimi_hip_domain_gather",
     "mimi_hip_rows_zero", "mimi_hip_rows_pack", "mimi_hip_rows_unpack_add",
     "mimi_hip_entries_pack", "mimi_hip_entries_unpack_add",
+    "mimi_hip_field_components", "mimi_hip_domain_point_field", "mimi_hip_domain_nodal_field",
+    "mimi_hip_domain_set_shape_values",
 ]
 
 
@@ -154,6 +156,10 @@ def lib():
     L.mimi_hip_domain_destroy.argtypes = [C.c_void_p]
     L.mimi_hip_domain_get_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
     L.mimi_hip_domain_reset_state.argtypes = [C.c_void_p]
+    L.mimi_hip_field_components.argtypes = [C.c_int, C.c_int]
+    L.mimi_hip_domain_point_field.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
+    L.mimi_hip_domain_nodal_field.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.mimi_hip_domain_set_shape_values.argtypes = [C.c_void_p, C.c_void_p]
     L.mimi_hip_domain_set_phase_timing.argtypes = [C.c_void_p, C.c_int]
     L.mimi_hip_domain_phase_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mimi_hip_domain_phase_ms_detail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -13,6 +13,7 @@
 #include "kernels_tensor_wgsym.hpp"
 #include "kernels_tensor_residual.hpp"
 #include "kernels_tensor_small.hpp"
+#include "kernels_fields.hpp"
 #include "tensor_dispatch.hpp"
 #include "domain_create.hpp"
 #include "domain_dispatch.hpp"
@@ -251,6 +252,31 @@ int mimi_hip_domain_get_state(mimi_hip_domain_t h, int what, double* out, int64_
   });
 }
 
+int mimi_hip_field_components(int field, int dim) { return field_components(field, dim); }
+
+int mimi_hip_domain_point_field(mimi_hip_domain_t h, const double* u, int field, double* out, int64_t capacity) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    run_point_field(h, u, field, out, capacity);
+  });
+}
+
+int mimi_hip_domain_nodal_field(mimi_hip_domain_t h, const double* u, int field, double* sum, double* weight) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    run_nodal_field(h, u, field, sum, weight);
+  });
+}
+
+int mimi_hip_domain_set_shape_values(mimi_hip_domain_t h, const double* N) {
+  return guarded([&] {
+    if (!h || !N) fail("null argument");
+    if (h->geo.ptr) fail("mimi_hip_domain_set_shape_values: flat-table handles only (a patch handle has its own 1-D tables)");
+    MH_HIP(hipSetDevice(h->device));
+    h->shape_N.assign(N, (size_t)h->n_el * h->n_q * h->n_dof, h->stream);
+  });
+}
+
 int mimi_hip_domain_set_phase_timing(mimi_hip_domain_t h, int on) {
   return guarded([&] {
     if (!h) fail("null handle");
@@ -315,6 +341,7 @@ int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what) {
   case 5: return h->path;
   case 6: return h->structured_csr ? 1 : (h->structured_perm ? 2 : 0);
   case 7: return h->last_family;
+  case 8: return h->dN_dX.ptr ? 1 : 0;
   default: return -1;
   }
 }

@@ -64,5 +64,12 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   // staging for host-resident u / r / A
   mimi_hip::DeviceBuffer<double> stage_u, stage_r, stage_A;
 
+  // field output (kernels_fields.hpp): shape values of the general route [n_el][n_q][n_dof], element pieces of the nodal
+  // form [n_el][n_dof][ncomp + 1], a node -> (element, local node) adjacency when the handle has none yet (adj_ptr / adj
+  // belong to the general row gather, which checks the CSR rows before it builds them), staging for host-resident outputs
+  mimi_hip::DeviceBuffer<double> shape_N, field_pieces, stage_f, stage_w;
+  mimi_hip::DeviceBuffer<int64_t> field_adj_ptr;
+  mimi_hip::DeviceBuffer<int32_t> field_adj;
+
   ~mimi_hip_domain_s();
 };

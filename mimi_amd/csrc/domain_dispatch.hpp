@@ -4,6 +4,7 @@
 #pragma once
 
 #include "domain_create.hpp"
+#include "kernels_fields.hpp"
 #include "kernels_tensor_residual.hpp"
 #include "kernels_tensor_wgsym.hpp"
 
@@ -42,7 +43,7 @@ inline GeneralArgs general_args(mimi_hip_domain_s* h, const DomainCall& c) {
 }
 
 // node -> incident (element << 6 | local node) lists of the general row gather
-inline void build_adjacency(mimi_hip_domain_s* h) {
+inline void fill_adjacency(mimi_hip_domain_s* h, DeviceBuffer<int64_t>& adj_ptr, DeviceBuffer<int32_t>& adj_out) {
   const size_t n = (size_t)h->n_el * h->n_dof;
   const std::vector<int32_t> dofs = to_host(h->dofs.ptr, n);
   const int64_t n_nodes = h->n_vdofs / h->dim;
@@ -52,9 +53,11 @@ inline void build_adjacency(mimi_hip_domain_s* h) {
   std::vector<int32_t> adj(n);
   std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
   for (size_t k = 0; k < n; ++k) adj[fill[dofs[k]]++] = (int32_t)(((k / h->n_dof) << 6) | (k % h->n_dof));
-  h->adj_ptr.assign(ptr.data(), ptr.size(), h->stream);
-  h->adj.assign(adj.data(), adj.size(), h->stream);
+  adj_ptr.assign(ptr.data(), ptr.size(), h->stream);
+  adj_out.assign(adj.data(), adj.size(), h->stream);
 }
+
+inline void build_adjacency(mimi_hip_domain_s* h) { fill_adjacency(h, h->adj_ptr, h->adj); }
 
 // two-phase general path: element blocks / residual vectors densely into scratch_k / scratch_r, then
 // general_gather_kernel.  Needs n_el * n_tdof^2 doubles (77 GB at 128 x 128 x 16 p = 3) and the node -> element adjacency;
@@ -269,6 +272,119 @@ inline void run_post_time_advance(mimi_hip_domain_s* h, const double* u) {
   else if (h->path == 1) launch_tensor_post(h, c);
   else launch_general_post(h, c);
   if (mu.host) check_status(h);
+}
+
+// ---- field output (kernels_fields.hpp) ---------------------------------------------------------------------------------
+
+// by_material_family with neo-Hookean as a family of its own (FIELD_NEOHOOKEAN)
+template<class F>
+void by_field_family(int kind, F&& f) {
+  if (kind == MIMI_HIP_MAT_NEOHOOKEAN) f(std::integral_constant<int, FIELD_NEOHOOKEAN>{});
+  else by_material_family(kind, f);
+}
+
+template<int DIM, int P>
+void launch_field_tensor_dp(mimi_hip_domain_s* h, const TensorArgs& a, const FieldArgs& fa) {
+  by_field_family(h->mat.m.kind, [&](auto K) {
+    launch(field_tensor_kernel<DIM, P, decltype(K)::value>, dim3((unsigned)h->n_el), dim3(FieldShape<DIM, P>::THREADS),
+           (size_t)FieldShape<DIM, P>::total(fa.ncomp + 1) * sizeof(double), h->stream, a, fa);
+  });
+}
+
+// the element kernel of the handle's route: the tensor kernel for every tensor_usable handle (no per-point table is built),
+// the general kernel otherwise
+inline void launch_field(mimi_hip_domain_s* h, const double* u, FieldArgs fa) {
+  const DomainCall c{u};
+  if (tensor_usable(h)) {
+    const TensorArgs a = tensor_args(h, c);
+    const int p = h->degree[0];
+    if (h->dim == 2) {
+      if (p == 1) launch_field_tensor_dp<2, 1>(h, a, fa);
+      else if (p == 2) launch_field_tensor_dp<2, 2>(h, a, fa);
+      else launch_field_tensor_dp<2, 3>(h, a, fa);
+    } else {
+      if (p == 1) launch_field_tensor_dp<3, 1>(h, a, fa);
+      else if (p == 2) launch_field_tensor_dp<3, 2>(h, a, fa);
+      else launch_field_tensor_dp<3, 3>(h, a, fa);
+    }
+    return;
+  }
+  ensure_general_tables(h);
+  if (fa.nodal) {
+    if (!h->shape_N.ptr) {
+      if (!h->geo.ptr)
+        fail("nodal field on a flat-table handle: the tables carry no shape values, give them with mimi_hip_domain_set_shape_values");
+      const int64_t total = (int64_t)h->n_el * h->n_q * h->n_dof;
+      h->shape_N.resize((size_t)total);
+      auto kernel = h->dim == 2 ? expand_shape_kernel<2> : expand_shape_kernel<3>;
+      launch(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, patch_dev(h, nullptr), h->shape_N.ptr);
+    }
+    fa.N = h->shape_N.ptr;
+  }
+  const GeneralArgs a = general_args(h, c);
+  const size_t lds = ((size_t)h->n_dof * h->dim + (size_t)(h->dim * h->dim + 1) * h->n_q) * sizeof(double);
+  by_field_family(h->mat.m.kind, [&](auto K) {
+    constexpr int FK = decltype(K)::value;
+    auto kernel = h->dim == 2 ? field_general_kernel<2, FK> : field_general_kernel<3, FK>;
+    launch(kernel, dim3((unsigned)h->n_el), dim3(256), lds, h->stream, a, fa);
+  });
+}
+
+// what a field call checks before anything runs; returns the field's components
+inline int field_begin(mimi_hip_domain_s* h, const double* u, int field, FieldArgs& fa) {
+  MH_HIP(hipSetDevice(h->device));
+  const int ncomp = field_components(field, h->dim);
+  if (ncomp < 0) fail("unknown field id %d", field);
+  const bool of_state = field == MIMI_HIP_FIELD_EQPS || field == MIMI_HIP_FIELD_TEMPERATURE;
+  if (of_state && !material_has_state(h->mat.m.kind)) fail("material has no state");
+  if (!of_state && !u) fail("null vector argument");
+  fa = FieldArgs{};
+  fa.field = field;
+  fa.ncomp = ncomp;
+  fa.need_F = of_state ? 0 : 1;
+  return ncomp;
+}
+
+// out[e][q][c], overwritten
+inline void run_point_field(mimi_hip_domain_s* h, const double* u, int field, double* out, int64_t capacity) {
+  FieldArgs fa;
+  const int ncomp = field_begin(h, u, field, fa);
+  if (!out) fail("null argument");
+  const int64_t need = h->n_pts * ncomp;
+  if (capacity < need) fail("field buffer too small (%lld < %lld)", (long long)capacity, (long long)need);
+  Mirror<double> mu;
+  if (fa.need_F) mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
+  const bool out_host = !is_device_pointer(out);
+  if (out_host) h->stage_f.resize((size_t)need);
+  fa.out = out_host ? h->stage_f.ptr : out;
+  launch_field(h, mu.dev, fa);
+  if (out_host) MH_HIP(hipMemcpyAsync(out, fa.out, (size_t)need * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out_host || mu.host) check_status(h);  // synchronous for host-resident arguments
+}
+
+// sum[A][c] += ..., weight[A] += ... : element pieces, then one thread per (node, component) over the adjacency
+inline void run_nodal_field(mimi_hip_domain_s* h, const double* u, int field, double* sum, double* weight) {
+  FieldArgs fa;
+  const int ncomp = field_begin(h, u, field, fa);
+  if (!sum) fail("null argument");
+  const int64_t n_nodes = h->n_vdofs / h->dim;
+  Mirror<double> mu, mw;
+  if (fa.need_F) mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
+  Mirror<double> ms = Mirror<double>::inout(sum, (size_t)n_nodes * ncomp, h->stage_f, h->stream);
+  if (weight) mw = Mirror<double>::inout(weight, (size_t)n_nodes, h->stage_w, h->stream);
+  h->field_pieces.resize((size_t)h->n_el * h->n_dof * (ncomp + 1));
+  fa.nodal = 1;
+  fa.out = h->field_pieces.ptr;
+  launch_field(h, mu.dev, fa);
+  if (!h->adj_ptr.ptr && !h->field_adj_ptr.ptr) fill_adjacency(h, h->field_adj_ptr, h->field_adj);
+  const int64_t* adj_ptr = h->adj_ptr.ptr ? h->adj_ptr.ptr : h->field_adj_ptr.ptr;
+  const int32_t* adj = h->adj_ptr.ptr ? h->adj.ptr : h->field_adj.ptr;
+  const int64_t total = n_nodes * (ncomp + 1);
+  launch(field_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, n_nodes, h->n_dof, ncomp, adj_ptr, adj,
+         (const double*)h->field_pieces.ptr, ms.dev, mw.dev);
+  ms.finish(h->stream);
+  if (weight) mw.finish(h->stream);
+  if (mu.host || ms.host || mw.host) check_status(h);
 }
 
 }  // namespace mimi_hip

@@ -142,6 +142,8 @@ class NonlinearSolid(NonlinearBase):
             d.csr_col = ptr(self.pattern_.col, "int32").value
             check(L.mimi_hip_domain_create(C.byref(d), C.byref(mat), self.device_, C.byref(h)))
         self._h = h
+        if self.patch_ is None and self.tables_.get("N") is not None:
+            self.SetShapeValues(self.tables_["N"])
         self.n_elements_ = int(L.mimi_hip_domain_info(h, 0))
         self.n_quad_ = int(L.mimi_hip_domain_info(h, 1))
         self.n_dof_ = int(L.mimi_hip_domain_info(h, 2))
@@ -223,6 +225,65 @@ class NonlinearSolid(NonlinearBase):
         out = np.empty(shape)
         check(_capi.lib().mimi_hip_domain_get_state(self._handle(), ids[what], ptr(out), out.size))
         return out
+
+    # -- field output (mimi_hip.h: "field output") ---------------------------------------------------
+    FIELDS = {"cauchy_stress": 0, "von_mises_stress": 1, "det_F": 2, "accumulated_plastic_strain": 3, "temperature": 4}
+
+    def _dim(self):
+        return self.patch_.dim if self.patch_ is not None else self.tables_["dim"]
+
+    def _field(self, name):
+        if name not in self.FIELDS:
+            raise ValueError(f"unknown field {name!r} (known: {', '.join(self.FIELDS)})")
+        return self.FIELDS[name]
+
+    def FieldComponents(self, name):
+        """components of a field: dim^2 for "cauchy_stress" (column-major, [i + j dim]), 1 for the others"""
+        return int(_capi.lib().mimi_hip_field_components(self._field(name), self._dim()))
+
+    def SetShapeValues(self, N):
+        """flat-table handles: the shape values N[e, q, a] (QuadData::N) the nodal projection needs; taken from
+        tables["N"] at Prepare() when the dict has it"""
+        N = np.ascontiguousarray(N, dtype=np.float64)
+        if N.ndim != 3:
+            raise ValueError(f"shape values must be [n_elements, n_quad, n_dof], got {N.shape}")
+        L = _capi.lib()
+        want = (int(L.mimi_hip_domain_info(self._handle(), 0)), int(L.mimi_hip_domain_info(self._handle(), 1)),
+                int(L.mimi_hip_domain_info(self._handle(), 2)))
+        if N.shape != want:
+            raise ValueError(f"shape values must be {want}, got {N.shape}")
+        check(L.mimi_hip_domain_set_shape_values(self._handle(), ptr(N)))
+
+    def PointField(self, name, u, out=None):
+        """the field at the quadrature points, [n_el, n_q, ncomp] (overwritten; allocated on the host when out is None).
+        "cauchy_stress": sigma = P F^T / det F with the P AddDomainResidual would integrate at u (committed state, the
+        pushed dt; no state changes); "von_mises_stress": sqrt(3/2) |sigma - tr(sigma)/dim I|, the trace taken over dim as
+        in the reference's Dev -- the q of its J2 yield function, in 3-D the usual von Mises stress; "det_F";
+        "accumulated_plastic_strain" and "temperature": the committed state (u may be None).  numpy arrays or torch
+        device tensors."""
+        field = self._field(name)
+        ncomp = self.FieldComponents(name)
+        if out is None:
+            out = np.empty((self.n_elements_, self.n_quad_, ncomp))
+        self._push_dt()
+        self._follow_torch(u, out)
+        size = out.size if isinstance(out, np.ndarray) else out.numel()
+        check(_capi.lib().mimi_hip_domain_point_field(self._handle(), fptr(u), field, fptr(out), size))
+        return out
+
+    def NodalField(self, name, u, sum, weight=None):
+        """the lumped L2 projection in accumulate form: sum[A, c] += sum_e sum_q w det N_A f_c, weight[A] += sum_e sum_q
+        w det N_A over this handle's elements (A: the caller's node ids); the caller divides.  sum [n_nodes, ncomp],
+        weight [n_nodes] or None."""
+        field = self._field(name)
+        self._push_dt()
+        self._follow_torch(u, sum, weight)
+        check(_capi.lib().mimi_hip_domain_nodal_field(self._handle(), fptr(u), field, fptr(sum), fptr(weight)))
+        return sum
+
+    def HoldsGradientTables(self):
+        """whether the handle holds per-point gradient tables (mimi_hip_domain_info(h, 8))"""
+        return bool(_capi.lib().mimi_hip_domain_info(self._handle(), 8))
 
     def SetPhaseTiming(self, on=True):
         check(_capi.lib().mimi_hip_domain_set_phase_timing(self._handle(), 1 if on else 0))

@@ -760,6 +760,11 @@ class NonlinearSolid(Solid):
                 rc.save_dynamic_vector("x_", self.in_reference_numbering(x))
             if rc.should_save("v"):
                 rc.save_dynamic_vector("v_", self.in_reference_numbering(v))
+            # nodal fields (beyond the reference, which saves x_ / v_ only): <field name>_<step>, in its node order
+            for name in NonlinearSolidIntegrator.FIELDS:
+                if rc.should_save(name):
+                    f = self.field(name)
+                    rc.save_dynamic_vector(name + "_", self.in_reference_numbering(f, ncomp=f.shape[1]))
             rc.next_time_step(dt)
 
     def step_time2(self):
@@ -886,13 +891,52 @@ class NonlinearSolid(Solid):
         self.surfaces_[bid] = s
         return s
 
-    def in_reference_numbering(self, vec):
+    def field(self, name, where="nodes", u=None):
+        """A stress / state field as a host array: "cauchy_stress" ([i + j dim], sigma = P F^T / det F),
+        "von_mises_stress" (sqrt(3/2) |sigma - tr(sigma)/dim I|: the trace over dim as in the reference's Dev, so the q of
+        its J2 yield function; in 3-D the usual von Mises stress), "det_F", "accumulated_plastic_strain", "temperature".
+
+        where = "points": [n_el, n_q, ncomp] at the quadrature points; "nodes": [n_nodes, ncomp], the lumped L2 projection
+        sum_q w det N_A f / sum_q w det N_A (reproduces constants, stays within the point values around a node).  u: a
+        displacement in this facade's numbering (default: the committed one).  With periodic boundaries sum and weight are
+        computed on the unwrapped nodes and folded before the division: the result is in the folded numbering, like
+        solution_view."""
+        if name not in NonlinearSolidIntegrator.FIELDS:
+            raise ValueError(f"unknown field {name!r} (known: {', '.join(NonlinearSolidIntegrator.FIELDS)})")
+        if where not in ("nodes", "points"):
+            raise ValueError(f"where must be 'nodes' or 'points', got {where!r}")
+        if getattr(self, "domain_", None) is None:
+            raise RuntimeError("field() needs setup()")
+        torch = self._torch
+        x = self.d_x_ if u is None else torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64).reshape(-1)).to(self.d_x_.device)
+        if x.numel() != self.d_x_.numel():
+            raise ValueError(f"u has {x.numel()} entries, the displacement has {self.d_x_.numel()}")
+        xu = self._expand(x) if self.fold_ is not None else x
+        self.domain_.dt_ = self.time_step_size      # (the effective dts do not reach the material)
+        ncomp = self.domain_.FieldComponents(name)
+        if where == "points":
+            return self.domain_.PointField(name, xu)
+        n_u = self.patch_.n_nodes
+        s = torch.zeros((n_u, ncomp), dtype=torch.float64, device=x.device)
+        w = torch.zeros(n_u, dtype=torch.float64, device=x.device)
+        self.domain_.NodalField(name, xu, s, w)
+        s, w = s.cpu().numpy(), w.cpu().numpy()
+        if self.node_map_ is not None:
+            n_f = int(self.node_map_.max()) + 1
+            sf, wf = np.zeros((n_f, ncomp)), np.zeros(n_f)
+            np.add.at(sf, self.node_map_, s)
+            np.add.at(wf, self.node_map_, w)
+            s, w = sf, wf
+        return s / w[:, None]
+
+    def in_reference_numbering(self, vec, ncomp=None):
         """byVDIM vector of this facade (lexicographic nodes) -> the reference's dof order (MFEM's NURBS numbering).
+        ncomp: components per node (default: dim, a displacement-like vector; 1 for a scalar nodal field).
 
         With periodic boundaries the vector is expanded first (every copy of a joined node gets its value) and written
         in the NON-periodic reference numbering: MFEM's numbering of a periodic space cannot be restated without MFEM."""
         order = self._nurbs.mfem_order()
-        v = np.asarray(vec).reshape(-1, self._dim)
+        v = np.asarray(vec).reshape(-1, self._dim if ncomp is None else int(ncomp))
         if getattr(self, "node_map_", None) is not None and len(v) != len(order):
             v = v[self.node_map_]
         return np.ascontiguousarray(v[order]).reshape(-1)

@@ -1,0 +1,352 @@
+"""Field output on the device (include/mimi_hip.h, "field output") against the numpy yardstick of tests/_fields.py on the
+oracle, against closed forms, and its properties: range, reproducibility, composition over element boxes, numbering,
+storage, no table materialisation on the tensor route, errors, and the facade (field(), save cadence, periodic fold, example).
+
+Bars.  Parity: relmax = max|a - b| / max|b| <= 1e-11, the project's tangent bar (the residual's 1e-12 is a bar on sums of
+these point values; sigma = P F^T / det F adds a small matrix product and a division per point, the nodal quotient one
+more division).  Closed forms: 1e-13 in the same measure (a handful of fp64 operations on numbers of one magnitude on either
+side).  Composition: 1e-14 (the same products, added in another order: at most 27 / 64 terms of one sign per node)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import _fields
+from _cases import product_material
+from _fields import DT, J2_MODELS, MATERIALS, SHAPES
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def relmax(a, b):
+    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+
+
+def make_handle(shape, matname, D, with_N=True, **kw):
+    import mimi_amd
+    from mimi_amd.integrators import CSRPattern, NonlinearSolid
+    n_el, p, lengths, creator = SHAPES[shape]
+    pattern = kw.pop("pattern", None) or CSRPattern(D.rowptr.astype(np.int64), D.col.astype(np.int32), D.nnz)
+    if creator == "tables":
+        tables = dict(dim=D.patch.dim, n_nodes=D.patch.n_nodes, dofs=D.conn, dN_dX=D.dN_dX, weight_det=D.weight * D.det)
+        if with_N:
+            tables["N"] = D.tables["N"]
+        G = NonlinearSolid("domain", product_material(matname), pattern, tables=tables).Prepare()
+    else:
+        patch = mimi_amd.BSplinePatch.block(n_el, p, lengths)
+        G = NonlinearSolid("domain", product_material(matname), pattern, patch=patch, **kw).Prepare()
+    G.dt_ = DT
+    return G
+
+
+def committed(shape, matname, **kw):
+    """the shared reference of (shape, material) and a product handle in the same committed state"""
+    ref = _fields.reference(shape, matname)
+    P, D, u0 = ref[:3]
+    G = make_handle(shape, matname, D, **kw)
+    if D.has_states:
+        G.DomainPostTimeAdvance(u0)
+    return ref, G
+
+
+def nodal(G, name, u, n_nodes):
+    ncomp = G.FieldComponents(name)
+    s, w = np.zeros((n_nodes, ncomp)), np.zeros(n_nodes)
+    G.NodalField(name, u, s, w)
+    return s, w
+
+
+def holds_tables(G):
+    from mimi_amd import _capi
+    return int(_capi.lib().mimi_hip_domain_info(G._h, 8))
+
+
+# ---- 1. parity ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("matname", MATERIALS)
+@pytest.mark.parametrize("shape", list(SHAPES))
+def test_parity_with_the_yardstick(shape, matname):
+    (P, D, u0, u, pts, nod), G = committed(shape, matname)
+    # what the inputs are meant to exercise
+    assert pts["det_F"].min() > 0.5
+    if matname in J2_MODELS:
+        share = (D.eqps > 0).mean()
+        print(f"plastic share {share:.2f}")
+        assert 0.2 < share < 0.8
+    creator = SHAPES[shape][3]
+    assert G.path_ == (1 if creator == "bspline" else 0)
+    worst = 0.0
+    for name in _fields.FIELDS:
+        if name not in pts:
+            with pytest.raises(RuntimeError, match="no state"):
+                G.PointField(name, None)
+            continue
+        a = G.PointField(name, u)
+        assert a.shape == pts[name].shape
+        s, w = nodal(G, name, u, P.n_nodes)
+        assert w.min() > 0
+        e_pt, e_nd = relmax(a, pts[name]), relmax(s / w[:, None], nod[name])
+        print(f"{shape} {matname} {name}: points {e_pt:.2e} nodes {e_nd:.2e}")
+        worst = max(worst, e_pt, e_nd)
+        assert e_pt <= 1e-11 and e_nd <= 1e-11
+        if name in ("accumulated_plastic_strain", "temperature"):
+            assert np.array_equal(a[..., 0], G.State(name))
+            assert np.array_equal(G.PointField(name, None), a)           # no u needed
+    print(f"{shape} {matname} worst {worst:.2e}")
+    if creator == "bspline":
+        assert holds_tables(G) == 0
+        assert G.LastKernelFamily() != "general"
+
+
+# ---- 2. closed form, no oracle -------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("matname", ["neohook", "stvk"])
+@pytest.mark.parametrize("n_el", [(4, 3, 3), (3, 4)], ids=["4x3x3", "3x4"])
+def test_closed_form_homogeneous_deformation(n_el, matname):
+    import mimi_amd
+    from mimi_amd.integrators import CSRPattern, NonlinearSolid
+    patch = mimi_amd.BSplinePatch.block(n_el, 2)
+    dim = patch.dim
+    G = NonlinearSolid("domain", product_material(matname), CSRPattern.of_bspline_patch(patch), patch=patch).Prepare()
+    F0 = _fields.homogeneous_F(dim)
+    u = _fields.homogeneous_u(patch.control_points, F0)
+    sig = _fields.closed_form_sigma(matname, F0)
+    exact = {"cauchy_stress": sig.ravel(order="F"), "von_mises_stress": np.array([_fields.von_mises_of(sig)]),
+             "det_F": np.array([np.linalg.det(F0)])}
+    for name, value in exact.items():
+        a = G.PointField(name, u)
+        s, w = nodal(G, name, u, patch.n_nodes)
+        e_pt, e_nd = relmax(a, np.broadcast_to(value, a.shape)), relmax(s / w[:, None], np.broadcast_to(value, s.shape))
+        print(f"{n_el} {matname} {name}: points {e_pt:.2e} nodes {e_nd:.2e}")
+        assert e_pt <= 1e-13 and e_nd <= 1e-13
+
+
+# ---- 3. properties ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape,matname", [("4x3x3p2", "j2"), ("4x4x5p3", "j2"), ("3x4p2", "j2log"), ("3x2x2p2-tables", "j2")])
+def test_range_reproducibility_and_no_side_effects(shape, matname):
+    (P, D, u0, u, pts, nod), G = committed(shape, matname)
+    state0 = {k: G.State(k) for k in ("accumulated_plastic_strain", "temperature", "plastic_strain")}
+    r0 = np.zeros(P.n_vdofs)
+    G.AddDomainResidual(u, r0)
+    conn = D.tables["conn"]
+    for name in ("von_mises_stress", "det_F", "accumulated_plastic_strain", "temperature"):
+        a = G.PointField(name, u)
+        s, w = nodal(G, name, u, P.n_nodes)
+        f = (s / w[:, None])[:, 0]
+        # within the point values of the elements around the node
+        lo, hi = np.full(P.n_nodes, np.inf), np.full(P.n_nodes, -np.inf)
+        np.minimum.at(lo, conn, a.min(axis=(1, 2))[:, None])
+        np.maximum.at(hi, conn, a.max(axis=(1, 2))[:, None])
+        slack = 1e-12 * np.abs(a).max()
+        assert (f >= lo - slack).all() and (f <= hi + slack).all()
+        if name == "von_mises_stress":
+            assert (a >= 0).all() and (f >= 0).all()
+        # a second call: identical bytes
+        assert np.array_equal(G.PointField(name, u), a)
+        s2, w2 = nodal(G, name, u, P.n_nodes)
+        assert np.array_equal(s2, s) and np.array_equal(w2, w)
+    s, w = nodal(G, "cauchy_stress", u, P.n_nodes)
+    s2, w2 = nodal(G, "cauchy_stress", u, P.n_nodes)
+    assert np.array_equal(s2, s) and np.array_equal(w2, w)
+    # nothing else moved: the state and a following residual assembly are bitwise what they were
+    for k, v in state0.items():
+        assert np.array_equal(G.State(k), v)
+    r1 = np.zeros(P.n_vdofs)
+    G.AddDomainResidual(u, r1)
+    assert np.array_equal(r1, r0)
+
+
+# ---- 4. composition over element boxes ---------------------------------------------------------------------------------------
+@pytest.mark.parametrize("axis", [0, 1, 2])
+@pytest.mark.parametrize("matname", ["neohook", "j2"])
+def test_element_boxes_compose(axis, matname):
+    shape = "4x3x3p2"
+    (P, D, u0, u, pts, nod), G = committed(shape, matname)
+    n_el = SHAPES[shape][0]
+    for name in ("cauchy_stress", "von_mises_stress"):
+        s_all, w_all = nodal(G, name, u, P.n_nodes)
+        s, w = np.zeros_like(s_all), np.zeros_like(w_all)
+        for b, e in ((0, 1), (1, n_el[axis])):
+            begin, end = [0, 0, 0], list(n_el)
+            begin[axis], end[axis] = b, e
+            Gb = make_handle(shape, matname, D, element_box=(begin, end))
+            if D.has_states:
+                Gb.DomainPostTimeAdvance(u0)
+            Gb.NodalField(name, u, s, w)
+            assert holds_tables(Gb) == 0
+        assert relmax(s, s_all) <= 1e-14 and relmax(w, w_all) <= 1e-14
+
+
+# ---- 5. numbering and storage ----------------------------------------------------------------------------------------------------
+def test_permuted_node_ids_device_tensors_and_accumulation():
+    import scipy.sparse as sp
+    import torch
+    from mimi_amd.integrators import CSRPattern
+    shape, matname = "4x3x3p2", "j2"
+    (P, D, u0, u, pts, nod), G = committed(shape, matname)
+    perm = np.random.default_rng(11).permutation(P.n_nodes).astype(np.int64)
+    dofperm = (perm[:, None] * 3 + np.arange(3)[None, :]).ravel()
+    rows = np.repeat(np.arange(P.n_vdofs), np.diff(D.rowptr))
+    S = sp.coo_matrix((np.ones(D.nnz), (dofperm[rows], dofperm[D.col])), shape=(P.n_vdofs, P.n_vdofs)).tocsr()
+    S.sort_indices()
+    pattern = CSRPattern(S.indptr.astype(np.int64), S.indices.astype(np.int32), D.nnz)
+    Gp = make_handle(shape, matname, D, pattern=pattern, node_ids=perm)
+    u_p, u0_p = np.empty_like(u), np.empty_like(u0)
+    u_p[dofperm], u0_p[dofperm] = u, u0
+    Gp.DomainPostTimeAdvance(u0_p)
+    for name in ("cauchy_stress", "accumulated_plastic_strain"):
+        s, w = nodal(G, name, u, P.n_nodes)
+        sp_, wp = nodal(Gp, name, u_p, P.n_nodes)
+        assert np.array_equal(sp_[perm], s) and np.array_equal(wp[perm], w)          # the same sums, at the caller's ids
+        assert np.array_equal(Gp.PointField(name, u_p), G.PointField(name, u))
+    assert holds_tables(Gp) == 0
+    # device tensors: the same bytes as host arrays
+    dev = torch.device("cuda", 0)
+    tu = torch.from_numpy(np.array(u)).to(dev)
+    for name in ("cauchy_stress", "von_mises_stress"):
+        ncomp = G.FieldComponents(name)
+        a = G.PointField(name, u)
+        ta = torch.full(a.shape, float("nan"), dtype=torch.float64, device=dev)
+        G.PointField(name, tu, ta)
+        G.Synchronize()
+        assert np.array_equal(ta.cpu().numpy(), a)
+        s, w = nodal(G, name, u, P.n_nodes)
+        ts = torch.zeros((P.n_nodes, ncomp), dtype=torch.float64, device=dev)
+        tw = torch.zeros(P.n_nodes, dtype=torch.float64, device=dev)
+        G.NodalField(name, tu, ts, tw)
+        G.Synchronize()
+        assert np.array_equal(ts.cpu().numpy(), s) and np.array_equal(tw.cpu().numpy(), w)
+        # accumulate form: old value + the field sum; weight may be left out
+        rng = np.random.default_rng(2)
+        s0, w0 = rng.standard_normal(s.shape), rng.standard_normal(w.shape)
+        s1, w1 = s0.copy(), w0.copy()
+        G.NodalField(name, u, s1, w1)
+        assert np.array_equal(s1, s0 + s) and np.array_equal(w1, w0 + w)
+        s2 = s0.copy()
+        G.NodalField(name, u, s2)
+        assert np.array_equal(s2, s1)
+
+
+# ---- 6. no table materialisation ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", ["4x3x3p2", "4x4x5p3"])
+def test_tensor_route_builds_no_per_point_tables(shape):
+    (P, D, u0, u, pts, nod), G = committed(shape, "neohook")
+    assert holds_tables(G) == 0
+    G.PointField("cauchy_stress", u)
+    nodal(G, "von_mises_stress", u, P.n_nodes)
+    assert holds_tables(G) == 0
+    # (what the query answers on a handle that has them)
+    (_, D2, *_), G2 = committed("3x2x2p2-tables", "neohook")
+    assert holds_tables(G2) == 1
+
+
+# ---- 7. errors -------------------------------------------------------------------------------------------------------------------
+def test_errors():
+    from mimi_amd import _capi
+    shape = "3x2x2p2-tables"
+    (P, D, u0, u, pts, nod), G = committed(shape, "neohook", with_N=False)
+    s, w = np.zeros((P.n_nodes, 1)), np.zeros(P.n_nodes)
+    with pytest.raises(RuntimeError, match="set_shape_values"):
+        G.NodalField("von_mises_stress", u, s, w)
+    assert np.array_equal(G.PointField("det_F", u), G.PointField("det_F", u))      # the point form needs no shape values
+    G.SetShapeValues(D.tables["N"])
+    G.NodalField("von_mises_stress", u, s, w)
+    assert relmax(s / w[:, None], nod["von_mises_stress"]) <= 1e-11
+    L = _capi.lib()
+    out = np.zeros(P.n_el * D.weight.shape[1] * 9)
+    with pytest.raises(RuntimeError, match="unknown field"):
+        _capi.check(L.mimi_hip_domain_point_field(G._h, _capi.fptr(u), 7, _capi.fptr(out), out.size))
+    with pytest.raises(RuntimeError, match="unknown field"):
+        _capi.check(L.mimi_hip_domain_nodal_field(G._h, _capi.fptr(u), -1, _capi.fptr(s), None))
+    with pytest.raises(RuntimeError, match="too small"):
+        _capi.check(L.mimi_hip_domain_point_field(G._h, _capi.fptr(u), 0, _capi.fptr(out), out.size - 1))
+    with pytest.raises(RuntimeError, match="null"):
+        _capi.check(L.mimi_hip_domain_point_field(G._h, None, 0, _capi.fptr(out), out.size))
+    # shape values belong to flat-table handles
+    (_, D3, *_), G3 = committed("3x4p2", "neohook")
+    with pytest.raises(RuntimeError, match="flat-table"):
+        G3.SetShapeValues(D3.tables["N"])
+
+
+# ---- 8. facade -------------------------------------------------------------------------------------------------------------------
+def test_facade_fields_and_save_cadence(tmp_path):
+    from test_nonlinear_solid import beam
+    nl = beam("j2")
+    rc = nl.runtime_communication
+    archive = os.path.join(str(tmp_path), "fields.npz")
+    rc.set_fname(archive)
+    rc.append_should_save("x", 1)
+    rc.append_should_save("von_mises_stress", 1)
+    rc.append_should_save("accumulated_plastic_strain", 1)
+    n = nl.n_vertices()
+    expect = []
+    for i in range(3):
+        nl.step_time2()
+        expect.append((nl.in_reference_numbering(nl.field("von_mises_stress"), ncomp=1),
+                       nl.in_reference_numbering(nl.field("accumulated_plastic_strain"), ncomp=1)))
+    with np.load(archive) as z:
+        for i, (q, eqps) in enumerate(expect):
+            assert z[f"von_mises_stress_{i}"].shape == (n,)
+            assert np.array_equal(z[f"von_mises_stress_{i}"], q)
+            assert np.array_equal(z[f"accumulated_plastic_strain_{i}"], eqps)
+            assert f"x_{i}" in z.files
+    eqps = nl.field("accumulated_plastic_strain")
+    assert eqps.shape == (n, 1) and (eqps >= 0).all() and eqps.max() > 0
+    pts = nl.field("accumulated_plastic_strain", where="points")
+    assert pts.shape[2] == 1 and np.array_equal(pts[..., 0], nl.domain_.State("accumulated_plastic_strain"))
+    sig = nl.field("cauchy_stress")
+    assert sig.shape == (n, 4) and np.abs(sig[:, 1] - sig[:, 2]).max() <= 1e-12 * np.abs(sig).max()
+    # u: another displacement than the committed one
+    assert np.abs(nl.field("det_F", u=np.zeros(2 * n)) - 1.0).max() <= 1e-14
+    with pytest.raises(ValueError):
+        nl.field("stress")
+
+
+def test_facade_periodic_fold_of_a_homogeneous_state():
+    """a (3, 3, 2) degree-2 block periodic in x and y; u = g Z (a shear and a stretch along z) is periodic and has the
+    homogeneous F = I + g e_z^T: the folded nodal field is the closed-form constant at every folded node"""
+    import mimi_amd as mimi
+    nl = mimi.NonlinearSolid()
+    nl.read_mesh(os.path.join(ROOT, "tests", "golden", "meshes", "cube-nurbs.mesh"))
+    nl.elevate_degrees(1)
+    nb = nl._nurbs
+    knots = [np.concatenate([[0.0] * 3, np.arange(1, m) / m, [1.0] * 3]) for m in (3, 3, 2)]
+    nl._nurbs = nb._apply(knots, list(nb.degrees))
+    nl.set_material(product_material("neohook"))
+    bc = mimi.BoundaryConditions()
+    for c in range(3):
+        bc.initial.dirichlet(0, c)
+    bc.initial.periodic(6, 4)
+    bc.initial.periodic(3, 5)
+    nl.boundary_condition = bc
+    nl.setup(1)
+    assert nl.fold_ is not None and list(nl.patch_.n_ctrl) == [5, 5, 4]
+    assert [int(v) for v in nl._nurbs.n_spans] == [3, 3, 2]
+    g = np.array([0.04, -0.03, 0.05])
+    F0 = np.eye(3)
+    F0[:, 2] += g
+    X = nl.solution_view("displacement", "x_ref").reshape(-1, 3)         # folded nodes
+    u = np.outer(X[:, 2], g).ravel()
+    sig = _fields.closed_form_sigma("neohook", F0)
+    n_f = len(X)
+    assert n_f == int(nl.node_map_.max()) + 1 < nl.patch_.n_nodes
+    for name, value in (("cauchy_stress", sig.ravel(order="F")), ("von_mises_stress", np.array([_fields.von_mises_of(sig)])),
+                        ("det_F", np.array([np.linalg.det(F0)]))):
+        f = nl.field(name, u=u)
+        assert f.shape == (n_f, len(value))
+        assert relmax(f, np.broadcast_to(value, f.shape)) <= 1e-13
+
+
+def test_example_stress_output(tmp_path):
+    archive = os.path.join(str(tmp_path), "stress_output.npz")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "examples", "stress_output.py"), "--steps", "5", "--out", archive],
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("step")]
+    assert len(lines) == 5
+    with np.load(archive) as z:
+        for i in range(5):
+            assert z[f"von_mises_stress_{i}"].max() > 0
+            assert z[f"accumulated_plastic_strain_{i}"].min() >= 0
+        assert z["accumulated_plastic_strain_4"].max() > 0

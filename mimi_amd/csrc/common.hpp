@@ -80,8 +80,6 @@ inline bool env_starts(const char* name, char c) {
 inline bool env_general_no_two_phase() { static const bool on = env_starts("MIMI_HIP_GENERAL_NO_TWO_PHASE", '1'); return on; }
 inline bool env_general_no_wpe() { static const bool on = env_starts("MIMI_HIP_GENERAL_NO_WPE", '1'); return on; }
 inline bool env_general_no_mfma() { static const bool on = env_starts("MIMI_HIP_GENERAL_NO_MFMA", '1'); return on; }
-inline bool env_tensor_variant_full() { static const bool on = env_starts("MIMI_HIP_TENSOR_VARIANT", 'w'); return on; }
-inline bool env_residual_variant_element() { static const bool on = env_starts("MIMI_HIP_RESIDUAL_VARIANT", 'e'); return on; }
 // at every create
 inline bool env_force_general() { return env_starts("MIMI_HIP_FORCE_GENERAL", '1'); }
 inline bool env_keep_general() { return env_starts("MIMI_HIP_KEEP_GENERAL", '1'); }

@@ -14,12 +14,11 @@
 
 namespace mimi_hip {
 
-struct ResidualLds {
-  static constexpr int ND = 27, NB = 3, NQ = 4, NQ3 = 64, NB2 = 9;
+struct ResidualLds : P2Shape {
   static constexpr int off_ue = 0;                      // [3][27] (+1)
   static constexpr int off_tab = off_ue + 3 * ND + 1;   // [3][2][3][4]
   static constexpr int off_r = off_tab + 6 * NB * NQ;   // stage-R scratch
-  static constexpr int r_size = 3 * NQ3 + 3 * NB * NQ * NQ + 3 * NB2 * NQ;   // stage R: 444 doubles
+  static constexpr int r_size = p2_stage_r_size(1);                          // stage R, one row per pass: 444 doubles
   static constexpr int g_size = 2 * 3 * NQ * NB2 + 3 * 3 * NQ * NQ * NB;     // grad u stages (before stage R): 648 doubles
   static constexpr int per_wave = off_r + (g_size > r_size ? g_size : r_size);
 };
@@ -27,7 +26,8 @@ struct ResidualLds {
 template<int KIND>
 __global__ __launch_bounds__(256) void tensor_residual_kernel(TensorArgs p, int n_el) {
   using L = ResidualLds;
-  constexpr int P = 2, NB = 3, NQ = 4, NB2 = 9, ND = 27, NQ3 = 64;
+  constexpr int P = L::P, NB = L::NB, NQ = L::NQ, NB2 = L::NB2, ND = L::ND, NQ3 = L::NQ3;
+  static_assert(KIND == MIMI_HIP_MAT_J2 || KIND == WGS_KIND_RECORD, "the neo-Hookean law: tensor_residual_col_kernel");
   __shared__ double lds_all[4][L::per_wave];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t e = (int64_t)blockIdx.x * 4 + wave;
@@ -108,10 +108,7 @@ __global__ __launch_bounds__(256) void tensor_residual_kernel(TensorArgs p, int 
     status = evaluate_pk1<3>(mat, p.dt, p.state, e * NQ3 + lane, F, w);
   }
   if (status) atomicOr(p.status, status);
-  // element residual piece of every component by sum factorisation (as kernels_tensor_2phase.hpp, stage R)
-  double* PH = RS;                   // [3 m][64]
-  double* V = PH + 3 * NQ3;          // [3 m][3 a2][16]
-  double* W = V + 3 * NB * NQ * NQ;  // [3 m][9 a1a2][4]
+  // element residual piece of every component (one row per pass: RS is sized by the grad u stages)
 #pragma unroll
   for (int I = 0; I < 3; ++I) {
 #pragma unroll
@@ -119,51 +116,15 @@ __global__ __launch_bounds__(256) void tensor_residual_kernel(TensorArgs p, int 
       double sp = 0.0;
 #pragma unroll
       for (int J = 0; J < 3; ++J) sp += w.P[I + J * 3] * Ji[m * 3 + J];
-      PH[m * NQ3 + lane] = wd * sp;
+      RS[m * NQ3 + lane] = wd * sp;
     }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < NB * NQ * NQ) {
-      const int q01 = lane % (NQ * NQ), a2 = lane / (NQ * NQ);
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        const double* T2 = tab_ptr<P>(tab, 2, m == 2 ? 1 : 0) + a2 * NQ;
-        double sv = 0.0;
-#pragma unroll
-        for (int q2 = 0; q2 < NQ; ++q2) sv += T2[q2] * PH[m * NQ3 + q01 + NQ * NQ * q2];
-        V[(m * NB + a2) * NQ * NQ + q01] = sv;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < NB2 * NQ) {
-      const int q0 = lane % NQ, a12 = lane / NQ, a1 = a12 % NB, a2 = a12 / NB;
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        const double* T1 = tab_ptr<P>(tab, 1, m == 1 ? 1 : 0) + a1 * NQ;
-        double sw = 0.0;
-#pragma unroll
-        for (int q1 = 0; q1 < NQ; ++q1) sw += T1[q1] * V[(m * NB + a2) * NQ * NQ + q0 + NQ * q1];
-        W[(m * NB2 + a12) * NQ + q0] = sw;
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
-    if (lane < ND) {
-      const int a0 = lane % NB, a12 = lane / NB;
-      double sr = 0.0;
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        const double* T0 = tab_ptr<P>(tab, 0, m == 0 ? 1 : 0) + a0 * NQ;
-#pragma unroll
-        for (int q0 = 0; q0 < NQ; ++q0) sr += T0[q0] * W[(m * NB2 + a12) * NQ + q0];
-      }
-      p.scratch_r[(e * ND + lane) * 3 + I] = sr;
-    }
-    __builtin_amdgcn_wave_barrier();
+    p2_stage_r<1>(tab, RS, lane, p.scratch_r + e * ND * 3, I);
   }
 }
 
 // one wave per node: lane = element (dz, dy, dx) of the 3 x 3 x 3 neighbourhood, fixed-shape tree sum
 __global__ __launch_bounds__(256) void tensor_residual_gather_kernel(TensorArgs p, int64_t n_nodes) {
-  constexpr int P = 2, NB = 3, ND = 27;
+  constexpr int P = P2Shape::P, NB = P2Shape::NB, ND = P2Shape::ND;
   const int64_t Al = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);   // node index inside the shard's node box
   const int lane = threadIdx.x & 63;
   if (Al >= n_nodes) return;
@@ -278,7 +239,7 @@ MH_DEV void rc_4to3_add(double T, const double (&in)[4], double (&out)[3]) {
 template<int KIND>
 __global__ __launch_bounds__(256) void tensor_residual_col_kernel(TensorArgs p, int n_cols) {
   using L = ResidualColLds;
-  constexpr int NB = 3, NQ = 4, NB2 = 9, ND = 27, NQ3 = 64;
+  constexpr int NB = P2Shape::NB, NQ = P2Shape::NQ, NB2 = P2Shape::NB2, ND = P2Shape::ND, NQ3 = P2Shape::NQ3;
   extern __shared__ __align__(16) double lds_col[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   // (a wave beyond the last column walks the last column again and stores nothing but what that column's wave stores too:
@@ -529,7 +490,7 @@ __global__ __launch_bounds__(256) void tensor_residual_col_kernel(TensorArgs p, 
 
 // one thread per node of the shard: the 3 x 3 columns that contain it, in a fixed order
 __global__ __launch_bounds__(256) void tensor_residual_col_gather_kernel(TensorArgs p, int64_t n_nodes) {
-  constexpr int P = 2, ND = 27;
+  constexpr int P = P2Shape::P, ND = P2Shape::ND;
   const int64_t Al = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (Al >= n_nodes) return;
   const int n0 = p.n_ctrl[0], n1 = p.n_ctrl[1];
@@ -554,8 +515,7 @@ __global__ __launch_bounds__(256) void tensor_residual_col_gather_kernel(TensorA
 
 inline void launch_tensor_residual(mimi_hip_domain_s* h, TensorArgs a) {
   const int kind = h->mat.m.kind;
-  // MIMI_HIP_RESIDUAL_VARIANT=element: one wave per element (rounds 1-3; kept for A/B timing)
-  if (!env_residual_variant_element() && kind == MIMI_HIP_MAT_NEOHOOKEAN) {
+  if (kind == MIMI_HIP_MAT_NEOHOOKEAN) {
     const int n_cols = a.box_n[0] * a.box_n[1];
     h->scratch_r.resize(std::max((size_t)h->n_el * 3 * 27, (size_t)n_cols * (a.box_n[2] + 2) * 27));
     a.scratch_r = h->scratch_r.ptr;
@@ -570,8 +530,7 @@ inline void launch_tensor_residual(mimi_hip_domain_s* h, TensorArgs a) {
   a.scratch_r = h->scratch_r.ptr;
   const unsigned blocks = (unsigned)((h->n_el + 3) / 4);
   by_material_family(kind, [&](auto K) {
-    auto kernel = decltype(K)::value != 0 ? tensor_residual_kernel<WGS_KIND_RECORD>
-                  : kind == MIMI_HIP_MAT_NEOHOOKEAN ? tensor_residual_kernel<MIMI_HIP_MAT_NEOHOOKEAN> : tensor_residual_kernel<MIMI_HIP_MAT_J2>;
+    auto kernel = decltype(K)::value != 0 ? tensor_residual_kernel<WGS_KIND_RECORD> : tensor_residual_kernel<MIMI_HIP_MAT_J2>;
     launch(kernel, dim3(blocks), dim3(256), 0, h->stream, a, (int)h->n_el);
   });
   const int64_t n_nodes = (int64_t)(a.box_n[0] + 2) * (a.box_n[1] + 2) * (a.box_n[2] + 2);   // nodes of the shard

@@ -7,9 +7,10 @@
 // split over four waves of one workgroup so that each wave fits in half a register file and two workgroups
 // (8 waves) share a CU:
 //
-//   wave 0  "X"   quadrature-point stage: gathers u, evaluates F and the material ONCE per point
-//                 (the single-wave kernel repeated this for every row i), then per row i the
-//                 residual piece (sum factorisation) and the pulled-back tangent row
+//   wave 0  "X"   quadrature-point stage: the point's material ONCE per point (the single-wave kernel
+//                 repeated this for every row i) -- here read from the record of the material pre-pass,
+//                 in kernels_tensor_wgsym.hpp from F --, then per row i the residual piece (sum
+//                 factorisation) and the pulled-back tangent row
 //                 Ahat_i[m][j][n] -> LDS (lane = quadrature point, private slots).
 //   wave 1+i "Y_i" contraction of row i:  S1 (matrix pipe, q2) -> S2 (vector pipe, q1, wave-uniform
 //                 coefficients) -> S3 (matrix pipe, q0), with the tile TRANSPOSED with respect to
@@ -37,13 +38,21 @@
 
 namespace mimi_hip {
 
-struct WgsLds {
-  static constexpr int NB = 3, NQ = 4, NB2 = 9, ND = 27, NQ3 = 64, NROW = 81;
-  static constexpr int off_ue = 0;                       // [3][27] (+1 pad)           X private
-  static constexpr int off_tab = off_ue + 3 * ND + 1;    // [2 parity][3 dir][2][3][4]  X -> Y
-  static constexpr int off_r = off_tab + 2 * 6 * NB * NQ;  // stage-R scratch            X private
-  static constexpr int r_size = 3 * NQ3 + 3 * NB * NQ * NQ + 3 * NB2 * NQ;
-  static constexpr int off_ah = off_r + r_size;          // [3 i][27 (m,j,n)][64]        X -> Y_i
+// The shape all degree-2 3-D kernels share: degree, basis functions and quadrature points per direction, their products
+struct P2Shape {
+  static constexpr int P = 2, NB = 3, NQ = 4, NB2 = 9, ND = 27, NQ3 = 64, NROW = 81;
+};
+
+// LDS doubles of stage R (p2_stage_r) at `rows` rows per pass: PH [rows][3 m][64], V [rows][3 m][3 a2][16], W [rows][3 m][9 a1a2][4]
+constexpr int p2_stage_r_size(int rows) {
+  using S = P2Shape;
+  return rows * 3 * (S::NQ3 + S::NB * S::NQ * S::NQ + S::NB2 * S::NQ);
+}
+
+struct WgsLds : P2Shape {
+  static constexpr int off_tab = 0;                      // [2 parity][3 dir][2][3][4]  X -> Y
+  static constexpr int off_r = off_tab + 2 * 6 * NB * NQ;  // stage-R scratch, one row    X private
+  static constexpr int off_ah = off_r + p2_stage_r_size(1);  // [3 i][27 (m,j,n)][64]        X -> Y_i
   static constexpr int n_final = 9 * NROW + 18 * ND;     // 1215 entries stored by a non-last element
   static constexpr int n_carry = 18 * 2 * ND;            // 972 more by the last element of a column
   static constexpr int st_size = n_final + 1;
@@ -80,7 +89,7 @@ MH_DEV void swap32_f64(double c, double o, double& c_hi_in_lo, double& o_lo_in_h
 constexpr int WGS_PT_FIELDS = 24;
 
 MH_DEV void wgs_point_store(double* rec, int lane, const mimi_hip_material& m, const PointResult<3>& w) {
-  constexpr int NQ3 = 64;
+  constexpr int NQ3 = P2Shape::NQ3;
   constexpr int sym_i[6] = {0, 1, 2, 1, 2, 2}, sym_j[6] = {0, 0, 0, 1, 1, 2};
 #pragma unroll
   for (int k = 0; k < 9; ++k) rec[k * NQ3 + lane] = w.Finv[k];
@@ -90,19 +99,15 @@ MH_DEV void wgs_point_store(double* rec, int lane, const mimi_hip_material& m, c
     rec[(10 + k) * NQ3 + lane] = w.sigma[sym_i[k] + 3 * sym_j[k]];
     rec[(16 + k) * NQ3 + lane] = w.s_trial[sym_i[k] + 3 * sym_j[k]];
   }
-  double beta = 1.0, gamma = 0.0;
-  if (w.plastic) {
-    const double q = w.q, G = m.G;
-    beta = 1.0 - 3.0 * G * w.delta / q;
-    gamma = 3.0 * G * (1.5 / q) * (1.0 / ((3.0 * G + w.hprime) * q) - w.delta / (q * q));
-  }
+  double beta, gamma;
+  j2_beta_gamma<3>(m, w, beta, gamma);
   rec[22 * NQ3 + lane] = beta;
   rec[23 * NQ3 + lane] = gamma;
 }
 
 // w gets Finv, detF, sigma, s_trial and (recomputed as the material does, pk1_from_cauchy) P
 MH_DEV void wgs_point_load(const double* rec, int lane, PointResult<3>& w, double& beta, double& gamma) {
-  constexpr int NQ3 = 64;
+  constexpr int NQ3 = P2Shape::NQ3;
   constexpr int sym_i[6] = {0, 1, 2, 1, 2, 2}, sym_j[6] = {0, 0, 0, 1, 1, 2};
 #pragma unroll
   for (int k = 0; k < 9; ++k) w.Finv[k] = rec[k * NQ3 + lane];
@@ -135,7 +140,7 @@ constexpr int WGS_KIND_RECORD = 100;   // compile-time "material kind" of the ke
 // SIMD: 4.8 ms for the 16.8 M points of the north-star mesh with J2)
 template<int FAMILY, int COMMIT = 0>
 __global__ __launch_bounds__(256) void tensor_point_kernel(TensorArgs p, int n_el) {
-  constexpr int P = 2, NB = 3, NQ = 4, ND = 27, NQ3 = 64;
+  constexpr int P = P2Shape::P, NB = P2Shape::NB, NQ = P2Shape::NQ, ND = P2Shape::ND, NQ3 = P2Shape::NQ3;
   constexpr int FK = FAMILY >= 2 ? FAMILY : -1;
   __shared__ double ue_all[4][3 * ND];
   __shared__ double tab_all[4][6 * NB * NQ];
@@ -341,67 +346,127 @@ MH_DEV void wgs_j2_point(const mimi_hip_material& m, const PointResult<3>& w, do
     }
 }
 
-template<int KIND>
-MH_DEV int wgs_x_point(const TensorArgs& p, int64_t pt, const double* F, const double* Ji, double wd, WgsPoint<KIND>& s) {
-  if constexpr (KIND == MIMI_HIP_MAT_NEOHOOKEAN) {
-    PointResult<3> w;
-    neo_hookean_stress<3>(p.mat.m, F, w);
-    const double J = w.detF;
-    s.mu_w = wd * p.mat.m.mu;
-    s.c1_w = wd * (p.mat.m.lambda * J * (J - 1.) - p.mat.m.mu);
-    s.c2_w = wd * (p.mat.m.lambda * (2. * J - 1.) * J);
+// fills WgsPoint<neo-Hookean> from F at the point (no pre-pass: the law is a dozen instructions)
+MH_DEV void wgs_neohookean_point(const mimi_hip_material& mat, const double* F, const double* Ji, double wd,
+                                 WgsPoint<MIMI_HIP_MAT_NEOHOOKEAN>& s) {
+  PointResult<3> w;
+  neo_hookean_stress<3>(mat, F, w);
+  const double J = w.detF;
+  s.mu_w = wd * mat.mu;
+  s.c1_w = wd * (mat.lambda * J * (J - 1.) - mat.mu);
+  s.c2_w = wd * (mat.lambda * (2. * J - 1.) * J);
+#pragma unroll
+  for (int m = 0; m < 3; ++m)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      double g = 0.0;
+#pragma unroll
+      for (int Jx = 0; Jx < 3; ++Jx) g += Ji[m * 3 + Jx] * w.Finv[Jx + i * 3];
+      s.G[m * 3 + i] = g;
+    }
+  {
+    int c = 0;
 #pragma unroll
     for (int m = 0; m < 3; ++m)
 #pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        double g = 0.0;
+      for (int n = m; n < 3; ++n) {
+        double v = 0.0;
 #pragma unroll
-        for (int Jx = 0; Jx < 3; ++Jx) g += Ji[m * 3 + Jx] * w.Finv[Jx + i * 3];
-        s.G[m * 3 + i] = g;
+        for (int Jx = 0; Jx < 3; ++Jx) v += Ji[m * 3 + Jx] * Ji[n * 3 + Jx];
+        s.M[c++] = v;
       }
-    {
-      int c = 0;
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      double sp = 0.0;
+#pragma unroll
+      for (int Jx = 0; Jx < 3; ++Jx) sp += w.P[i + Jx * 3] * Ji[m * 3 + Jx];
+      s.Phat[i * 3 + m] = wd * sp;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// stage R: residual rows of one element by sum factorisation, three passes through LDS
+// ------------------------------------------------------------------------------------------------
+// Rows I0 .. I0 + ROWS - 1 of an element.  In: the caller has stored Phat, RS[(I * 3 + m) * 64 + point] (lane = point); tab =
+// the element's tables.  Out: er[a * 3 + I0 + I], er = the element's part of scratch_r ([element][a][i]: tensor_p2_kernel
+// reads a node's three rows from one sector).  The rows of a call share the LDS passes.
+// Lane -> output maps of the three passes (as in the degree-3 pre-pass): a lane owns ONE pair of the indices that are neither
+// summed nor a tensor component, reads its table values once and walks (I, m) with compile-time offsets -- 48 / 36 / 54 (one row:
+// 27) of the 64 lanes busy, a third of the instructions of loops over the flat output index (20 - 30 integer instructions of
+// index arithmetic per four multiply-adds).  Every sum runs in index order as a chain of fused multiply-adds from 0.0.
+template<int ROWS>
+MH_DEV void p2_stage_r(const double* tab, double* RS, int lane, double* er, int I0) {
+  using S = P2Shape;
+  constexpr int P = S::P, NB = S::NB, NQ = S::NQ, NB2 = S::NB2, ND = S::ND, NQ3 = S::NQ3;
+  double* PH = RS;                              // [ROWS I][3 m][64]
+  double* V = PH + ROWS * 3 * NQ3;              // [ROWS I][3 m][3 a2][16]
+  double* W = V + ROWS * 3 * NB * NQ * NQ;      // [ROWS I][3 m][9 a1a2][4]
+  __builtin_amdgcn_wave_barrier();
+  // V[I m][a2][q0 q1] = sum_q2 T2^m[a2][q2] PH[I m][q0 q1 q2]
+  if (lane < NB * NQ * NQ) {
+    const int q01 = lane & 15, a2 = lane >> 4;
+    double T[2][NQ];
+#pragma unroll
+    for (int v = 0; v < 2; ++v)
+#pragma unroll
+      for (int q2 = 0; q2 < NQ; ++q2) T[v][q2] = tab_ptr<P>(tab, 2, v)[a2 * NQ + q2];
+#pragma unroll
+    for (int im = 0; im < ROWS * 3; ++im) {
+      double sv = 0.0;
+#pragma unroll
+      for (int q2 = 0; q2 < NQ; ++q2) sv = __builtin_fma(T[im % 3 == 2 ? 1 : 0][q2], PH[im * NQ3 + q01 + NQ * NQ * q2], sv);
+      V[im * (NB * NQ * NQ) + lane] = sv;   // (im * NB + a2) * 16 + q01
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  // W[I m][a1 a2][q0] = sum_q1 T1^m[a1][q1] V[I m][a2][q0 q1]
+  if (lane < NB2 * NQ) {
+    const int q0 = lane & 3, a12 = lane >> 2, a1 = a12 % NB, a2 = a12 / NB;
+    double T[2][NQ];
+#pragma unroll
+    for (int v = 0; v < 2; ++v)
+#pragma unroll
+      for (int q1 = 0; q1 < NQ; ++q1) T[v][q1] = tab_ptr<P>(tab, 1, v)[a1 * NQ + q1];
+#pragma unroll
+    for (int im = 0; im < ROWS * 3; ++im) {
+      double sw = 0.0;
+#pragma unroll
+      for (int q1 = 0; q1 < NQ; ++q1) sw = __builtin_fma(T[im % 3 == 1 ? 1 : 0][q1], V[(im * NB + a2) * NQ * NQ + q0 + NQ * q1], sw);
+      W[im * (NB2 * NQ) + lane] = sw;   // (im * NB2 + a12) * 4 + q0
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  // er[a][I] = sum_m sum_q0 T0^m[a0][q0] W[I m][a1 a2][q0]: lanes 0..26 take the even rows, lanes 27..53 the odd ones
+  if (lane < (ROWS > 1 ? 2 : 1) * ND) {
+    const int a = lane < ND ? lane : lane - ND, a0 = a % NB, a12 = a / NB;
+    double T[2][NQ];
+#pragma unroll
+    for (int v = 0; v < 2; ++v)
+#pragma unroll
+      for (int q0 = 0; q0 < NQ; ++q0) T[v][q0] = tab_ptr<P>(tab, 0, v)[a0 * NQ + q0];
+    const int n_rows = lane < ND ? (ROWS + 1) / 2 : ROWS / 2;
+    for (int k = 0; k < n_rows; ++k) {
+      const int I = lane < ND ? 2 * k : 2 * k + 1;
+      double sr = 0.0;
 #pragma unroll
       for (int m = 0; m < 3; ++m)
 #pragma unroll
-        for (int n = m; n < 3; ++n) {
-          double v = 0.0;
-#pragma unroll
-          for (int Jx = 0; Jx < 3; ++Jx) v += Ji[m * 3 + Jx] * Ji[n * 3 + Jx];
-          s.M[c++] = v;
-        }
+        for (int q0 = 0; q0 < NQ; ++q0) sr = __builtin_fma(T[m == 0 ? 1 : 0][q0], W[((I * 3 + m) * NB2 + a12) * NQ + q0], sr);
+      er[a * 3 + I0 + I] = sr;
     }
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int m = 0; m < 3; ++m) {
-        double sp = 0.0;
-#pragma unroll
-        for (int Jx = 0; Jx < 3; ++Jx) sp += w.P[i + Jx * 3] * Ji[m * 3 + Jx];
-        s.Phat[i * 3 + m] = wd * sp;
-      }
-    return 0;
-  } else {
-    MaterialDev mat = p.mat;
-    mat.m.kind = KIND;
-    PointResult<3> w;
-    const int status = evaluate_pk1<3>(mat, p.dt, p.state, pt, F, w);
-    double beta = 1.0, gamma = 0.0;
-    if (w.plastic) {
-      const double q = w.q, G = p.mat.m.G;
-      beta = 1.0 - 3.0 * G * w.delta / q;
-      gamma = 3.0 * G * (1.5 / q) * (1.0 / ((3.0 * G + w.hprime) * q) - w.delta / (q * q));
-    }
-    wgs_j2_point(p.mat.m, w, beta, gamma, Ji, wd, s);
-    return status;
   }
+  __builtin_amdgcn_wave_barrier();
 }
 
 // row I of one element: Ahat_I -> LDS (lane = quadrature point), residual piece -> scratch_r
 template<int KIND, int I>
 MH_DEV void wgs_x_row(const TensorArgs& p, double* lds, int lane, int64_t e, int par, const WgsPoint<KIND>& s) {
   using L = WgsLds;
-  constexpr int P = 2, NB = 3, NQ = 4, NB2 = 9, ND = 27, NQ3 = 64;
+  constexpr int NB = L::NB, NQ = L::NQ, ND = L::ND, NQ3 = L::NQ3;
+  static_assert(KIND == MIMI_HIP_MAT_J2 || KIND == WGS_KIND_RECORD, "nine-block kernel: the material comes from the pre-pass");
   const double* tab = lds + L::off_tab + par * 6 * NB * NQ;
   double* AH = lds + L::off_ah + I * ND * NQ3;
   double* RS = lds + L::off_r;
@@ -414,26 +479,6 @@ MH_DEV void wgs_x_row(const TensorArgs& p, double* lds, int lane, int64_t e, int
     for (int k = 0; k < ND; ++k) v[k] = s.rec[(int64_t)(I * ND + k) * NQ3];
 #pragma unroll
     for (int k = 0; k < ND; ++k) AH[k * NQ3 + lane] = v[k];
-  } else if constexpr (KIND == MIMI_HIP_MAT_NEOHOOKEAN) {
-#pragma unroll
-    for (int m = 0; m < 3; ++m) Phat[m] = s.Phat[I * 3 + m];
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      const double c2gm = s.c2_w * s.G[m * 3 + I];
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        const double c1gm = s.c1_w * s.G[m * 3 + j];
-#pragma unroll
-        for (int n = 0; n < 3; ++n) {
-          double v = c2gm * s.G[n * 3 + j] - c1gm * s.G[n * 3 + I];
-          if (I == j) {
-            const int lo = m < n ? m : n, hi = m < n ? n : m;
-            v += s.mu_w * s.M[lo * 3 - lo * (lo - 1) / 2 + (hi - lo)];
-          }
-          AH[((m * 3 + j) * 3 + n) * NQ3 + lane] = v;
-        }
-      }
-    }
   } else {
 #pragma unroll
     for (int m = 0; m < 3; ++m) Phat[m] = s.Phat[I * 3 + m];
@@ -462,190 +507,134 @@ MH_DEV void wgs_x_row(const TensorArgs& p, double* lds, int lane, int64_t e, int
           AH[((m * 3 + j) * 3 + n) * NQ3 + lane] = s.wdJ * v;
         }
   }
-  // residual row I by sum factorisation (as kernels_tensor_2phase.hpp)
-  double* PH = RS;                   // [3 m][64]
-  double* V = PH + 3 * NQ3;          // [3 m][3 a2][16]
-  double* W = V + 3 * NB * NQ * NQ;  // [3 m][9 a1a2][4]
+  // residual row I (one row per pass: the LDS of two workgroups per CU has room for one row's buffers)
 #pragma unroll
-  for (int m = 0; m < 3; ++m) PH[m * NQ3 + lane] = Phat[m];
-  __builtin_amdgcn_wave_barrier();
-  if (lane < NB * NQ * NQ) {
-    const int q01 = lane % (NQ * NQ), a2 = lane / (NQ * NQ);
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      const double* T2 = tab_ptr<P>(tab, 2, m == 2 ? 1 : 0) + a2 * NQ;
-      double sv = 0.0;
-#pragma unroll
-      for (int q2 = 0; q2 < NQ; ++q2) sv += T2[q2] * PH[m * NQ3 + q01 + NQ * NQ * q2];
-      V[(m * NB + a2) * NQ * NQ + q01] = sv;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  if (lane < NB2 * NQ) {
-    const int q0 = lane % NQ, a12 = lane / NQ, a1 = a12 % NB, a2 = a12 / NB;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      const double* T1 = tab_ptr<P>(tab, 1, m == 1 ? 1 : 0) + a1 * NQ;
-      double sw = 0.0;
-#pragma unroll
-      for (int q1 = 0; q1 < NQ; ++q1) sw += T1[q1] * V[(m * NB + a2) * NQ * NQ + q0 + NQ * q1];
-      W[(m * NB2 + a12) * NQ + q0] = sw;
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  if (lane < ND) {
-    const int a0 = lane % NB, a12 = lane / NB;
-    double sr = 0.0;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      const double* T0 = tab_ptr<P>(tab, 0, m == 0 ? 1 : 0) + a0 * NQ;
-#pragma unroll
-      for (int q0 = 0; q0 < NQ; ++q0) sr += T0[q0] * W[(m * NB2 + a12) * NQ + q0];
-    }
-    p.scratch_r[(e * ND + lane) * 3 + I] = sr;
-  }
-  __builtin_amdgcn_wave_barrier();
+  for (int m = 0; m < 3; ++m) RS[m * NQ3 + lane] = Phat[m];
+  p2_stage_r<1>(tab, RS, lane, p.scratch_r + e * ND * 3, I);
 }
 
-template<int KIND>
-MH_DEV void wgs_x_loop(const TensorArgs& p, double* lds, int eu, int ev, int& status) {
-  using L = WgsLds;
-  constexpr int P = 2, NB = 3, NQ = 4, ND = 27, NQ3 = 64;
-  constexpr int TROUNDS = 2;  // 72 table values
-  const int lane = threadIdx.x & 63;
-  double* ue = lds + L::off_ue;
-  const int n_seq = p.box_n[2];
-  auto element_at = [&](int es) -> int64_t { return eu + (int64_t)p.box_n[0] * (ev + (int64_t)p.box_n[1] * es); };
-  auto table_src = [&](int es, int t) -> const double* {
-    const int dir = t / (2 * NB * NQ);
-    const int rem = t % (2 * NB * NQ);
-    const int isD = rem / (NB * NQ);
-    const int k = rem % (NB * NQ);
-    const int span = (dir == 0 ? p.box_begin[0] + eu : dir == 1 ? p.box_begin[1] + ev : p.box_begin[2] + es);
-    return (isD ? (dir == 0 ? p.tabD[0] : dir == 1 ? p.tabD[1] : p.tabD[2])
-                : (dir == 0 ? p.tabB[0] : dir == 1 ? p.tabB[1] : p.tabB[2])) + (int64_t)span * NB * NQ + k;
-  };
-  // The operands of an element are requested at the END of the previous element's last step (they are
-  // in flight across the two barriers, not across the row computations, which need the registers);
-  // the connectivity one element earlier still.
-  int32_t node_n = lane < ND ? p.dofs[element_at(0) * ND + lane] : 0;
-  double ue_r[3], tab_r[TROUNDS], geo_r[10];
-  auto request = [&](int es) {
-    const int64_t e_n = element_at(es);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) ue_r[c] = p.u[(int64_t)node_n * 3 + c];
-#pragma unroll
-    for (int rd = 0; rd < TROUNDS; ++rd) {
-      const int t = rd * 64 + lane;
-      tab_r[rd] = *table_src(es, t < 6 * NB * NQ ? t : 0);
+// ------------------------------------------------------------------------------------------------
+// the column walk of a workgroup, and what the point wave requests along it (also used by kernels_tensor_wgsym.hpp)
+// ------------------------------------------------------------------------------------------------
+// A workgroup walks some units back to back, a unit = one segment of p.seg_len elements of an element column (unit index =
+// column * segments-per-column + segment; the nine-block kernel: one unit, a whole column).  The walk keeps the element, its
+// spans and its layer and moves one element at a time: the unit's column by division when a unit begins, then one layer further
+// per step (asked for by division at every use -- g / seg_len, % segments, column % n0, column / n0 -- they were ~12 run-time
+// integer divisions, 300 - 400 scalar instructions per element, in the point wave and ~80 in a contraction wave).
+struct ColumnWalk {
+  int first, nseg;     // the workgroup's first unit; segments per column
+  int g, pos, unit;    // sequence index = unit * seg_len + pos; position inside the unit; unit inside the workgroup
+  int cx, cy, ez;      // the element inside the box: the spans of its column, its layer
+  int64_t e;           // the element
+  MH_DEV ColumnWalk(const TensorArgs& p, int first_unit) : first(first_unit), nseg(p.box_n[2] / p.seg_len), g(0) { begin_unit(p, 0); }
+  MH_DEV void begin_unit(const TensorArgs& p, int u) {
+    const int un = first + u, col = un / nseg;
+    unit = u;
+    pos = 0;
+    cx = col % p.box_n[0];
+    cy = col / p.box_n[0];
+    ez = (un % nseg) * p.seg_len;
+    e = cx + (int64_t)p.box_n[0] * (cy + (int64_t)p.box_n[1] * ez);
+  }
+  MH_DEV void advance(const TensorArgs& p) {
+    ++g;
+    if (++pos == p.seg_len) {
+      begin_unit(p, unit + 1);
+    } else {
+      ++ez;
+      e += (int64_t)p.box_n[0] * p.box_n[1];
     }
-    const double* g = p.geo + e_n * 10 * NQ3 + lane;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) geo_r[k] = g[(int64_t)k * NQ3];
-    if (es + 1 < n_seq) node_n = lane < ND ? p.dofs[element_at(es + 1) * ND + lane] : 0;
-  };
-  request(0);
+  }
+};
 
-  WgsPoint<KIND> s;
-  // quadrature-point stage of element es from the requested operands (tables -> LDS parity es & 1)
-  auto point_stage = [&](int es) {
-    const int par = es & 1;
-    const int64_t e = element_at(es);
-    double* tab = lds + L::off_tab + par * 6 * NB * NQ;
-    if (lane < ND) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) ue[c * ND + lane] = ue_r[c];
-    }
+// Tables (72 values, [3 dir][B, D][3][4] as they lie in LDS: two per lane) and geometry (10 per lane) of an element, requested
+// at the END of the previous element's last step: they are in flight across the two barriers, not across the row
+// computations, which need the registers.
+struct WgsOperands {
+  static constexpr int NT = 6 * P2Shape::NB * P2Shape::NQ, TROUNDS = 2;
+  double tab[TROUNDS], geo[10];
+  MH_DEV static const double* table_src(const TensorArgs& p, const ColumnWalk& c, int t) {
+    constexpr int NBQ = P2Shape::NB * P2Shape::NQ;
+    const int dir = t / (2 * NBQ);
+    const int rem = t % (2 * NBQ);
+    const int isD = rem / NBQ;
+    const int k = rem % NBQ;
+    const int span = (dir == 0 ? p.box_begin[0] + c.cx : dir == 1 ? p.box_begin[1] + c.cy : p.box_begin[2] + c.ez);
+    return (isD ? (dir == 0 ? p.tabD[0] : dir == 1 ? p.tabD[1] : p.tabD[2])
+                : (dir == 0 ? p.tabB[0] : dir == 1 ? p.tabB[1] : p.tabB[2])) + (int64_t)span * NBQ + k;
+  }
+  MH_DEV void request(const TensorArgs& p, const ColumnWalk& c, int lane) {
 #pragma unroll
     for (int rd = 0; rd < TROUNDS; ++rd) {
       const int t = rd * 64 + lane;
-      if (t < 6 * NB * NQ) tab[t] = tab_r[rd];
+      tab[rd] = *table_src(p, c, t < NT ? t : 0);
     }
-    double Ji[9];
+    const double* g = p.geo + c.e * 10 * P2Shape::NQ3 + lane;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) Ji[k] = geo_r[k];
-    const double wd = geo_r[9];
-    __builtin_amdgcn_wave_barrier();
-    if constexpr (KIND == MIMI_HIP_MAT_NEOHOOKEAN) {
-      // F at the quadrature point of this lane, q = q0 + 4 q1 + 16 q2
-      double F[9];
-      {
-        const int q0 = lane & 3, q1 = (lane >> 2) & 3, q2 = lane >> 4;
-        double b0[NB], d0[NB], b1[NB], d1[NB], b2[NB], d2[NB];
+    for (int k = 0; k < 10; ++k) geo[k] = g[(int64_t)k * P2Shape::NQ3];
+  }
+  MH_DEV void tables_to_lds(double* dst, int lane) const {
 #pragma unroll
-        for (int a = 0; a < NB; ++a) {
-          b0[a] = tab_ptr<P>(tab, 0, 0)[a * NQ + q0];
-          d0[a] = tab_ptr<P>(tab, 0, 1)[a * NQ + q0];
-          b1[a] = tab_ptr<P>(tab, 1, 0)[a * NQ + q1];
-          d1[a] = tab_ptr<P>(tab, 1, 1)[a * NQ + q1];
-          b2[a] = tab_ptr<P>(tab, 2, 0)[a * NQ + q2];
-          d2[a] = tab_ptr<P>(tab, 2, 1)[a * NQ + q2];
-        }
-        double H[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) H[k] = 0.0;
-#pragma unroll
-        for (int a2 = 0; a2 < NB; ++a2)
-#pragma unroll
-          for (int a1 = 0; a1 < NB; ++a1) {
-            const double tbb = b1[a1] * b2[a2], tdb = d1[a1] * b2[a2], tbd = b1[a1] * d2[a2];
-#pragma unroll
-            for (int a0 = 0; a0 < NB; ++a0) {
-              const int a = a0 + NB * (a1 + NB * a2);
-              const double dn0 = d0[a0] * tbb, dn1 = b0[a0] * tdb, dn2 = b0[a0] * tbd;
-#pragma unroll
-              for (int i = 0; i < 3; ++i) {
-                const double uu = ue[i * ND + a];
-                H[i * 3 + 0] += uu * dn0;
-                H[i * 3 + 1] += uu * dn1;
-                H[i * 3 + 2] += uu * dn2;
-              }
-            }
-            // keep the LDS reads of later (a1, a2) where they are (hoisted together they need 162 registers)
-            #pragma unroll
-            for (int k = 0; k < 9; ++k) asm volatile("" : "+v"(H[k]) : : "memory");
-          }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-          for (int J = 0; J < 3; ++J) {
-            double sf = (i == J) ? 1.0 : 0.0;
-#pragma unroll
-            for (int m = 0; m < 3; ++m) sf += H[i * 3 + m] * Ji[m * 3 + J];
-            F[i + J * 3] = sf;
-          }
-      }
-      status |= wgs_x_point<KIND>(p, e * NQ3 + lane, F, Ji, wd, s);
-    } else if constexpr (KIND == WGS_KIND_RECORD) {
-      s.rec = p.scratch_pt + e * (int64_t)(WGS_REC_FIELDS * NQ3) + lane;
+    for (int rd = 0; rd < TROUNDS; ++rd) {
+      const int t = rd * 64 + lane;
+      if (t < NT) dst[t] = tab[rd];
+    }
+  }
+};
+
+// wave X of the nine-block kernel: per element the point's record of the material pre-pass, then the three rows
+template<int KIND>
+MH_DEV void wgs_x_loop(const TensorArgs& p, double* lds, int unit) {
+  using L = WgsLds;
+  const int lane = threadIdx.x & 63;
+  const int n_seq = p.seg_len;
+  ColumnWalk cq(p, unit);   // the element whose operands are requested next
+  ColumnWalk cs = cq;       // the element of the next quadrature-point stage
+  ColumnWalk cr = cq;       // the element whose rows are written next
+  WgsOperands op;
+  auto request = [&]() {
+    op.request(p, cq, lane);
+    if (cq.g + 1 < n_seq) cq.advance(p);
+  };
+  WgsPoint<KIND> s;
+  // quadrature-point stage of the element at cs from the requested operands (tables -> LDS parity g & 1)
+  auto point_stage = [&]() {
+    op.tables_to_lds(lds + L::off_tab + (cs.g & 1) * WgsOperands::NT, lane);
+    if constexpr (KIND == WGS_KIND_RECORD) {
+      s.rec = p.scratch_pt + cs.e * (int64_t)(WGS_REC_FIELDS * L::NQ3) + lane;
     } else {
       // J2: the material was evaluated by tensor_point_kernel
       PointResult<3> w;
       double beta, gamma;
-      wgs_point_load(p.scratch_pt + e * (int64_t)(WGS_PT_FIELDS * NQ3), lane, w, beta, gamma);
-      wgs_j2_point(p.mat.m, w, beta, gamma, Ji, wd, s);
+      wgs_point_load(p.scratch_pt + cs.e * (int64_t)(WGS_PT_FIELDS * L::NQ3), lane, w, beta, gamma);
+      wgs_j2_point(p.mat.m, w, beta, gamma, op.geo, op.geo[9], s);
     }
     __builtin_amdgcn_wave_barrier();
+    if (cs.g + 1 < n_seq) cs.advance(p);
   };
-  auto rows = [&](int es) {
-    wgs_x_row<KIND, 0>(p, lds, lane, element_at(es), es & 1, s);
-    wgs_x_row<KIND, 1>(p, lds, lane, element_at(es), es & 1, s);
-    wgs_x_row<KIND, 2>(p, lds, lane, element_at(es), es & 1, s);
+  auto rows = [&]() {
+    wgs_x_row<KIND, 0>(p, lds, lane, cr.e, cr.g & 1, s);
+    wgs_x_row<KIND, 1>(p, lds, lane, cr.e, cr.g & 1, s);
+    wgs_x_row<KIND, 2>(p, lds, lane, cr.e, cr.g & 1, s);
   };
   // prologue: point stage and rows of element 0
-  point_stage(0);
-  if (1 < n_seq) request(1);
-  rows(0);
+  request();
+  point_stage();
+  if (1 < n_seq) request();
+  rows();
   wgs_barrier();
   for (int it = 0; it < n_seq; ++it) {
-    // free running: point stage of element it + 1 (its own ue / point data, the table buffer of the OTHER parity)
+    // free running: point stage of element it + 1 (its own point data, the table buffer of the OTHER parity)
     if (it + 1 < n_seq) {
-      point_stage(it + 1);
-      if (it + 2 < n_seq) request(it + 2);
+      point_stage();
+      if (it + 2 < n_seq) request();
     }
     // lock step: rows of element it + 1, once every contraction wave holds its last operands of element it
     wgs_barrier();
-    if (it + 1 < n_seq) rows(it + 1);
+    if (it + 1 < n_seq) {
+      cr.advance(p);
+      rows();
+    }
     wgs_barrier();
   }
 }
@@ -668,7 +657,7 @@ struct WgsLane {
 // for_dump: the lanes / registers without an entry get zero offsets and strides (what they index is the dump region of
 // wgs_contract_block, never a staging buffer)
 MH_DEV WgsLane wgs_lane_constants(bool for_dump = false) {
-  constexpr int NB = 3, ND = 27, NROW = 81;
+  constexpr int NB = P2Shape::NB, ND = P2Shape::ND, NROW = P2Shape::NROW;
   WgsLane c;
   c.lane = threadIdx.x & 63;
   const int col = c.lane & 15;
@@ -718,7 +707,7 @@ template<int MODE, bool DUMP = false>
 MH_DEV void wgs_contract_block(const WgsLane& lc, const double (&ah)[9], const double (&aS0)[4], const double (&aS2)[4],
                                const double (&uB1)[3][4], const double (&uD1)[3][4], double (&C)[9],
                                double* st_n, int jn, double* st_t, int jt, double* dump = nullptr) {
-  constexpr int NB = 3, NQ = 4, ND = 27, NROW = 81;
+  constexpr int NB = P2Shape::NB, NQ = P2Shape::NQ, ND = P2Shape::ND, NROW = P2Shape::NROW;
   const mh_d4 zero4 = {0.0, 0.0, 0.0, 0.0};
   const int grp = lc.grp;
   double* const dn0 = lc.col_ok ? st_n : dump;
@@ -817,7 +806,7 @@ MH_DEV void wgs_contract_block(const WgsLane& lc, const double (&ah)[9], const d
 // carried rows of the last element of a column -> the third part of the element block (st_n / st_t: P2Block::carry_of(E, i))
 template<int MODE>
 MH_DEV void wgs_stage_carry(const WgsLane& lc, const double (&C)[9], double* st_n, int jn, double* st_t, int jt) {
-  constexpr int NB = 3;
+  constexpr int NB = P2Shape::NB;
 #pragma unroll
   for (int a1b1 = 0; a1b1 < 9; ++a1b1) {
     const int a1 = a1b1 / NB, b1 = a1b1 % NB;
@@ -833,7 +822,7 @@ MH_DEV void wgs_stage_carry(const WgsLane& lc, const double (&C)[9], double* st_
 #define WGS_PIECE_STORE(ptr, v) (*(ptr) = (v))
 // buffer (compact: nine rows of 81, eighteen rows of 27) -> this piece's runs in the element block E (P2Block)
 MH_DEV void wgs_flush_final(int lane, const double* ST, double* E, int I) {
-  constexpr int NROW = 81, ND = 27;
+  constexpr int NROW = P2Shape::NROW, ND = P2Shape::ND;
   {
     // rows a2 = 0: E[a 243 + I 81 + k], k < 81: the first 64 values of a row per instruction, then the 17 others of
     // three rows together (lanes 0..16, 17..33, 34..50)
@@ -866,39 +855,66 @@ MH_DEV void wgs_flush_final(int lane, const double* ST, double* E, int I) {
   }
 }
 
+// The tables of a contraction wave as wgs_contract_block takes them, from the element's tables in LDS: aS0, aS2 = pair tables of
+// directions 0 and 2 (variants B.B, D.B, B.D, D.D; matrix operand: pair index (a, b) on lane bits 3:0, contraction index on bits
+// 5:4), uB1, uD1 = wave-uniform direction-1 tables.
+// The tables of directions 0 and 1 belong to the element COLUMN: a caller that keeps the arrays from one element to the next
+// asks for them (24 LDS reads, 48 v_readfirstlane, the pair products of direction 0) with column_too at the first element of
+// a unit only -- every vector instruction of a contraction wave is on the kernel's critical path;
+// direction 2 changes with every element
+MH_DEV void wgs_load_tables(const double* tab, int lane, bool column_too, double (&aS0)[4], double (&aS2)[4],
+                            double (&uB1)[P2Shape::NB][P2Shape::NQ], double (&uD1)[P2Shape::NB][P2Shape::NQ]) {
+  constexpr int P = P2Shape::P, NB = P2Shape::NB, NQ = P2Shape::NQ;
+  const int mrow = lane & 15, mk = lane >> 4;
+  const bool mrow_ok = mrow < P2Shape::NB2;
+  const int mra = mrow_ok ? mrow / NB : 0, mrb = mrow_ok ? mrow % NB : 0;
+  auto pair_products = [&](int dir, double (&aS)[4]) {
+    const double Ba = tab_ptr<P>(tab, dir, 0)[mra * NQ + mk], Da = tab_ptr<P>(tab, dir, 1)[mra * NQ + mk];
+    const double Bb = tab_ptr<P>(tab, dir, 0)[mrb * NQ + mk], Db = tab_ptr<P>(tab, dir, 1)[mrb * NQ + mk];
+    aS[0] = mrow_ok ? Ba * Bb : 0.0;
+    aS[1] = mrow_ok ? Da * Bb : 0.0;
+    aS[2] = mrow_ok ? Ba * Db : 0.0;
+    aS[3] = mrow_ok ? Da * Db : 0.0;
+  };
+  if (column_too) {
+    pair_products(0, aS0);
+#pragma unroll
+    for (int a = 0; a < NB; ++a)
+#pragma unroll
+      for (int q1 = 0; q1 < NQ; ++q1) {
+        const unsigned long long vb = __double_as_longlong(tab_ptr<P>(tab, 1, 0)[a * NQ + q1]);
+        const unsigned long long vd = __double_as_longlong(tab_ptr<P>(tab, 1, 1)[a * NQ + q1]);
+        const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)vb), bhi = __builtin_amdgcn_readfirstlane((unsigned)(vb >> 32));
+        const unsigned dlo = __builtin_amdgcn_readfirstlane((unsigned)vd), dhi = __builtin_amdgcn_readfirstlane((unsigned)(vd >> 32));
+        uB1[a][q1] = __longlong_as_double(((unsigned long long)bhi << 32) | blo);
+        uD1[a][q1] = __longlong_as_double(((unsigned long long)dhi << 32) | dlo);
+      }
+  }
+  pair_products(2, aS2);
+}
+
 // ------------------------------------------------------------------------------------------------
 // wave Y_I of the nine-block kernel: row I, one column component j per step
 // ------------------------------------------------------------------------------------------------
 template<int I>
-MH_DEV void wgs_y_loop(const TensorArgs& p, double* lds, int eu, int ev) {
+MH_DEV void wgs_y_loop(const TensorArgs& p, double* lds, int unit) {
   using L = WgsLds;
-  constexpr int P = 2, NB = 3, NQ = 4, NB2 = 9, ND = 27, NQ3 = 64, NROW = 81, NK = ND * NROW;
+  constexpr int NB = L::NB, NQ = L::NQ, NB2 = L::NB2, ND = L::ND, NQ3 = L::NQ3;
   const WgsLane lc = wgs_lane_constants();
   const int lane = lc.lane;
   double* AH = lds + L::off_ah + I * ND * NQ3;
   double* ST = lds + L::off_st + I * L::st_size;
-  const int n_seq = p.box_n[2];
-  auto block_of = [&](int es) -> double* {
-    return p.scratch_k + (eu + (int64_t)p.box_n[0] * (ev + (int64_t)p.box_n[1] * es)) * (int64_t)P2Block::size;
-  };
-  // matrix-operand lane constants: pair index on bits 3:0, contraction index on bits 5:4
-  const int mrow = lane & 15, mk = lane >> 4;
-  const bool mrow_ok = mrow < NB2;
-  const int mra = mrow_ok ? mrow / NB : 0, mrb = mrow_ok ? mrow % NB : 0;
+  const int n_seq = p.seg_len;
+  ColumnWalk c(p, unit);
+  auto block_of = [&](int64_t e) -> double* { return p.scratch_k + e * (int64_t)P2Block::size; };
 
   double C[3][NB2];  // packed carry [j][a1b1]
 #pragma unroll
   for (int j = 0; j < 3; ++j)
 #pragma unroll
     for (int k = 0; k < NB2; ++k) C[j][k] = 0.0;
-  double aS0[4], aS2[4];            // pair tables of directions 0 and 2 (variants B.B, D.B, B.D, D.D)
-  double uB1[NB][NQ], uD1[NB][NQ];  // wave-uniform direction-1 tables
-#pragma unroll
-  for (int v = 0; v < 4; ++v) aS0[v] = aS2[v] = 0.0;
-#pragma unroll
-  for (int a = 0; a < NB; ++a)
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) uB1[a][q] = uD1[a][q] = 0.0;
+  double aS0[4], aS2[4];
+  double uB1[NB][NQ], uD1[NB][NQ];
   auto load_slice = [&](int j, double (&ah)[9]) {
 #pragma unroll
     for (int m = 0; m < 3; ++m)
@@ -910,36 +926,9 @@ MH_DEV void wgs_y_loop(const TensorArgs& p, double* lds, int eu, int ev) {
   for (int it = 0; it < n_seq; ++it) {
     // ---- free running: tables, column components j = 0, 1 (the store-transposition buffer of this wave is private;
     // the operands read here were written before the previous barrier and are rewritten after the next one) -----
-    {
-      const double* tab = lds + L::off_tab + (it & 1) * 6 * NB * NQ;
-      {
-        const double Ba = tab_ptr<P>(tab, 0, 0)[mra * NQ + mk], Da = tab_ptr<P>(tab, 0, 1)[mra * NQ + mk];
-        const double Bb = tab_ptr<P>(tab, 0, 0)[mrb * NQ + mk], Db = tab_ptr<P>(tab, 0, 1)[mrb * NQ + mk];
-        aS0[0] = mrow_ok ? Ba * Bb : 0.0;
-        aS0[1] = mrow_ok ? Da * Bb : 0.0;
-        aS0[2] = mrow_ok ? Ba * Db : 0.0;
-        aS0[3] = mrow_ok ? Da * Db : 0.0;
-      }
-      {
-        const double Ba = tab_ptr<P>(tab, 2, 0)[mra * NQ + mk], Da = tab_ptr<P>(tab, 2, 1)[mra * NQ + mk];
-        const double Bb = tab_ptr<P>(tab, 2, 0)[mrb * NQ + mk], Db = tab_ptr<P>(tab, 2, 1)[mrb * NQ + mk];
-        aS2[0] = mrow_ok ? Ba * Bb : 0.0;
-        aS2[1] = mrow_ok ? Da * Bb : 0.0;
-        aS2[2] = mrow_ok ? Ba * Db : 0.0;
-        aS2[3] = mrow_ok ? Da * Db : 0.0;
-      }
-#pragma unroll
-      for (int a = 0; a < NB; ++a)
-#pragma unroll
-        for (int q1 = 0; q1 < NQ; ++q1) {
-          const unsigned long long vb = __double_as_longlong(tab_ptr<P>(tab, 1, 0)[a * NQ + q1]);
-          const unsigned long long vd = __double_as_longlong(tab_ptr<P>(tab, 1, 1)[a * NQ + q1]);
-          const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)vb), bhi = __builtin_amdgcn_readfirstlane((unsigned)(vb >> 32));
-          const unsigned dlo = __builtin_amdgcn_readfirstlane((unsigned)vd), dhi = __builtin_amdgcn_readfirstlane((unsigned)(vd >> 32));
-          uB1[a][q1] = __longlong_as_double(((unsigned long long)bhi << 32) | blo);
-          uD1[a][q1] = __longlong_as_double(((unsigned long long)dhi << 32) | dlo);
-        }
-    }
+    // (all three directions at every element: with the column's tables held from its first element on, as the symmetric-half
+    // kernel holds them, this kernel spills 30 registers -- profiles/p2_point_wave_refactor.txt)
+    wgs_load_tables(lds + L::off_tab + (it & 1) * WgsOperands::NT, lane, true, aS0, aS2, uB1, uD1);
     {
       double ah[9];
       load_slice(0, ah);
@@ -958,22 +947,21 @@ MH_DEV void wgs_y_loop(const TensorArgs& p, double* lds, int eu, int ev) {
       wgs_contract_block<0>(lc, ah, aS0, aS2, uB1, uD1, C[2], ST, 2, ST, 2);
       // this wave's piece of the element is complete: buffer -> scratch
       __builtin_amdgcn_wave_barrier();
-      wgs_flush_final(lane, ST, block_of(it), I);
+      wgs_flush_final(lane, ST, block_of(c.e), I);
       __builtin_amdgcn_wave_barrier();
       wgs_barrier();
     }
+    if (it + 1 < n_seq) c.advance(p);
   }
   // the carried rows of the last element have no successor: straight from the registers into the third part of the piece
   {
-    double* Sc = P2Block::carry_of(block_of(n_seq - 1), I);
+    double* Sc = P2Block::carry_of(block_of(c.e), I);
 #pragma unroll
     for (int jj = 0; jj < 3; ++jj) wgs_stage_carry<0>(lc, C[jj], Sc, jj, Sc, jj);
   }
 }
 
-#define WGS_Y_ARGS p, smem_wgs, eu, ev
-
-// Two workgroups per CU (256 registers per wave) for both materials.
+// Two workgroups per CU (256 registers per wave) for every material.
 template<int KIND>
 __global__ __launch_bounds__(256, 2) void tensor_wgs_kernel(TensorArgs p) {
   extern __shared__ __align__(16) double smem_wgs[];
@@ -983,19 +971,11 @@ __global__ __launch_bounds__(256, 2) void tensor_wgs_kernel(TensorArgs p) {
 #define WGS_ROT(b) ((b) >> 3)
 #endif
   const int role = __builtin_amdgcn_readfirstlane((int)((threadIdx.x >> 6) + WGS_ROT(blockIdx.x)) & 3);
-  const int unit = blockIdx.x;
-  const int eu = unit % p.box_n[0], ev = unit / p.box_n[0];
-  if (role == 0) {
-    int status = 0;
-    wgs_x_loop<KIND>(p, smem_wgs, eu, ev, status);
-    if (status) atomicOr(p.status, status);
-  } else if (role == 1) {
-    wgs_y_loop<0>(WGS_Y_ARGS);
-  } else if (role == 2) {
-    wgs_y_loop<1>(WGS_Y_ARGS);
-  } else {
-    wgs_y_loop<2>(WGS_Y_ARGS);
-  }
+  const int unit = blockIdx.x;   // one element column per workgroup
+  if (role == 0) wgs_x_loop<KIND>(p, smem_wgs, unit);
+  else if (role == 1) wgs_y_loop<0>(p, smem_wgs, unit);
+  else if (role == 2) wgs_y_loop<1>(p, smem_wgs, unit);
+  else wgs_y_loop<2>(p, smem_wgs, unit);
 }
 
 inline void launch_tensor_wgs(mimi_hip_domain_s* h, const DomainCall& c, TensorArgs a) {
@@ -1007,21 +987,17 @@ inline void launch_tensor_wgs(mimi_hip_domain_s* h, const DomainCall& c, TensorA
   a.n_units_v = a.box_n[1];
   const size_t lds = WgsLds::total * sizeof(double);
   const int kind = h->mat.m.kind;
-  const bool has_prepass = kind != MIMI_HIP_MAT_NEOHOOKEAN;
-  if (has_prepass) {
-    h->scratch_pt.resize((size_t)h->n_el * (material_closed_form(kind) ? WGS_PT_FIELDS : WGS_REC_FIELDS) * 64);
-    a.scratch_pt = h->scratch_pt.ptr;
-  }
-  // phase 1 = material pre-pass + nine-block kernel
+  h->scratch_pt.resize((size_t)h->n_el * (material_closed_form(kind) ? WGS_PT_FIELDS : WGS_REC_FIELDS) * 64);
+  a.scratch_pt = h->scratch_pt.ptr;
+  // phase 1 = material pre-pass + nine-block kernel (the neo-Hookean law goes to launch_tensor_wgsym)
   by_material_family(kind, [&](auto K) {
     constexpr int FK = decltype(K)::value;
     run_two_phase(
-        h, c, has_prepass,
+        h, c, true,
         [&] { launch(tensor_point_kernel<FK>, dim3((unsigned)((h->n_el + 3) / 4)), dim3(256), 0, h->stream, a, (int)h->n_el); },
         [&] {
           // (the other four materials come to the nine-block kernel as the pre-pass's tangent record)
-          auto kernel = FK != 0 ? tensor_wgs_kernel<WGS_KIND_RECORD>
-                        : kind == MIMI_HIP_MAT_NEOHOOKEAN ? tensor_wgs_kernel<MIMI_HIP_MAT_NEOHOOKEAN> : tensor_wgs_kernel<MIMI_HIP_MAT_J2>;
+          auto kernel = FK != 0 ? tensor_wgs_kernel<WGS_KIND_RECORD> : tensor_wgs_kernel<MIMI_HIP_MAT_J2>;
           launch(kernel, dim3(a.box_n[0] * a.box_n[1]), dim3(256), lds, h->stream, a);
         },
         [&] { launch_tensor_p2(h, a); });

@@ -41,13 +41,11 @@ namespace mimi_hip {
 #define WGSYM_DIAG_MODE 2   // 2: contract only the a1 >= b1 chains of a diagonal block; 0: all nine
 #endif
 
-struct WgsymLds {
-  static constexpr int NB = 3, NQ = 4, NB2 = 9, ND = 27, NQ3 = 64, NROW = 81;
+struct WgsymLds : P2Shape {
   static constexpr int off_ue = 0;                          // [3][27] (+1 pad)              X private
   static constexpr int off_tab = off_ue + 3 * ND + 1;       // [2 parity][3 dir][2][3][4]     X -> Y
   static constexpr int off_r = off_tab + 2 * 6 * NB * NQ;   // residual scratch, three rows    X private
-  static constexpr int r_size = 3 * (3 * NQ3 + 3 * NB * NQ * NQ + 3 * NB2 * NQ);
-  static constexpr int off_ah = off_r + r_size;             // [6 blocks (i, j <= i)][9 (m,n)][64]  X -> Y
+  static constexpr int off_ah = off_r + p2_stage_r_size(3);  // [6 blocks (i, j <= i)][9 (m,n)][64]  X -> Y
   static constexpr int off_st = off_ah + 6 * 9 * NQ3;       // [3 i][1216] store transposition      Y
   static constexpr int off_dump = off_st + 3 * WgsLds::st_size;   // where lanes without an entry store (wgs_contract_block)
   static constexpr int total = off_dump + 512;
@@ -60,13 +58,11 @@ struct WgsymLds {
 template<int KIND>
 MH_DEV void wgsym_x_rows(const TensorArgs& p, double* lds, int lane, int64_t e, int par, const WgsPoint<KIND>& s) {
   using L = WgsymLds;
-  constexpr int P = 2, NB = 3, NQ = 4, NB2 = 9, ND = 27, NQ3 = 64;
+  constexpr int ND = L::ND, NQ3 = L::NQ3;
   static_assert(KIND == MIMI_HIP_MAT_NEOHOOKEAN, "symmetric-half kernel: hyperelastic materials only");
-  const double* tab = lds + L::off_tab + par * 6 * NB * NQ;
+  const double* tab = lds + L::off_tab + par * WgsOperands::NT;
   double* AH = lds + L::off_ah;
   double* PH = lds + L::off_r;                  // [3 I][3 m][64]
-  double* V = PH + 9 * NQ3;                     // [3 I][3 m][3 a2][16]
-  double* W = V + 9 * NB * NQ * NQ;             // [3 I][3 m][9 a1a2][4]
 #pragma unroll
   for (int I = 0; I < 3; ++I)
 #pragma unroll
@@ -88,161 +84,51 @@ MH_DEV void wgsym_x_rows(const TensorArgs& p, double* lds, int lane, int64_t e, 
     }
 #pragma unroll
   for (int k = 0; k < 9; ++k) PH[k * NQ3 + lane] = s.Phat[k];   // k = I * 3 + m
-  __builtin_amdgcn_wave_barrier();
-  // Lane -> output maps of the three stages (round 5, as in the degree-3 pre-pass): a lane owns ONE pair of the indices that are
-  // neither summed nor a tensor component, reads its table values once and walks (I, m) with compile-time offsets -- 48 / 36 /
-  // 54 of the 64 lanes busy, a third of the instructions of the loops over the flat output index they replace (20 - 30 integer
-  // instructions of index arithmetic per four multiply-adds); the sums run in the same order: same bits.
-  // V[I m][a2][q0 q1] = sum_q2 T2^m[a2][q2] PH[I m][q0 q1 q2]
-  if (lane < NB * NQ * NQ) {
-    const int q01 = lane & 15, a2 = lane >> 4;
-    double T[2][NQ];
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-      for (int q2 = 0; q2 < NQ; ++q2) T[v][q2] = tab_ptr<P>(tab, 2, v)[a2 * NQ + q2];
-#pragma unroll
-    for (int im = 0; im < 9; ++im) {
-      double sv = 0.0;
-#pragma unroll
-      for (int q2 = 0; q2 < NQ; ++q2) sv = __builtin_fma(T[im % 3 == 2 ? 1 : 0][q2], PH[im * NQ3 + q01 + NQ * NQ * q2], sv);
-      V[im * (NB * NQ * NQ) + lane] = sv;   // (im * NB + a2) * 16 + q01
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  // W[I m][a1 a2][q0] = sum_q1 T1^m[a1][q1] V[I m][a2][q0 q1]
-  if (lane < NB2 * NQ) {
-    const int q0 = lane & 3, a12 = lane >> 2, a1 = a12 % NB, a2 = a12 / NB;
-    double T[2][NQ];
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-      for (int q1 = 0; q1 < NQ; ++q1) T[v][q1] = tab_ptr<P>(tab, 1, v)[a1 * NQ + q1];
-#pragma unroll
-    for (int im = 0; im < 9; ++im) {
-      double sw = 0.0;
-#pragma unroll
-      for (int q1 = 0; q1 < NQ; ++q1) sw = __builtin_fma(T[im % 3 == 1 ? 1 : 0][q1], V[(im * NB + a2) * NQ * NQ + q0 + NQ * q1], sw);
-      W[im * (NB2 * NQ) + lane] = sw;   // (im * NB2 + a12) * 4 + q0
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
-  // rows: lanes 0..26 take I = 0 and then I = 2, lanes 27..53 take I = 1
-  if (lane < 2 * ND) {
-    const int a = lane < ND ? lane : lane - ND, a0 = a % NB, a12 = a / NB;
-    double T[2][NQ];
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-      for (int q0 = 0; q0 < NQ; ++q0) T[v][q0] = tab_ptr<P>(tab, 0, v)[a0 * NQ + q0];
-    const int n_rows = lane < ND ? 2 : 1;
-    for (int k = 0; k < n_rows; ++k) {
-      const int I = lane < ND ? 2 * k : 1;
-      double sr = 0.0;
-#pragma unroll
-      for (int m = 0; m < 3; ++m)
-#pragma unroll
-        for (int q0 = 0; q0 < NQ; ++q0) sr = __builtin_fma(T[m == 0 ? 1 : 0][q0], W[((I * 3 + m) * NB2 + a12) * NQ + q0], sr);
-      p.scratch_r[(e * ND + a) * 3 + I] = sr;       // [element][a][i]: tensor_p2_kernel reads a node's three rows from one sector
-    }
-  }
-  __builtin_amdgcn_wave_barrier();
+  p2_stage_r<3>(tab, PH, lane, p.scratch_r + e * ND * 3, 0);
 }
 
 // ------------------------------------------------------------------------------------------------
 // wave X, two steps per element
 // ------------------------------------------------------------------------------------------------
 template<int KIND>
-MH_DEV void wgsym_x_loop(const TensorArgs& p, double* lds, int col0, int n_cols, int& status) {
+MH_DEV void wgsym_x_loop(const TensorArgs& p, double* lds, int col0, int n_cols) {
   using L = WgsymLds;
-  constexpr int P = 2, NB = 3, NQ = 4, ND = 27, NQ3 = 64;
-  constexpr int TROUNDS = 2;
+  constexpr int P = L::P, NB = L::NB, NQ = L::NQ, ND = L::ND;
   const int lane = threadIdx.x & 63;
   double* ue = lds + L::off_ue;
-  // the workgroup walks n_cols units back to back, a unit = one segment of seg_len elements of an element column
-  // (unit index = column * segments-per-column + segment): sequence index g = unit-in-workgroup * seg_len + position
-  const int sl = p.seg_len, nseg = p.box_n[2] / sl;
-  const int n_seq = n_cols * sl;
-  // The element of sequence index g, its spans and its layer, kept by a cursor that moves one element at a time (round 5: the
-  // point wave asked for them by division -- g / sl, % nseg, col % n0, col / n0 at every use: ~ 12 run-time integer divisions,
-  // 300 - 400 scalar instructions per element; the contraction waves went incremental in round 4): the unit's column by
-  // division when a unit begins, then one layer further per step.
-  struct Cursor {
-    int g, pos, unit, cx, cy, ez;
-    int64_t e;
-  };
-  const int64_t e_step = (int64_t)p.box_n[0] * p.box_n[1];
-  auto cursor_at_unit = [&](int g, int u) -> Cursor {
-    Cursor c;
-    c.g = g;
-    c.pos = 0;
-    c.unit = u;
-    const int un = col0 + u, col = un / nseg;
-    c.cx = col % p.box_n[0];
-    c.cy = col / p.box_n[0];
-    c.ez = (un % nseg) * sl;
-    c.e = c.cx + (int64_t)p.box_n[0] * (c.cy + (int64_t)p.box_n[1] * c.ez);
-    return c;
-  };
-  auto advance = [&](Cursor& c) {
-    ++c.g;
-    if (++c.pos == sl) {
-      c = cursor_at_unit(c.g, c.unit + 1);
-    } else {
-      ++c.ez;
-      c.e += e_step;
-    }
-  };
-  auto table_src = [&](const Cursor& c, int t) -> const double* {
-    const int dir = t / (2 * NB * NQ);
-    const int rem = t % (2 * NB * NQ);
-    const int isD = rem / (NB * NQ);
-    const int k = rem % (NB * NQ);
-    const int span = (dir == 0 ? p.box_begin[0] + c.cx : dir == 1 ? p.box_begin[1] + c.cy : p.box_begin[2] + c.ez);
-    return (isD ? (dir == 0 ? p.tabD[0] : dir == 1 ? p.tabD[1] : p.tabD[2])
-                : (dir == 0 ? p.tabB[0] : dir == 1 ? p.tabB[1] : p.tabB[2])) + (int64_t)span * NB * NQ + k;
-  };
-  Cursor cq = cursor_at_unit(0, 0);      // the element whose operands are requested next
-  Cursor cs = cq;                        // the element of the next quadrature-point stage
-  Cursor cr = cq;                        // the element whose rows are written next
+  const int n_seq = n_cols * p.seg_len;   // the workgroup walks n_cols units back to back (ColumnWalk)
+  ColumnWalk cq(p, col0);     // the element whose operands are requested next
+  ColumnWalk cs = cq;         // the element of the next quadrature-point stage
+  ColumnWalk cr = cq;         // the element whose rows are written next
+  // the connectivity travels one element further ahead than the other operands
   int32_t node_n = lane < ND ? p.dofs[cq.e * ND + lane] : 0;
-  double ue_r[3], tab_r[TROUNDS], geo_r[10];
-  // requests the operands of the element at cq (the cursor moves on), and the node ids of the one after it
+  double ue_r[3];
+  WgsOperands op;
+  // requests the operands of the element at cq (the walk moves on), and the node ids of the one after it
   auto request = [&]() {
 #pragma unroll
     for (int c = 0; c < 3; ++c) ue_r[c] = p.u[(int64_t)node_n * 3 + c];
-#pragma unroll
-    for (int rd = 0; rd < TROUNDS; ++rd) {
-      const int t = rd * 64 + lane;
-      tab_r[rd] = *table_src(cq, t < 6 * NB * NQ ? t : 0);
-    }
-    const double* g = p.geo + cq.e * 10 * NQ3 + lane;
-#pragma unroll
-    for (int k = 0; k < 10; ++k) geo_r[k] = g[(int64_t)k * NQ3];
+    op.request(p, cq, lane);
     if (cq.g + 1 < n_seq) {
-      advance(cq);
+      cq.advance(p);
       node_n = lane < ND ? p.dofs[cq.e * ND + lane] : 0;
     }
   };
   WgsPoint<KIND> s;
-  // quadrature-point stage of element es from the requested operands (tables -> LDS parity es & 1)
+  // quadrature-point stage of the element at cs from the requested operands (tables -> LDS parity g & 1)
   auto point_stage = [&]() {
-    const int es = cs.g;
-    double* tab = lds + L::off_tab + (es & 1) * 6 * NB * NQ;
+    double* tab = lds + L::off_tab + (cs.g & 1) * WgsOperands::NT;
     if (lane < ND) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) ue[c * ND + lane] = ue_r[c];
     }
-#pragma unroll
-    for (int rd = 0; rd < TROUNDS; ++rd) {
-      const int t = rd * 64 + lane;
-      if (t < 6 * NB * NQ) tab[t] = tab_r[rd];
-    }
+    op.tables_to_lds(tab, lane);
     double Ji[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) Ji[k] = geo_r[k];
-    const double wd = geo_r[9];
+    for (int k = 0; k < 9; ++k) Ji[k] = op.geo[k];
+    const double wd = op.geo[9];
     __builtin_amdgcn_wave_barrier();
+    // F at the quadrature point of this lane, q = q0 + 4 q1 + 16 q2
     double F[9];
     {
       const int q0 = lane & 3, q1 = (lane >> 2) & 3, q2 = lane >> 4;
@@ -290,9 +176,9 @@ MH_DEV void wgsym_x_loop(const TensorArgs& p, double* lds, int col0, int n_cols,
           F[i + J * 3] = sf;
         }
     }
-    status |= wgs_x_point<KIND>(p, cs.e * NQ3 + lane, F, Ji, wd, s);
+    wgs_neohookean_point(p.mat.m, F, Ji, wd, s);
     __builtin_amdgcn_wave_barrier();
-    if (cs.g + 1 < n_seq) advance(cs);
+    if (cs.g + 1 < n_seq) cs.advance(p);
   };
 
   request();
@@ -311,7 +197,7 @@ MH_DEV void wgsym_x_loop(const TensorArgs& p, double* lds, int col0, int n_cols,
     // ---- O(it), lock step: rows of element it + 1 once every contraction wave holds its operands of element it --
     wgs_barrier();
     if (it + 1 < n_seq) {
-      advance(cr);
+      cr.advance(p);
       wgsym_x_rows<KIND>(p, lds, lane, cr.e, (it + 1) & 1, s);
     }
     wgs_barrier();
@@ -324,35 +210,24 @@ MH_DEV void wgsym_x_loop(const TensorArgs& p, double* lds, int col0, int n_cols,
 template<int W>
 MH_DEV void wgsym_y_loop(const TensorArgs& p, double* lds, int col0, int n_cols) {
   using L = WgsymLds;
-  constexpr int P = 2, NB = 3, NQ = 4, NB2 = 9, ND = 27, NQ3 = 64, NROW = 81, NK = ND * NROW;
+  constexpr int NB2 = L::NB2, NQ3 = L::NQ3;
   // step O blocks: Y0 (1,0), Y1 (2,0), Y2 (2,1)
   constexpr int I1 = W == 0 ? 1 : 2, J1 = W == 2 ? 1 : 0;
   const WgsLane lc = wgs_lane_constants(true);
   const int lane = lc.lane;
-  const int sl = p.seg_len, nseg = p.box_n[2] / sl;
-  const int n_seq = n_cols * sl;   // sequence index g = unit-in-workgroup * seg_len + position (see wgsym_x_loop)
+  const int n_seq = n_cols * p.seg_len;
   const double* AH0 = lds + L::off_ah + L::ah_block(W, W) * NQ3;
   const double* AH1 = lds + L::off_ah + L::ah_block(I1, J1) * NQ3;
   auto st_of = [&](int piece) -> double* { return lds + L::off_st + piece * WgsLds::st_size; };
-  // the element of sequence index g, kept incrementally (round 4: four integer divisions by run-time numbers per element
-  // and wave were ~80 scalar instructions of the loop): first element of a unit by division, then + one layer per step
-  auto unit_first = [&](int u) -> int64_t {
-    const int unit = col0 + u, col = unit / nseg;
-    return col % p.box_n[0] + (int64_t)p.box_n[0] * (col / p.box_n[0] + (int64_t)p.box_n[1] * ((unit % nseg) * sl));
-  };
-  const int64_t e_step = (int64_t)p.box_n[0] * p.box_n[1];
   auto block_at = [&](int64_t e) -> double* { return p.scratch_k + e * (int64_t)P2Block::size; };
-  int pos = 0, unit_i = 0;        // position inside the unit (= it % seg_len), unit inside the workgroup
-  int64_t e_cur = unit_first(0), e_prev = e_cur;
-  const int mrow = lane & 15, mk = lane >> 4;
-  const bool mrow_ok = mrow < NB2;
-  const int mra = mrow_ok ? mrow / NB : 0, mrb = mrow_ok ? mrow % NB : 0;
+  ColumnWalk c(p, col0);
+  int64_t e_prev = c.e;
 
   double C0[NB2], C1[NB2];  // packed carries of the two blocks
 #pragma unroll
   for (int k = 0; k < NB2; ++k) C0[k] = C1[k] = 0.0;
   double aS0[4], aS2[4];
-  double uB1[NB][NQ], uD1[NB][NQ];
+  double uB1[L::NB][L::NQ], uD1[L::NB][L::NQ];
 
   // ---- prologue: X writes the rows of element 0 ---------------------------------------------------------------
   wgs_barrier();
@@ -360,37 +235,7 @@ MH_DEV void wgsym_y_loop(const TensorArgs& p, double* lds, int col0, int n_cols)
     // ---- D(it), free running: flush element it - 1, tables of element it, diagonal block ----------------------
     {
       if (it >= 1) wgs_flush_final(lane, st_of(W), block_at(e_prev), W);
-      const double* tab = lds + L::off_tab + (it & 1) * 6 * NB * NQ;
-      // the tables of directions 0 and 1 belong to the element COLUMN: read (24 LDS reads, 48 v_readfirstlane, the pair
-      // products of direction 0) at the first element of a unit only -- every vector instruction of a contraction wave
-      // is on the kernel's critical path; direction 2 changes with every element
-      if (pos == 0) {
-        const double Ba = tab_ptr<P>(tab, 0, 0)[mra * NQ + mk], Da = tab_ptr<P>(tab, 0, 1)[mra * NQ + mk];
-        const double Bb = tab_ptr<P>(tab, 0, 0)[mrb * NQ + mk], Db = tab_ptr<P>(tab, 0, 1)[mrb * NQ + mk];
-        aS0[0] = mrow_ok ? Ba * Bb : 0.0;
-        aS0[1] = mrow_ok ? Da * Bb : 0.0;
-        aS0[2] = mrow_ok ? Ba * Db : 0.0;
-        aS0[3] = mrow_ok ? Da * Db : 0.0;
-#pragma unroll
-        for (int a = 0; a < NB; ++a)
-#pragma unroll
-          for (int q1 = 0; q1 < NQ; ++q1) {
-            const unsigned long long vb = __double_as_longlong(tab_ptr<P>(tab, 1, 0)[a * NQ + q1]);
-            const unsigned long long vd = __double_as_longlong(tab_ptr<P>(tab, 1, 1)[a * NQ + q1]);
-            const unsigned blo = __builtin_amdgcn_readfirstlane((unsigned)vb), bhi = __builtin_amdgcn_readfirstlane((unsigned)(vb >> 32));
-            const unsigned dlo = __builtin_amdgcn_readfirstlane((unsigned)vd), dhi = __builtin_amdgcn_readfirstlane((unsigned)(vd >> 32));
-            uB1[a][q1] = __longlong_as_double(((unsigned long long)bhi << 32) | blo);
-            uD1[a][q1] = __longlong_as_double(((unsigned long long)dhi << 32) | dlo);
-          }
-      }
-      {
-        const double Ba = tab_ptr<P>(tab, 2, 0)[mra * NQ + mk], Da = tab_ptr<P>(tab, 2, 1)[mra * NQ + mk];
-        const double Bb = tab_ptr<P>(tab, 2, 0)[mrb * NQ + mk], Db = tab_ptr<P>(tab, 2, 1)[mrb * NQ + mk];
-        aS2[0] = mrow_ok ? Ba * Bb : 0.0;
-        aS2[1] = mrow_ok ? Da * Bb : 0.0;
-        aS2[2] = mrow_ok ? Ba * Db : 0.0;
-        aS2[3] = mrow_ok ? Da * Db : 0.0;
-      }
+      wgs_load_tables(lds + L::off_tab + (it & 1) * WgsOperands::NT, lane, c.pos == 0, aS0, aS2, uB1, uD1);
       double ah[9];
 #pragma unroll
       for (int k = 0; k < 9; ++k) ah[k] = AH0[k * NQ3 + lane];
@@ -407,24 +252,18 @@ MH_DEV void wgsym_y_loop(const TensorArgs& p, double* lds, int col0, int n_cols)
       wgs_barrier();
       wgs_contract_block<1, true>(lc, ah, aS0, aS2, uB1, uD1, C1, st_of(I1), J1, st_of(J1), I1, lds + L::off_dump);
       wgs_barrier();
-      if (pos == sl - 1) {
+      if (c.pos == p.seg_len - 1) {
         // last element of a unit (column, or column segment): the carried rows have no successor -- straight from the registers into the third
         // part of the pieces (no LDS, no lock step) -- and the next column starts with an empty carry
-        double* E = block_at(e_cur);
+        double* E = block_at(c.e);
         wgs_stage_carry<WGSYM_DIAG_MODE>(lc, C0, P2Block::carry_of(E, W), W, P2Block::carry_of(E, W), W);
         wgs_stage_carry<1>(lc, C1, P2Block::carry_of(E, I1), J1, P2Block::carry_of(E, J1), I1);
 #pragma unroll
         for (int k = 0; k < NB2; ++k) C0[k] = C1[k] = 0.0;
       }
     }
-    e_prev = e_cur;
-    if (++pos == sl) {
-      pos = 0;
-      ++unit_i;
-      if (unit_i < n_cols) e_cur = unit_first(unit_i);
-    } else {
-      e_cur += e_step;
-    }
+    e_prev = c.e;
+    if (it + 1 < n_seq) c.advance(p);
   }
   // ---- after the last element (no more lock steps): its pieces from the buffers ------------------------------------
   wgs_flush_final(lane, st_of(W), block_at(e_prev), W);
@@ -437,15 +276,10 @@ __global__ __launch_bounds__(256, 2) void tensor_wgsym_kernel(TensorArgs p) {
   const int n_cols_all = p.box_n[0] * p.box_n[1] * (p.box_n[2] / p.seg_len);   // units
   const int col0 = blockIdx.x * p.cols_per_wg;
   const int n_cols = n_cols_all - col0 < p.cols_per_wg ? n_cols_all - col0 : p.cols_per_wg;
-  if (role == 0) {
-    int status = 0;
-    wgsym_x_loop<KIND>(p, smem_wgsym, col0, n_cols, status);
-    if (status) atomicOr(p.status, status);
-  } else {
-    if (role == 1) wgsym_y_loop<0>(p, smem_wgsym, col0, n_cols);
-    else if (role == 2) wgsym_y_loop<1>(p, smem_wgsym, col0, n_cols);
-    else wgsym_y_loop<2>(p, smem_wgsym, col0, n_cols);
-  }
+  if (role == 0) wgsym_x_loop<KIND>(p, smem_wgsym, col0, n_cols);
+  else if (role == 1) wgsym_y_loop<0>(p, smem_wgsym, col0, n_cols);
+  else if (role == 2) wgsym_y_loop<1>(p, smem_wgsym, col0, n_cols);
+  else wgsym_y_loop<2>(p, smem_wgsym, col0, n_cols);
 }
 
 inline void launch_tensor_wgsym(mimi_hip_domain_s* h, const DomainCall& c, TensorArgs a) {

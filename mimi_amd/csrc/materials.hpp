@@ -350,6 +350,18 @@ struct PointResult {
   bool plastic;
 };
 
+// beta, gamma of the J2 algorithmic tangent (radial return); 1, 0 at an elastic point
+template<int DIM>
+MH_DEV void j2_beta_gamma(const mimi_hip_material& m, const PointResult<DIM>& w, double& beta, double& gamma) {
+  beta = 1.0;
+  gamma = 0.0;
+  if (w.plastic) {
+    const double q = w.q, G = m.G;
+    beta = 1.0 - 3.0 * G * w.delta / q;
+    gamma = 3.0 * G * (1.5 / q) * (1.0 / ((3.0 * G + w.hprime) * q) - w.delta / (q * q));
+  }
+}
+
 #define MH_M(T, i, j) (T)[(i) + (j) * DIM]
 
 template<int DIM>
@@ -501,12 +513,8 @@ MH_DEV void tangent_of(const mimi_hip_material& m, const PointResult<DIM>& w, do
     return;
   }
   // J2: P_iJ = J sigma_ik Finv_Jk, sigma = radial return of the small-strain trial state
-  double beta = 1.0, gamma = 0.0;
-  if (w.plastic) {
-    const double q = w.q, G = m.G;
-    beta = 1.0 - 3.0 * G * w.delta / q;
-    gamma = 3.0 * G * (1.5 / q) * (1.0 / ((3.0 * G + w.hprime) * q) - w.delta / (q * q));
-  }
+  double beta, gamma;
+  j2_beta_gamma<DIM>(m, w, beta, gamma);
   const double G2 = 2.0 * m.G;
 #pragma unroll
   for (int i = 0; i < DIM; ++i)
@@ -551,12 +559,8 @@ MH_DEV void tangent_row_of(const mimi_hip_material& m, const PointResult<DIM>& w
         }
     return;
   }
-  double beta = 1.0, gamma = 0.0;
-  if (w.plastic) {
-    const double q = w.q, G = m.G;
-    beta = 1.0 - 3.0 * G * w.delta / q;
-    gamma = 3.0 * G * (1.5 / q) * (1.0 / ((3.0 * G + w.hprime) * q) - w.delta / (q * q));
-  }
+  double beta, gamma;
+  j2_beta_gamma<DIM>(m, w, beta, gamma);
   const double G2 = 2.0 * m.G;
 #pragma unroll
   for (int Jx = 0; Jx < DIM; ++Jx)

@@ -28,10 +28,9 @@ inline int launch_tensor(mimi_hip_domain_s* h, const DomainCall& c) {
     launch_tensor_p3(h, c, a);
     return 2;
   }
-  // MIMI_HIP_TENSOR_VARIANT=wgs: the full nine-block kernel also for hyperelastic materials (default: symmetric half)
-  const bool want_full = env_tensor_variant_full();
+  // the symmetric-half kernel for the hyperelastic law, the nine-block kernel behind the material pre-pass for the others
   if (!c.grad) launch_tensor_residual(h, a);
-  else if (h->mat.m.kind == MIMI_HIP_MAT_NEOHOOKEAN && !want_full) launch_tensor_wgsym(h, c, a);
+  else if (h->mat.m.kind == MIMI_HIP_MAT_NEOHOOKEAN) launch_tensor_wgsym(h, c, a);
   else launch_tensor_wgs(h, c, a);
   return 1;
 }

@@ -117,12 +117,8 @@ MH_DEV void t3_closed_form_record(const mimi_hip_material& mm, const PointResult
       }
     return;
   }
-  double beta = 1.0, gamma = 0.0;
-  if (w.plastic) {
-    const double q = w.q, Gm = mm.G;
-    beta = 1.0 - 3.0 * Gm * w.delta / q;
-    gamma = 3.0 * Gm * (1.5 / q) * (1.0 / ((3.0 * Gm + w.hprime) * q) - w.delta / (q * q));
-  }
+  double beta, gamma;
+  j2_beta_gamma<3>(mm, w, beta, gamma);
   const double G2 = 2.0 * mm.G;
   const double wdJ = wd * w.detF, Kc = mm.K - beta * G2 / 3.0, hb = 0.5 * beta * G2, gg = G2 * gamma;
   double N[9], Q[9];

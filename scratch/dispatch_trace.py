@@ -9,7 +9,8 @@ builds of the library (MIMI_HIP_LIBRARY=scratch/lib_parent.so, then the tree's o
 
 Entries reached: create from tables and from a B-spline, residual, residual + tangent, from-base in its three residences,
 post-time-advance, integrate + gather over partial windows, phase timing.  Kernel families: 2-D degree 1-3, 3-D degree 1,
-3-D degree 2 and 3 with neo-Hookean / J2 / a record material, 3-D degree 2 with node_ids, the general kernels
+3-D degree 2 and 3 with neo-Hookean / J2 / a record material (tangent and residual-only also after a committed step), 3-D
+degree 2 with node_ids and on an element box cut along the walked axis, the general kernels
 (MIMI_HIP_FORCE_GENERAL) with a closed-form and a record material, the reference-FD tangent.  Switches:
 MIMI_HIP_P3_CONTRACT flipped between two calls, MIMI_HIP_NO_STRUCTURED set between two creates.  Every route sums in a
 fixed order, so every hash must agree; --atomics runs the general path's atomics route
@@ -77,6 +78,9 @@ def run():
             r, A = seeded(n_vdofs, 2), seeded(nnz, 3)
             G.AddDomainResidualAndGrad(u, 0.37, r, A)
             out(case, "committed A", sha(A))
+            r = seeded(n_vdofs, 2)
+            G.AddDomainResidual(u, r)
+            out(case, "committed r", sha(r))
         if fd:
             G.SetTangentMode(1)
             r, A = seeded(n_vdofs, 2), seeded(nnz, 3)
@@ -176,6 +180,10 @@ def run():
         G.AddDomainResidual(u, r)
         G.Synchronize()
         out(case, "residual r", sha(r))
+    # degree 2, an element box cut along the walked (third) axis and along one other
+    for mat in ("neohook", "j2", "j2simo"):
+        patch, pattern, G = handle((5, 6, 8), 2, mat, element_box=([0, 1, 2], [5, 5, 6]))
+        assemblies(f"element box 5x6x8 p2 {mat}", G, patch.n_vdofs, pattern.nnz, mat)
     # MIMI_HIP_P3_CONTRACT flipped between two calls of one handle
     patch, pattern, G = handle((2, 3, 4), 3, "neohook")
     u = seeded(patch.n_vdofs, 1, 0.05)

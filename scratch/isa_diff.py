@@ -67,6 +67,14 @@ def main():
                 print(f"  instruction stream differs: {n} ({len(a[n][0])} -> {len(b[n][0])} instructions)")
             for n in diff_r:
                 print(f"  resource block differs: {n}")
+            # what decides a changed kernel's occupancy, before -> after (workgroups of 256 threads; dynamic LDS is the launcher's)
+            for n in sorted(set(diff_i) | set(diff_r) | set(only_a) | set(only_b)):
+                for side, k in ((rev, a.get(n)), ("working tree", b.get(n))):
+                    if k:
+                        res = dict(k[1][1])
+                        sgpr = re.search(r"\.amdhsa_next_free_sgpr (\d+)", k[1][0])
+                        print(f"    {n} at {side}: {len(k[0])} instructions, {res} sgpr {sgpr.group(1) if sgpr else '?'}, "
+                              f"{isa_lint.waves_per_simd(res, 256):g} waves per SIMD")
             bad += len(only_a) + len(only_b) + len(diff_i) + len(diff_r)
     print("IDENTICAL" if not bad else f"DIFFERENT ({bad} findings)")
     sys.exit(1 if bad else 0)

@@ -124,8 +124,10 @@ void launch_general_dim(mimi_hip_domain_s* h, const DomainCall& c) {
   size_t lds = general_lds_bytes(DIM, h->n_dof, h->n_q, grad);
   if (lds > 160 * 1024) fail("element too large for LDS (%zu bytes)", lds);
   // small elements (one pass of the node-pair phase fits one wave: 2-D p <= 3, 3-D p = 1): one wave per element, four
-  // elements per workgroup
-  const bool wpe = !no_wpe && grad != 2 && h->n_dof * ((h->n_dof + 2) / 3) <= 128 && h->n_q <= 64;
+  // elements per workgroup -- when the LDS blocks of four elements fit (a 3-D tangent assembly with 64 points per element,
+  // degrees (2,1,1) / (2,2,1) at the default order, needs 51 - 54 KB per element: one workgroup per element then)
+  const bool wpe = !no_wpe && grad != 2 && h->n_dof * ((h->n_dof + 2) / 3) <= 128 && h->n_q <= 64 &&
+                   (lds + 15) / 16 * 16 * 4 <= 160 * 1024;
   if (wpe) {
     a.lds_per_element = (int)((lds + 15) / 16 * 16);
     lds = (size_t)a.lds_per_element * 4;

@@ -207,11 +207,18 @@ class InterfaceExchange:
         in owner mode 3 of the 5 column planes remain: 11.7 instead of 19.5 MB per neighbour and direction at the
         north-star size on 8 ranks -- what has to hide behind the last gather.  Sender and receiver list the
         same (row, column) pairs in the same order, each from the slab bounds alone.  False: whole rows (csrc/exchange.hip's
-        row kernels)."""
+        row kernels).  "Layer l touches the planes l .. l + p" holds only without repeated interior knots along the sharding
+        axis (first basis function of span l = l): a patch (SlabShard) or local patch (LocalSlabShard) that has one is
+        refused with trim=True -- its messages would silently lose entries; whole rows (trim=False) carry them."""
         import torch
         import torch.distributed as dist
         if mode not in ("replicate", "owner"):
             raise ValueError(mode)
+        ax = shard.axis
+        if trim and int(shard.patch.n_ctrl[ax]) != int(shard.patch.n_spans[ax]) + int(shard.patch.degrees[ax]):
+            raise RuntimeError(f"trimmed messages need span l to touch the node planes l .. l + p along the sharding axis: "
+                               f"axis {ax} has a repeated interior knot ({shard.patch.n_ctrl[ax]} node planes for "
+                               f"{shard.patch.n_spans[ax]} spans of degree {shard.patch.degrees[ax]}); use trim=False")
         self.torch, self.dist = torch, dist
         self.shard, self.r, self.A, self.mode = shard, r, A, mode
         self.loopback = bool(loopback)

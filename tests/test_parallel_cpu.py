@@ -428,3 +428,41 @@ def test_trimmed_messages_drop_structural_zeros_only(p, mode, monkeypatch):
     assert up["srows"].numel() == down["rrows"].numel()
     # (both ranks index the whole patch's pattern here: the same pairs in the same order are the same positions)
     assert torch.equal(up["sidx"], down["ridx"]) and torch.equal(up["ridx"], down["sidx"])
+
+
+@pytest.mark.parametrize("local", [False, True], ids=["SlabShard", "LocalSlabShard"])
+def test_trimmed_messages_refuse_a_repeated_knot_on_the_cut_axis(local, monkeypatch):
+    """a trimmed message keeps the entries with max(a, c) - p <= l <= min(a, c) for the sender's layers l,
+    which assumes that span l touches the node planes l .. l + p.  With a repeated interior knot along the sharding axis
+    (rep3d_p2 of tests/_patches.py: [1, 2, 2, 3] along axis 0, first functions 0, 1, 3, 4) that drops entries the sender
+    wrote, so InterfaceExchange(trim=True) raises -- for the whole patch's shard and for a local slab patch alike; whole rows
+    (trim=False) are still accepted, and so is a cut along an axis without a repeat."""
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import torch
+    import torch.distributed as dist
+    import _patches
+    from mimi_amd import parallel
+    from mimi_amd.integrators import CSRPattern
+    monkeypatch.setattr(dist, "get_rank", lambda *a, **k: 0)
+
+    def exchange(case, **kw):
+        P, B = _patches.patches(case)
+        rowptr, col = P.sparsity()
+        pattern = CSRPattern(rowptr, col, rowptr[-1])
+        shard = parallel.SlabShard(B, pattern, 0, 2, axis=0)
+        if local:      # (rank 0 of 2 with its p = 2 ghost layers above: the local patch is the whole patch, 2 + 2 spans)
+            assert shard.ghost_layers() == (0, 2)
+            shard = shard.localized(B, pattern, ghost=shard.ghost_layers())
+        return parallel.InterfaceExchange(shard, torch.zeros(P.n_vdofs, dtype=torch.float64),
+                                          torch.zeros(int(rowptr[-1]), dtype=torch.float64), loopback=True, **kw)
+
+    B = _patches.patches("rep3d_p2")[1]
+    assert B.n_spans == [4, 2, 3] and B.n_ctrl[0] == 7 != B.n_spans[0] + 2
+    with pytest.raises(RuntimeError, match="repeated interior knot"):
+        exchange("rep3d_p2")
+    with pytest.raises(RuntimeError, match="repeated interior knot"):
+        exchange("rep3d_p2", trim=True, mode="owner")
+    assert not exchange("rep3d_p2", trim=False).trim
+    # unequal spans without a repeat ([0.2, 1.5, 1.7] along axis 0) are taken
+    assert exchange("nonuni3d_p2").trim

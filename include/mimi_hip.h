@@ -216,6 +216,20 @@ int mimi_hip_domain_nodal_field(mimi_hip_domain_t h, const double* u, int field,
  * no shape values, and the nodal projection needs them.  Without it mimi_hip_domain_nodal_field on such a handle reports
  * an error that says so. */
 int mimi_hip_domain_set_shape_values(mimi_hip_domain_t h, const double* N);
+/* ---- mass, damping and body-force forms -----------------------------------------------------------------------------
+ * The element integrals of set-up, assembled into the caller's CSR / vector (py_nonlinear_solid.cpp:155-192,221-283), over
+ * the handle's elements (an element-box handle adds its box only: boxes and ranks compose by addition) with the handle's
+ * own rule, w det and dN/dX -- the quantities the residual integrates with.  Outputs are accumulated; of a node block only
+ * the dim diagonal-component entries are written, the i != j entries are not touched.  No state and no material is read,
+ * no essential dofs are involved (the caller eliminates).  Host or device arrays: synchronous for host arrays,
+ * stream-ordered otherwise.  No atomics: two calls on equal inputs give equal bytes.  Mass and body force on a flat-table
+ * handle need mimi_hip_domain_set_shape_values.
+ *   A_values[(A,i),(B,i)] += density   * sum_e sum_q w_q det_q N_a(q) N_b(q)                 i < dim   (VectorMassIntegrator) */
+int mimi_hip_domain_add_mass(mimi_hip_domain_t h, double density, double* A_values);
+/* A_values[(A,i),(B,i)] += viscosity * sum_e sum_q w_q det_q dN_a/dX_J(q) dN_b/dX_J(q)     i < dim   (VectorDiffusionIntegrator) */
+int mimi_hip_domain_add_diffusion(mimi_hip_domain_t h, double viscosity, double* A_values);
+/* r[(A,i)] += b[i] * sum_e sum_q w_q det_q N_a(q);   b: dim doubles on the host              (VectorDomainLFIntegrator) */
+int mimi_hip_domain_add_body_force(mimi_hip_domain_t h, const double* b, double* r);
 /* The two-step form of mimi_hip_domain_add_residual_and_grad, for a caller that needs some rows before the others (the
  * rows a neighbour rank is waiting for: mimi_amd/parallel.py, bench.py): integrate() runs the integration kernels of the
  * whole handle -- element row pieces and element residual pieces into the handle's scratch, nothing into r / A_values --

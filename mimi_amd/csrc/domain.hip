@@ -17,6 +17,7 @@
 #include "tensor_dispatch.hpp"
 #include "domain_create.hpp"
 #include "domain_dispatch.hpp"
+#include "kernels_forms.hpp"
 
 #include <memory>
 
@@ -274,6 +275,27 @@ int mimi_hip_domain_set_shape_values(mimi_hip_domain_t h, const double* N) {
     if (h->geo.ptr) fail("mimi_hip_domain_set_shape_values: flat-table handles only (a patch handle has its own 1-D tables)");
     MH_HIP(hipSetDevice(h->device));
     h->shape_N.assign(N, (size_t)h->n_el * h->n_q * h->n_dof, h->stream);
+  });
+}
+
+int mimi_hip_domain_add_mass(mimi_hip_domain_t h, double density, double* A_values) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    run_form(h, FORM_MASS, density, A_values);
+  });
+}
+
+int mimi_hip_domain_add_diffusion(mimi_hip_domain_t h, double viscosity, double* A_values) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    run_form(h, FORM_DIFFUSION, viscosity, A_values);
+  });
+}
+
+int mimi_hip_domain_add_body_force(mimi_hip_domain_t h, const double* b, double* r) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    run_body_force(h, b, r);
   });
 }
 

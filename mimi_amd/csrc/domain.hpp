@@ -71,5 +71,10 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   mimi_hip::DeviceBuffer<int64_t> field_adj_ptr;
   mimi_hip::DeviceBuffer<int32_t> field_adj;
 
+  // linear forms (kernels_forms.hpp): the lumped weight of the body force [n_nodes]; the longest CSR row, once the general
+  // route has measured it (its row image is GG_MAX_ROW entries)
+  mimi_hip::DeviceBuffer<double> lumped_w;
+  int64_t longest_row = -1;
+
   ~mimi_hip_domain_s();
 };

@@ -285,6 +285,18 @@ void by_field_family(int kind, F&& f) {
   else by_material_family(kind, f);
 }
 
+// N[e][q][a] of the general route's nodal form: the caller's on a flat-table handle, expanded from the 1-D tables on a
+// patch handle
+inline void ensure_shape_values(mimi_hip_domain_s* h) {
+  if (h->shape_N.ptr) return;
+  if (!h->geo.ptr)
+    fail("nodal field on a flat-table handle: the tables carry no shape values, give them with mimi_hip_domain_set_shape_values");
+  const int64_t total = (int64_t)h->n_el * h->n_q * h->n_dof;
+  h->shape_N.resize((size_t)total);
+  auto kernel = h->dim == 2 ? expand_shape_kernel<2> : expand_shape_kernel<3>;
+  launch(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, patch_dev(h, nullptr), h->shape_N.ptr);
+}
+
 template<int DIM, int P>
 void launch_field_tensor_dp(mimi_hip_domain_s* h, const TensorArgs& a, const FieldArgs& fa) {
   by_field_family(h->mat.m.kind, [&](auto K) {
@@ -313,14 +325,7 @@ inline void launch_field(mimi_hip_domain_s* h, const double* u, FieldArgs fa) {
   }
   ensure_general_tables(h);
   if (fa.nodal) {
-    if (!h->shape_N.ptr) {
-      if (!h->geo.ptr)
-        fail("nodal field on a flat-table handle: the tables carry no shape values, give them with mimi_hip_domain_set_shape_values");
-      const int64_t total = (int64_t)h->n_el * h->n_q * h->n_dof;
-      h->shape_N.resize((size_t)total);
-      auto kernel = h->dim == 2 ? expand_shape_kernel<2> : expand_shape_kernel<3>;
-      launch(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, patch_dev(h, nullptr), h->shape_N.ptr);
-    }
+    ensure_shape_values(h);
     fa.N = h->shape_N.ptr;
   }
   const GeneralArgs a = general_args(h, c);

@@ -281,6 +281,29 @@ class NonlinearSolid(NonlinearBase):
         check(_capi.lib().mimi_hip_domain_nodal_field(self._handle(), fptr(u), field, fptr(sum), fptr(weight)))
         return sum
 
+    # -- mass, damping and body-force forms (mimi_hip.h) -------------------------------------------
+    def AddMass(self, density, values):
+        """values[(A,i),(B,i)] += density * sum_e sum_q w det N_a N_b over this handle's elements (VectorMassIntegrator);
+        the i != j entries of a node block are not touched.  numpy array or torch device tensor of nnz doubles."""
+        self._follow_torch(values)
+        check(_capi.lib().mimi_hip_domain_add_mass(self._handle(), float(density), fptr(values)))
+        return values
+
+    def AddDiffusion(self, viscosity, values):
+        """values[(A,i),(B,i)] += viscosity * sum_e sum_q w det dN_a/dX . dN_b/dX (VectorDiffusionIntegrator)"""
+        self._follow_torch(values)
+        check(_capi.lib().mimi_hip_domain_add_diffusion(self._handle(), float(viscosity), fptr(values)))
+        return values
+
+    def AddBodyForce(self, b, r):
+        """r[(A,i)] += b[i] * sum_e sum_q w det N_a (VectorDomainLFIntegrator); b: dim numbers"""
+        b = np.ascontiguousarray(np.asarray(b, dtype=np.float64).ravel())
+        if b.size != self._dim():
+            raise ValueError(f"body force must have {self._dim()} components, got {b.size}")
+        self._follow_torch(r)
+        check(_capi.lib().mimi_hip_domain_add_body_force(self._handle(), ptr(b), fptr(r)))
+        return r
+
     def HoldsGradientTables(self):
         """whether the handle holds per-point gradient tables (mimi_hip_domain_info(h, 8))"""
         return bool(_capi.lib().mimi_hip_domain_info(self._handle(), 8))

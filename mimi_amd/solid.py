@@ -21,6 +21,7 @@ NURBS numbering); meshes must be single-cell degree-1 descriptions with unit wei
 the refined control net is the cell's multilinear map at the Greville abscissae), which
 covers every mesh the reference's solver tests use.
 """
+import os
 import re
 
 import numpy as np
@@ -397,7 +398,23 @@ class NonlinearSolid(Solid):
         # mass (VectorMassIntegrator(rho), FormSystemMatrix(zero_dofs); :155-173), damping (:176-192:
         # VectorDiffusionIntegrator(viscosity): C_(a,i),(b,j) = d_ij nu int grad N_a . grad N_b, integrated with the same
         # rule as the mass matrix -- exact on affine patches; mfem's own default rule for this integrator cannot be read
-        # here and no reference fixture sets a viscosity: parity unpinned) and rhs (:221-283), in chunks of elements
+        # here and no reference fixture sets a viscosity: parity unpinned) and rhs (:221-283): on the device
+        # (_device_setup, once the integrator and the eliminations exist) unless the host pass is asked for with
+        # MIMI_HIP_HOST_SETUP=1 or rc.set_int("host_setup", 1)
+        self.host_setup_ = bool(rc.get_int("host_setup", 0)) or os.environ.get("MIMI_HIP_HOST_SETUP", "") == "1"
+        self._mass_host, self._visc_host = None, None
+        self.d_mass_, self.d_visc_ = None, None
+        self.host_nnz_arrays_ = 0                                    # host arrays of nnz doubles made since setup began
+        if self.host_setup_:
+            self._host_setup(patch, bc, rowptr, col, n)
+        # integrators (py_nonlinear_solid.cpp:197-218, 286-326)
+        q_order = rc.get_int("nonlinear_solid_quadrature_order", -1)
+        self.domain_ = self._make_domain(q_order)
+        self.domain_.SetTangentMode(self.tangent_mode)
+        self._finish_setup(patch, bc, rc, q_order)
+
+    def _host_setup(self, patch, bc, rowptr, col, n):
+        """mass, damping and right-hand side in numpy on the host"""
         viscosity = getattr(self.material, "viscosity", -1.0)
         mass, visc, rhs = _assemble_mass_viscosity_rhs(patch, self.pattern_u_.rowptr, self.material.density, viscosity,
                                                        bc.initial.body_force_)
@@ -415,26 +432,124 @@ class NonlinearSolid(Solid):
                 self.fold_.Add(None, None, visc, None, visc_f)
                 visc = visc_f
         self.mass_ = mass
+        self.host_nnz_arrays_ += 1 + (visc is not None)
         _eliminate_row_col(rowptr, col, self.mass_, self.dirichlet_)
         self.visc_ = visc
         if visc is not None:
             _eliminate_row_col(rowptr, col, self.visc_, self.dirichlet_)
         self.rhs_ = _load_vector(patch, self._faces, bc.initial.traction_ if self.fold_ is None else {}, rhs, self.dirichlet_)
-        # integrators (py_nonlinear_solid.cpp:197-218, 286-326)
-        q_order = rc.get_int("nonlinear_solid_quadrature_order", -1)
+
+    def _make_domain(self, q_order):
+        """the domain integrator of the patch with the rule of `q_order`"""
+        patch, dim = self.patch_, self._dim
         try:
-            self.domain_ = NonlinearSolidIntegrator("nonlinear_solid", self.material, self.pattern_u_, patch=patch,
-                                                    device=self.device, quadrature_order=q_order).Prepare()
+            return NonlinearSolidIntegrator("nonlinear_solid", self.material, self.pattern_u_, patch=patch,
+                                            device=self.device, quadrature_order=q_order).Prepare()
         except RuntimeError as exc:
             if "not a tensor product" not in str(exc):
                 raise
-            # NURBS weights that do not factorise: the reference's flat per-point tables (general kernels)
-            _, wd_t, conn_t, dN_dX = _element_tables(patch, q_order, with_gradients=True)
-            tables = dict(dim=dim, n_nodes=patch.n_nodes, dofs=conn_t.astype(np.int32), dN_dX=np.ascontiguousarray(dN_dX),
-                          weight_det=np.ascontiguousarray(wd_t))
-            self.domain_ = NonlinearSolidIntegrator("nonlinear_solid", self.material, self.pattern_u_, tables=tables,
-                                                    device=self.device).Prepare()
-        self.domain_.SetTangentMode(self.tangent_mode)
+        # NURBS weights that do not factorise: the reference's flat per-point tables (general kernels), with the shape
+        # values the mass and body-force forms need
+        N_t, wd_t, conn_t, dN_dX = _element_tables(patch, q_order, with_gradients=True)
+        tables = dict(dim=dim, n_nodes=patch.n_nodes, dofs=conn_t.astype(np.int32), dN_dX=np.ascontiguousarray(dN_dX),
+                      weight_det=np.ascontiguousarray(wd_t), N=np.ascontiguousarray(N_t))
+        return NonlinearSolidIntegrator("nonlinear_solid", self.material, self.pattern_u_, tables=tables,
+                                        device=self.device).Prepare()
+
+    def _forms_domain(self):
+        """(integrator, temporary) the mass, damping and body-force forms are assembled with: they use the default rule,
+        which is the domain integrator's unless nonlinear_solid_quadrature_order is set -- then a handle of its own, which
+        the caller drops"""
+        if self.runtime_communication.get_int("nonlinear_solid_quadrature_order", -1) < 0:
+            return self.domain_, False
+        return self._make_domain(-1), True
+
+    def _body_force_vector(self, forms):
+        """the body-force vector of the unwrapped patch, assembled on the device: n_vdofs doubles on the host"""
+        import torch
+        r_u = torch.zeros(self.patch_.n_vdofs, dtype=torch.float64, device=torch.device("cuda", self.device))
+        b = np.zeros(self._dim)
+        for comp, value in self.bc_.initial.body_force_.items():
+            b[comp] += value
+        if np.any(b != 0.0):
+            forms.AddBodyForce(b, r_u)
+        return r_u.cpu().numpy()
+
+    def _load_vector_folded(self, rhs):
+        """body force `rhs` (unwrapped, modified) + traction, folded, zero on the Dirichlet dofs: what _host_setup does"""
+        patch, bc = self.patch_, self.bc_
+        if self.fold_ is None:
+            return _load_vector(patch, self._faces, bc.initial.traction_, rhs, self.dirichlet_)
+        rhs = _load_vector(patch, self._faces, bc.initial.traction_, rhs, np.zeros(0, dtype=np.int64))
+        rhs_f = np.zeros(self.fold_.n_f_)
+        self.fold_.Add(rhs, rhs_f)
+        return _load_vector(patch, self._faces, {}, rhs_f, self.dirichlet_)
+
+    def _device_setup(self):
+        """mass, damping and body force assembled by the domain integrator's forms into zeroed device arrays on the unwrapped
+        pattern, folded (PeriodicFold.Add) and eliminated (LinearSolver.Eliminate: EliminateRowCol(DIAG_ONE)) there: no
+        array of nnz doubles exists on the host or crosses PCIe.  The traction stays on the host (face work)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        forms, temporary = self._forms_domain()
+
+        def assembled(add, factor):
+            a = torch.zeros(self.pattern_u_.nnz, dtype=torch.float64, device=dev)
+            add(factor, a)
+            if self.fold_ is not None:
+                a_f = torch.empty(self.pattern_.nnz, dtype=torch.float64, device=dev)
+                self.fold_.Add(None, None, a, None, a_f)
+                a = a_f
+            self.linear_.Eliminate(None, a)
+            return a
+
+        self.d_mass_ = assembled(forms.AddMass, self.material.density)
+        viscosity = getattr(self.material, "viscosity", -1.0)
+        self.d_visc_ = assembled(forms.AddDiffusion, viscosity) if viscosity > 0.0 else None
+        self.rhs_ = self._load_vector_folded(self._body_force_vector(forms))
+        if temporary:
+            forms.Synchronize()
+            del forms
+
+    # mass_ / visc_: the host copies of d_mass_ / d_visc_, downloaded on first read (the direct-solve route and _csr read
+    # them; the iterative route never does)
+    @property
+    def mass_(self):
+        if self._mass_host is None and self.d_mass_ is not None:
+            self._mass_host = self.d_mass_.cpu().numpy()
+            self.host_nnz_arrays_ += 1
+        return self._mass_host
+
+    @mass_.setter
+    def mass_(self, values):
+        self._mass_host = values
+
+    @property
+    def visc_(self):
+        if self._visc_host is None and self.d_visc_ is not None:
+            self._visc_host = self.d_visc_.cpu().numpy()
+            self.host_nnz_arrays_ += 1
+        return self._visc_host
+
+    @visc_.setter
+    def visc_(self, values):
+        self._visc_host = values
+
+    def set_body_force(self, dim, value):
+        """new body force in direction `dim` (after setup(); the counterpart of set_pressure): the body-force vector is
+        assembled again on the device and rhs_ rebuilt IN PLACE -- body force + traction, zero on the Dirichlet dofs --
+        so the array linear_form_view2("rhs") handed out stays the one in use; takes effect from the next solve"""
+        self.bc_.initial.body_force_[dim] = value
+        forms, temporary = self._forms_domain()
+        self.rhs_[:] = self._load_vector_folded(self._body_force_vector(forms))
+        if temporary:
+            forms.Synchronize()
+            del forms
+        self.has_rhs_ = True
+        self.d_rhs_.copy_(self._torch.from_numpy(self.rhs_))
+
+    def _finish_setup(self, patch, bc, rc, q_order):
+        dim = self._dim
         self.contacts_ = []
         for bid, body in bc.current.contact_.items():
             axis, side = self._faces[bid + 1]
@@ -461,6 +576,8 @@ class NonlinearSolid(Solid):
         # (mimi_amd/linear.py); else a sparse direct solve on the host (UMFPack in the reference, SuperLU here)
         self.linear_ = LinearSolver(self.pattern_, self.dirichlet_, device=self.device)
         self.use_iterative_solver_ = bool(rc.get_int("use_iterative_solver", 0))
+        if not self.host_setup_:
+            self._device_setup()
         self._to_device()
 
     def _folded_dofs(self, nodes, comp):
@@ -505,9 +622,11 @@ class NonlinearSolid(Solid):
         self._torch = torch
         dev = torch.device("cuda", self.device)
         f = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-        self.d_mass_, self.d_rhs_ = f(self.mass_), f(self.rhs_)
+        if self.host_setup_:
+            self.d_mass_ = f(self.mass_)
+            self.d_visc_ = f(self.visc_) if self.visc_ is not None else None
+        self.d_rhs_ = f(self.rhs_)
         self._rhs = self.d_rhs_           # what the residual subtracts (_update_rhs)
-        self.d_visc_ = f(self.visc_) if self.visc_ is not None else None
         self.d_jac_ = torch.zeros_like(self.d_mass_)
         self.d_dirichlet_ = torch.from_numpy(np.asarray(self.dirichlet_, dtype=np.int64)).to(dev)
         self.d_x_, self.d_v_ = f(self.x), f(self.x_dot)

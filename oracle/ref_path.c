@@ -698,7 +698,9 @@ static int j2log_stress(const oracle_material* m, int dim, double dt, int accumu
     w->plastic = 1;
     w->delta = delta;
     w->hprime = return_map_slope(&c, delta);
-    for (int i = 0; i < dd; ++i) Np[i] = 1.5 / q * s[i];
+    /* (q == 0 is reached only under delta_fixed = 0, when a point of the oracle tangent's stencil is a pure dilatation:
+     * s = 0 there and nothing is returned; the reference yields only with q > 0) */
+    for (int i = 0; i < dd; ++i) Np[i] = q > 0.0 ? 1.5 / q * s[i] : 0.0;
     for (int i = 0; i < dd; ++i) s[i] += -2.0 * m->G * delta * Np[i];
     if (accumulate) {
       double inc[9], ex[9], old[9];

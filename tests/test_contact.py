@@ -1,7 +1,10 @@
 """Contact integrator: oracle self-checks (CPU) and HIP-vs-oracle parity (GPU).
 
 No reference test exercises MortarContact and its closest-point query (splinepy) is absent, so parity with the
-reference's own numbers cannot be pinned.  What is pinned: the arithmetic downstream of the query by the oracle
+reference's own numbers cannot be pinned.  What is pinned: everything upstream of the gap function -- the face tables, their
+orientation, the quadrature, the nodal sums -- by the independent long-double face reference of tests/_face_reference.py, on
+every face of non-block patches (tests/test_faces_cpu.py for the oracle and the tables, tests/test_faces_gpu.py for the
+kernels); the arithmetic downstream of the query by the oracle
 (oracle/contact_path.c) and by the closed forms below (uniform and tilted penetration, objectivity of the tangent); the
 closest-point search of a rigid SPLINE body, in the kernels and in the oracle alike, by the long-double brute-force
 reference of tests/_closest_point.py (tests/test_spline_body_cpu.py, tests/test_contact_spline_gpu.py)."""

@@ -3,8 +3,9 @@
 numpy restatement of the iterative linear solver the reference configures when "use_iterative_solver" is set
 (src/mimi/py/py_nonlinear_solid.cpp:329-339): mfem::GMRESSolver (rel 1e-8, abs 1e-12, 300 iterations, m = 50) with an
 mfem::DSmoother (Jacobi, one sweep from zero) preconditioner.  MFEM is an absent, un-pinned submodule of the
-reference; this follows its published algorithm (mfem linalg/solvers.cpp, GMRESSolver::Mult; DSmoother::Mult) -- parity
-unpinned by any reference fixture."""
+reference; this follows its published algorithm (mfem linalg/solvers.cpp, GMRESSolver::Mult; DSmoother::Mult).
+gmres and cg are held, with equal iteration counts, to the 120-digit reference of tests/_krylov_reference.py, which is written
+from the definition of the methods (tests/test_krylov_reference_cpu.py)."""
 import numpy as np
 
 

@@ -1,0 +1,491 @@
+"""Shapes, inputs and bars of tests/test_domain_reference_{cpu,gpu}.py: the domain integrator against the long-double
+reference of tests/_domain_reference.py.  Every case is plain arrays (degrees, knots, control points, weights, order); the
+oracle's iga.Patch and the product's BSplinePatch are made from the same arrays.
+
+Cases, the smallest shapes at which each route of csrc/domain_dispatch.hpp / tensor_dispatch.hpp can still go wrong (none
+above 3100 points); the family is asserted after every call:
+  tensor_small         rep2d_p2, rep2d_p3, rep3d_p1 of tests/_patches.py; one element of degree 1 in 2-D
+  tensor_p2_two_phase  nonuni3d_p2; one element; col8_p2, a jittered Greville patch of 2 x 2 x 8 uniform spans whose columns
+                       launch_tensor_wgsym cuts into two segments of four (kernels_tensor_wgsym.hpp:298: 8 % 2 == 0 and
+                       8 / 2 >= 4, 8 / 4 < 4); the same patch through element boxes [0, 3) and [3, 8) that cut the columns
+                       (lengths 3 and 5: not split).  Neo-Hookean takes the symmetric-half kernel, every other law the
+                       nine-block kernel behind the material pre-pass, the residual-only call the column kernel.
+  tensor_p3_two_phase  nonuni3d_p3; one element; col5_p3, a jittered 2 x 1 x 5 patch: a column of 5 next to those of 1 and 4
+                       (the stand-in stores of element 0, the clamped prefetch of the last element, both tile parities)
+  general              rep3d_p2, rep3d_p3, mix2d_31, mix3d_231, mix3d_322; orders (rep3d_p2, 3) and (mix3d_221, 5); one
+                       flat-table 2-D block of degree 4
+  rational             tensor-product weights on a 3-D degree-2 patch (tensor route); weights that do not factorise through
+                       flat tables (general route) -- the patches of test_domain_gpu.py::test_tensor_product_nurbs_weights
+                       and ::test_rational_weights_general_path
+Flat tables (dofs, dN/dX, w det) are the reference's own, rounded to double; CSR patterns are the union of the element blocks
+found from the reference's values.
+
+Materials: neohook, stvk, j2 (the default law, _cases.JC_TEST) on every case; j2[PowerLaw], j2[JohnsonCookRate] (the rate
+term active at DT = 0.5) and j2linear on one case per family (EXTRA).  J2Simo and J2Log are out of scope: there is no
+long-double eigen-solver; they stay pinned at 50 digits under homogeneous deformation (tests/test_finite_strain_*.py) and
+against the oracle elsewhere.
+
+Inputs: displacements as _patches.inputs (u0 = synthetic_u(scale 0.03, seed) committed first for the stateful laws, the
+assemblies at u = synthetic_u(scale 0.02 h | 0.05 h, seed)), the seeds of the stateful laws chosen per case (SEEDS) by
+scanning on the reference until the conditions of `conditions` hold -- they are conditions on the inputs, asserted in
+tests/test_domain_reference_cpu.py, never relaxed."""
+import functools
+import types
+
+import numpy as np
+
+import _domain_reference as dr
+import _face_reference as fr
+import _patches
+import _radial_return as rr
+from _cases import synthetic_u
+
+LD = np.longdouble
+DT = _patches.DT
+GRAD_FACTOR = _patches.GRAD_FACTOR
+RHO, NU, B3 = 1.7, 0.3, np.array([0.4, -9.81, 2.5])     # the linear forms, as tests/test_linear_forms_gpu.py
+
+# bars (relative max-norm unless said otherwise)
+RESIDUAL_BAR, TANGENT_BAR, FORMS_BAR, SYMMETRY_BAR = 1e-12, 1e-11, 1e-13, 1e-12
+MARGIN = 0.125                                          # the oracle sits this far inside the bars (tests/test_faces_cpu.py)
+STATE_BAR = 2.0 * rr.SOLVER_XTOL                        # |delta - delta_exact| of a solver that stops at |d delta| < 1e-10
+
+
+def _greville(knots, p):
+    return np.array([knots[i + 1:i + p + 1].mean() for i in range(len(knots) - p - 1)])
+
+
+def _jittered(degrees, knots, jitter, seed):
+    """control points of _patches.greville_patch from the arrays alone"""
+    g = [_greville(np.asarray(k, dtype=np.float64), p) for k, p in zip(knots, degrees)]
+    ctrl = np.stack([gr.ravel(order="F") for gr in np.meshgrid(*g, indexing="ij")], axis=1)
+    return ctrl + jitter * np.random.default_rng(seed).standard_normal(ctrl.shape)
+
+
+def _uniform_case(degrees, spans, family, **kw):
+    return dict(degrees=degrees, inner=tuple(_patches.uniform(m) for m in spans), family=family, **kw)
+
+
+def _named(case, **kw):
+    degrees, inner, family = _patches.CASES[case]
+    return dict(degrees=degrees, inner=inner, family=kw.pop("family", family), **kw)
+
+
+CASES = {
+    "rep2d_p2": _named("rep2d_p2"), "rep2d_p3": _named("rep2d_p3"), "rep3d_p1": _named("rep3d_p1"),
+    "one2d_p1": _uniform_case((1, 1), (1, 1), "tensor_small"),
+    "nonuni3d_p2": _named("nonuni3d_p2"),
+    "one3d_p2": _uniform_case((2, 2, 2), (1, 1, 1), "tensor_p2_two_phase"),
+    "col8_p2": _uniform_case((2, 2, 2), (2, 2, 8), "tensor_p2_two_phase"),
+    "nonuni3d_p3": _named("nonuni3d_p3"),
+    "one3d_p3": _uniform_case((3, 3, 3), (1, 1, 1), "tensor_p3_two_phase"),
+    "col5_p3": _uniform_case((3, 3, 3), (2, 1, 5), "tensor_p3_two_phase"),
+    "rep3d_p2": _named("rep3d_p2"), "rep3d_p3": _named("rep3d_p3"), "mix2d_31": _named("mix2d_31"),
+    "mix3d_231": _named("mix3d_231"), "mix3d_322": _named("mix3d_322"),
+    "rep3d_p2_o3": _named("rep3d_p2", order=3), "mix3d_221_o5": _named("mix3d_221", order=5),
+    "flat2d_p4": _uniform_case((4, 4), (2, 2), "general", flat=True),
+    "nurbs_tp_p2": _uniform_case((2, 2, 2), (4, 3, 3), "tensor_p2_two_phase", weights="tensor", jitter=0.05, seed=5),
+    "nurbs_flat_p2": _uniform_case((2, 2, 2), (4, 3, 3), "general", weights="general", jitter=0.05, seed=21, flat=True),
+}
+# the element boxes of col8_p2: complementary, cutting every column
+BOXES = [([0, 0, 0], [2, 2, 3]), ([0, 0, 3], [2, 2, 8])]
+BOX_CASE = "col8_p2"
+BASE_MATERIALS = ("neohook", "stvk", "j2")
+EXTRA_MATERIALS = ("j2[PowerLaw]", "j2[JohnsonCookRate]", "j2linear")
+EXTRA = {"tensor_small": "rep2d_p3", "tensor_p2_two_phase": "col8_p2", "tensor_p3_two_phase": "col5_p3", "general": "mix3d_231"}
+PAIRS = [(c, m) for c in CASES for m in BASE_MATERIALS] + [(c, m) for c in EXTRA.values() for m in EXTRA_MATERIALS]
+# the linear forms: one case per family and both rational cases
+FORMS_CASES = ["rep2d_p2", "nonuni3d_p2", "col5_p3", "mix3d_231", "nurbs_tp_p2", "nurbs_flat_p2"]
+
+# (case, material) -> (seed of u0, seed of u): what the scan `scan_seeds` finds first (the seed of u0 from 7 upwards until the
+# commit satisfies `conditions`, then the seed of u from 20241008 upwards); pairs not listed use _patches' own (7, 20241008)
+SEEDS = {
+    ("one2d_p1", "j2"): (7, 20241009),   # plastic 0.44 / 0.11
+    ("nonuni3d_p2", "j2"): (13, 20241008),   # plastic 0.86 / 0.15
+    ("col8_p2", "j2"): (8, 20241009),   # plastic 0.70 / 0.17
+    ("nonuni3d_p3", "j2"): (34, 20241008),   # plastic 0.69 / 0.14
+    ("col5_p3", "j2"): (10, 20241008),   # plastic 0.77 / 0.33
+    ("rep3d_p2", "j2"): (21, 20241008),   # plastic 0.75 / 0.12
+    ("rep3d_p3", "j2"): (14, 20241008),   # plastic 0.66 / 0.22
+    ("mix2d_31", "j2"): (7, 20241009),   # plastic 0.44 / 0.12
+    ("mix3d_231", "j2"): (9, 20241012),   # plastic 0.75 / 0.26
+    ("mix3d_322", "j2"): (15, 20241010),   # plastic 0.75 / 0.28
+    ("rep3d_p2_o3", "j2"): (7, 20241009),   # plastic 0.78 / 0.07
+    ("nurbs_tp_p2", "j2"): (12, 20241008),   # plastic 0.64 / 0.23
+    ("nurbs_flat_p2", "j2"): (12, 20241008),   # plastic 0.65 / 0.22
+    ("col8_p2", "j2[JohnsonCookRate]"): (8, 20241009),   # plastic 0.70 / 0.17
+    ("col5_p3", "j2[JohnsonCookRate]"): (10, 20241008),   # plastic 0.77 / 0.33
+    ("mix3d_231", "j2[JohnsonCookRate]"): (9, 20241012),   # plastic 0.75 / 0.25
+}
+
+# Tangent of the plastic branch: not derivable (tests/test_closed_form_gpu.py, PLASTIC_TANGENT_BAR: a tangent taken at the
+# solver's own root differs from one at the exact root by |dA / d delta| x 1e-10), so MEASURED the project's way -- on the CPU,
+# on the oracle, against the reference's K v (three probe vectors), relative to max |K v|, never on the kernels; printed by
+# tests/test_domain_reference_cpu.py::test_j2_tangent_table.  Worst over the cases, per law (the Johnson-Cook figures come from
+# the points that have just yielded, where H' ~ eqps^(n - 1) is steep: col8_p2 3.1e-9, mix3d_231 1.4e-9, nurbs_tp_p2 1.2e-9,
+# every other case <= 5.4e-10; PowerLaw <= 8.0e-13 everywhere).  The bar of a law is 10 x its figure, capped at 1e-8, on top
+# of the rounding bar 1e-11.
+J2_TANGENT_MEASURED = {"j2": 3.1e-09, "j2[PowerLaw]": 8.0e-13, "j2[JohnsonCookRate]": 3.1e-09}
+J2_TANGENT_BAR = {k: min(1e-8, 10 * v) for k, v in J2_TANGENT_MEASURED.items()}
+
+
+def is_j2(matname):
+    return matname.startswith("j2") and matname != "j2linear"
+
+
+def law_of(matname):
+    """'j2[PowerLaw]' -> 'PowerLaw'; 'j2' -> None (the default law)"""
+    return matname[3:-1] if "[" in matname else None
+
+
+def reference_material(matname):
+    return dr.material("j2", law_of(matname)) if is_j2(matname) else dr.material(matname)
+
+
+def oracle_material(matname):
+    from _cases import oracle_material as om
+    return om("j2", law_of(matname)) if is_j2(matname) and law_of(matname) else om(matname)
+
+
+def product_material(matname):
+    from _cases import product_material as pm
+    return pm("j2", law_of(matname)) if is_j2(matname) and law_of(matname) else pm(matname)
+
+
+@functools.lru_cache(maxsize=None)
+def arrays(case):
+    """the plain arrays of a case; shared, never modified"""
+    c = CASES[case]
+    degrees = tuple(c["degrees"])
+    knots = [_patches.open_knots(p, k) for p, k in zip(degrees, c["inner"])]
+    ctrl = _jittered(degrees, knots, c.get("jitter", 0.04), c.get("seed", 1))
+    n_ctrl = [len(k) - p - 1 for k, p in zip(knots, degrees)]
+    weights = None
+    if c.get("weights") == "tensor":            # test_domain_gpu.py::test_tensor_product_nurbs_weights
+        rng = np.random.default_rng(5)
+        w1d = [1.0 + 0.4 * rng.uniform(-1, 1, n) for n in n_ctrl]
+        w = w1d[0]
+        for d in range(1, len(degrees)):
+            w = np.multiply.outer(w1d[d], w)
+        weights = 0.7 * w.ravel()
+    elif c.get("weights") == "general":         # ::test_rational_weights_general_path
+        weights = 1.0 + 0.3 * np.random.default_rng(21).uniform(-1, 1, int(np.prod(n_ctrl)))
+    for a in knots + [ctrl] + ([weights] if weights is not None else []):
+        a.setflags(write=False)
+    spans = [np.diff(np.unique(k)) for k in knots]
+    return types.SimpleNamespace(case=case, degrees=degrees, knots=knots, ctrl=ctrl, weights=weights, order=c.get("order", -1),
+                                 family=c["family"], flat=c.get("flat", False), dim=len(degrees), n_ctrl=n_ctrl,
+                                 n_nodes=int(np.prod(n_ctrl)), n_vdofs=int(np.prod(n_ctrl)) * len(degrees),
+                                 smallest_span=min(float(s.min()) for s in spans))
+
+
+def oracle_patch(case):
+    from oracle import iga
+    a = arrays(case)
+    return iga.Patch(list(a.degrees), a.knots, a.ctrl, a.weights)
+
+
+def product_patch(case):
+    import mimi_amd
+    a = arrays(case)
+    return mimi_amd.BSplinePatch(list(a.degrees), a.knots, a.ctrl, a.weights)
+
+
+def inputs(case, matname, seeds=None):
+    """(u0 of the commit, u of the assemblies), as _patches.inputs: scale 0.03 / (0.05 neo-Hookean and StVK, 0.02 the J2
+    laws) x the smallest knot span where that is below 1"""
+    a = arrays(case)
+    shim = types.SimpleNamespace(n_vdofs=a.n_vdofs, dim=a.dim, boundary_nodes=lambda axis, side: fr.face_node_ids(a.n_ctrl, axis, side))
+    s0, s = seeds or SEEDS.get((case, matname), (7, 20241008))
+    h = min(1.0, a.smallest_span)
+    scale = (0.05 if matname in ("neohook", "stvk") else 0.02) * h
+    return synthetic_u(shim, scale=_patches.COMMIT_SCALE, seed=s0), synthetic_u(shim, scale=scale, seed=s)
+
+
+def probes(case):
+    """the three vectors a tangent is applied to: random, smooth, supported on a single (interior, where there is one) node"""
+    a = arrays(case)
+    random = np.random.default_rng(5).standard_normal(a.n_vdofs)
+    smooth = np.stack([np.sin(0.7 * a.ctrl[:, (i + 1) % a.dim] + 0.3 * i) + 0.2 * a.ctrl[:, i] for i in range(a.dim)], axis=1).ravel()
+    single = np.zeros((a.n_nodes, a.dim))
+    mid = [n // 2 for n in a.n_ctrl]
+    node = 0
+    for d in reversed(range(a.dim)):
+        node = node * a.n_ctrl[d] + mid[d]
+    single[node] = [1.0, -0.5, 0.25][:a.dim]
+    return [random, smooth, single.ravel()]
+
+
+@functools.lru_cache(maxsize=None)
+def geometry(case):
+    a = arrays(case)
+    sp = dr.space(a.degrees, a.knots, a.weights, a.order)
+    return dr.geometry(sp, a.ctrl)
+
+
+@functools.lru_cache(maxsize=None)
+def pattern(case):
+    """(rowptr, col, conn) of the union of the element blocks, from the reference's values"""
+    out = dr.support_pattern(geometry(case).sp)
+    for x in out:
+        x.setflags(write=False)
+    return out
+
+
+def compute(case, matname, seeds=None):
+    """the reference of (case, material): commit at u0 (stateful laws), then residual and K v at u from the committed state"""
+    geo = geometry(case)
+    mat = reference_material(matname)
+    u0, u = inputs(case, matname, seeds)
+    out = types.SimpleNamespace(case=case, matname=matname, geo=geo, mat=mat, u0=u0, u=u, vectors=probes(case), commit=None, state=None)
+    if mat.stateful:
+        virgin = dr.virgin_state(mat, geo.sp.n_points, geo.sp.dim)
+        out.commit = dr.point_law(mat, dr.deformation_gradient(geo, u0), virgin, DT)
+        out.state = out.commit.new
+        out.state_before = dict(commit=virgin, assembly=out.state)
+    out.asm = dr.assemble(geo, mat, u, out.state, DT, out.vectors)
+    for v in (u0, u):
+        v.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def reference(case, matname):
+    """compute() with the seeds of SEEDS: computed once, shared among the tests, never modified"""
+    return compute(case, matname)
+
+
+def conditions(ref):
+    """the conditions on the inputs of a reference, as a list of the ones that FAIL (empty: all hold), and the figures:
+      det(dX/dxi) > 0 (asserted by dr.geometry) and det F > 0.25 at every point, for u0 and u;
+      10 - 90 % of the points plastic at the commit, at least 5 % plastic and 5 % elastic in the assembly;
+      no point where the law is discontinuous or kinked (tests/_radial_return.py): no virgin point under a Johnson-Cook law
+      with yield margin in (-1e-6 sigma_y, 0.1] (the 1e-13 switch jumps by ~0.03 there and the equation may have no root),
+      no point with |margin| < 1e-6 sigma_y otherwise, and for the rate laws no plastic point with
+      |delta / dt - eps0_dot| < 1e-6 eps0_dot;
+      and one more, found while pinning the oracle: no plastic point at which the reference's own ScalarSolve stops more than
+      SOLVER_XTOL from the root (`reference_solver`, its iteration followed in long double).  The 2 x SOLVER_XTOL bars assume
+      that the stop |d delta| < 1e-10 bounds the error; on the steep start of a Johnson-Cook curve it need not: at rep3d_p2
+      with the seeds (19, 20241020) a virgin point at margin 0.27 has delta = 2.66e-10, the bisection from the upper bound
+      reaches 8.5e-10, a Newton step from there lands at 7.8e-12, the next one is 4.7e-11 long and the solver stops at
+      5.5e-11 -- and so does the oracle, which follows it line by line."""
+    geo, mat = ref.geo, ref.mat
+    bad, fig = [], {}
+    fig["min_det"] = float(geo.det.min())
+    for name, u in (("u0", ref.u0), ("u", ref.u)):
+        if name == "u0" and not mat.stateful:
+            continue
+        dF = float(dr.det(dr.deformation_gradient(geo, u)).min())
+        fig[f"min_detF_{name}"] = dF
+        if not dF > 0.25:
+            bad.append(f"det F {dF} at {name}")
+    if not mat.stateful:
+        return bad, fig
+    sigma_y = mat.hardening.sigma_y if mat.name == "j2" else float(mat.sigma_y)
+    johnson_cook = mat.name == "j2" and mat.hardening.johnson_cook
+    s0, s1 = float(ref.commit.plastic.mean()), float(ref.asm.pt.plastic.mean())
+    fig["plastic_commit"], fig["plastic_assembly"] = s0, s1
+    if not 0.1 < s0 < 0.9:
+        bad.append(f"plastic share {s0} at the commit")
+    if not (s1 >= 0.05 and 1 - s1 >= 0.05):
+        bad.append(f"plastic share {s1} in the assembly")
+    fig["min_abs_margin"] = np.inf
+    for name, pt, eqps_before in (("commit", ref.commit, np.zeros(len(geo.det))), ("assembly", ref.asm.pt, ref.state.eqps)):
+        margin = np.asarray(pt.margin, dtype=np.float64)
+        virgin = np.asarray(eqps_before == 0)
+        fig["min_abs_margin"] = min(fig["min_abs_margin"], float(np.abs(margin).min()))
+        if johnson_cook and np.any(virgin & (margin > -1e-6 * sigma_y) & (margin <= 0.1)):
+            bad.append(f"a virgin point in the Johnson-Cook window at the {name}")
+        if np.any(np.abs(margin[~virgin if johnson_cook else slice(None)]) < 1e-6 * sigma_y):
+            bad.append(f"a point on the yield surface at the {name}")
+        if mat.name == "j2":
+            off = np.abs(reference_solver(mat.hardening, pt, eqps_before, ref.state_before[name]) - pt.delta)[np.asarray(pt.plastic)]
+            fig["solver_stop"] = max(fig.get("solver_stop", 0.0), float(off.max()))
+            if np.any(off > rr.SOLVER_XTOL):
+                bad.append(f"the reference's solver stops {float(off.max()):.2e} from the root at the {name}")
+        if mat.name == "j2" and mat.hardening.has_rate:
+            r0 = float(mat.hardening.a["eps0_dot"])
+            rate = np.asarray(pt.delta, dtype=np.float64)[np.asarray(pt.plastic)] / DT
+            fig["min_rate_gap"] = min(fig.get("min_rate_gap", np.inf), float(np.abs(rate - r0).min() / r0))
+            if np.any(np.abs(rate - r0) < 1e-6 * r0):
+                bad.append(f"a plastic point at the reference rate at the {name}")
+    return bad, fig
+
+
+def reference_solver(h, pt, eqps, state):
+    """what the reference's ScalarSolve (solvers/newton.hpp:53-169: Newton from 0, bisection where a step leaves the bracket
+    or does not halve the residual, stop at |dx| < 1e-10 or |R| < sigma_y 1e-10; its derivative holds the rate factor fixed,
+    material_hardening.hpp:69-71) returns for the scalar equation of every point of pt, followed in long double -- only to
+    see where it stops (`conditions`), never as an answer"""
+    G3 = 3 * dr.constants()[3]
+    q, dt = pt.q, LD(DT)
+    thermo = h.thermo(state.temperature)
+    xtol, rtol = LD(rr.SOLVER_XTOL), LD(h.sigma_y) * LD(1e-10)
+
+    def R(x):
+        fac = h.rate(x / dt) * thermo
+        return q - G3 * x - h.H(eqps + x) * fac, -G3 - h.dH(eqps + x) * fac
+
+    lower, upper = np.zeros_like(q), np.where(pt.plastic, (q - h.H(eqps) * thermo) / G3, LD(0))
+    fl, fh = R(lower)[0], R(upper)[0]
+    x = np.where(np.abs(fl) < xtol, lower, upper)
+    done = ~np.asarray(pt.plastic) | (np.abs(fl) < xtol) | (np.abs(fh) < xtol)
+    xl, xh = np.where(fl > 0, upper, lower), np.where(fl > 0, lower, upper)
+    x = np.where(done, x, LD(0))
+    dx = dx_old = np.abs(upper - lower)
+    f, df = R(x)
+    for _ in range(100):
+        bisect = ((x - xh) * df - f > 0) | ((x - xl) * df - f < 0) | (np.abs(2 * f) > np.abs(dx_old * df))
+        step = np.where(bisect, (xh - xl) / 2, f / df)
+        x = np.where(done, x, np.where(bisect, xl + step, x - step))
+        dx_old, dx = dx, step
+        f, df = R(x)
+        xl, xh = np.where(~done & (f < 0), x, xl), np.where(~done & ~(f < 0), x, xh)
+        done = done | (np.abs(dx) < xtol) | (np.abs(f) < rtol)
+        if done.all():
+            break
+    assert done.all(), "the reference's solver does not converge"
+    return np.where(pt.plastic, x, LD(0))
+
+
+def _trial_margins(geo64, mat, u, state):
+    """(yield margin of the trial state, det F, virgin) at every point, in doubles: the quick look of the scan"""
+    dNdX, dim = geo64
+    F = np.eye(dim) + np.einsum("Ai,qAJ->qiJ", u.reshape(-1, dim), dNdX)
+    n = len(F)
+    st = dr.virgin_state(mat, n, dim) if state is None else state
+    eps = 0.5 * (F + np.swapaxes(F, 1, 2)) - np.eye(dim) - np.asarray(st.plastic_strain, dtype=np.float64)
+    G = float(dr.constants()[3])
+    s = 2 * G * (eps - np.trace(eps, axis1=1, axis2=2)[:, None, None] / dim * np.eye(dim))
+    if mat.name == "j2":
+        h = mat.hardening
+        q = np.sqrt(1.5) * np.sqrt((s * s).sum(axis=(1, 2)))
+        margin = q - np.asarray(h.H(st.eqps) * h.thermo(st.temperature), dtype=np.float64)
+    else:
+        eta = s - np.asarray(st.beta, dtype=np.float64)
+        margin = np.sqrt(1.5) * np.sqrt((eta * eta).sum(axis=(1, 2))) - np.asarray(mat.sigma_y + mat.h_iso * st.eqps, dtype=np.float64)
+    return margin, np.linalg.det(F), np.asarray(st.eqps == 0)
+
+
+def _quick(geo64, mat, u, state, share):
+    """the conditions that need no return map, on the trial state in doubles (the scan's sieve; `conditions` decides)"""
+    margin, detF, virgin = _trial_margins(geo64, mat, u, state)
+    sigma_y = mat.hardening.sigma_y if mat.name == "j2" else float(mat.sigma_y)
+    s = float((margin > 0).mean())
+    if detF.min() <= 0.25 or not share[0] < s < share[1]:
+        return False
+    if mat.name == "j2" and mat.hardening.johnson_cook:
+        if np.any(virgin & (margin > -1e-6 * sigma_y) & (margin <= 0.1)):
+            return False
+        return not np.any(np.abs(margin[~virgin]) < 1e-6 * sigma_y)
+    return not np.any(np.abs(margin) < 1e-6 * sigma_y)
+
+
+def scan_seeds(case, matname, tries=20000):
+    """the seeds of SEEDS: the first seed 7 + k of u0 at which the commit satisfies the conditions, then the first seed
+    20241008 + k of u at which the whole of `conditions` holds"""
+    geo, mat = geometry(case), reference_material(matname)
+    geo64 = (np.asarray(geo.dNdX, dtype=np.float64), geo.sp.dim)
+    a = arrays(case)
+    for k0 in range(tries):
+        u0 = inputs(case, matname, (7 + k0, 0))[0]
+        if not _quick(geo64, mat, u0, None, (0.1, 0.9)):
+            continue
+        try:
+            virgin = dr.virgin_state(mat, geo.sp.n_points, geo.sp.dim)
+            pt = dr.point_law(mat, dr.deformation_gradient(geo, u0), virgin, DT)
+        except AssertionError:          # (the reference's own bracket check: a root that does not exist)
+            continue
+        state = pt.new
+        if mat.name == "j2" and np.any(np.abs(reference_solver(mat.hardening, pt, virgin.eqps, virgin) - pt.delta) > rr.SOLVER_XTOL):
+            continue
+        for k in range(200):
+            u = inputs(case, matname, (7 + k0, 20241008 + k))[1]
+            if not _quick(geo64, mat, u, state, (0.05, 0.95)):
+                continue
+            try:
+                bad, _ = conditions(compute(case, matname, (7 + k0, 20241008 + k)))
+            except AssertionError:
+                continue
+            if not bad:
+                return 7 + k0, 20241008 + k
+    raise RuntimeError(f"no seed of {tries} satisfies the conditions for {case} {matname}")
+
+
+# ---- bars of the J2 laws ---------------------------------------------------------------------------------------------------
+def residual_bar(ref, mask=None):
+    """per row (A, i): 1e-12 max |r|, and for the J2 laws with a solver the derived sum_q w det sum_J |dN_A/dX_J| stress_bar(q)
+    (tests/_radial_return.py) over the plastic points.  A point that was plastic at the commit carries the solver's 1e-10 in
+    its committed state into the trial stress of the assembly (2 G sqrt(3/2) 1e-10, the same bound), a point that is plastic in
+    the assembly adds its own: one stress_bar for either, two for both, as test_closed_form_gpu.py's two-step test."""
+    r = np.asarray(ref.asm.r if mask is None else dr.nodal(ref.geo, ref.asm.pt.P, mask), dtype=np.float64)
+    bar = np.full(r.size, RESIDUAL_BAR * np.abs(r).max())
+    if is_j2(ref.matname):
+        geo = ref.geo
+        count = np.asarray(ref.commit.plastic, dtype=np.float64) + np.asarray(ref.asm.pt.plastic, dtype=np.float64)
+        per_point = rr.stress_bar(np.asarray(ref.asm.pt.JFinvT_norm, dtype=np.float64)) * count
+        if mask is not None:
+            per_point = per_point * mask
+        row = np.einsum("q,qA->A", np.asarray(geo.wdet, dtype=np.float64) * per_point, np.abs(np.asarray(geo.dNdX, dtype=np.float64)).sum(axis=2))
+        bar = bar + np.repeat(row, geo.sp.dim)
+    return bar
+
+
+def tangent_bar(matname):
+    return TANGENT_BAR + J2_TANGENT_BAR.get(matname, 0.0)
+
+
+def state_bars(ref):
+    """absolute bars of the committed state per point: eqps, plastic strain (and back stress), temperature.  J2: from
+    |delta - delta_exact| <= 2 x SOLVER_XTOL: eqps that, plastic strain sqrt(3/2) x (|N_p| = sqrt(3/2)), temperature
+    chi q / (rho c) x.  J2Linear's return is closed-form: rounding only, 1e-12 of the largest entry."""
+    new = ref.commit.new
+    if ref.matname == "j2linear":
+        return dict(eqps=1e-12 * float(np.abs(new.eqps).max()), plastic_strain=1e-12 * float(np.abs(new.plastic_strain).max()),
+                    state2=1e-12 * float(np.abs(new.beta).max()))
+    th = ref.mat.hardening.thermal
+    heat = float(th["heat_fraction"] / th["specific_heat"]) * np.asarray(ref.commit.q, dtype=np.float64)
+    return dict(eqps=STATE_BAR, plastic_strain=np.sqrt(1.5) * STATE_BAR, temperature=heat * STATE_BAR)
+
+
+def f64(a):
+    return np.asarray(a, dtype=np.float64)
+
+
+def compare_state(ref, get, grid, label=""):
+    """the committed state of `get(name)` ([e, q] / [e, q, i + J dim]) against the reference's at grid[e, q]: sorted values
+    first (a misread layout then shows as a layout error, not a value error), then point by point.  Returns the worst
+    error / bar"""
+    new, bars = ref.commit.new, state_bars(ref)
+    n = len(new.eqps)
+    want = dict(eqps=f64(new.eqps), plastic_strain=f64(np.swapaxes(new.plastic_strain, 1, 2).reshape(n, -1)))
+    names = dict(eqps="accumulated_plastic_strain", plastic_strain="plastic_strain", temperature="temperature", state2="state2")
+    if ref.matname == "j2linear":
+        want["state2"] = f64(np.swapaxes(new.beta, 1, 2).reshape(n, -1))
+    else:
+        want["temperature"] = f64(new.temperature)
+    worst = 0.0
+    for key, w in want.items():
+        got = np.asarray(get(names[key]))
+        w = w[grid]
+        assert got.shape == w.shape, (key, got.shape, w.shape)
+        bar = bars[key][grid] if np.ndim(bars[key]) else bars[key]
+        flat_bar = np.max(bar)
+        assert np.all(np.abs(np.sort(got.ravel()) - np.sort(w.ravel())) <= flat_bar), f"{label} {key}: the VALUES differ"
+        err = np.abs(got - w) / (bar[..., None] if np.ndim(bar) and got.ndim == 3 else bar)
+        assert err.max() <= 1.0, f"{label} {key}: the values agree as a set but not point by point -- the LAYOUT differs ({err.max():.2e} of the bar)"
+        worst = max(worst, float(err.max()))
+    return worst
+
+
+@functools.lru_cache(maxsize=None)
+def flat_tables(case):
+    """the tables of mimi_hip_domain_create from the reference's values rounded to double: dofs[e, a] (ascending node ids),
+    dN_dX[e, q, J, a], weight_det[e, q], N[e, q, a], in the (element, point) layout"""
+    geo = geometry(case)
+    sp_, conn = geo.sp, pattern(case)[2]
+    grid = dr.layout(sp_)
+    pts = grid[:, :, None]
+    return dict(dim=sp_.dim, n_nodes=sp_.n_nodes, dofs=np.ascontiguousarray(conn),
+                dN_dX=np.ascontiguousarray(np.transpose(f64(geo.dNdX[pts, conn[:, None, :], :]), (0, 1, 3, 2))),
+                weight_det=np.ascontiguousarray(f64(geo.wdet[grid])), N=np.ascontiguousarray(f64(sp_.N[pts, conn[:, None, :]])))

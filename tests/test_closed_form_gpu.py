@@ -19,7 +19,11 @@ for both at full size.
 J2 BEYOND yield, for every hardening law (kinds "j2_plastic[<law>]"): the radial return reduces to one scalar equation,
 solved by bisection at 50 digits in tests/_radial_return.py -- no oracle and no kernel in that answer.  The residual bar is
 the one derived there from the reference solver's own stop (|d delta| < 1e-10); the commit kernels are pinned by the two-step
-form (test_j2_beyond_yield_two_steps); the tangent bar is PLASTIC_TANGENT_BAR below."""
+form (test_j2_beyond_yield_two_steps); the tangent bar is PLASTIC_TANGENT_BAR below.
+
+What a homogeneous deformation cannot see -- a point that reads another point's state, points permuted inside an element, a
+mis-weighted non-affine mode of the contraction, a curved or rational geometry map -- is checked with no oracle in the loop in
+tests/test_domain_reference_gpu.py, against the long-double element sum of tests/_domain_reference.py under inhomogeneous fields."""
 import numpy as np
 import pytest
 

@@ -1,0 +1,170 @@
+"""The domain kernels (kernels_tensor_small / _residual / _wgs / _wgsym / _2phase, tensor_p3.hip, kernels_general, kernels_forms)
+against the long-double reference of tests/_domain_reference.py under INHOMOGENEOUS fields -- no oracle in the loop.  Cases,
+inputs and bars: tests/_domain_cases.py; the reference itself and the inputs are checked without a GPU in
+tests/test_domain_reference_cpu.py.
+
+Per (case, material): DomainPostTimeAdvance(u0) where the law has state and State(...) per point (sorted values first, so that
+a misread layout shows as a layout error, then point by point through the (element, point) layout of include/mimi_hip.h);
+AddDomainResidual, then AddDomainResidualAndGrad twice, in accumulate form on random r0 / A0 with grad_factor 0.37: the
+residual increments entrywise, the increment of A times a random, a smooth and a single-node vector against the reference's
+K v row by row, and for the hyperelastic laws the symmetry of the increment (the symmetric-half kernel assumes it).  Every
+assembly asserts its kernel family.  Element boxes: each handle against the reference restricted to its parameter range, and
+their sum against the whole.  Linear forms: body force entrywise, mass and viscosity through the three vectors.
+
+Bars: residual 1e-12 and tangent 1e-11 of the largest reference entry; J2 residual per row the derived
+_domain_cases.residual_bar, J2 tangent + _domain_cases.J2_TANGENT_BAR (measured on the CPU on the oracle, never here), J2 state
+2 x SOLVER_XTOL (eqps), sqrt(3/2) x (plastic strain), chi q / (rho c) x (temperature); linear forms 1e-13; symmetry 1e-12.
+
+Measured on the MI355X (worst per family; test_report prints this table): residual relative to max |r| (and as a share of
+its row bar), K v relative to max |K v|, asymmetry, state as a share of its bar
+  family               neo-Hookean                StVK                       J2Linear                  J2 (all three laws)
+  tensor_small         1.3e-15 (1.4e-3), 3.2e-15  1.1e-15 (1.1e-3), 3.7e-15  8.3e-16, 1.6e-15, 1.1e-3  1.6e-11 (1.2e-2), 1.5e-10, state 0.12
+  tensor_p2_two_phase  2.0e-15 (2.0e-3), 3.7e-15  1.9e-15 (2.0e-3), 3.0e-15  8.6e-16, 2.3e-15, 3.8e-3  2.6e-11 (4.3e-3), 3.1e-9,  state 0.37
+  tensor_p3_two_phase  2.3e-15 (2.3e-3), 4.0e-15  2.1e-15 (2.1e-3), 5.3e-15  8.9e-16, 1.8e-15, 2.7e-3  1.8e-11 (2.3e-3), 1.8e-11, state 0.40
+  general              1.4e-15 (1.4e-3), 4.8e-15  1.3e-15 (1.3e-3), 5.9e-15  7.9e-16, 2.6e-15, 1.9e-3  2.0e-11 (1.9e-3), 1.4e-9,  state 0.41
+  asymmetry of the hyperelastic increments <= 7.3e-16 (bar 1e-12); the J2 tangent figures are the oracle's own to two digits
+  (_domain_cases.J2_TANGENT_MEASURED: the solver's root, not rounding), bar 1e-8 (Johnson-Cook laws) and 1.8e-11 (PowerLaw)
+  linear forms         body force <= 1.1e-15, mass <= 2.3e-15, viscosity <= 9.7e-15 (nonuni3d_p2), bar 1e-13
+The whole module takes 12 s."""
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+import _domain_cases as dc
+import _domain_reference as dr
+from _domain_cases import DT, GRAD_FACTOR, f64
+
+pytestmark = pytest.mark.gpu
+
+WORST = {}          # (family, material class) -> {figure: worst}, for test_report
+
+
+def note(family, matname, **fig):
+    cls = "j2" if dc.is_j2(matname) else matname
+    w = WORST.setdefault((family, cls), {})
+    for k, v in fig.items():
+        w[k] = max(w.get(k, 0.0), float(v))
+
+
+def relmax(a, b):
+    return float(np.abs(f64(a) - f64(b)).max() / max(np.abs(f64(b)).max(), 1e-300))
+
+
+def handle(case, matname, element_box=None):
+    from mimi_amd.integrators import CSRPattern, NonlinearSolid
+    a = dc.arrays(case)
+    rowptr, col, _ = dc.pattern(case)
+    pattern = CSRPattern(np.array(rowptr, dtype=np.int64), np.array(col, dtype=np.int32), len(col))
+    if a.flat:
+        assert element_box is None
+        G = NonlinearSolid("domain", dc.product_material(matname), pattern, tables=dict(dc.flat_tables(case))).Prepare()
+    else:
+        G = NonlinearSolid("domain", dc.product_material(matname), pattern, patch=dc.product_patch(case),
+                           quadrature_order=a.order, element_box=element_box).Prepare()
+    G.dt_ = DT
+    assert G.path_ == (0 if a.family == "general" else 1)
+    return G
+
+
+def csr(case, values):
+    rowptr, col, _ = dc.pattern(case)
+    n = len(rowptr) - 1
+    return sp.csr_matrix((values, col, rowptr), shape=(n, n))
+
+
+def check_assemblies(G, ref, family, label, mask=None):
+    """the three assemblies in accumulate form against the reference (restricted to the points of `mask`); returns the
+    increments (r, A) of the tangent call"""
+    case, matname, geo = ref.case, ref.matname, ref.geo
+    want_r = f64(ref.asm.r if mask is None else dr.nodal(geo, ref.asm.pt.P, mask))
+    want_Kv = [f64(k) if mask is None else f64(dr.nodal(geo, dP, mask)) for k, dP in zip(ref.asm.Kv, ref.asm.pt.dP)]
+    bar_r = dc.residual_bar(ref, mask)
+    n, nnz = want_r.size, len(dc.pattern(case)[1])
+    r0 = np.random.default_rng(3).standard_normal(n)
+    A0 = np.random.default_rng(4).standard_normal(nnz)
+    r_g = r0.copy()
+    G.AddDomainResidual(ref.u, r_g)
+    assert G.LastKernelFamily() == family
+    fig = dict(residual_only=(np.abs((r_g - r0) - want_r) / bar_r).max())
+    for k in range(2):
+        r_g, A_g = r0.copy(), A0.copy()
+        G.AddDomainResidualAndGrad(ref.u, GRAD_FACTOR, r_g, A_g)
+        assert G.LastKernelFamily() == family
+        dr_, dA = r_g - r0, A_g - A0
+        fig["residual"] = max(fig.get("residual", 0.0), (np.abs(dr_ - want_r) / bar_r).max())
+        K = csr(case, dA)
+        for v, Kv in zip(ref.vectors, want_Kv):
+            fig["tangent"] = max(fig.get("tangent", 0.0), relmax(K @ v, GRAD_FACTOR * Kv))
+        if matname in ("neohook", "stvk"):
+            fig["symmetry"] = max(fig.get("symmetry", 0.0), abs(K - K.T).max() / np.abs(dA).max())
+    print(f"{label} {matname} [{family}]: residual-only {fig['residual_only']:.2e} and residual {fig['residual']:.2e} of the row bar "
+          f"(relative {relmax(dr_, want_r):.2e}), tangent {fig['tangent']:.2e} (bar {dc.tangent_bar(matname):.2e})"
+          + (f", asymmetry {fig['symmetry']:.2e}" if "symmetry" in fig else ""))
+    note(family, matname, relative_residual=relmax(dr_, want_r), **fig)
+    assert fig["residual_only"] <= 1.0 and fig["residual"] <= 1.0
+    assert fig["tangent"] <= dc.tangent_bar(matname)
+    assert fig.get("symmetry", 0.0) <= dc.SYMMETRY_BAR
+    return dr_, dA
+
+
+# ---- residual, tangent and committed state ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("case,matname", dc.PAIRS, ids=lambda v: v)
+def test_kernels_against_the_reference(case, matname):
+    ref = dc.reference(case, matname)
+    family = dc.arrays(case).family
+    G = handle(case, matname)
+    grid = dr.layout(ref.geo.sp)
+    assert (G.n_elements_, G.n_quad_) == grid.shape
+    if ref.mat.stateful:
+        G.DomainPostTimeAdvance(ref.u0)           # (a commit records no family: mimi_hip_domain_info(h, 7) is the last ASSEMBLY's)
+        note(family, matname, state=dc.compare_state(ref, G.State, grid, f"{case} {matname}"))
+    check_assemblies(G, ref, family, case)
+
+
+# ---- element boxes ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("matname", ["neohook", "stvk", "j2"])
+def test_element_boxes_match_their_parameter_range(matname):
+    case = dc.BOX_CASE
+    ref = dc.reference(case, matname)
+    family = dc.arrays(case).family
+    r_sum, A_sum = 0.0, 0.0
+    for begin, end in dc.BOXES:
+        G = handle(case, matname, element_box=(begin, end))
+        grid = dr.layout(ref.geo.sp, begin, end)
+        assert (G.n_elements_, G.n_quad_) == grid.shape
+        if ref.mat.stateful:
+            G.DomainPostTimeAdvance(ref.u0)
+            dc.compare_state(ref, G.State, grid, f"{case} box {begin}-{end} {matname}")
+        r, A = check_assemblies(G, ref, family, f"{case} box {begin}-{end}", mask=dr.in_box(ref.geo.sp, begin, end))
+        r_sum, A_sum = r_sum + r, A_sum + A
+    assert (np.abs(r_sum - f64(ref.asm.r)) / dc.residual_bar(ref)).max() <= 1.0
+    K = csr(case, A_sum)
+    for v, Kv in zip(ref.vectors, ref.asm.Kv):
+        assert relmax(K @ v, GRAD_FACTOR * f64(Kv)) <= dc.tangent_bar(matname)
+
+
+# ---- mass, viscosity and body force ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", dc.FORMS_CASES)
+def test_linear_forms_against_the_reference(case):
+    geo = dc.geometry(case)
+    a = dc.arrays(case)
+    G = handle(case, "neohook")
+    nnz = len(dc.pattern(case)[1])
+    b = dc.B3[:a.dim]
+    M = csr(case, G.AddMass(dc.RHO, np.zeros(nnz)))
+    C = csr(case, G.AddDiffusion(dc.NU, np.zeros(nnz)))
+    f = np.zeros(a.n_vdofs)
+    G.AddBodyForce(b, f)
+    fig = dict(body=relmax(f, dr.body_force(geo, b)), mass=0.0, viscosity=0.0)
+    for v in dc.probes(case):
+        fig["mass"] = max(fig["mass"], relmax(M @ v, dr.mass_times(geo, dc.RHO, v)))
+        fig["viscosity"] = max(fig["viscosity"], relmax(C @ v, dr.diffusion_times(geo, dc.NU, v)))
+    print(f"{case} [{a.family}]: " + ", ".join(f"{k} {v:.2e}" for k, v in fig.items()))
+    note(a.family, "forms", **fig)
+    assert max(fig.values()) <= dc.FORMS_BAR
+
+
+def test_report():
+    """the worst figures of this session per family and material class (what the module docstring records)"""
+    for (family, cls), fig in sorted(WORST.items()):
+        print(f"  {family:20s} {cls:9s} " + ", ".join(f"{k} {v:.1e}" for k, v in fig.items()))

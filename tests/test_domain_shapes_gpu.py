@@ -1,7 +1,9 @@
 """The domain integrator (through the C ABI) on patches that are not Patch.block -- non-uniform knots, repeated interior knots,
 a different degree per axis, quadrature orders other than the default -- and on flat tables of 25, 36 and 64 nodes per
 element, against the oracle on the same inputs (tests/_patches.py; the inputs themselves are vetted without a GPU in
-tests/test_domain_shapes_cpu.py).  Every assembly asserts the kernel family it ran on.
+tests/test_domain_shapes_cpu.py).  Every assembly asserts the kernel family it ran on.  The oracle is not the only reference
+under these inhomogeneous fields: tests/test_domain_reference_gpu.py holds the same kernel families to the long-double element
+sum of tests/_domain_reference.py, and tests/test_domain_reference_cpu.py pins the oracle to it.
 
 Bars, those of test_domain_gpu.py / test_materials_gpu.py / test_fields_gpu.py: residual 1e-12 relative (max-norm); analytic
 tangent 1e-11 (1e-10 for the record materials); reference-FD tangent 5e-4; committed state rtol 1e-9, atol 1e-13; temperature

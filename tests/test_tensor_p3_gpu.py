@@ -1,6 +1,8 @@
 """Parity of the sum-factorised two-phase kernels for 3-D p = 3 patches (mimi_amd/csrc/tensor_p3.hip; BASELINE
 configuration 3 at oracle size) against the oracle, through the C ABI.  Bars as tests/test_domain_gpu.py:
-residual <= 1e-12, analytic tangent vs the oracle's exact tangent <= 1e-11 (relative, max-norm), J2 state 1e-9."""
+residual <= 1e-12, analytic tangent vs the oracle's exact tangent <= 1e-11 (relative, max-norm), J2 state 1e-9.
+The same kernels against a long-double reference that shares nothing with the oracle, under inhomogeneous fields (columns of 1, 4
+and 5 elements included): tests/test_domain_reference_gpu.py; the oracle against that reference: tests/test_domain_reference_cpu.py."""
 import numpy as np
 import pytest
 

@@ -489,16 +489,34 @@ int mimi_hip_linear_add_mult(mimi_hip_linear_t h, const double* A_values, const 
 /* The reference's iterative linear solver (py/py_nonlinear_solid.cpp:329-339: mfem::GMRESSolver + mfem::DSmoother,
  * rel 1e-8, abs 1e-12, 300 iterations; kdim <= 0 = mfem's default 50): x = 0 start, left-preconditioned restarted
  * GMRES, modified Gram-Schmidt, stops when the preconditioned residual estimate <= max(rel_tol * ||M b||, abs_tol).
- * use_jacobi = 0 runs it unpreconditioned.  A_values / b / x host or device. */
+ * preconditioner: 1 = the reference's Jacobi, 0 = none, 2 = the Kronecker operator below (needs set_kronecker and
+ * set_kronecker_coefficients first; an error otherwise).  A_values / b / x host or device. */
 int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol,
-                          double abs_tol, int max_iter, int kdim, int use_jacobi, int32_t* iterations,
+                          double abs_tol, int max_iter, int kdim, int preconditioner, int32_t* iterations,
                           double* final_norm, int32_t* converged);
 /* The mass solve of operators::NonlinearSolid (operators/nonlinear_solid.cpp:39-50,155; .hpp:38-42: mfem::CGSolver +
  * mfem::DSmoother, rel 1e-8, abs 1e-12, 1000 iterations): x = 0 start, preconditioned conjugate gradients, stops when
  * (r, M r) <= max(rel_tol^2 (r0, M r0), abs_tol^2); final_norm = sqrt of that product. */
 int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol,
-                       double abs_tol, int max_iter, int use_jacobi, int32_t* iterations, double* final_norm,
+                       double abs_tol, int max_iter, int preconditioner, int32_t* iterations, double* final_norm,
                        int32_t* converged);
+/* Fast-diagonalisation (Kronecker) preconditioner for systems on ONE tensor-product patch in the byVDIM numbering, dof
+ * ((i2 n1 + i1) n0 + i0) dim + c (no reference counterpart: the reference has Jacobi only).  Per component c
+ *   P_c = mass (x)_d M_d + sum_d stiff[c][d] K_d (x) (M of the other axes),
+ * given by the generalised eigenpairs of the 1-D matrices, K_d U_cd = M_d U_cd diag(lambda_cd), U_cd^T M_d U_cd = I:
+ *   z = P^-1 r = (U_c0 (x) U_c1 (x) U_c2) D_c (U_c0 (x) U_c1 (x) U_c2)^T r,  D_c = 1 / (mass + sum_d stiff[c][d] lambda_cd[i_d]),
+ * then z[ess] = r[ess] on the handle's essential dofs (what EliminateRowCol(DIAG_ONE) leaves of those rows).
+ * n_dir[dim]: nodes per axis, prod n_dir * dim must be the handle's n.  U: the matrices U_cd, n_d x n_d row-major,
+ * concatenated over [component][axis]; lambda: the vectors lambda_cd concatenated the same way.  A 1-D function that is
+ * removed from a component (a Dirichlet face) has a zero row and column in U_cd and a NEGATIVE lambda, which makes the
+ * scaling zero there.  Host or device arrays (copied). */
+int mimi_hip_linear_set_kronecker(mimi_hip_linear_t h, int32_t dim, const int32_t* n_dir, const double* U,
+                                  const double* lambda);
+/* mass and stiff[c * dim + d] (host) of the operator above; the scaling array is rebuilt on the device */
+int mimi_hip_linear_set_kronecker_coefficients(mimi_hip_linear_t h, double mass_coef, const double* stiff_coef);
+/* z = M r with the preconditioner the solvers apply: kind 1 Jacobi (z = r / diag(A); needs A_values), 2 Kronecker
+ * (A_values may be NULL).  Host or device arrays; z == r is allowed. */
+int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const double* A_values, const double* r, double* z);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,7 @@ EXPORTS = [
     "mimi_hip_linear_create", "mimi_hip_linear_destroy", "mimi_hip_linear_set_stream", "mimi_hip_linear_info", "mimi_hip_linear_eliminate",
     "mimi_hip_linear_add_mult",
     "mimi_hip_linear_gmres", "mimi_hip_linear_cg",
+    "mimi_hip_linear_set_kronecker", "mimi_hip_linear_set_kronecker_coefficients", "mimi_hip_linear_apply_preconditioner",
     "mimi_hip_domain_integrate", "mimi_hip_domain_gather",
     "mimi_hip_rows_zero", "mimi_hip_rows_pack", "mimi_hip_rows_unpack_add",
     "mimi_hip_entries_pack", "mimi_hip_entries_unpack_add",
@@ -236,6 +237,9 @@ def lib():
                                         C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mimi_hip_linear_cg.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mimi_hip_linear_set_kronecker.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mimi_hip_linear_set_kronecker_coefficients.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+    L.mimi_hip_linear_apply_preconditioner.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

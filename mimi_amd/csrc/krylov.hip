@@ -8,6 +8,8 @@
 //       submodule of the reference; what is restated here is its published algorithm (mfem linalg/solvers.cpp,
 //       GMRESSolver::Mult): left-preconditioned restarted GMRES(m = 50), modified Gram-Schmidt, Givens rotations,
 //       convergence on the preconditioned residual  |s_{i+1}| <= max(rel_tol * ||M r_0||, abs_tol).
+//   Beyond the reference: M may be the Kronecker (fast-diagonalisation) operator of kronecker.hpp instead of Jacobi
+//       (preconditioner id 2 of both solvers); ids 0 and 1 run the kernels and give the bits they always did.
 //
 // Everything vector-sized stays in HBM; per Arnoldi step the host sees one Hessenberg column.  Reductions are
 // deterministic: a fixed grid writes per-block partial sums, every consumer adds them in the same order.
@@ -21,6 +23,7 @@
 
 #include "../../include/mimi_hip.h"
 #include "common.hpp"
+#include "kronecker.hpp"
 
 namespace mimi_hip {
 
@@ -345,6 +348,7 @@ struct mimi_hip_linear_s : StreamHandle {
   bool nodecol = false;   // ... and, g = 3, the list is made of node triples: `ncol` holds the nodes (kr_nodecol_kernel)
   DeviceBuffer<int32_t> ncol;
   DeviceBuffer<double> dinv, V, w, r, partials, totals, ycoef, stage_val, stage_b, stage_x;
+  Kronecker kron;         // mimi_hip_linear_set_kronecker: preconditioner id 2
   int* status_dev = nullptr;
   double* column_host[2] = {nullptr, nullptr};   // pinned: the Hessenberg column of the step before last and of the last one
   hipEvent_t column_ready[2] = {nullptr, nullptr};
@@ -384,6 +388,30 @@ void spmv(mimi_hip_linear_s* h, const double* val, const double* x, const double
     hipLaunchKernelGGL((kr_spmv_kernel<1, false>), dim3((unsigned)((h->n + 3) / 4)), dim3(256), 0, h->stream, h->n, h->rowptr, h->col,
                        val, x, b, dinv, y);
   MH_HIP(hipGetLastError());
+}
+
+// the preconditioner ids of mimi_hip_linear_gmres / _cg / _apply_preconditioner
+enum { PRECOND_NONE = 0, PRECOND_JACOBI = 1, PRECOND_KRONECKER = 2 };
+
+void check_preconditioner(const mimi_hip_linear_s* h, int id) {
+  if (id < PRECOND_NONE || id > PRECOND_KRONECKER) fail("unknown preconditioner id %d (0 none, 1 Jacobi, 2 Kronecker)", id);
+  if (id != PRECOND_KRONECKER) return;
+  if (!h->kron.set) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker first");
+  if (!h->kron.have_coefficients) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker_coefficients first");
+}
+
+// z = P^-1 r, z[ess] = r[ess]  (z == r allowed)
+void kron_apply(mimi_hip_linear_s* h, const double* r, double* z) {
+  h->kron.apply(r, z, h->n_ess > 0 ? h->is_ess.ptr : nullptr, h->stream);
+}
+
+// 1 / diag(A) (mfem::DSmoother) into the handle's dinv
+const double* jacobi_diagonal(mimi_hip_linear_s* h, const double* val) {
+  h->dinv.resize((size_t)h->n);
+  hipLaunchKernelGGL(kr_diag_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->n, h->rowptr, h->diag_pos.ptr, val,
+                     h->dinv.ptr);
+  MH_HIP(hipGetLastError());
+  return h->dinv.ptr;
 }
 
 }  // namespace
@@ -525,9 +553,10 @@ int mimi_hip_linear_add_mult(mimi_hip_linear_t h, const double* A_values, const 
 }
 
 int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol, double abs_tol,
-                          int max_iter, int kdim, int use_jacobi, int32_t* iterations, double* final_norm, int32_t* converged) {
+                          int max_iter, int kdim, int preconditioner, int32_t* iterations, double* final_norm, int32_t* converged) {
   return guarded([&] {
     if (!h || !A_values || !b || !x) fail("null argument");
+    check_preconditioner(h, preconditioner);
     if (kdim < 1) kdim = 50;   // mfem::GMRESSolver default m
     MH_HIP(hipSetDevice(h->device));
     const int64_t n = h->n;
@@ -542,14 +571,9 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
     h->totals.resize((size_t)(kdim + 2));
     h->ycoef.resize((size_t)kdim);
     h->reserve_columns(kdim + 2);
-    const double* dinv = nullptr;
-    if (use_jacobi) {
-      h->dinv.resize((size_t)n);
-      hipLaunchKernelGGL(kr_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, h->rowptr, h->diag_pos.ptr, mA.dev,
-                         h->dinv.ptr);
-      MH_HIP(hipGetLastError());
-      dinv = h->dinv.ptr;
-    }
+    // Jacobi is fused into the products (dinv); the Kronecker operator is applied in place behind a plain product
+    const double* dinv = preconditioner == PRECOND_JACOBI ? jacobi_diagonal(h, mA.dev) : nullptr;
+    const bool kronecker = preconditioner == PRECOND_KRONECKER;
     double* V = h->V.ptr;
     double* w = h->w.ptr;
     double* r = h->r.ptr;
@@ -591,6 +615,7 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
     {
       // r = M (b - A x) with x = 0
       spmv(h, mA.dev, mx.dev, mb.dev, dinv, r);
+      if (kronecker) kron_apply(h, r, r);
     }
     double beta = norm_of(r);
     double goal = std::fmax(rel_tol * beta, abs_tol);
@@ -605,6 +630,7 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
     // launched ahead is simply not used (the update reads v_0 .. v_i only).
     auto launch_step = [&](int i) {
       spmv(h, mA.dev, V + (int64_t)i * n, nullptr, dinv, w);
+      if (kronecker) kron_apply(h, w, w);
       for (int k = 0; k <= i + 1; ++k) {
         const double* v_prev = k > 0 ? V + (int64_t)(k - 1) * n : nullptr;
         const double* p_prev = k > 0 ? part + (int64_t)(k - 1) * KR_BLOCKS : nullptr;
@@ -669,6 +695,7 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
       update(i);
       // r = M (b - A x)
       spmv(h, mA.dev, mx.dev, mb.dev, dinv, r);
+      if (kronecker) kron_apply(h, r, r);
       beta = norm_of(r);
       if (beta <= goal) {
         finish(j - 1, beta, true);
@@ -683,9 +710,10 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
  * 39-50, .hpp:38-42: rel 1e-8, abs 1e-12, 1000 iterations, iterative_mode false): preconditioned conjugate gradients,
  * stops when (r, M r) <= max(rel_tol^2 (r0, M r0), abs_tol^2)  (mfem linalg/solvers.cpp, CGSolver::Mult) */
 int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol, double abs_tol,
-                       int max_iter, int use_jacobi, int32_t* iterations, double* final_norm, int32_t* converged) {
+                       int max_iter, int preconditioner, int32_t* iterations, double* final_norm, int32_t* converged) {
   return guarded([&] {
     if (!h || !A_values || !b || !x) fail("null argument");
+    check_preconditioner(h, preconditioner);
     MH_HIP(hipSetDevice(h->device));
     const int64_t n = h->n;
     hipStream_t s = h->stream;
@@ -696,18 +724,23 @@ int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double
     h->r.resize((size_t)n);
     h->partials.resize((size_t)2 * KR_BLOCKS);
     h->totals.resize(2);
-    const double* dinv = nullptr;
-    if (use_jacobi) {
-      h->dinv.resize((size_t)n);
-      hipLaunchKernelGGL(kr_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, h->rowptr, h->diag_pos.ptr, mA.dev,
-                         h->dinv.ptr);
-      dinv = h->dinv.ptr;
-    }
+    const double* dinv = preconditioner == PRECOND_JACOBI ? jacobi_diagonal(h, mA.dev) : nullptr;
+    const bool kronecker = preconditioner == PRECOND_KRONECKER;
     double* d = h->V.ptr;
     double* z = d + n;
     double* q = z + n;
     double* r = h->r.ptr;
     double* part = h->partials.ptr;
+    // z = M r and the partial sums of r . z
+    auto precondition = [&] {
+      if (kronecker) {
+        kron_apply(h, r, z);
+        hipLaunchKernelGGL(kr_mgs_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, z, (const double*)nullptr, (const double*)nullptr,
+                           (const double*)r, part);
+      } else {
+        hipLaunchKernelGGL(kr_cg_precond_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, r, dinv, z, part);
+      }
+    };
     auto total_of = [&]() -> double {
       hipLaunchKernelGGL(kr_totals_kernel, dim3(1), dim3(KR_THREADS), 0, s, part, h->totals.ptr);
       MH_HIP(hipGetLastError());
@@ -726,7 +759,7 @@ int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double
     // x = 0, r = b, z = M r, d = z
     MH_HIP(hipMemsetAsync(mx.dev, 0, sizeof(double) * n, s));
     MH_HIP(hipMemcpyAsync(r, mb.dev, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(kr_cg_precond_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, r, dinv, z, part);
+    precondition();
     MH_HIP(hipMemcpyAsync(d, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
     double nom = total_of();
     const double r0 = std::fmax(nom * rel_tol * rel_tol, abs_tol * abs_tol);
@@ -746,7 +779,7 @@ int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double
     for (;; ++it) {
       const double alpha = nom / den;
       hipLaunchKernelGGL(kr_cg_update_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, alpha, d, q, mx.dev, r);
-      hipLaunchKernelGGL(kr_cg_precond_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, r, dinv, z, part);
+      precondition();
       const double betanom = total_of();
       if (betanom <= r0) {
         finish(it, betanom, true);
@@ -768,6 +801,62 @@ int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double
       }
       nom = betanom;
     }
+  });
+}
+
+int mimi_hip_linear_set_kronecker(mimi_hip_linear_t h, int32_t dim, const int32_t* n_dir, const double* U, const double* lambda) {
+  return guarded([&] {
+    if (!h || !n_dir || !U || !lambda) fail("null argument");
+    if (dim != 2 && dim != 3) fail("Kronecker preconditioner: dim %d (2 or 3)", dim);
+    int64_t n = dim;
+    for (int d = 0; d < dim; ++d) {
+      if (n_dir[d] < 1) fail("Kronecker preconditioner: %d nodes along axis %d", n_dir[d], d);
+      n *= n_dir[d];
+    }
+    if (n != h->n)
+      fail("Kronecker preconditioner: a grid of %d x %d x %d nodes with %d components has %lld dofs, the handle has %lld", n_dir[0],
+           n_dir[1], dim == 3 ? n_dir[2] : 1, dim, (long long)n, (long long)h->n);
+    MH_HIP(hipSetDevice(h->device));
+    h->kron.assign(dim, n_dir, U, lambda, h->stream);
+    MH_HIP(hipStreamSynchronize(h->stream));
+  });
+}
+
+int mimi_hip_linear_set_kronecker_coefficients(mimi_hip_linear_t h, double mass_coef, const double* stiff_coef) {
+  return guarded([&] {
+    if (!h || !stiff_coef) fail("null argument");
+    if (!h->kron.set) fail("mimi_hip_linear_set_kronecker_coefficients needs mimi_hip_linear_set_kronecker first");
+    MH_HIP(hipSetDevice(h->device));
+    KronCoefficients k{};
+    k.mass = mass_coef;
+    for (int e = 0; e < h->kron.dim * h->kron.dim; ++e) k.stiff[e] = stiff_coef[e];
+    h->kron.set_coefficients(k, h->stream);
+  });
+}
+
+int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const double* A_values, const double* r, double* z) {
+  return guarded([&] {
+    if (!h || !r || !z) fail("null argument");
+    if (kind != PRECOND_JACOBI && kind != PRECOND_KRONECKER) fail("preconditioner kind %d (1 Jacobi, 2 Kronecker)", kind);
+    check_preconditioner(h, kind);
+    if (kind == PRECOND_JACOBI && !A_values) fail("the Jacobi preconditioner needs the matrix values");
+    MH_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    Mirror<double> mr = Mirror<double>::in(r, (size_t)h->n, h->stage_b, s);
+    Mirror<double> mz = Mirror<double>::inout(z, (size_t)h->n, h->stage_x, s);
+    bool staged = mr.host || mz.host;
+    if (kind == PRECOND_JACOBI) {
+      Mirror<double> mA = Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, s);
+      staged |= mA.host != nullptr;
+      h->partials.resize((size_t)KR_BLOCKS);
+      hipLaunchKernelGGL(kr_cg_precond_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, h->n, mr.dev, jacobi_diagonal(h, mA.dev), mz.dev,
+                         h->partials.ptr);
+      MH_HIP(hipGetLastError());
+    } else {
+      kron_apply(h, mr.dev, mz.dev);
+    }
+    mz.finish(s);
+    if (staged) MH_HIP(hipStreamSynchronize(s));
   });
 }
 

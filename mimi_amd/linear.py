@@ -19,7 +19,24 @@ class LinearSolver(_capi.Handle):
     abs_tol = 1e-12
     max_iter = 300
     kdim = 50
-    use_jacobi = True          # mfem::DSmoother
+    # "jacobi": mfem::DSmoother, the reference's; "kronecker": the fast-diagonalisation operator of SetKronecker; "none"
+    preconditioner = "jacobi"
+    _PRECONDITIONER_IDS = {"none": 0, "jacobi": 1, "kronecker": 2}
+
+    @property
+    def use_jacobi(self):
+        """the boolean this attribute used to be: True for "jacobi"; assigning True / False selects "jacobi" / "none" """
+        return self.preconditioner == "jacobi"
+
+    @use_jacobi.setter
+    def use_jacobi(self, on):
+        self.preconditioner = "jacobi" if on else "none"
+
+    def _preconditioner_id(self):
+        try:
+            return self._PRECONDITIONER_IDS[self.preconditioner]
+        except KeyError:
+            raise ValueError(f"preconditioner {self.preconditioner!r}: one of {sorted(self._PRECONDITIONER_IDS)}") from None
 
     def __init__(self, pattern, essential_dofs=None, device=0):
         self.pattern_ = pattern
@@ -52,12 +69,30 @@ class LinearSolver(_capi.Handle):
         check(_capi.lib().mimi_hip_linear_add_mult(self._h, fptr(A_values), fptr(x), float(alpha), fptr(y)))
         return y
 
+    def SetKronecker(self, op):
+        """the eigen-decompositions of a mimi_amd.kronecker.KroneckerOperator (copied to the device); the coefficients
+        follow with SetKroneckerCoefficients"""
+        n_dir = np.ascontiguousarray(op.n_dir, dtype=np.int32)
+        check(_capi.lib().mimi_hip_linear_set_kronecker(self._h, int(op.dim), ptr(n_dir, "int32"), fptr(op.U), fptr(op.lam)))
+
+    def SetKroneckerCoefficients(self, mass, stiff):
+        """P_c = mass (x) M_d + sum_d stiff[c * dim + d] K_d (x) M...: rebuilds the scaling array on the device"""
+        stiff = np.ascontiguousarray(stiff, dtype=np.float64).ravel()
+        check(_capi.lib().mimi_hip_linear_set_kronecker_coefficients(self._h, float(mass), fptr(stiff)))
+
+    def ApplyPreconditioner(self, kind, A_values, r, z):
+        """z = M r as the solvers apply it: kind "jacobi" / 1 (needs A_values) or "kronecker" / 2 (A_values may be None)"""
+        kind = self._PRECONDITIONER_IDS.get(kind, kind)
+        self._follow_torch(A_values, r, z)
+        check(_capi.lib().mimi_hip_linear_apply_preconditioner(self._h, int(kind), fptr(A_values), fptr(r), fptr(z)))
+        return z
+
     def Mult(self, A_values, b, x):
         """x = A^-1 b to the configured tolerances (x is overwritten: iterative_mode false)"""
         it, conv, nrm = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
         self._follow_torch(A_values, b, x)
         check(_capi.lib().mimi_hip_linear_gmres(self._h, fptr(A_values), fptr(b), fptr(x), self.rel_tol, self.abs_tol,
-                                                int(self.max_iter), int(self.kdim), 1 if self.use_jacobi else 0,
+                                                int(self.max_iter), int(self.kdim), self._preconditioner_id(),
                                                 C.byref(it), C.byref(nrm), C.byref(conv)))
         self.final_iter_, self.final_norm_, self.converged_ = it.value, nrm.value, bool(conv.value)
         return x
@@ -68,6 +103,6 @@ class LinearSolver(_capi.Handle):
         it, conv, nrm = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
         self._follow_torch(A_values, b, x)
         check(_capi.lib().mimi_hip_linear_cg(self._h, fptr(A_values), fptr(b), fptr(x), rel_tol, abs_tol, int(max_iter),
-                                             1 if self.use_jacobi else 0, C.byref(it), C.byref(nrm), C.byref(conv)))
+                                             self._preconditioner_id(), C.byref(it), C.byref(nrm), C.byref(conv)))
         self.final_iter_, self.final_norm_, self.converged_ = it.value, nrm.value, bool(conv.value)
         return x

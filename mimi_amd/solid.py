@@ -31,6 +31,7 @@ import scipy.sparse.linalg as spla
 from . import nurbs_mesh, splines
 from .integrators import (CouplingSurface, CSRPattern, FollowerPressure, MortarContact,
                           NonlinearSolid as NonlinearSolidIntegrator, PeriodicFold, periodic_node_map)
+from .kronecker import KroneckerOperator, stiffness_coefficients
 from .linear import LinearSolver
 from .splines import BSplinePatch
 
@@ -351,6 +352,11 @@ class NonlinearSolid(Solid):
         dim = self._dim
         bc = self.boundary_condition or BoundaryConditions()
         axes = self._periodic_axes(bc)                               # refusals come before any device work
+        rc = self.runtime_communication
+        if axes and rc is not None and rc.get_int("use_iterative_solver", 0) and rc.get_int("use_kronecker_preconditioner", 0):
+            raise RuntimeError("use_kronecker_preconditioner cannot be combined with a periodic boundary "
+                               "(boundary_condition.initial.periodic): the folded numbering needs periodic 1-D matrices, "
+                               "which the Kronecker preconditioner does not build -- unset one of the two")
         self.patch_ = patch = self.patch()
         n = patch.n_vdofs
         # the integrators' pattern: the patch's unwrapped structured one (the tensor kernels' own) -- with periodic
@@ -576,6 +582,13 @@ class NonlinearSolid(Solid):
         # (mimi_amd/linear.py); else a sparse direct solve on the host (UMFPack in the reference, SuperLU here)
         self.linear_ = LinearSolver(self.pattern_, self.dirichlet_, device=self.device)
         self.use_iterative_solver_ = bool(rc.get_int("use_iterative_solver", 0))
+        # "use_kronecker_preconditioner" (with the iterative solver only): the fast-diagonalisation operator of
+        # mimi_amd/kronecker.py in place of Jacobi, for the Newton solves and the explicit mass solve
+        self.use_kronecker_ = self.use_iterative_solver_ and bool(rc.get_int("use_kronecker_preconditioner", 0))
+        self._kronecker_pushed = None
+        if self.use_kronecker_:
+            self.linear_.SetKronecker(KroneckerOperator(patch, self.dirichlet_, dim))
+            self.linear_.preconditioner = "kronecker"
         if not self.host_setup_:
             self._device_setup()
         self._to_device()
@@ -722,9 +735,19 @@ class NonlinearSolid(Solid):
         self.linear_.Eliminate(y, None)
         return y, self.d_jac_
 
+    def _push_kronecker(self, fac0, fac1):
+        """the coefficients of the Kronecker operator for J = M + fac0 K + fac1 C, pushed when they change"""
+        if not self.use_kronecker_ or self._kronecker_pushed == (fac0, fac1):
+            return
+        m = self.material
+        self.linear_.SetKroneckerCoefficients(m.density, stiffness_coefficients(m.lambda_, m.mu, fac0, fac1,
+                                                                                  getattr(m, "viscosity", -1.0), self._dim))
+        self._kronecker_pushed = (fac0, fac1)
+
     def _solve(self, J, r):
         """the linear solve of a Newton iteration (py_nonlinear_solid.cpp:327-343)"""
         if self.use_iterative_solver_:
+            self._push_kronecker(self._fac0, self._fac1)
             return self.linear_.Mult(J, r, self._torch.zeros_like(r))        # GMRES + Jacobi, all in HBM
         # the reference's default: a sparse direct solve (UMFPack there, SuperLU here) -- on the host
         Jh = J.cpu().numpy()
@@ -819,6 +842,7 @@ class NonlinearSolid(Solid):
             z = self._rhs - z
             if self.use_iterative_solver_:
                 # mass_inv_: mfem::CGSolver + DSmoother (operators/nonlinear_solid.cpp:39-50,155)
+                self._push_kronecker(0.0, 0.0)
                 self._a = self.linear_.MultCG(self.d_mass_, z, torch.zeros_like(z))
             else:
                 self._a = torch.from_numpy(spla.splu(self._csr(self.mass_).tocsc()).solve(z.cpu().numpy())).to(x.device)

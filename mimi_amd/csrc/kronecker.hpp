@@ -218,8 +218,7 @@ struct Kronecker {
   }
 
   void set_coefficients(const KronCoefficients& k, hipStream_t s) {
-    hipLaunchKernelGGL(kq_scaling_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, dim, nd[0], nd[1], nd[2], lambda.ptr, k, D.ptr);
-    MH_HIP(hipGetLastError());
+    launch(kq_scaling_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, dim, nd[0], nd[1], nd[2], lambda.ptr, k, D.ptr);
     have_coefficients = true;
   }
 
@@ -228,16 +227,15 @@ struct Kronecker {
     const unsigned tiles = (unsigned)((nd[d] + KQ_TI - 1) / KQ_TI);
     if (d == 0) {
       const int64_t lines = n / ((int64_t)nd[0] * VDIM);
-      hipLaunchKernelGGL((kq_mode_contiguous_kernel<VDIM>), dim3((unsigned)((lines + KQ_LB - 1) / KQ_LB), tiles), dim3(KQ_LB * VDIM), 0, s,
-                         nd[0], lines, W + u_off[0], u_comp_stride, X, Y, ep);
+      launch(kq_mode_contiguous_kernel<VDIM>, dim3((unsigned)((lines + KQ_LB - 1) / KQ_LB), tiles), dim3(KQ_LB * VDIM), 0, s, nd[0], lines,
+             W + u_off[0], u_comp_stride, X, Y, ep);
     } else {
       int64_t inner = VDIM;
       for (int e = 0; e < d; ++e) inner *= nd[e];
       const int64_t total = n / nd[d];
-      hipLaunchKernelGGL((kq_mode_strided_kernel<VDIM>), dim3((unsigned)((total + KQ_THREADS - 1) / KQ_THREADS), tiles), dim3(KQ_THREADS), 0,
-                         s, nd[d], inner, total, W + u_off[d], u_comp_stride, X, Y, ep);
+      launch(kq_mode_strided_kernel<VDIM>, dim3((unsigned)((total + KQ_THREADS - 1) / KQ_THREADS), tiles), dim3(KQ_THREADS), 0, s, nd[d],
+             inner, total, W + u_off[d], u_comp_stride, X, Y, ep);
     }
-    MH_HIP(hipGetLastError());
   }
 
   // out = P^-1 in, then out[ess] = in[ess] (is_ess may be null).  out == in is allowed; neither may be t0 / t1.

@@ -19,10 +19,12 @@
 #include <cmath>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mimi_hip.h"
 #include "common.hpp"
+#include "gmres_host.hpp"
 #include "kronecker.hpp"
 
 namespace mimi_hip {
@@ -251,7 +253,7 @@ __global__ __launch_bounds__(KR_THREADS) void kr_mgs_kernel(int64_t n, double* _
   if (threadIdx.x == 0) partial_out[blockIdx.x] = t;
 }
 
-// v = w / sqrt(total(partial)); scalars[slot] for the host: the totals of n_cols partial arrays
+// v = w / sqrt(total(partial_norm2)), v = 0 where that norm is 0
 __global__ __launch_bounds__(KR_THREADS) void kr_normalize_kernel(int64_t n, const double* __restrict__ w,
                                                                   const double* __restrict__ partial_norm2, double* __restrict__ v) {
   __shared__ double sh[KR_THREADS / 64];
@@ -349,7 +351,7 @@ struct mimi_hip_linear_s : StreamHandle {
   DeviceBuffer<int32_t> ncol;
   DeviceBuffer<double> dinv, V, w, r, partials, totals, ycoef, stage_val, stage_b, stage_x;
   Kronecker kron;         // mimi_hip_linear_set_kronecker: preconditioner id 2
-  int* status_dev = nullptr;
+  DeviceBuffer<int> status;                      // one word: what the pattern checks of create found
   double* column_host[2] = {nullptr, nullptr};   // pinned: the Hessenberg column of the step before last and of the last one
   hipEvent_t column_ready[2] = {nullptr, nullptr};
   int column_cap = 0;
@@ -368,50 +370,119 @@ struct mimi_hip_linear_s : StreamHandle {
       if (column_host[k]) (void)hipHostFree(column_host[k]);
       if (column_ready[k]) (void)hipEventDestroy(column_ready[k]);
     }
-    if (status_dev) (void)hipFree(status_dev);
   }
 };
 
 namespace {
 
+const dim3 KR_GRID(KR_BLOCKS), KR_BLOCK(KR_THREADS);   // of every reduction and vector kernel
+
+// The product form of the pattern, found at create (kr_groups_kernel, kr_nodecol_kernel): the one switch over it.
+// f(ROWS, NODECOL, units of ROWS rows, the column list the form reads)
+template<class F>
+void by_product_form(const mimi_hip_linear_s* h, F&& f) {
+  using std::integral_constant;
+  if (h->nodecol) f(integral_constant<int, 3>{}, std::true_type{}, h->n / 3, (const int32_t*)h->ncol.ptr);
+  else if (h->group == 3) f(integral_constant<int, 3>{}, std::false_type{}, h->n / 3, h->col);
+  else if (h->group == 2) f(integral_constant<int, 2>{}, std::false_type{}, h->n / 2, h->col);
+  else f(integral_constant<int, 1>{}, std::false_type{}, h->n, h->col);
+}
+
+dim3 wave_per_unit(int64_t units) { return dim3((unsigned)((units + 3) / 4)); }   // workgroups of 256: four waves
+
+// y = dinv o (A x), dinv o (b - A x) with b, plain without dinv
 void spmv(mimi_hip_linear_s* h, const double* val, const double* x, const double* b, const double* dinv, double* y) {
-  if (h->nodecol)
-    hipLaunchKernelGGL((kr_spmv_kernel<3, true>), dim3((unsigned)((h->n / 3 + 3) / 4)), dim3(256), 0, h->stream, h->n / 3, h->rowptr,
-                       h->ncol.ptr, val, x, b, dinv, y);
-  else if (h->group == 3)
-    hipLaunchKernelGGL((kr_spmv_kernel<3, false>), dim3((unsigned)((h->n / 3 + 3) / 4)), dim3(256), 0, h->stream, h->n / 3, h->rowptr,
-                       h->col, val, x, b, dinv, y);
-  else if (h->group == 2)
-    hipLaunchKernelGGL((kr_spmv_kernel<2, false>), dim3((unsigned)((h->n / 2 + 3) / 4)), dim3(256), 0, h->stream, h->n / 2, h->rowptr,
-                       h->col, val, x, b, dinv, y);
-  else
-    hipLaunchKernelGGL((kr_spmv_kernel<1, false>), dim3((unsigned)((h->n + 3) / 4)), dim3(256), 0, h->stream, h->n, h->rowptr, h->col,
-                       val, x, b, dinv, y);
-  MH_HIP(hipGetLastError());
+  by_product_form(h, [&](auto R, auto NC, int64_t n_units, const int32_t* col) {
+    launch(kr_spmv_kernel<decltype(R)::value, decltype(NC)::value>, wave_per_unit(n_units), dim3(256), 0, h->stream, n_units, h->rowptr,
+           col, val, x, b, dinv, y);
+  });
+}
+
+// partial_out = the partial sums of a . b (a == b: of the squared norm)
+void dot(mimi_hip_linear_s* h, const double* a, const double* b, double* partial_out) {
+  launch(kr_mgs_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, const_cast<double*>(a), nullptr, nullptr, b, partial_out);
+}
+
+// the scalar behind the first partial array of the handle, on the host
+double total_to_host(mimi_hip_linear_s* h) {
+  launch(kr_totals_kernel, dim3(1), KR_BLOCK, 0, h->stream, h->partials.ptr, h->totals.ptr);
+  double t = 0.0;
+  MH_HIP(hipMemcpyAsync(&t, h->totals.ptr, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  MH_HIP(hipStreamSynchronize(h->stream));
+  return t;
 }
 
 // the preconditioner ids of mimi_hip_linear_gmres / _cg / _apply_preconditioner
 enum { PRECOND_NONE = 0, PRECOND_JACOBI = 1, PRECOND_KRONECKER = 2 };
 
-void check_preconditioner(const mimi_hip_linear_s* h, int id) {
-  if (id < PRECOND_NONE || id > PRECOND_KRONECKER) fail("unknown preconditioner id %d (0 none, 1 Jacobi, 2 Kronecker)", id);
-  if (id != PRECOND_KRONECKER) return;
-  if (!h->kron.set) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker first");
-  if (!h->kron.have_coefficients) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker_coefficients first");
-}
+// M of one solve: the identity, 1 / diag(A) of THIS solve's values (mfem::DSmoother; the values change between Newton
+// iterations, so nothing of it outlives the solve), or the Kronecker operator the handle holds.  Which kernels apply M is
+// decided here and nowhere else.
+struct Preconditioner {
+  mimi_hip_linear_s* h;
+  int id;
+  const double* dinv = nullptr;   // Jacobi; fused into the kernels that take it
 
-// z = P^-1 r, z[ess] = r[ess]  (z == r allowed)
-void kron_apply(mimi_hip_linear_s* h, const double* r, double* z) {
-  h->kron.apply(r, z, h->n_ess > 0 ? h->is_ess.ptr : nullptr, h->stream);
-}
+  Preconditioner(mimi_hip_linear_s* h_, int id_, const double* val) : h(h_), id(id_) {
+    if (id < PRECOND_NONE || id > PRECOND_KRONECKER) fail("unknown preconditioner id %d (0 none, 1 Jacobi, 2 Kronecker)", id);
+    if (id == PRECOND_KRONECKER) {
+      if (!h->kron.set) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker first");
+      if (!h->kron.have_coefficients) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker_coefficients first");
+    } else if (id == PRECOND_JACOBI) {
+      if (!val) fail("the Jacobi preconditioner needs the matrix values");
+      h->dinv.resize((size_t)h->n);
+      launch(kr_diag_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->n, h->rowptr, h->diag_pos.ptr, val,
+             h->dinv.ptr);
+      dinv = h->dinv.ptr;
+    }
+  }
 
-// 1 / diag(A) (mfem::DSmoother) into the handle's dinv
-const double* jacobi_diagonal(mimi_hip_linear_s* h, const double* val) {
-  h->dinv.resize((size_t)h->n);
-  hipLaunchKernelGGL(kr_diag_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->n, h->rowptr, h->diag_pos.ptr, val,
-                     h->dinv.ptr);
-  MH_HIP(hipGetLastError());
-  return h->dinv.ptr;
+  // z = P^-1 r, z[ess] = r[ess]  (z == r allowed)
+  void kronecker(const double* r, double* z) const { h->kron.apply(r, z, h->n_ess > 0 ? h->is_ess.ptr : nullptr, h->stream); }
+
+  // y = M (b - A x), or M A x without b: Jacobi inside the product, the Kronecker operator in place behind a plain one
+  void product(const double* val, const double* x, const double* b, double* y) const {
+    spmv(h, val, x, b, dinv, y);
+    if (id == PRECOND_KRONECKER) kronecker(y, y);
+  }
+
+  // z = M r, and the partial sums of r . z into partial_rz when the caller wants them
+  void apply(const double* r, double* z, double* partial_rz) const {
+    if (id == PRECOND_KRONECKER) {
+      kronecker(r, z);
+      if (partial_rz) dot(h, z, r, partial_rz);
+      return;
+    }
+    if (!partial_rz) {   // (the fused kernel writes them always)
+      h->partials.resize((size_t)KR_BLOCKS);
+      partial_rz = h->partials.ptr;
+    }
+    launch(kr_cg_precond_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, r, dinv, z, partial_rz);
+  }
+};
+
+// every exit of a solve: what it reports, and x back to a caller on the host
+struct SolveExit {
+  mimi_hip_linear_s* h;
+  Mirror<double>& x;
+  int32_t* iterations;
+  double* final_norm;
+  int32_t* converged;
+  void operator()(int it, double nrm, bool conv) const {
+    if (iterations) *iterations = it;
+    if (final_norm) *final_norm = nrm;
+    if (converged) *converged = conv ? 1 : 0;
+    x.finish(h->stream);
+    MH_HIP(hipStreamSynchronize(h->stream));
+  }
+};
+
+// the status word of create after the checks launched so far
+int read_status(mimi_hip_linear_s* h) {
+  int status = 0;
+  MH_HIP(hipMemcpyAsync(&status, h->status.ptr, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  MH_HIP(hipStreamSynchronize(h->stream));
+  return status;
 }
 
 }  // namespace
@@ -440,36 +511,23 @@ int mimi_hip_linear_create(int64_t n, const int64_t* csr_rowptr, const int32_t* 
       h->col_own.assign(csr_col, (size_t)nnz, h->stream);
       h->col = h->col_own.ptr;
     }
-    MH_HIP(hipMalloc(reinterpret_cast<void**>(&h->status_dev), sizeof(int)));
-    MH_HIP(hipMemsetAsync(h->status_dev, 0, sizeof(int), h->stream));
+    h->status.resize(1);
+    MH_HIP(hipMemsetAsync(h->status.ptr, 0, sizeof(int), h->stream));
     h->diag_pos.resize((size_t)n);
-    hipLaunchKernelGGL(kr_diag_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, h->rowptr, h->col,
-                       h->diag_pos.ptr, h->status_dev);
-    MH_HIP(hipGetLastError());
-    int status = 0;
-    MH_HIP(hipMemcpyAsync(&status, h->status_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    MH_HIP(hipStreamSynchronize(h->stream));
-    if (status) fail("CSR pattern has a row without a diagonal entry");
+    launch(kr_diag_pos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, h->rowptr, h->col, h->diag_pos.ptr,
+           h->status.ptr);
+    if (read_status(h.get())) fail("CSR pattern has a row without a diagonal entry");
     // the dofs of a node (byVDIM numbering) have identical rows in the pattern the integrators assemble into
     for (int g = 3; g >= 2; --g)
       if (n % g == 0)
-        hipLaunchKernelGGL(kr_groups_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, h->stream, n, g, h->rowptr, h->col, 1 << g,
-                           h->status_dev);
-    MH_HIP(hipGetLastError());
-    MH_HIP(hipMemcpyAsync(&status, h->status_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    MH_HIP(hipStreamSynchronize(h->stream));
+        launch(kr_groups_kernel, wave_per_unit(n), dim3(256), 0, h->stream, n, g, h->rowptr, h->col, 1 << g, h->status.ptr);
+    const int status = read_status(h.get());
     h->group = (n % 3 == 0 && !(status & 8)) ? 3 : (n % 2 == 0 && !(status & 4)) ? 2 : 1;
     if (h->group == 3 && nnz % 9 == 0) {
-      hipLaunchKernelGGL(kr_nodecol_kernel, dim3((unsigned)((n / 3 + 3) / 4)), dim3(256), 0, h->stream, n / 3, h->rowptr, h->col, 16,
-                         h->status_dev, (int32_t*)nullptr);
-      MH_HIP(hipGetLastError());
-      MH_HIP(hipMemcpyAsync(&status, h->status_dev, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      MH_HIP(hipStreamSynchronize(h->stream));
-      if (!(status & 16)) {
+      launch(kr_nodecol_kernel, wave_per_unit(n / 3), dim3(256), 0, h->stream, n / 3, h->rowptr, h->col, 16, h->status.ptr, nullptr);
+      if (!(read_status(h.get()) & 16)) {
         h->ncol.resize((size_t)(nnz / 9));
-        hipLaunchKernelGGL(kr_nodecol_kernel, dim3((unsigned)((n / 3 + 3) / 4)), dim3(256), 0, h->stream, n / 3, h->rowptr, h->col, 16,
-                           h->status_dev, h->ncol.ptr);
-        MH_HIP(hipGetLastError());
+        launch(kr_nodecol_kernel, wave_per_unit(n / 3), dim3(256), 0, h->stream, n / 3, h->rowptr, h->col, 16, h->status.ptr, h->ncol.ptr);
         h->nodecol = true;
       }
     }
@@ -479,9 +537,7 @@ int mimi_hip_linear_create(int64_t n, const int64_t* csr_rowptr, const int32_t* 
     if (n_ess > 0) {
       if (!ess_dofs) fail("null essential dof list");
       h->ess.assign(ess_dofs, (size_t)n_ess, h->stream);
-      hipLaunchKernelGGL(kr_mark_kernel, dim3((unsigned)((n_ess + 255) / 256)), dim3(256), 0, h->stream, n_ess, h->ess.ptr,
-                         h->is_ess.ptr);
-      MH_HIP(hipGetLastError());
+      launch(kr_mark_kernel, dim3((unsigned)((n_ess + 255) / 256)), dim3(256), 0, h->stream, n_ess, h->ess.ptr, h->is_ess.ptr);
     }
     MH_HIP(hipStreamSynchronize(h->stream));
     *out = h.release();
@@ -509,17 +565,13 @@ int mimi_hip_linear_eliminate(mimi_hip_linear_t h, double* r, double* A_values) 
     if (h->n_ess == 0) return;
     if (r) {
       Mirror<double> mr = Mirror<double>::inout(r, (size_t)h->n, h->stage_b, h->stream);
-      hipLaunchKernelGGL(kr_zero_entries_kernel, dim3((unsigned)((h->n_ess + 255) / 256)), dim3(256), 0, h->stream, h->n_ess,
-                         h->ess.ptr, mr.dev);
-      MH_HIP(hipGetLastError());
+      launch(kr_zero_entries_kernel, dim3((unsigned)((h->n_ess + 255) / 256)), dim3(256), 0, h->stream, h->n_ess, h->ess.ptr, mr.dev);
       mr.finish(h->stream);
       if (mr.host) MH_HIP(hipStreamSynchronize(h->stream));
     }
     if (A_values) {
       Mirror<double> mA = Mirror<double>::inout(A_values, (size_t)h->nnz, h->stage_val, h->stream);
-      hipLaunchKernelGGL(kr_eliminate_kernel, dim3((unsigned)((h->n + 3) / 4)), dim3(256), 0, h->stream, h->n, h->rowptr, h->col,
-                         h->is_ess.ptr, mA.dev);
-      MH_HIP(hipGetLastError());
+      launch(kr_eliminate_kernel, wave_per_unit(h->n), dim3(256), 0, h->stream, h->n, h->rowptr, h->col, h->is_ess.ptr, mA.dev);
       mA.finish(h->stream);
       if (mA.host) MH_HIP(hipStreamSynchronize(h->stream));
     }
@@ -534,19 +586,10 @@ int mimi_hip_linear_add_mult(mimi_hip_linear_t h, const double* A_values, const 
     Mirror<double> mA = Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, h->stream);
     Mirror<double> mx = Mirror<double>::in(x, (size_t)h->n, h->stage_x, h->stream);
     Mirror<double> my = Mirror<double>::inout(y, (size_t)h->n, h->stage_b, h->stream);
-    if (h->nodecol)
-      hipLaunchKernelGGL((kr_add_mult_kernel<3, true>), dim3((unsigned)((h->n / 3 + 3) / 4)), dim3(256), 0, h->stream, h->n / 3,
-                         h->rowptr, h->ncol.ptr, mA.dev, mx.dev, alpha, my.dev);
-    else if (h->group == 3)
-      hipLaunchKernelGGL((kr_add_mult_kernel<3, false>), dim3((unsigned)((h->n / 3 + 3) / 4)), dim3(256), 0, h->stream, h->n / 3,
-                         h->rowptr, h->col, mA.dev, mx.dev, alpha, my.dev);
-    else if (h->group == 2)
-      hipLaunchKernelGGL((kr_add_mult_kernel<2, false>), dim3((unsigned)((h->n / 2 + 3) / 4)), dim3(256), 0, h->stream, h->n / 2,
-                         h->rowptr, h->col, mA.dev, mx.dev, alpha, my.dev);
-    else
-      hipLaunchKernelGGL((kr_add_mult_kernel<1, false>), dim3((unsigned)((h->n + 3) / 4)), dim3(256), 0, h->stream, h->n, h->rowptr,
-                         h->col, mA.dev, mx.dev, alpha, my.dev);
-    MH_HIP(hipGetLastError());
+    by_product_form(h, [&](auto R, auto NC, int64_t n_units, const int32_t* col) {
+      launch(kr_add_mult_kernel<decltype(R)::value, decltype(NC)::value>, wave_per_unit(n_units), dim3(256), 0, h->stream, n_units,
+             h->rowptr, col, mA.dev, mx.dev, alpha, my.dev);
+    });
     my.finish(h->stream);
     if (mA.host || mx.host || my.host) MH_HIP(hipStreamSynchronize(h->stream));
   });
@@ -556,7 +599,6 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
                           int max_iter, int kdim, int preconditioner, int32_t* iterations, double* final_norm, int32_t* converged) {
   return guarded([&] {
     if (!h || !A_values || !b || !x) fail("null argument");
-    check_preconditioner(h, preconditioner);
     if (kdim < 1) kdim = 50;   // mfem::GMRESSolver default m
     MH_HIP(hipSetDevice(h->device));
     const int64_t n = h->n;
@@ -571,54 +613,28 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
     h->totals.resize((size_t)(kdim + 2));
     h->ycoef.resize((size_t)kdim);
     h->reserve_columns(kdim + 2);
-    // Jacobi is fused into the products (dinv); the Kronecker operator is applied in place behind a plain product
-    const double* dinv = preconditioner == PRECOND_JACOBI ? jacobi_diagonal(h, mA.dev) : nullptr;
-    const bool kronecker = preconditioner == PRECOND_KRONECKER;
+    const Preconditioner M(h, preconditioner, mA.dev);
+    const SolveExit finish{h, mx, iterations, final_norm, converged};
     double* V = h->V.ptr;
     double* w = h->w.ptr;
     double* r = h->r.ptr;
     double* part = h->partials.ptr;
-    std::vector<double> H((size_t)(kdim + 1) * kdim, 0.0), sv(kdim + 1, 0.0), cs(kdim + 1, 0.0), sn(kdim + 1, 0.0),
-        y(kdim);
-    auto Hat = [&](int i, int j) -> double& { return H[(size_t)i + (size_t)j * (kdim + 1)]; };
-    auto norm_of = [&](const double* vec) -> double {   // vec also goes to `part[0..)` as its squared norm
-      hipLaunchKernelGGL(kr_mgs_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, const_cast<double*>(vec), (const double*)nullptr,
-                         (const double*)nullptr, vec, part);
-      hipLaunchKernelGGL(kr_totals_kernel, dim3(1), dim3(KR_THREADS), 0, s, part, h->totals.ptr);
-      MH_HIP(hipGetLastError());
-      double t = 0.0;
-      MH_HIP(hipMemcpyAsync(&t, h->totals.ptr, sizeof(double), hipMemcpyDeviceToHost, s));
-      MH_HIP(hipStreamSynchronize(s));
-      return std::sqrt(t);
+    GmresLeastSquares ls(kdim);
+    auto norm_of_r = [&]() -> double {   // its partial sums stay in part[0..) for the normalisation that follows
+      dot(h, r, r, part);
+      return std::sqrt(total_to_host(h));
     };
     auto update = [&](int k_count) {   // GMRESSolver: Update(x, k, H, s, v)
-      for (int i = k_count - 1; i >= 0; --i) {
-        double t = sv[i];
-        for (int j = i + 1; j < k_count; ++j) t -= Hat(i, j) * y[j];
-        y[i] = t / Hat(i, i);
-      }
-      MH_HIP(hipMemcpyAsync(h->ycoef.ptr, y.data(), sizeof(double) * k_count, hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(kr_update_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, k_count, V, n, h->ycoef.ptr, mx.dev);
-      MH_HIP(hipGetLastError());
+      MH_HIP(hipMemcpyAsync(h->ycoef.ptr, ls.solve(k_count), sizeof(double) * k_count, hipMemcpyHostToDevice, s));
+      launch(kr_update_kernel, KR_GRID, KR_BLOCK, 0, s, n, k_count, V, n, h->ycoef.ptr, mx.dev);
       MH_HIP(hipStreamSynchronize(s));   // y is host memory reused by the next cycle
     };
-    auto finish = [&](int it, double nrm, bool conv) {
-      if (iterations) *iterations = it;
-      if (final_norm) *final_norm = nrm;
-      if (converged) *converged = conv ? 1 : 0;
-      mx.finish(s);
-      MH_HIP(hipStreamSynchronize(s));
-    };
 
-    // x = 0; r = M b
+    // x = 0; r = M (b - A x)
     MH_HIP(hipMemsetAsync(mx.dev, 0, sizeof(double) * n, s));
-    {
-      // r = M (b - A x) with x = 0
-      spmv(h, mA.dev, mx.dev, mb.dev, dinv, r);
-      if (kronecker) kron_apply(h, r, r);
-    }
-    double beta = norm_of(r);
-    double goal = std::fmax(rel_tol * beta, abs_tol);
+    M.product(mA.dev, mx.dev, mb.dev, r);
+    double beta = norm_of_r();
+    const double goal = std::fmax(rel_tol * beta, abs_tol);
     if (beta <= goal) {
       finish(0, beta, true);
       return;
@@ -629,63 +645,30 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
     // the round trip of the column is hidden behind the next step, and when column i ends the solve the step that was
     // launched ahead is simply not used (the update reads v_0 .. v_i only).
     auto launch_step = [&](int i) {
-      spmv(h, mA.dev, V + (int64_t)i * n, nullptr, dinv, w);
-      if (kronecker) kron_apply(h, w, w);
+      M.product(mA.dev, V + (int64_t)i * n, nullptr, w);
       for (int k = 0; k <= i + 1; ++k) {
         const double* v_prev = k > 0 ? V + (int64_t)(k - 1) * n : nullptr;
         const double* p_prev = k > 0 ? part + (int64_t)(k - 1) * KR_BLOCKS : nullptr;
         const double* v_next = k <= i ? V + (int64_t)k * n : w;
-        hipLaunchKernelGGL(kr_mgs_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, w, v_prev, p_prev, v_next,
-                           part + (int64_t)k * KR_BLOCKS);
+        launch(kr_mgs_kernel, KR_GRID, KR_BLOCK, 0, s, n, w, v_prev, p_prev, v_next, part + (int64_t)k * KR_BLOCKS);
       }
-      hipLaunchKernelGGL(kr_normalize_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, w, part + (int64_t)(i + 1) * KR_BLOCKS,
-                         V + (int64_t)(i + 1) * n);
-      hipLaunchKernelGGL(kr_totals_kernel, dim3(i + 2), dim3(KR_THREADS), 0, s, part, h->totals.ptr);
-      MH_HIP(hipGetLastError());
+      launch(kr_normalize_kernel, KR_GRID, KR_BLOCK, 0, s, n, w, part + (int64_t)(i + 1) * KR_BLOCKS, V + (int64_t)(i + 1) * n);
+      launch(kr_totals_kernel, dim3(i + 2), KR_BLOCK, 0, s, part, h->totals.ptr);
       MH_HIP(hipMemcpyAsync(h->column_host[i & 1], h->totals.ptr, sizeof(double) * (i + 2), hipMemcpyDeviceToHost, s));
       MH_HIP(hipEventRecord(h->column_ready[i & 1], s));
     };
     int j = 1;
     while (j <= max_iter) {
       // v_0 = r / beta (partials of ||r||^2 are in part[0..))
-      hipLaunchKernelGGL(kr_normalize_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, r, part, V);
-      std::fill(sv.begin(), sv.end(), 0.0);
-      sv[0] = beta;
+      launch(kr_normalize_kernel, KR_GRID, KR_BLOCK, 0, s, n, r, part, V);
+      ls.start_cycle(beta);
       const int steps = std::min(kdim, max_iter - j + 1);   // of this cycle, unless one of them converges
       launch_step(0);
       int i = 0;
       for (; i < steps; ++i, ++j) {
         if (i + 1 < steps) launch_step(i + 1);
         MH_HIP(hipEventSynchronize(h->column_ready[i & 1]));
-        const double* col = h->column_host[i & 1];
-        for (int k = 0; k <= i; ++k) Hat(k, i) = col[k];
-        Hat(i + 1, i) = std::sqrt(col[i + 1]);
-        // Givens rotations (GMRESSolver: ApplyPlaneRotation / GeneratePlaneRotation)
-        for (int k = 0; k < i; ++k) {
-          const double t = cs[k] * Hat(k, i) + sn[k] * Hat(k + 1, i);
-          Hat(k + 1, i) = -sn[k] * Hat(k, i) + cs[k] * Hat(k + 1, i);
-          Hat(k, i) = t;
-        }
-        {
-          const double dx = Hat(i, i), dy = Hat(i + 1, i);
-          if (dy == 0.0) {
-            cs[i] = 1.0;
-            sn[i] = 0.0;
-          } else if (std::fabs(dy) > std::fabs(dx)) {
-            const double t = dx / dy;
-            sn[i] = 1.0 / std::sqrt(1.0 + t * t);
-            cs[i] = t * sn[i];
-          } else {
-            const double t = dy / dx;
-            cs[i] = 1.0 / std::sqrt(1.0 + t * t);
-            sn[i] = t * cs[i];
-          }
-          Hat(i, i) = cs[i] * dx + sn[i] * dy;
-          Hat(i + 1, i) = 0.0;
-          sv[i + 1] = -sn[i] * sv[i];
-          sv[i] = cs[i] * sv[i];
-        }
-        const double resid = std::fabs(sv[i + 1]);
+        const double resid = ls.push_column(i, h->column_host[i & 1]);
         if (resid <= goal) {
           update(i + 1);
           finish(j, resid, true);
@@ -693,10 +676,8 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
         }
       }
       update(i);
-      // r = M (b - A x)
-      spmv(h, mA.dev, mx.dev, mb.dev, dinv, r);
-      if (kronecker) kron_apply(h, r, r);
-      beta = norm_of(r);
+      M.product(mA.dev, mx.dev, mb.dev, r);
+      beta = norm_of_r();
       if (beta <= goal) {
         finish(j - 1, beta, true);
         return;
@@ -713,7 +694,6 @@ int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double
                        int max_iter, int preconditioner, int32_t* iterations, double* final_norm, int32_t* converged) {
   return guarded([&] {
     if (!h || !A_values || !b || !x) fail("null argument");
-    check_preconditioner(h, preconditioner);
     MH_HIP(hipSetDevice(h->device));
     const int64_t n = h->n;
     hipStream_t s = h->stream;
@@ -724,53 +704,28 @@ int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double
     h->r.resize((size_t)n);
     h->partials.resize((size_t)2 * KR_BLOCKS);
     h->totals.resize(2);
-    const double* dinv = preconditioner == PRECOND_JACOBI ? jacobi_diagonal(h, mA.dev) : nullptr;
-    const bool kronecker = preconditioner == PRECOND_KRONECKER;
+    const Preconditioner M(h, preconditioner, mA.dev);
+    const SolveExit report{h, mx, iterations, final_norm, converged};
+    auto finish = [&](int it, double nom, bool conv) { report(it, std::sqrt(std::fabs(nom)), conv); };   // reports sqrt|(r, M r)|
     double* d = h->V.ptr;
     double* z = d + n;
     double* q = z + n;
     double* r = h->r.ptr;
     double* part = h->partials.ptr;
-    // z = M r and the partial sums of r . z
-    auto precondition = [&] {
-      if (kronecker) {
-        kron_apply(h, r, z);
-        hipLaunchKernelGGL(kr_mgs_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, z, (const double*)nullptr, (const double*)nullptr,
-                           (const double*)r, part);
-      } else {
-        hipLaunchKernelGGL(kr_cg_precond_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, r, dinv, z, part);
-      }
-    };
-    auto total_of = [&]() -> double {
-      hipLaunchKernelGGL(kr_totals_kernel, dim3(1), dim3(KR_THREADS), 0, s, part, h->totals.ptr);
-      MH_HIP(hipGetLastError());
-      double t = 0.0;
-      MH_HIP(hipMemcpyAsync(&t, h->totals.ptr, sizeof(double), hipMemcpyDeviceToHost, s));
-      MH_HIP(hipStreamSynchronize(s));
-      return t;
-    };
-    auto finish = [&](int it, double nom, bool conv) {
-      if (iterations) *iterations = it;
-      if (final_norm) *final_norm = std::sqrt(std::fabs(nom));
-      if (converged) *converged = conv ? 1 : 0;
-      mx.finish(s);
-      MH_HIP(hipStreamSynchronize(s));
-    };
     // x = 0, r = b, z = M r, d = z
     MH_HIP(hipMemsetAsync(mx.dev, 0, sizeof(double) * n, s));
     MH_HIP(hipMemcpyAsync(r, mb.dev, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    precondition();
+    M.apply(r, z, part);
     MH_HIP(hipMemcpyAsync(d, z, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    double nom = total_of();
+    double nom = total_to_host(h);
     const double r0 = std::fmax(nom * rel_tol * rel_tol, abs_tol * abs_tol);
     if (nom <= r0) {
       finish(0, nom, true);
       return;
     }
     spmv(h, mA.dev, d, nullptr, nullptr, q);
-    hipLaunchKernelGGL(kr_mgs_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, q, (const double*)nullptr, (const double*)nullptr,
-                       (const double*)d, part);
-    double den = total_of();
+    dot(h, q, d, part);
+    double den = total_to_host(h);
     if (!(den > 0.0)) {   // not positive definite: mfem warns and stops
       finish(0, nom, false);
       return;
@@ -778,9 +733,9 @@ int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double
     int it = 1;
     for (;; ++it) {
       const double alpha = nom / den;
-      hipLaunchKernelGGL(kr_cg_update_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, alpha, d, q, mx.dev, r);
-      precondition();
-      const double betanom = total_of();
+      launch(kr_cg_update_kernel, KR_GRID, KR_BLOCK, 0, s, n, alpha, d, q, mx.dev, r);
+      M.apply(r, z, part);
+      const double betanom = total_to_host(h);
       if (betanom <= r0) {
         finish(it, betanom, true);
         return;
@@ -790,11 +745,10 @@ int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double
         return;
       }
       const double beta = betanom / nom;
-      hipLaunchKernelGGL(kr_cg_direction_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, beta, z, d);
+      launch(kr_cg_direction_kernel, KR_GRID, KR_BLOCK, 0, s, n, beta, z, d);
       spmv(h, mA.dev, d, nullptr, nullptr, q);
-      hipLaunchKernelGGL(kr_mgs_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, n, q, (const double*)nullptr, (const double*)nullptr,
-                         (const double*)d, part);
-      den = total_of();
+      dot(h, q, d, part);
+      den = total_to_host(h);
       if (!(den > 0.0)) {
         finish(it, betanom, false);
         return;
@@ -838,25 +792,16 @@ int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const do
   return guarded([&] {
     if (!h || !r || !z) fail("null argument");
     if (kind != PRECOND_JACOBI && kind != PRECOND_KRONECKER) fail("preconditioner kind %d (1 Jacobi, 2 Kronecker)", kind);
-    check_preconditioner(h, kind);
-    if (kind == PRECOND_JACOBI && !A_values) fail("the Jacobi preconditioner needs the matrix values");
     MH_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     Mirror<double> mr = Mirror<double>::in(r, (size_t)h->n, h->stage_b, s);
     Mirror<double> mz = Mirror<double>::inout(z, (size_t)h->n, h->stage_x, s);
-    bool staged = mr.host || mz.host;
-    if (kind == PRECOND_JACOBI) {
-      Mirror<double> mA = Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, s);
-      staged |= mA.host != nullptr;
-      h->partials.resize((size_t)KR_BLOCKS);
-      hipLaunchKernelGGL(kr_cg_precond_kernel, dim3(KR_BLOCKS), dim3(KR_THREADS), 0, s, h->n, mr.dev, jacobi_diagonal(h, mA.dev), mz.dev,
-                         h->partials.ptr);
-      MH_HIP(hipGetLastError());
-    } else {
-      kron_apply(h, mr.dev, mz.dev);
-    }
+    Mirror<double> mA;   // the values: Jacobi alone reads them
+    if (kind == PRECOND_JACOBI && A_values) mA = Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, s);
+    const Preconditioner M(h, kind, mA.dev);
+    M.apply(mr.dev, mz.dev, nullptr);
     mz.finish(s);
-    if (staged) MH_HIP(hipStreamSynchronize(s));
+    if (mr.host || mz.host || mA.host) MH_HIP(hipStreamSynchronize(s));
   });
 }
 

@@ -9,8 +9,11 @@ from the definition of the methods (tests/test_krylov_reference_cpu.py)."""
 import numpy as np
 
 
-def gmres(A, b, rel_tol=1e-8, abs_tol=1e-12, max_iter=300, kdim=50, jacobi=True):
-    """(x, iterations, final_norm, converged); A: scipy CSR; x starts at 0 (iterative_mode false)."""
+def gmres(A, b, rel_tol=1e-8, abs_tol=1e-12, max_iter=300, kdim=50, jacobi=True, trace=None):
+    """(x, iterations, final_norm, converged); A: scipy CSR; x starts at 0 (iterative_mode false).
+    trace: a list that receives the least-squares side of the solve, in order: ("cycle", beta) at the start of a cycle,
+    ("column", i, [h_0 .. h_i, ||w||^2], resid) per step -- the Hessenberg column before the rotations and the residual
+    estimate after them --, ("solve", k, R, s, y) where the k coefficients are solved for (R: the rotated H, triangular)."""
     n = len(b)
     dinv = 1.0 / A.diagonal() if jacobi else np.ones(n)
     x = np.zeros(n)
@@ -22,6 +25,8 @@ def gmres(A, b, rel_tol=1e-8, abs_tol=1e-12, max_iter=300, kdim=50, jacobi=True)
     m = kdim
     j = 1
     while j <= max_iter:
+        if trace is not None:
+            trace.append(("cycle", beta))
         V = np.zeros((m + 1, n))
         H = np.zeros((m + 1, m))
         cs, sn, s = np.zeros(m + 1), np.zeros(m + 1), np.zeros(m + 1)
@@ -33,7 +38,9 @@ def gmres(A, b, rel_tol=1e-8, abs_tol=1e-12, max_iter=300, kdim=50, jacobi=True)
             for k in range(i + 1):                     # modified Gram-Schmidt
                 H[k, i] = w @ V[k]
                 w -= H[k, i] * V[k]
-            H[i + 1, i] = np.linalg.norm(w)
+            norm2 = w @ w
+            H[i + 1, i] = np.sqrt(norm2)               # (np.linalg.norm(w), written out)
+            column = np.append(H[:i + 1, i], norm2)
             V[i + 1] = w / H[i + 1, i]
             for k in range(i):                         # ApplyPlaneRotation
                 t = cs[k] * H[k, i] + sn[k] * H[k + 1, i]
@@ -55,12 +62,18 @@ def gmres(A, b, rel_tol=1e-8, abs_tol=1e-12, max_iter=300, kdim=50, jacobi=True)
             s[i + 1] = -sn[i] * s[i]
             s[i] = cs[i] * s[i]
             resid = abs(s[i + 1])
+            if trace is not None:
+                trace.append(("column", i, column, resid))
             if resid <= goal:
                 y = np.linalg.solve(np.triu(H[:i + 1, :i + 1]), s[:i + 1])
+                if trace is not None:
+                    trace.append(("solve", i + 1, np.triu(H[:i + 1, :i + 1]), s[:i + 1].copy(), y))
                 return x + y @ V[:i + 1], j, resid, True
             i += 1
             j += 1
         y = np.linalg.solve(np.triu(H[:i, :i]), s[:i])
+        if trace is not None:
+            trace.append(("solve", i, np.triu(H[:i, :i]), s[:i].copy(), y))
         x = x + y @ V[:i]
         r = dinv * (b - A @ x)
         beta = np.linalg.norm(r)

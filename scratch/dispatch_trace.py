@@ -3,6 +3,7 @@
 builds of the library (MIMI_HIP_LIBRARY=scratch/lib_parent.so, then the tree's own) across a refactor of its host side.
 
   python scratch/dispatch_trace.py [--atomics] > hashes.txt       one line per result: case, what, SHA-256 of the bytes
+  python scratch/dispatch_trace.py --linear > hashes.txt          the linear-solver section alone (a refactor of csrc/krylov.hip)
   rocprofv3 --kernel-trace --output-format csv -d DIR -- python scratch/dispatch_trace.py   (kernel trace alone, no counters)
   python scratch/dispatch_trace.py --compare-hashes A.txt B.txt
   python scratch/dispatch_trace.py --compare-traces DIR_A DIR_B   (kernel name, grid, workgroup, LDS) in dispatch order
@@ -18,7 +19,9 @@ tests/_patches.py with a repeated interior knot (tensor route and general route)
 degree 2 with node_ids and on an element box cut along the walked axis, the general kernels
 (MIMI_HIP_FORCE_GENERAL) with a closed-form and a record material, the reference-FD tangent.  Switches:
 MIMI_HIP_P3_CONTRACT flipped between two calls, MIMI_HIP_NO_STRUCTURED set between two creates.  Every route sums in a
-fixed order, so every hash must agree; --atomics runs the general path's atomics route
+fixed order, so every hash must agree.  The linear-solver section (csrc/krylov.hip; it closes every run): GMRES and CG with
+preconditioner ids 0, 1, 2, every product form, a restarting and a cut solve, add_mult, eliminate, apply_preconditioner kinds
+1 and 2, arrays on the host and in HBM -- SHA-256 of x, the iterations, the final norm in hex.  --atomics runs the general path's atomics route
 (MIMI_HIP_GENERAL_NO_TWO_PHASE=1, read once per process) instead, whose sums do not: trace it, do not compare its hashes."""
 import csv
 import glob
@@ -42,6 +45,74 @@ def out(case, what, value):
     print(f"{case:44s} {what:14s} {value}", flush=True)
 
 
+def run_linear():
+    """csrc/krylov.hip through LinearSolver on systems of tests/_krylov_cases.py and one of tests/_kronecker_cases.py"""
+    import numpy as np
+    import torch
+    import _krylov_cases as kc
+    import _kronecker_cases as qc
+    from mimi_amd.integrators import CSRPattern
+    from mimi_amd.kronecker import KroneckerOperator
+    from mimi_amd.linear import LinearSolver
+    dev = torch.device("cuda", 0)
+    host = lambda a: a if isinstance(a, np.ndarray) else a.cpu().numpy()
+
+    def solves(case, S, to, val, b, ids, kdims=(50,), max_iter=300):
+        for pid in ids:
+            S.preconditioner = pid
+            for kdim in kdims:
+                S.kdim, S.max_iter = kdim, max_iter
+                x = S.Mult(to(val), to(b), to(np.full(len(b), np.nan)))
+                out(case, f"gmres {pid[:4]} k{kdim}", f"{sha(host(x))} {S.final_iter_} {float(S.final_norm_).hex()} {S.converged_}")
+            x = S.MultCG(to(val), to(b), to(np.full(len(b), np.nan)), max_iter=max_iter)
+            out(case, f"cg {pid[:4]}", f"{sha(host(x))} {S.final_iter_} {float(S.final_norm_).hex()} {S.converged_}")
+
+    for where in ("host", "device"):
+        to = (lambda a: np.array(a, dtype=np.float64)) if where == "host" else (lambda a: torch.from_numpy(np.array(a, dtype=np.float64)).to(dev))
+        ti = (lambda a: a) if where == "host" else (lambda a: torch.from_numpy(a).to(dev))
+        # every product form (RowGroup 1, 2, 3 without and with node columns); kdim 5 restarts, max_iter 7 cuts mid-cycle
+        for name in ("n7", "nodes17x2", "nodes12x3_dropped", "nodes12x3", "spd36_cg"):
+            A, b = kc.system(name)
+            rng = np.random.default_rng(83)
+            ess = np.sort(rng.choice(A.shape[0], 3, replace=False)).astype(np.int64)
+            S = LinearSolver(CSRPattern(ti(A.indptr.astype(np.int64)), ti(A.indices.astype(np.int32)), A.nnz), ess)
+            case = f"linear {name} {where}"
+            out(case, "form", f"{S.RowGroup()} {S.NodeColumns()}")
+            solves(case, S, to, A.data, b, ("none", "jacobi"), kdims=(5, 50))
+            solves(case + " cut7", S, to, A.data, b, ("jacobi",), kdims=(5,), max_iter=7)
+            y = S.AddMult(to(A.data), to(seeded(A.shape[0], 84)), to(seeded(A.shape[0], 85)), alpha=-0.75)
+            out(case, "add_mult", sha(host(y)))
+            r, val = to(b), to(A.data)
+            S.Eliminate(r, val)
+            out(case, "eliminate r", sha(host(r)))
+            out(case, "eliminate A", sha(host(val)))
+            solves(case + " eliminated", S, to, host(val), host(r), ("jacobi",))
+            z = S.ApplyPreconditioner(1, to(A.data), to(b), to(np.zeros(len(b))))
+            out(case, "apply kind 1", sha(host(z)))
+        # the Kronecker operator (id 2) on the matrices of two bent blocks, 2-D and 3-D; ids 0 and 1 on the same handle
+        for name, fac0 in (("2d_p3_8x4", 1e-2), ("p2_6x4x2", 1.0)):
+            o = qc.oracle_system(name, fac0)
+            P, B = qc.solve_patch(name)
+            S = LinearSolver(CSRPattern(ti(o.D.rowptr.astype(np.int64)), ti(o.D.col.astype(np.int32)), o.D.nnz), o.ess)
+            S.SetKronecker(KroneckerOperator(B, o.ess, P.dim))
+            S.SetKroneckerCoefficients(qc.RHO, qc.stiff(P.dim, fac0))
+            case = f"linear kron {name} {where}"
+            out(case, "form", f"{S.RowGroup()} {S.NodeColumns()}")
+            solves(case, S, to, o.J.data, o.b, ("kronecker", "jacobi", "none", "kronecker"), kdims=(5, 50), max_iter=120)
+            z = S.ApplyPreconditioner(2, None, to(o.b), to(np.zeros(len(o.b))))
+            out(case, "apply kind 2", sha(host(z)))
+            z = to(o.b)
+            S.ApplyPreconditioner(2, None, z, z)
+            out(case, "apply in place", sha(host(z)))
+            z = S.ApplyPreconditioner(1, to(o.J.data), to(o.b), to(np.zeros(len(o.b))))
+            out(case, "apply kind 1", sha(host(z)))
+
+
+def seeded(n, seed, scale=1.0):
+    import numpy as np
+    return scale * np.random.default_rng(seed).standard_normal(n)
+
+
 def run():
     import numpy as np
     import scipy.sparse as sp
@@ -50,9 +121,6 @@ def run():
     from _cases import product_material
     from mimi_amd.integrators import CSRPattern, NonlinearSolid
     dev = torch.device("cuda", 0)
-
-    def seeded(n, seed, scale=1.0):
-        return scale * np.random.default_rng(seed).standard_normal(n)
 
     def handle(n_el, p, mat, env=None, **kw):
         patch = mimi_amd.BSplinePatch.block(n_el, p)
@@ -122,6 +190,8 @@ def run():
             G.Synchronize()
             out(case, "from " + name, sha(A))
 
+    if "--linear" in sys.argv:
+        return run_linear()
     if "--atomics" in sys.argv:
         os.environ["MIMI_HIP_GENERAL_NO_TWO_PHASE"] = "1"
         for n_el, p, mat in [((4, 3), 2, "neohook"), ((3, 2, 2), 2, "j2simo")]:
@@ -249,6 +319,7 @@ def run():
     for env in (None, {"MIMI_HIP_NO_STRUCTURED": "1"}, None):
         patch, pattern, G = handle((4, 3, 3), 2, "neohook", env=env)
         assemblies("no-structured " + ("set" if env else "unset"), G, patch.n_vdofs, pattern.nnz, "neohook")
+    run_linear()
 
 
 def compare_hashes(a, b):

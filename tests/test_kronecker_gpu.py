@@ -122,7 +122,8 @@ def test_gmres_with_the_kronecker_preconditioner(name, fac0):
 
 
 def test_ids_0_and_1_are_untouched_by_the_operator():
-    """a handle that holds the operator solves with "none" and "jacobi" to the bits of a handle that never saw it"""
+    """a handle that holds the operator solves with "none" and "jacobi" to the bits of a handle that never saw it; and one
+    handle taken through changing matrix values and the ids 1, 2, 0, 2, 1 gives, at every solve, the bits of a fresh one"""
     from mimi_amd.linear import LinearSolver
     name, fac0 = "2d_p3_8x4", 1e-2
     S, J, vals, P, ess, b = _device_system(name, fac0)
@@ -139,6 +140,22 @@ def test_ids_0_and_1_are_untouched_by_the_operator():
         assert got[0][1] > 1
     S.use_jacobi = False                       # the alias of old
     assert S.preconditioner == "none" and not S.use_jacobi
+    # one handle through changing matrix values (rows scaled, so the diagonal moves) and alternating ids, 2 among them:
+    # every solve gives the bytes of a handle made for it
+    _, B = kc.solve_patch(name)
+    rng = np.random.default_rng(73)
+    rows = np.repeat(np.arange(P.n_vdofs), np.diff(np.asarray(S.pattern_.rowptr)))
+    for preconditioner in ("jacobi", "kronecker", "none", "kronecker", "jacobi"):
+        vals = vals * rng.uniform(0.5, 2.0, P.n_vdofs)[rows]
+        got = []
+        for handle in (S, _kronecker_solver(S.pattern_, B, ess, P.dim, kc.RHO, kc.stiff(P.dim, fac0))):
+            handle.preconditioner = preconditioner
+            x = handle.Mult(vals, b, np.full(len(b), np.nan))
+            got.append((x.tobytes(), handle.final_iter_, np.float64(handle.final_norm_).tobytes(), handle.converged_))
+            x = handle.MultCG(vals, b, np.full(len(b), np.nan), max_iter=60)      # (no longer symmetric: a short leash)
+            got.append((x.tobytes(), handle.final_iter_, np.float64(handle.final_norm_).tobytes(), handle.converged_))
+        assert got[0] == got[2] and got[1] == got[3]
+        assert got[0][1] > 1
 
 
 @pytest.mark.parametrize("kind", ["face", "none"])

@@ -104,7 +104,8 @@ def test_x_is_overwritten(name, where):
 @pytest.mark.parametrize("where", ["host", "device"])
 def test_one_handle_reused_across_kdim_and_methods(where):
     """V, the partial sums and the pinned Hessenberg columns grow with kdim, and CG takes V as d, z, q: every solve of the
-    sequence gives the bytes of a fresh handle"""
+    sequence gives the bytes of a fresh handle -- also when the matrix values change between solves and the preconditioner id
+    alternates 1, 0, 1 (the Jacobi scaling belongs to one solve)"""
     name = "spd36_cg"                  # symmetric positive definite: GMRES and CG both solve it
     A, b = kc.system(name)
     sequence = [("gmres", dict(kdim=7)), ("gmres", dict(kdim=50)), ("gmres", dict(kdim=1)), ("cg", dict()), ("gmres", dict(kdim=50))]
@@ -116,6 +117,22 @@ def test_one_handle_reused_across_kdim_and_methods(where):
             got.append(_run(S, method, st, to(A.data), to(b), to(np.full(len(b), np.nan))))
         assert got[0][2] > 0 and got[0][3]
         assert got[0][0].tobytes() == got[1][0].tobytes() and got[0][1:] == got[1][1:]
+    # the matrix values change between solves (rows scaled, so the diagonal moves) and the preconditioner id alternates:
+    # nothing of one solve's Jacobi scaling may reach the next
+    rng = np.random.default_rng(71)
+    rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
+    val = A.data.copy()
+    for jacobi in (True, False, True):
+        val = val * rng.uniform(0.5, 2.0, A.shape[0])[rows]
+        for method in ("gmres", "cg"):
+            # (rows scaled: no longer symmetric, so conjugate gradients get a short leash; their bytes are compared all the same)
+            st = {**(kc.GMRES_DEFAULTS if method == "gmres" else {**kc.CG_DEFAULTS, "max_iter": 60}), "jacobi": jacobi}
+            got = []
+            for S, to in (shared, _solver(A, where)):
+                x, it, nrm, conv = _run(S, method, st, to(val), to(b), to(np.full(len(b), np.nan)))
+                got.append((x.tobytes(), it, np.float64(nrm).tobytes(), conv))
+            assert got[0] == got[1]
+            assert method == "cg" or (got[0][1] > 1 and got[0][3])
 
 
 @pytest.mark.parametrize("copies", [3972, 31776])

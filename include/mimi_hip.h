@@ -230,6 +230,22 @@ int mimi_hip_domain_add_mass(mimi_hip_domain_t h, double density, double* A_valu
 int mimi_hip_domain_add_diffusion(mimi_hip_domain_t h, double viscosity, double* A_values);
 /* r[(A,i)] += b[i] * sum_e sum_q w_q det_q N_a(q);   b: dim doubles on the host              (VectorDomainLFIntegrator) */
 int mimi_hip_domain_add_body_force(mimi_hip_domain_t h, const double* b, double* r);
+/* ---- tangent action: the product with the Jacobian without the matrix.  Together the two entries stand in for
+ * forms::Nonlinear::AddMultGrad followed by SparseMatrix::Mult inside the reference's GMRES: linearize() is the part of
+ * AddMultGrad that depends on u, apply_tangent() the product with what it assembled.
+ * linearize: the snapshot of the tangent at u -- the committed state, the dt of set_dt; changes no state.  Neo-Hookean
+ * handles keep a device copy of u and nothing per point (the action recomputes F); every other material keeps the record
+ * w det dP/dF, dim^4 doubles per point.  A later commit, set_dt, or the caller overwriting u does not change what
+ * apply_tangent returns.  u host or device. */
+int mimi_hip_domain_linearize(mimi_hip_domain_t h, const double* u);
+/* y += density * M x + stiffness * K(u_lin) x + viscosity * C x over the handle's elements (boxes and ranks compose by
+ * addition); M, C the forms of mimi_hip_domain_add_mass / _add_diffusion with coefficient 1, K the tangent
+ * add_residual_and_grad assembles with grad_factor 1.  No essential dofs (the caller masks).  x, y host or device.
+ * stiffness != 0 needs a linearize() first; stiffness == 0 needs none.  The mass term on a flat-table handle needs
+ * mimi_hip_domain_set_shape_values.  No atomics: equal inputs give equal bytes.  Stands in for SparseMatrix::Mult on the
+ * matrix forms::Nonlinear::AddMultGrad assembled. */
+int mimi_hip_domain_apply_tangent(mimi_hip_domain_t h, double density, double stiffness, double viscosity,
+                                  const double* x, double* y);
 /* The two-step form of mimi_hip_domain_add_residual_and_grad, for a caller that needs some rows before the others (the
  * rows a neighbour rank is waiting for: mimi_amd/parallel.py, bench.py): integrate() runs the integration kernels of the
  * whole handle -- element row pieces and element residual pieces into the handle's scratch, nothing into r / A_values --
@@ -252,7 +268,9 @@ int mimi_hip_domain_phase_ms_detail(mimi_hip_domain_t h, double* prepass_ms, dou
 /* sizes: what = 0 n_elements, 1 n_quad, 2 n_dof, 3 nnz, 4 n_vdofs, 5 path (0 general, 1 tensor), 6 CSR kind (0 any,
  * 1 structured lexicographic, 2 structured permuted), 7 kernel family of the last assembly on the handle (0 none yet,
  * 1 two-phase tensor degree 2, 2 two-phase tensor degree 3, 3 small-element tensor, 4 general), 8 whether the handle
- * currently holds per-point gradient tables dN_dX (flat-table handles always; patch handles once a general kernel ran) */
+ * currently holds per-point gradient tables dN_dX (flat-table handles always; patch handles once a general kernel ran),
+ * 9 kernel family of the last tangent action on the handle (the codes of 7), 10 bytes of linearisation record the handle
+ * holds (0 before a linearize and on neo-Hookean handles) */
 int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what);
 
 /* ---- structured sparsity: PrecomputedData::PrepareSparsity (precomputed.cpp:151-174) ----
@@ -517,6 +535,14 @@ int mimi_hip_linear_set_kronecker_coefficients(mimi_hip_linear_t h, double mass_
 /* z = M r with the preconditioner the solvers apply: kind 1 Jacobi (z = r / diag(A); needs A_values), 2 Kronecker
  * (A_values may be NULL).  Host or device arrays; z == r is allowed. */
 int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const double* A_values, const double* r, double* z);
+/* A domain handle in place of the matrix: with an operator set, A_values == NULL in mimi_hip_linear_gmres / _cg means
+ * "the product is density M + stiffness K(u_lin) + viscosity C of `domain`" (mimi_hip_domain_apply_tangent), eliminated
+ * like the matrix: y = mask(A (mask x)) + x[ess].  Stands in for SparseMatrix::Mult on the matrix
+ * forms::Nonlinear::AddMultGrad assembled.  A non-null A_values takes the CSR kernels as ever.  Preconditioner ids 0 and
+ * 2 work with the operator, id 1 (Jacobi) needs the matrix values.  The action runs on the solver's stream; a solve
+ * waits once on the event behind the domain's last linearize.  The domain must be on the solver's device and have its n;
+ * it must outlive the setting.  domain == NULL clears it. */
+int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, double density, double stiffness, double viscosity);
 
 #ifdef __cplusplus
 }

@@ -100,6 +100,7 @@ EXPORTS = [
     "mimi_hip_field_components", "mimi_hip_domain_point_field", "mimi_hip_domain_nodal_field",
     "mimi_hip_domain_set_shape_values",
     "mimi_hip_domain_add_mass", "mimi_hip_domain_add_diffusion", "mimi_hip_domain_add_body_force",
+    "mimi_hip_domain_linearize", "mimi_hip_domain_apply_tangent", "mimi_hip_linear_set_operator",
 ]
 
 
@@ -165,6 +166,9 @@ def lib():
     L.mimi_hip_domain_add_mass.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
     L.mimi_hip_domain_add_diffusion.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
     L.mimi_hip_domain_add_body_force.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mimi_hip_domain_linearize.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_domain_apply_tangent.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p]
+    L.mimi_hip_linear_set_operator.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double]
     L.mimi_hip_domain_set_phase_timing.argtypes = [C.c_void_p, C.c_int]
     L.mimi_hip_domain_phase_ms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mimi_hip_domain_phase_ms_detail.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -1,0 +1,23 @@
+// What the Krylov solvers (krylov.hip) see of a domain handle that stands in for the matrix
+// (mimi_hip_linear_set_operator): its size and device, and the tangent action launched on the SOLVER's stream.  Defined in
+// domain.hip; the kernels are kernels_apply.hpp.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+struct mimi_hip_domain_s;
+
+namespace mimi_hip {
+
+int64_t operator_size(const mimi_hip_domain_s* h);
+int operator_device(const mimi_hip_domain_s* h);
+// once per solve: the checks of mimi_hip_domain_apply_tangent, whatever the action builds on first use (finished before it
+// returns), and one wait of solver_stream on the event recorded behind the last mimi_hip_domain_linearize
+void operator_begin_solve(mimi_hip_domain_s* h, double density, double stiffness, hipStream_t solver_stream);
+// y += density M x + stiffness K x + viscosity C x; x, y on the device, everything on solver_stream
+void operator_add_action(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, const double* x, double* y,
+                         hipStream_t solver_stream);
+
+}  // namespace mimi_hip

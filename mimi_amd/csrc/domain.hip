@@ -4,6 +4,7 @@
 //   NonlinearSolid::AddDomainResidual            integrators/nonlinear_solid.cpp:151-160
 //   NonlinearSolid::AddDomainResidualAndGrad     integrators/nonlinear_solid.cpp:162-177
 //   NonlinearSolid::DomainPostTimeAdvance        integrators/nonlinear_solid.cpp:179-199
+#include "apply_seam.hpp"
 #include "domain_dispatch.hpp"
 
 #include <memory>
@@ -22,6 +23,22 @@ static void require_two_phase(mimi_hip_domain_s* h) {
 // the grad of a tangent assembly's DomainCall in the handle's tangent mode
 static int tangent_grad(const mimi_hip_domain_s* h) { return h->tangent_mode == MIMI_HIP_TANGENT_REFERENCE_FD ? 2 : 1; }
 
+// ---- the operator seam of the Krylov solvers (apply_seam.hpp) ----------------------------------------------------------------
+int64_t operator_size(const mimi_hip_domain_s* h) { return h->n_vdofs; }
+int operator_device(const mimi_hip_domain_s* h) { return h->device; }
+
+void operator_begin_solve(mimi_hip_domain_s* h, double density, double stiffness, hipStream_t solver_stream) {
+  apply_check(h, stiffness);
+  // tables, shape values and the adjacency on the handle's own stream, finished before the solver's stream reads them
+  if (apply_prepare(h, density)) MH_HIP(hipStreamSynchronize(h->stream));
+  if (h->lin_event && stiffness != 0.0) MH_HIP(hipStreamWaitEvent(solver_stream, h->lin_event, 0));
+}
+
+void operator_add_action(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, const double* x, double* y,
+                         hipStream_t solver_stream) {
+  launch_apply(h, density, stiffness, viscosity, x, y, solver_stream);
+}
+
 }  // namespace mimi_hip
 
 using namespace mimi_hip;
@@ -29,6 +46,7 @@ using namespace mimi_hip;
 mimi_hip_domain_s::~mimi_hip_domain_s() {
   for (auto& ev : phase_ev)
     if (ev) (void)hipEventDestroy(ev);
+  if (lin_event) (void)hipEventDestroy(lin_event);
   if (status_dev) (void)hipFree(status_dev);
   if (status_host) (void)hipHostFree(status_host);
 }
@@ -279,6 +297,21 @@ int mimi_hip_domain_add_diffusion(mimi_hip_domain_t h, double viscosity, double*
   });
 }
 
+int mimi_hip_domain_linearize(mimi_hip_domain_t h, const double* u) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    run_linearize(h, u);
+  });
+}
+
+int mimi_hip_domain_apply_tangent(mimi_hip_domain_t h, double density, double stiffness, double viscosity, const double* x,
+                                  double* y) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    run_apply_tangent(h, density, stiffness, viscosity, x, y);
+  });
+}
+
 int mimi_hip_domain_add_body_force(mimi_hip_domain_t h, const double* b, double* r) {
   return guarded([&] {
     if (!h) fail("null handle");
@@ -351,6 +384,8 @@ int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what) {
   case 6: return h->structured_csr ? 1 : (h->structured_perm ? 2 : 0);
   case 7: return h->last_family;
   case 8: return h->dN_dX.ptr ? 1 : 0;
+  case 9: return h->apply_family;
+  case 10: return (h->linearized && h->lin_rec.ptr) ? h->n_pts * (int64_t)(h->dim * h->dim * h->dim * h->dim) * (int64_t)sizeof(double) : 0;
   default: return -1;
   }
 }

@@ -76,5 +76,13 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   mimi_hip::DeviceBuffer<double> lumped_w;
   int64_t longest_row = -1;
 
+  // tangent action (kernels_apply.hpp): what mimi_hip_domain_linearize left -- the device copy of u (neo-Hookean) or the
+  // record w det dP/dF [dim^4][n_pts] (every other material) -- the event recorded behind it (a solver on another stream
+  // waits on it once per solve), the kernel family of the last action (mimi_hip_domain_info(h, 9)), staging for a host x
+  mimi_hip::DeviceBuffer<double> lin_u, lin_rec, stage_x;
+  bool linearized = false;
+  hipEvent_t lin_event = nullptr;
+  int apply_family = 0;
+
   ~mimi_hip_domain_s();
 };

@@ -1,9 +1,11 @@
 // Dispatch of one call of the domain integrator: the general kernels and their row gather, the small-element tensor kernels,
-// the choice between them and the two-phase tensor kernels (tensor_dispatch.hpp), the field output and the linear forms.
+// the choice between them and the two-phase tensor kernels (tensor_dispatch.hpp), the field output, the linear forms and the
+// matrix-free tangent action.
 // Every function reads the call from its DomainCall; the handle keeps only what outlives a call.
 #pragma once
 
 #include "domain_create.hpp"
+#include "kernels_apply.hpp"
 #include "kernels_fields.hpp"
 #include "kernels_forms.hpp"
 #include "tensor_dispatch.hpp"
@@ -494,6 +496,145 @@ inline void run_body_force(mimi_hip_domain_s* h, const double* b, double* r) {
          h->dim == 3 ? b[2] : 0.0, mr.dev);
   mr.finish(h->stream);
   if (mr.host) check_status(h);
+}
+
+// ---- tangent action (kernels_apply.hpp) ----------------------------------------------------------------------------------
+
+// the kernel family an action runs on, with the codes of last_family: the tensor route for every tensor_usable handle
+inline int apply_family_of(const mimi_hip_domain_s* h) {
+  if (tensor_small(h)) return 3;
+  if (tensor_usable(h)) return h->degree[0] == 3 ? 2 : 1;
+  return 4;
+}
+
+// the one switch over what a linearisation leaves: the neo-Hookean action recomputes, every other material has the record
+inline bool apply_recomputes(const mimi_hip_domain_s* h) { return h->mat.m.kind == MIMI_HIP_MAT_NEOHOOKEAN; }
+
+template<int DIM, int P, int MODE, int FAMILY = 0>
+void launch_apply_tensor_dp(mimi_hip_domain_s* h, const TensorArgs& a, const ApplyArgs& aa, hipStream_t stream) {
+  using S = ApplyShape<DIM, P, MODE>;
+  launch(apply_tensor_kernel<DIM, P, MODE, FAMILY>, dim3((unsigned)((h->n_el + S::EPW - 1) / S::EPW)), dim3(S::THREADS),
+         (size_t)S::total * S::EPW * sizeof(double), stream, a, aa);
+}
+
+template<int MODE, int FAMILY = 0>
+void launch_apply_general(mimi_hip_domain_s* h, const ApplyArgs& aa, hipStream_t stream) {
+  const GeneralArgs a = general_args(h, DomainCall{});
+  const size_t lds = ((size_t)2 * h->n_dof * h->dim + (size_t)h->dim * (h->dim + 1) * h->n_q) * sizeof(double);
+  auto kernel = h->dim == 2 ? apply_general_kernel<2, MODE, FAMILY> : apply_general_kernel<3, MODE, FAMILY>;
+  launch(kernel, dim3((unsigned)h->n_el), dim3(256), lds, stream, a, aa);
+}
+
+// what an action needs beyond the handle's own tables, built on h->stream at first use; true when something was launched
+inline bool apply_prepare(mimi_hip_domain_s* h, double density) {
+  MH_HIP(hipSetDevice(h->device));
+  bool built = false;
+  if (!tensor_usable(h)) {
+    // (the mass term on a flat-table handle fails here like add_mass, before anything is built)
+    if (density != 0.0 && !h->shape_N.ptr) {
+      ensure_shape_values(h);
+      built = true;
+    }
+    if (!h->dN_dX.ptr) built = true;
+    ensure_general_tables(h);
+  }
+  if (!h->adj_ptr.ptr && !h->field_adj_ptr.ptr) built = true;
+  const int64_t* adj_ptr = nullptr;
+  const int32_t* adj = nullptr;
+  form_adjacency(h, adj_ptr, adj);
+  const size_t need = (size_t)h->n_el * h->n_dof * h->dim;
+  if (h->scratch_r.count < need) {
+    MH_HIP(hipStreamSynchronize(h->stream));   // (nothing in flight reads the pieces that are released)
+    h->scratch_r.resize(need);
+  }
+  return built;
+}
+
+inline void apply_check(const mimi_hip_domain_s* h, double stiffness) {
+  if (stiffness != 0.0 && !h->linearized)
+    fail("mimi_hip_domain_apply_tangent with a stiffness coefficient before any mimi_hip_domain_linearize on this handle");
+}
+
+// y += density M x + stiffness K(u_lin) x + viscosity C x on `stream`; x, y on the device; apply_prepare has run
+inline void launch_apply(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, const double* x, double* y,
+                         hipStream_t stream) {
+  h->integrated = false;   // the element pieces of an earlier mimi_hip_domain_integrate are overwritten
+  ApplyArgs aa{};
+  aa.density = density;
+  aa.stiffness = stiffness;
+  aa.viscosity = viscosity;
+  aa.x = x;
+  aa.u_lin = h->lin_u.ptr;
+  aa.rec = h->lin_rec.ptr;
+  aa.pieces = h->scratch_r.ptr;
+  aa.N = h->shape_N.ptr;
+  aa.n_pts = h->n_pts;
+  aa.n_el = h->n_el;
+  const bool recompute = apply_recomputes(h);
+  if (tensor_usable(h)) {
+    const TensorArgs a = tensor_args(h, DomainCall{});
+    by_dim_degree(h, [&](auto D, auto Pd) {
+      constexpr int DIM = decltype(D)::value, P = decltype(Pd)::value;
+      if (recompute) launch_apply_tensor_dp<DIM, P, APPLY_NEOHOOKEAN>(h, a, aa, stream);
+      else launch_apply_tensor_dp<DIM, P, APPLY_RECORD>(h, a, aa, stream);
+    });
+  } else {
+    if (recompute) launch_apply_general<APPLY_NEOHOOKEAN>(h, aa, stream); else launch_apply_general<APPLY_RECORD>(h, aa, stream);
+  }
+  const int64_t* adj_ptr = h->adj_ptr.ptr ? h->adj_ptr.ptr : h->field_adj_ptr.ptr;
+  const int32_t* adj = h->adj_ptr.ptr ? h->adj.ptr : h->field_adj.ptr;
+  const int64_t total = h->n_vdofs;
+  launch(apply_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, h->n_vdofs / h->dim, h->n_dof, h->dim, adj_ptr, adj,
+         (const double*)h->scratch_r.ptr, y);
+  h->apply_family = apply_family_of(h);
+}
+
+inline void run_apply_tangent(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, const double* x, double* y) {
+  MH_HIP(hipSetDevice(h->device));
+  if (!x || !y) fail("null vector argument");
+  apply_check(h, stiffness);
+  apply_prepare(h, density);
+  Mirror<double> mx = Mirror<double>::in(x, h->n_vdofs, h->stage_x, h->stream);
+  Mirror<double> my = Mirror<double>::inout(y, h->n_vdofs, h->stage_r, h->stream);
+  launch_apply(h, density, stiffness, viscosity, mx.dev, my.dev, h->stream);
+  my.finish(h->stream);
+  if (mx.host || my.host) check_status(h);   // synchronous for host-resident arguments
+}
+
+// the snapshot of the tangent at u: committed state, the dt of set_dt; no state changes
+inline void run_linearize(mimi_hip_domain_s* h, const double* u) {
+  MH_HIP(hipSetDevice(h->device));
+  if (!u) fail("null vector argument");
+  // (an action launched by a solver on another stream has ended with its solve: nothing reads what is overwritten here)
+  if (apply_recomputes(h)) {
+    h->lin_u.resize((size_t)h->n_vdofs);
+    MH_HIP(hipMemcpyAsync(h->lin_u.ptr, u, (size_t)h->n_vdofs * sizeof(double), hipMemcpyDefault, h->stream));
+    if (!is_device_pointer(u)) MH_HIP(hipStreamSynchronize(h->stream));   // (the caller may overwrite u on return)
+  } else {
+    Mirror<double> mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
+    const int d4 = h->dim * h->dim * h->dim * h->dim;
+    h->lin_rec.resize((size_t)h->n_pts * d4);
+    ApplyArgs aa{};
+    aa.u_lin = mu.dev;
+    aa.rec = h->lin_rec.ptr;
+    aa.n_pts = h->n_pts;
+    aa.n_el = h->n_el;
+    if (tensor_usable(h)) {
+      const TensorArgs a = tensor_args(h, DomainCall{});
+      by_dim_degree(h, [&](auto D, auto Pd) {
+        by_material_family(h->mat.m.kind, [&](auto K) {
+          launch_apply_tensor_dp<decltype(D)::value, decltype(Pd)::value, APPLY_LINEARIZE, decltype(K)::value>(h, a, aa, h->stream);
+        });
+      });
+    } else {
+      ensure_general_tables(h);
+      by_material_family(h->mat.m.kind, [&](auto K) { launch_apply_general<APPLY_LINEARIZE, decltype(K)::value>(h, aa, h->stream); });
+    }
+    if (mu.host) check_status(h);
+  }
+  if (!h->lin_event) MH_HIP(hipEventCreateWithFlags(&h->lin_event, hipEventDisableTiming));
+  MH_HIP(hipEventRecord(h->lin_event, h->stream));
+  h->linearized = true;
 }
 
 }  // namespace mimi_hip

@@ -8,7 +8,8 @@
 //       submodule of the reference; what is restated here is its published algorithm (mfem linalg/solvers.cpp,
 //       GMRESSolver::Mult): left-preconditioned restarted GMRES(m = 50), modified Gram-Schmidt, Givens rotations,
 //       convergence on the preconditioned residual  |s_{i+1}| <= max(rel_tol * ||M r_0||, abs_tol).
-//   Beyond the reference: M may be the Kronecker (fast-diagonalisation) operator of kronecker.hpp instead of Jacobi
+//   Beyond the reference: the matrix may be a domain handle's matrix-free tangent action (mimi_hip_linear_set_operator:
+//       A_values == NULL in a solve), eliminated like the matrix by two vector kernels around it; M may be the Kronecker (fast-diagonalisation) operator of kronecker.hpp instead of Jacobi
 //       (preconditioner id 2 of both solvers); ids 0 and 1 run the kernels and give the bits they always did.
 //
 // Everything vector-sized stays in HBM; per Arnoldi step the host sees one Hessenberg column.  Reductions are
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "../../include/mimi_hip.h"
+#include "apply_seam.hpp"
 #include "common.hpp"
 #include "gmres_host.hpp"
 #include "kronecker.hpp"
@@ -328,6 +330,27 @@ __global__ __launch_bounds__(256) void kr_eliminate_kernel(int64_t n, const int6
   }
 }
 
+// the eliminated product with an operator, y = mask(A (mask x)) + x[ess], around the action "y += A xm":
+// before it xm = mask x, y = 0 ...
+__global__ __launch_bounds__(KR_THREADS) void kr_operator_mask_kernel(int64_t n, const unsigned char* __restrict__ is_ess,
+                                                                      const double* __restrict__ x, double* __restrict__ xm,
+                                                                      double* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * KR_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KR_THREADS) {
+    xm[i] = is_ess[i] ? 0.0 : x[i];
+    y[i] = 0.0;
+  }
+}
+
+// ... behind it y[ess] = x[ess], and y = b - y with b
+__global__ __launch_bounds__(KR_THREADS) void kr_operator_restore_kernel(int64_t n, const unsigned char* __restrict__ is_ess,
+                                                                         const double* __restrict__ x, const double* __restrict__ b,
+                                                                         double* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * KR_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KR_THREADS) {
+    const double t = is_ess[i] ? x[i] : y[i];
+    y[i] = b ? b[i] - t : t;
+  }
+}
+
 __global__ void kr_mark_kernel(int64_t n_ess, const int64_t* __restrict__ ess, unsigned char* __restrict__ is_ess) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k < n_ess) is_ess[ess[k]] = 1;
@@ -351,6 +374,10 @@ struct mimi_hip_linear_s : StreamHandle {
   DeviceBuffer<int32_t> ncol;
   DeviceBuffer<double> dinv, V, w, r, partials, totals, ycoef, stage_val, stage_b, stage_x;
   Kronecker kron;         // mimi_hip_linear_set_kronecker: preconditioner id 2
+  // mimi_hip_linear_set_operator: the domain handle whose tangent action is the product of a solve without matrix values
+  mimi_hip_domain_s* op_domain = nullptr;
+  double op_density = 0.0, op_stiffness = 0.0, op_viscosity = 0.0;
+  DeviceBuffer<double> op_x;   // the masked input of the action
   DeviceBuffer<int> status;                      // one word: what the pattern checks of create found
   double* column_host[2] = {nullptr, nullptr};   // pinned: the Hessenberg column of the step before last and of the last one
   hipEvent_t column_ready[2] = {nullptr, nullptr};
@@ -390,8 +417,15 @@ void by_product_form(const mimi_hip_linear_s* h, F&& f) {
 
 dim3 wave_per_unit(int64_t units) { return dim3((unsigned)((units + 3) / 4)); }   // workgroups of 256: four waves
 
-// y = dinv o (A x), dinv o (b - A x) with b, plain without dinv
+// y = dinv o (A x), dinv o (b - A x) with b, plain without dinv.  val == nullptr: A is the handle's operator (no dinv then:
+// Jacobi needs the values), y = mask(A (mask x)) + x[ess]
 void spmv(mimi_hip_linear_s* h, const double* val, const double* x, const double* b, const double* dinv, double* y) {
+  if (!val) {
+    launch(kr_operator_mask_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, (const unsigned char*)h->is_ess.ptr, x, h->op_x.ptr, y);
+    operator_add_action(h->op_domain, h->op_density, h->op_stiffness, h->op_viscosity, h->op_x.ptr, y, h->stream);
+    launch(kr_operator_restore_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, (const unsigned char*)h->is_ess.ptr, x, b, y);
+    return;
+  }
   by_product_form(h, [&](auto R, auto NC, int64_t n_units, const int32_t* col) {
     launch(kr_spmv_kernel<decltype(R)::value, decltype(NC)::value>, wave_per_unit(n_units), dim3(256), 0, h->stream, n_units, h->rowptr,
            col, val, x, b, dinv, y);
@@ -460,6 +494,17 @@ struct Preconditioner {
     launch(kr_cg_precond_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, r, dinv, z, partial_rz);
   }
 };
+
+// the matrix of one solve: the caller's values, or (none given) the operator of the handle, made ready for this solve
+Mirror<double> solve_matrix(mimi_hip_linear_s* h, const double* A_values, int preconditioner) {
+  if (A_values) return Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, h->stream);
+  if (!h->op_domain) fail("null argument (no matrix values, and no operator is set: mimi_hip_linear_set_operator)");
+  if (preconditioner == PRECOND_JACOBI) fail("the Jacobi preconditioner needs the matrix values");
+  h->op_x.resize((size_t)h->n);
+  operator_begin_solve(h->op_domain, h->op_density, h->op_stiffness, h->stream);
+  MH_HIP(hipSetDevice(h->device));
+  return Mirror<double>{};
+}
 
 // every exit of a solve: what it reports, and x back to a caller on the host
 struct SolveExit {
@@ -598,12 +643,12 @@ int mimi_hip_linear_add_mult(mimi_hip_linear_t h, const double* A_values, const 
 int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol, double abs_tol,
                           int max_iter, int kdim, int preconditioner, int32_t* iterations, double* final_norm, int32_t* converged) {
   return guarded([&] {
-    if (!h || !A_values || !b || !x) fail("null argument");
+    if (!h || !b || !x) fail("null argument");
     if (kdim < 1) kdim = 50;   // mfem::GMRESSolver default m
     MH_HIP(hipSetDevice(h->device));
     const int64_t n = h->n;
     hipStream_t s = h->stream;
-    Mirror<double> mA = Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, s);
+    Mirror<double> mA = solve_matrix(h, A_values, preconditioner);
     Mirror<double> mb = Mirror<double>::in(b, (size_t)n, h->stage_b, s);
     Mirror<double> mx = Mirror<double>::inout(x, (size_t)n, h->stage_x, s);   // overwritten: iterative_mode == false
     h->V.resize((size_t)(kdim + 1) * n);
@@ -693,11 +738,11 @@ int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const dou
 int mimi_hip_linear_cg(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol, double abs_tol,
                        int max_iter, int preconditioner, int32_t* iterations, double* final_norm, int32_t* converged) {
   return guarded([&] {
-    if (!h || !A_values || !b || !x) fail("null argument");
+    if (!h || !b || !x) fail("null argument");
     MH_HIP(hipSetDevice(h->device));
     const int64_t n = h->n;
     hipStream_t s = h->stream;
-    Mirror<double> mA = Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, s);
+    Mirror<double> mA = solve_matrix(h, A_values, preconditioner);
     Mirror<double> mb = Mirror<double>::in(b, (size_t)n, h->stage_b, s);
     Mirror<double> mx = Mirror<double>::inout(x, (size_t)n, h->stage_x, s);
     h->V.resize((size_t)3 * n);            // d, z, q
@@ -785,6 +830,22 @@ int mimi_hip_linear_set_kronecker_coefficients(mimi_hip_linear_t h, double mass_
     k.mass = mass_coef;
     for (int e = 0; e < h->kron.dim * h->kron.dim; ++e) k.stiff[e] = stiff_coef[e];
     h->kron.set_coefficients(k, h->stream);
+  });
+}
+
+int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, double density, double stiffness, double viscosity) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    if (domain) {
+      if (operator_device(domain) != h->device)
+        fail("operator: the domain handle is on device %d, the solver on device %d", operator_device(domain), h->device);
+      if (operator_size(domain) != h->n)
+        fail("operator: the domain handle has %lld dofs, the solver %lld", (long long)operator_size(domain), (long long)h->n);
+    }
+    h->op_domain = domain;
+    h->op_density = density;
+    h->op_stiffness = stiffness;
+    h->op_viscosity = viscosity;
   });
 }
 

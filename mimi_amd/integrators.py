@@ -304,6 +304,31 @@ class NonlinearSolid(NonlinearBase):
         check(_capi.lib().mimi_hip_domain_add_body_force(self._handle(), ptr(b), fptr(r)))
         return r
 
+    # -- matrix-free tangent action (mimi_hip.h: "tangent action") ------------------------------------
+    def Linearize(self, u):
+        """the snapshot of the tangent at u (committed state, the pushed dt; no state changes) that ApplyTangent's stiffness
+        term reads: a device copy of u on neo-Hookean handles, the record w det dP/dF per point on every other material.
+        Stands in, with ApplyTangent, for AddMultGrad followed by SparseMatrix::Mult inside the reference's GMRES."""
+        self._push_dt()
+        self._follow_torch(u)
+        check(_capi.lib().mimi_hip_domain_linearize(self._handle(), fptr(u)))
+
+    def ApplyTangent(self, x, y, stiffness=1.0, density=0.0, viscosity=0.0):
+        """y += density M x + stiffness K(u of Linearize) x + viscosity C x over this handle's elements, without a matrix; M and
+        C the forms of AddMass / AddDiffusion with coefficient 1.  No essential dofs.  numpy arrays or torch device tensors."""
+        self._follow_torch(x, y)
+        check(_capi.lib().mimi_hip_domain_apply_tangent(self._handle(), float(density), float(stiffness), float(viscosity),
+                                                        fptr(x), fptr(y)))
+        return y
+
+    def LastActionFamily(self):
+        """which kernel family the last ApplyTangent on this handle ran on (mimi_hip_domain_info(h, 9))"""
+        return self.KERNEL_FAMILIES[int(_capi.lib().mimi_hip_domain_info(self._handle(), 9))]
+
+    def LinearizationBytes(self):
+        """bytes of linearisation record the handle holds (mimi_hip_domain_info(h, 10)): 0 on neo-Hookean handles"""
+        return int(_capi.lib().mimi_hip_domain_info(self._handle(), 10))
+
     def HoldsGradientTables(self):
         """whether the handle holds per-point gradient tables (mimi_hip_domain_info(h, 8))"""
         return bool(_capi.lib().mimi_hip_domain_info(self._handle(), 8))

@@ -87,8 +87,20 @@ class LinearSolver(_capi.Handle):
         check(_capi.lib().mimi_hip_linear_apply_preconditioner(self._h, int(kind), fptr(A_values), fptr(r), fptr(z)))
         return z
 
+    def SetOperator(self, domain, density, stiffness, viscosity):
+        """a domain integrator in place of the matrix: Mult(None, b, x) / MultCG(None, b, x) then solve with the product
+        density M + stiffness K(u of domain.Linearize) + viscosity C, eliminated like the matrix.  Preconditioners "none" and
+        "kronecker"; "jacobi" needs the matrix values.  Solves that pass values run as ever."""
+        check(_capi.lib().mimi_hip_linear_set_operator(self._h, domain._handle(), float(density), float(stiffness), float(viscosity)))
+        self._operator = domain          # (the library reads the handle during every solve)
+
+    def ClearOperator(self):
+        check(_capi.lib().mimi_hip_linear_set_operator(self._h, None, 0.0, 0.0, 0.0))
+        self._operator = None
+
     def Mult(self, A_values, b, x):
-        """x = A^-1 b to the configured tolerances (x is overwritten: iterative_mode false)"""
+        """x = A^-1 b to the configured tolerances (x is overwritten: iterative_mode false); A_values None: the operator of
+        SetOperator"""
         it, conv, nrm = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
         self._follow_torch(A_values, b, x)
         check(_capi.lib().mimi_hip_linear_gmres(self._h, fptr(A_values), fptr(b), fptr(x), self.rel_tol, self.abs_tol,

@@ -357,6 +357,19 @@ class NonlinearSolid(Solid):
             raise RuntimeError("use_kronecker_preconditioner cannot be combined with a periodic boundary "
                                "(boundary_condition.initial.periodic): the folded numbering needs periodic 1-D matrices, "
                                "which the Kronecker preconditioner does not build -- unset one of the two")
+        # "matrix_free": the Newton solves take the domain integrator's tangent action in place of the assembled Jacobian
+        # (LinearSolver.SetOperator); only what the action covers
+        if rc is not None and rc.get_int("matrix_free", 0):
+            if not (rc.get_int("use_iterative_solver", 0) and rc.get_int("use_kronecker_preconditioner", 0)):
+                raise RuntimeError("matrix_free needs use_iterative_solver and use_kronecker_preconditioner: without matrix values "
+                                   "there is neither a direct solve nor a Jacobi preconditioner")
+            if bc.initial.contact_ or bc.current.contact_:
+                raise RuntimeError("matrix_free cannot be combined with a contact marker: the contact tangent has no matrix-free action")
+            if bc.initial.pressure_:
+                raise RuntimeError("matrix_free cannot be combined with a follower pressure marker: the pressure tangent has no "
+                                   "matrix-free action")
+            if axes:
+                raise RuntimeError("matrix_free cannot be combined with a periodic boundary: the action runs in the unwrapped numbering")
         self.patch_ = patch = self.patch()
         n = patch.n_vdofs
         # the integrators' pattern: the patch's unwrapped structured one (the tensor kernels' own) -- with periodic
@@ -589,6 +602,7 @@ class NonlinearSolid(Solid):
         if self.use_kronecker_:
             self.linear_.SetKronecker(KroneckerOperator(patch, self.dirichlet_, dim))
             self.linear_.preconditioner = "kronecker"
+        self.matrix_free_ = bool(rc.get_int("matrix_free", 0))       # (what it needs was checked at the top of setup)
         if not self.host_setup_:
             self._device_setup()
         self._to_device()
@@ -640,7 +654,8 @@ class NonlinearSolid(Solid):
             self.d_visc_ = f(self.visc_) if self.visc_ is not None else None
         self.d_rhs_ = f(self.rhs_)
         self._rhs = self.d_rhs_           # what the residual subtracts (_update_rhs)
-        self.d_jac_ = torch.zeros_like(self.d_mass_)
+        if not self.matrix_free_:
+            self.d_jac_ = torch.zeros_like(self.d_mass_)
         self.d_dirichlet_ = torch.from_numpy(np.asarray(self.dirichlet_, dtype=np.int64)).to(dev)
         self.d_x_, self.d_v_ = f(self.x), f(self.x_dot)
         if self.fold_ is not None:
@@ -710,6 +725,18 @@ class NonlinearSolid(Solid):
         # where "+=" would read J (mimi_hip_domain_add_residual_and_grad_from) -- no 2 x nnz copy, and the domain
         # integrator of a single-patch solid touches every row
         self._push(self.domain_)
+        if self.matrix_free_:
+            # no Jacobian: the residual-only assembly, the snapshot of the tangent at x_t, and the solver's product becomes
+            # rho M + fac0 K(x_t) + fac1 eta C of the domain integrator (no contact, pressure or periodic pair: setup)
+            self.domain_.AddDomainResidual(xt, y)
+            self.domain_.Linearize(xt)
+            eta = getattr(self.material, "viscosity", -1.0)
+            self.linear_.SetOperator(self.domain_, self.material.density, self._fac0,
+                                     self._fac1 * eta if self.d_visc_ is not None else 0.0)
+            self.linear_.Eliminate(y, None)
+            y -= self._rhs
+            self.linear_.Eliminate(y, None)
+            return y, None
         if self.fold_ is not None:
             # periodic route: expand x_t, every integrator into the zeroed unwrapped r_u / A_u, then ONE fold
             # y += P^T r_u, J = M + P^T A_u P in place of the from-base pass

@@ -1,11 +1,11 @@
 // C ABI of the domain integrator (include/mimi_hip.h): handle life cycle, table upload / generation, assemblies.  Handle
-// construction is domain_create.hpp, the kernel dispatch domain_dispatch.hpp.  Reference counterparts:
+// construction is domain_create.hpp, the kernel dispatch domain_dispatch.hpp and domain_dispatch_nodal.hpp.  Reference counterparts:
 //   NonlinearSolid::Prepare                      integrators/nonlinear_solid.cpp:31-46
 //   NonlinearSolid::AddDomainResidual            integrators/nonlinear_solid.cpp:151-160
 //   NonlinearSolid::AddDomainResidualAndGrad     integrators/nonlinear_solid.cpp:162-177
 //   NonlinearSolid::DomainPostTimeAdvance        integrators/nonlinear_solid.cpp:179-199
 #include "apply_seam.hpp"
-#include "domain_dispatch.hpp"
+#include "domain_dispatch_nodal.hpp"
 
 #include <memory>
 

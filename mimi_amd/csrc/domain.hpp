@@ -20,8 +20,8 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   mimi_hip::DeviceBuffer<double> wdet;       // [n_el][n_q]
   mimi_hip::DeviceBuffer<int32_t> pair_pos;  // [n_el][n_dof][n_dof]
   mimi_hip::DeviceBuffer<int64_t> rowptr_own;
-  mimi_hip::DeviceBuffer<int64_t> adj_ptr;   // two-phase general path: node -> incident (element, local index) list
-  mimi_hip::DeviceBuffer<int32_t> adj;
+  mimi_hip::DeviceBuffer<int64_t> adj_ptr;   // node -> incident (element << 6 | local node) list, built at first use (node_adjacency):
+  mimi_hip::DeviceBuffer<int32_t> adj;       // the general row gather, the form kernels, the node gather of fields and actions
   bool general_two_phase_failed = false;
   const int64_t* rowptr = nullptr;           // device
 
@@ -65,15 +65,12 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   mimi_hip::DeviceBuffer<double> stage_u, stage_r, stage_A;
 
   // field output (kernels_fields.hpp): shape values of the general route [n_el][n_q][n_dof], element pieces of the nodal
-  // form [n_el][n_dof][ncomp + 1], a node -> (element, local node) adjacency when the handle has none yet (adj_ptr / adj
-  // belong to the general row gather, which checks the CSR rows before it builds them), staging for host-resident outputs
+  // form [n_el][n_dof][ncomp + 1], staging for host-resident outputs
   mimi_hip::DeviceBuffer<double> shape_N, field_pieces, stage_f, stage_w;
-  mimi_hip::DeviceBuffer<int64_t> field_adj_ptr;
-  mimi_hip::DeviceBuffer<int32_t> field_adj;
 
-  // linear forms (kernels_forms.hpp): the lumped weight of the body force [n_nodes]; the longest CSR row, once the general
-  // route has measured it (its row image is GG_MAX_ROW entries)
+  // linear forms (kernels_forms.hpp): the lumped weight of the body force [n_nodes]
   mimi_hip::DeviceBuffer<double> lumped_w;
+  // the longest CSR row, once longest_row(h) has scanned it (the row image of the general gathers is GG_MAX_ROW entries)
   int64_t longest_row = -1;
 
   // tangent action (kernels_apply.hpp): what mimi_hip_domain_linearize left -- the device copy of u (neo-Hookean) or the

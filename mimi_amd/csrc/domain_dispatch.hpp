@@ -1,6 +1,7 @@
-// Dispatch of one call of the domain integrator: the general kernels and their row gather, the small-element tensor kernels,
-// the choice between them and the two-phase tensor kernels (tensor_dispatch.hpp), the field output, the linear forms and the
-// matrix-free tangent action.
+// Dispatch of one call of the domain integrator: what every route asks of the handle (the general tables, the node adjacency,
+// the longest CSR row, the switch over dimension and degree), the general kernels and their row gather, the small-element
+// tensor kernels, the choice between them and the two-phase tensor kernels (tensor_dispatch.hpp).  The field output, the
+// linear forms and the matrix-free tangent action are domain_dispatch_nodal.hpp, on top of this header.
 // Every function reads the call from its DomainCall; the handle keeps only what outlives a call.
 #pragma once
 
@@ -44,21 +45,32 @@ inline GeneralArgs general_args(mimi_hip_domain_s* h, const DomainCall& c) {
   return a;
 }
 
+// calls f(integral_constant DIM)
+template<class F>
+void by_dim(const mimi_hip_domain_s* h, F&& f) {
+  if (h->dim == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, 3>{});
+}
+
 // calls f(integral_constant DIM, integral_constant P) for a tensor_usable handle (tensor_supported: one degree, 1..3)
 template<class F>
 void by_dim_degree(const mimi_hip_domain_s* h, F&& f) {
-  auto by_degree = [&](auto D) {
+  by_dim(h, [&](auto D) {
     switch (h->degree[0]) {
     case 1: f(D, std::integral_constant<int, 1>{}); break;
     case 2: f(D, std::integral_constant<int, 2>{}); break;
     default: f(D, std::integral_constant<int, 3>{}); break;
     }
-  };
-  if (h->dim == 2) by_degree(std::integral_constant<int, 2>{}); else by_degree(std::integral_constant<int, 3>{});
+  });
 }
 
-// node -> incident (element << 6 | local node) lists of the general row gather
-inline void fill_adjacency(mimi_hip_domain_s* h, DeviceBuffer<int64_t>& adj_ptr, DeviceBuffer<int32_t>& adj_out) {
+// the handle's node -> incident (element << 6 | local node) lists, built at first use: what the general row gather, the form
+// kernels and node_gather_kernel walk
+struct NodeAdjacency {
+  const int64_t* ptr;
+  const int32_t* adj;
+};
+inline NodeAdjacency node_adjacency(mimi_hip_domain_s* h) {
+  if (h->adj_ptr.ptr) return {h->adj_ptr.ptr, h->adj.ptr};
   const size_t n = (size_t)h->n_el * h->n_dof;
   const std::vector<int32_t> dofs = to_host(h->dofs.ptr, n);
   const int64_t n_nodes = h->n_vdofs / h->dim;
@@ -68,28 +80,33 @@ inline void fill_adjacency(mimi_hip_domain_s* h, DeviceBuffer<int64_t>& adj_ptr,
   std::vector<int32_t> adj(n);
   std::vector<int64_t> fill(ptr.begin(), ptr.end() - 1);
   for (size_t k = 0; k < n; ++k) adj[fill[dofs[k]]++] = (int32_t)(((k / h->n_dof) << 6) | (k % h->n_dof));
-  adj_ptr.assign(ptr.data(), ptr.size(), h->stream);
-  adj_out.assign(adj.data(), adj.size(), h->stream);
+  h->adj_ptr.assign(ptr.data(), ptr.size(), h->stream);
+  h->adj.assign(adj.data(), adj.size(), h->stream);
+  return {h->adj_ptr.ptr, h->adj.ptr};
 }
 
-inline void build_adjacency(mimi_hip_domain_s* h) { fill_adjacency(h, h->adj_ptr, h->adj); }
+// the longest CSR row, scanned once (the row gathers keep one row in LDS, GG_MAX_ROW entries)
+inline int64_t longest_row(mimi_hip_domain_s* h) {
+  if (h->longest_row < 0) {
+    const std::vector<int64_t> rp = to_host(h->rowptr, (size_t)h->n_vdofs + 1);
+    h->longest_row = 0;
+    for (int64_t v = 0; v < h->n_vdofs; ++v) h->longest_row = std::max(h->longest_row, rp[v + 1] - rp[v]);
+  }
+  return h->longest_row;
+}
 
 // two-phase general path: element blocks / residual vectors densely into scratch_k / scratch_r, then
 // general_gather_kernel.  Needs n_el * n_tdof^2 doubles (77 GB at 128 x 128 x 16 p = 3) and the node -> element adjacency;
-// falls back to the atomics when the scratch does not fit (MIMI_HIP_GENERAL_NO_TWO_PHASE=1 forces that)
+// falls back to the atomics when the scratch does not fit (MIMI_HIP_GENERAL_NO_TWO_PHASE=1 forces that).  What it decides
+// depends on the CSR rows, the element size and the memory alone, never on what ran on the handle before
 inline bool ensure_general_two_phase(mimi_hip_domain_s* h, bool with_k) {
   if (env_general_no_two_phase() || h->general_two_phase_failed) return false;
   const size_t n_tdof = (size_t)h->n_dof * h->dim;
-  // what rules the path out is checked BEFORE anything is allocated (3-D degree >= 4 would be 1.1 MB per element)
-  if (!h->adj_ptr.ptr) {
-    // the gather kernel keeps one CSR row in LDS: rows longer than its image -> atomics
-    const std::vector<int64_t> rp = to_host(h->rowptr, (size_t)h->n_vdofs + 1);
-    int64_t longest = 0;
-    for (int64_t v = 0; v < h->n_vdofs; ++v) longest = std::max(longest, rp[v + 1] - rp[v]);
-    if (longest > GG_MAX_ROW || h->n_dof > 64) {
-      h->general_two_phase_failed = true;
-      return false;
-    }
+  // what rules the path out is checked BEFORE anything is allocated (3-D degree >= 4 would be 1.1 MB per element).
+  // The gather kernel keeps one CSR row in LDS: rows longer than its image -> atomics
+  if (longest_row(h) > GG_MAX_ROW || h->n_dof > 64) {
+    h->general_two_phase_failed = true;
+    return false;
   }
   const size_t need = with_k ? (size_t)h->n_el * n_tdof * n_tdof : 0;
   if (h->scratch_k.count < need) {
@@ -105,7 +122,7 @@ inline bool ensure_general_two_phase(mimi_hip_domain_s* h, bool with_k) {
     h->scratch_k.resize(need);
   }
   h->scratch_r.resize((size_t)h->n_el * n_tdof);
-  if (!h->adj_ptr.ptr) build_adjacency(h);
+  node_adjacency(h);
   return true;
 }
 
@@ -113,10 +130,12 @@ inline bool ensure_general_two_phase(mimi_hip_domain_s* h, bool with_k) {
 // (A_old: the call's base array, or A itself)
 inline void launch_general_gather(mimi_hip_domain_s* h, const DomainCall& c) {
   const int64_t n_rows = h->n_vdofs;
-  auto kernel = h->dim == 2 ? (c.grad ? general_gather_kernel<2, 1> : general_gather_kernel<2, 0>)
-                            : (c.grad ? general_gather_kernel<3, 1> : general_gather_kernel<3, 0>);
-  launch(kernel, dim3((unsigned)((n_rows + GG_WAVES - 1) / GG_WAVES)), dim3(64 * GG_WAVES), 0, h->stream, n_rows, h->n_dof, h->rowptr,
-         h->adj_ptr.ptr, h->adj.ptr, h->pair_pos.ptr, h->scratch_k.ptr, h->scratch_r.ptr, c.grad_factor, c.A_old(), c.A, c.r);
+  by_dim(h, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    launch(c.grad ? general_gather_kernel<DIM, 1> : general_gather_kernel<DIM, 0>, dim3((unsigned)((n_rows + GG_WAVES - 1) / GG_WAVES)),
+           dim3(64 * GG_WAVES), 0, h->stream, n_rows, h->n_dof, h->rowptr, h->adj_ptr.ptr, h->adj.ptr, h->pair_pos.ptr, h->scratch_k.ptr,
+           h->scratch_r.ptr, c.grad_factor, c.A_old(), c.A, c.r);
+  });
 }
 
 #ifndef GEN_BIG_PP
@@ -180,7 +199,7 @@ void launch_general_dim(mimi_hip_domain_s* h, const DomainCall& c) {
 
 inline void launch_general(mimi_hip_domain_s* h, const DomainCall& c) {
   ensure_general_tables(h);
-  if (h->dim == 2) launch_general_dim<2>(h, c); else launch_general_dim<3>(h, c);
+  by_dim(h, [&](auto D) { launch_general_dim<decltype(D)::value>(h, c); });
 }
 
 // DomainPostTimeAdvance on the general tables
@@ -190,8 +209,7 @@ inline void launch_general_post(mimi_hip_domain_s* h, const DomainCall& c) {
   const size_t lds = (size_t)h->n_dof * h->dim * sizeof(double);
   by_material_family(h->mat.m.kind, [&](auto K) {
     constexpr int REC = decltype(K)::value != 0 ? 1 : 0;
-    auto kernel = h->dim == 2 ? post_time_advance_general_kernel<2, REC> : post_time_advance_general_kernel<3, REC>;
-    launch(kernel, dim3(h->n_el), dim3(256), lds, h->stream, a);
+    by_dim(h, [&](auto D) { launch(post_time_advance_general_kernel<decltype(D)::value, REC>, dim3(h->n_el), dim3(256), lds, h->stream, a); });
   });
 }
 
@@ -289,352 +307,6 @@ inline void run_post_time_advance(mimi_hip_domain_s* h, const double* u) {
   else if (h->path == 1) launch_tensor_post(h, c);
   else launch_general_post(h, c);
   if (mu.host) check_status(h);
-}
-
-// ---- field output (kernels_fields.hpp) ---------------------------------------------------------------------------------
-
-// by_material_family with neo-Hookean as a family of its own (FIELD_NEOHOOKEAN)
-template<class F>
-void by_field_family(int kind, F&& f) {
-  if (kind == MIMI_HIP_MAT_NEOHOOKEAN) f(std::integral_constant<int, FIELD_NEOHOOKEAN>{});
-  else by_material_family(kind, f);
-}
-
-// N[e][q][a] of the general route's nodal form: the caller's on a flat-table handle, expanded from the 1-D tables on a
-// patch handle
-inline void ensure_shape_values(mimi_hip_domain_s* h) {
-  if (h->shape_N.ptr) return;
-  if (!h->geo.ptr)
-    fail("nodal field on a flat-table handle: the tables carry no shape values, give them with mimi_hip_domain_set_shape_values");
-  const int64_t total = (int64_t)h->n_el * h->n_q * h->n_dof;
-  h->shape_N.resize((size_t)total);
-  auto kernel = h->dim == 2 ? expand_shape_kernel<2> : expand_shape_kernel<3>;
-  launch(kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, patch_dev(h, nullptr), h->shape_N.ptr);
-}
-
-template<int DIM, int P>
-void launch_field_tensor_dp(mimi_hip_domain_s* h, const TensorArgs& a, const FieldArgs& fa) {
-  by_field_family(h->mat.m.kind, [&](auto K) {
-    launch(field_tensor_kernel<DIM, P, decltype(K)::value>, dim3((unsigned)h->n_el), dim3(FieldShape<DIM, P>::THREADS),
-           (size_t)FieldShape<DIM, P>::total(fa.ncomp + 1) * sizeof(double), h->stream, a, fa);
-  });
-}
-
-// the element kernel of the handle's route: the tensor kernel for every tensor_usable handle (no per-point table is built),
-// the general kernel otherwise
-inline void launch_field(mimi_hip_domain_s* h, const double* u, FieldArgs fa) {
-  const DomainCall c{u};
-  if (tensor_usable(h)) {
-    const TensorArgs a = tensor_args(h, c);
-    by_dim_degree(h, [&](auto D, auto Pd) { launch_field_tensor_dp<decltype(D)::value, decltype(Pd)::value>(h, a, fa); });
-    return;
-  }
-  ensure_general_tables(h);
-  if (fa.nodal) {
-    ensure_shape_values(h);
-    fa.N = h->shape_N.ptr;
-  }
-  const GeneralArgs a = general_args(h, c);
-  const size_t lds = ((size_t)h->n_dof * h->dim + (size_t)(h->dim * h->dim + 1) * h->n_q) * sizeof(double);
-  by_field_family(h->mat.m.kind, [&](auto K) {
-    constexpr int FK = decltype(K)::value;
-    auto kernel = h->dim == 2 ? field_general_kernel<2, FK> : field_general_kernel<3, FK>;
-    launch(kernel, dim3((unsigned)h->n_el), dim3(256), lds, h->stream, a, fa);
-  });
-}
-
-// what a field call checks before anything runs; returns the field's components
-inline int field_begin(mimi_hip_domain_s* h, const double* u, int field, FieldArgs& fa) {
-  MH_HIP(hipSetDevice(h->device));
-  const int ncomp = field_components(field, h->dim);
-  if (ncomp < 0) fail("unknown field id %d", field);
-  const bool of_state = field == MIMI_HIP_FIELD_EQPS || field == MIMI_HIP_FIELD_TEMPERATURE;
-  if (of_state && !material_has_state(h->mat.m.kind)) fail("material has no state");
-  if (!of_state && !u) fail("null vector argument");
-  fa = FieldArgs{};
-  fa.field = field;
-  fa.ncomp = ncomp;
-  fa.need_F = of_state ? 0 : 1;
-  return ncomp;
-}
-
-// out[e][q][c], overwritten
-inline void run_point_field(mimi_hip_domain_s* h, const double* u, int field, double* out, int64_t capacity) {
-  FieldArgs fa;
-  const int ncomp = field_begin(h, u, field, fa);
-  if (!out) fail("null argument");
-  const int64_t need = h->n_pts * ncomp;
-  if (capacity < need) fail("field buffer too small (%lld < %lld)", (long long)capacity, (long long)need);
-  Mirror<double> mu;
-  if (fa.need_F) mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
-  const bool out_host = !is_device_pointer(out);
-  if (out_host) h->stage_f.resize((size_t)need);
-  fa.out = out_host ? h->stage_f.ptr : out;
-  launch_field(h, mu.dev, fa);
-  if (out_host) MH_HIP(hipMemcpyAsync(out, fa.out, (size_t)need * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out_host || mu.host) check_status(h);  // synchronous for host-resident arguments
-}
-
-// sum[A][c] += ..., weight[A] += ... : element pieces, then one thread per (node, component) over the adjacency
-inline void run_nodal_field(mimi_hip_domain_s* h, const double* u, int field, double* sum, double* weight) {
-  FieldArgs fa;
-  const int ncomp = field_begin(h, u, field, fa);
-  if (!sum) fail("null argument");
-  const int64_t n_nodes = h->n_vdofs / h->dim;
-  Mirror<double> mu, mw;
-  if (fa.need_F) mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
-  Mirror<double> ms = Mirror<double>::inout(sum, (size_t)n_nodes * ncomp, h->stage_f, h->stream);
-  if (weight) mw = Mirror<double>::inout(weight, (size_t)n_nodes, h->stage_w, h->stream);
-  h->field_pieces.resize((size_t)h->n_el * h->n_dof * (ncomp + 1));
-  fa.nodal = 1;
-  fa.out = h->field_pieces.ptr;
-  launch_field(h, mu.dev, fa);
-  if (!h->adj_ptr.ptr && !h->field_adj_ptr.ptr) fill_adjacency(h, h->field_adj_ptr, h->field_adj);
-  const int64_t* adj_ptr = h->adj_ptr.ptr ? h->adj_ptr.ptr : h->field_adj_ptr.ptr;
-  const int32_t* adj = h->adj_ptr.ptr ? h->adj.ptr : h->field_adj.ptr;
-  const int64_t total = n_nodes * (ncomp + 1);
-  launch(field_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->stream, n_nodes, h->n_dof, ncomp, adj_ptr, adj,
-         (const double*)h->field_pieces.ptr, ms.dev, mw.dev);
-  ms.finish(h->stream);
-  if (weight) mw.finish(h->stream);
-  if (mu.host || ms.host || mw.host) check_status(h);
-}
-
-// ---- linear forms (kernels_forms.hpp) ----------------------------------------------------------------------------------
-
-// the node -> (element, local node) adjacency: the general row gather's when the handle has it, the field output's otherwise
-inline void form_adjacency(mimi_hip_domain_s* h, const int64_t*& adj_ptr, const int32_t*& adj) {
-  if (!h->adj_ptr.ptr && !h->field_adj_ptr.ptr) fill_adjacency(h, h->field_adj_ptr, h->field_adj);
-  adj_ptr = h->adj_ptr.ptr ? h->adj_ptr.ptr : h->field_adj_ptr.ptr;
-  adj = h->adj_ptr.ptr ? h->adj.ptr : h->field_adj.ptr;
-}
-
-template<int DIM, int P>
-void launch_form_tensor_dp(mimi_hip_domain_s* h, int kind, const TensorArgs& a, const FormArgs& fa) {
-  const int64_t n = (int64_t)fa.node_n[0] * fa.node_n[1] * fa.node_n[2];
-  auto kernel = kind == FORM_MASS ? form_tensor_kernel<DIM, P, FORM_MASS> : form_tensor_kernel<DIM, P, FORM_DIFFUSION>;
-  launch(kernel, dim3((unsigned)n), dim3(FormShape<DIM, P>::THREADS), 0, h->stream, a, fa);
-}
-
-inline void launch_form_tensor(mimi_hip_domain_s* h, int kind, double factor, double* A) {
-  const TensorArgs a = tensor_args(h, DomainCall{});
-  FormArgs fa{};
-  fa.factor = factor;
-  fa.A = A;
-  fa.node_ids = h->node_ids.ptr;
-  fa.pos_mode = h->structured_csr ? 0 : h->structured_perm ? (h->degree[0] == 3 ? 2 : 1) : 3;
-  if (fa.pos_mode == 3 && !h->pair_pos.ptr) fail("pair positions were not built for this handle");
-  const std::vector<int32_t> first = to_host(h->first1d.ptr, h->first1d.count);
-  for (int d = 0; d < 3; ++d) {
-    fa.node_lo[d] = 0;
-    fa.node_n[d] = 1;
-    if (d >= h->dim) continue;
-    fa.node_lo[d] = first[h->first_off[d] + h->el_begin[d]];
-    fa.node_n[d] = first[h->first_off[d] + h->el_end[d] - 1] + h->degree[d] + 1 - fa.node_lo[d];
-  }
-  by_dim_degree(h, [&](auto D, auto Pd) { launch_form_tensor_dp<decltype(D)::value, decltype(Pd)::value>(h, kind, a, fa); });
-}
-
-inline void launch_form_general(mimi_hip_domain_s* h, int kind, double factor, double* A) {
-  if (kind == FORM_MASS && !h->shape_N.ptr && !h->geo.ptr) ensure_shape_values(h);   // (fails before anything is built)
-  ensure_general_tables(h);
-  if (kind == FORM_MASS) ensure_shape_values(h);
-  if (h->longest_row < 0) {
-    const std::vector<int64_t> rp = to_host(h->rowptr, (size_t)h->n_vdofs + 1);
-    int64_t longest = 0;
-    for (int64_t v = 0; v < h->n_vdofs; ++v) longest = std::max(longest, rp[v + 1] - rp[v]);
-    h->longest_row = longest;
-  }
-  if (h->longest_row > GG_MAX_ROW) fail("mass / diffusion form: a CSR row of %lld entries is longer than the row image (%d)", (long long)h->longest_row, GG_MAX_ROW);
-  const int64_t* adj_ptr = nullptr;
-  const int32_t* adj = nullptr;
-  form_adjacency(h, adj_ptr, adj);
-  const int64_t n_nodes = h->n_vdofs / h->dim;
-  auto kernel = h->dim == 2 ? (kind == FORM_MASS ? form_general_kernel<2, FORM_MASS> : form_general_kernel<2, FORM_DIFFUSION>)
-                            : (kind == FORM_MASS ? form_general_kernel<3, FORM_MASS> : form_general_kernel<3, FORM_DIFFUSION>);
-  launch(kernel, dim3((unsigned)((n_nodes + GG_WAVES - 1) / GG_WAVES)), dim3(64 * GG_WAVES), 0, h->stream, n_nodes, h->n_dof, h->n_q, h->rowptr,
-         adj_ptr, adj, (const int32_t*)h->pair_pos.ptr, (const double*)h->shape_N.ptr, (const double*)h->dN_dX.ptr, (const double*)h->wdet.ptr,
-         factor, A);
-}
-
-// A_values += factor * (mass | diffusion form); A host or device
-inline void run_form(mimi_hip_domain_s* h, int kind, double factor, double* A_values) {
-  MH_HIP(hipSetDevice(h->device));
-  if (!A_values) fail("null argument");
-  Mirror<double> mA = Mirror<double>::inout(A_values, h->nnz, h->stage_A, h->stream);
-  if (tensor_usable(h)) launch_form_tensor(h, kind, factor, mA.dev);
-  else launch_form_general(h, kind, factor, mA.dev);
-  mA.finish(h->stream);
-  if (mA.host) check_status(h);   // synchronous for host-resident arguments
-}
-
-// r += b (x) lumped weight; b on the host, r host or device
-inline void run_body_force(mimi_hip_domain_s* h, const double* b, double* r) {
-  MH_HIP(hipSetDevice(h->device));
-  if (!b || !r) fail("null argument");
-  const int64_t n_nodes = h->n_vdofs / h->dim;
-  Mirror<double> mr = Mirror<double>::inout(r, h->n_vdofs, h->stage_r, h->stream);
-  // the nodal field output with no component: element pieces of w det N_a alone, gathered into a zeroed weight.  (The field
-  // named is det F without u: the point routine returns det 0 = 0 before it reads any state or material, and with ncomp 0
-  // nothing of it is staged -- the field kernels run as they are.)
-  FieldArgs fa{};
-  fa.field = MIMI_HIP_FIELD_DET_F;
-  fa.ncomp = 0;
-  fa.nodal = 1;
-  h->field_pieces.resize((size_t)h->n_el * h->n_dof);
-  fa.out = h->field_pieces.ptr;
-  launch_field(h, nullptr, fa);
-  const int64_t* adj_ptr = nullptr;
-  const int32_t* adj = nullptr;
-  form_adjacency(h, adj_ptr, adj);
-  h->lumped_w.resize((size_t)n_nodes);
-  MH_HIP(hipMemsetAsync(h->lumped_w.ptr, 0, (size_t)n_nodes * sizeof(double), h->stream));
-  launch(field_gather_kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, h->stream, n_nodes, h->n_dof, 0, adj_ptr, adj,
-         (const double*)h->field_pieces.ptr, (double*)nullptr, h->lumped_w.ptr);
-  auto kernel = h->dim == 2 ? form_body_force_kernel<2> : form_body_force_kernel<3>;
-  launch(kernel, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, h->stream, n_nodes, (const double*)h->lumped_w.ptr, b[0], b[1],
-         h->dim == 3 ? b[2] : 0.0, mr.dev);
-  mr.finish(h->stream);
-  if (mr.host) check_status(h);
-}
-
-// ---- tangent action (kernels_apply.hpp) ----------------------------------------------------------------------------------
-
-// the kernel family an action runs on, with the codes of last_family: the tensor route for every tensor_usable handle
-inline int apply_family_of(const mimi_hip_domain_s* h) {
-  if (tensor_small(h)) return 3;
-  if (tensor_usable(h)) return h->degree[0] == 3 ? 2 : 1;
-  return 4;
-}
-
-// the one switch over what a linearisation leaves: the neo-Hookean action recomputes, every other material has the record
-inline bool apply_recomputes(const mimi_hip_domain_s* h) { return h->mat.m.kind == MIMI_HIP_MAT_NEOHOOKEAN; }
-
-template<int DIM, int P, int MODE, int FAMILY = 0>
-void launch_apply_tensor_dp(mimi_hip_domain_s* h, const TensorArgs& a, const ApplyArgs& aa, hipStream_t stream) {
-  using S = ApplyShape<DIM, P, MODE>;
-  launch(apply_tensor_kernel<DIM, P, MODE, FAMILY>, dim3((unsigned)((h->n_el + S::EPW - 1) / S::EPW)), dim3(S::THREADS),
-         (size_t)S::total * S::EPW * sizeof(double), stream, a, aa);
-}
-
-template<int MODE, int FAMILY = 0>
-void launch_apply_general(mimi_hip_domain_s* h, const ApplyArgs& aa, hipStream_t stream) {
-  const GeneralArgs a = general_args(h, DomainCall{});
-  const size_t lds = ((size_t)2 * h->n_dof * h->dim + (size_t)h->dim * (h->dim + 1) * h->n_q) * sizeof(double);
-  auto kernel = h->dim == 2 ? apply_general_kernel<2, MODE, FAMILY> : apply_general_kernel<3, MODE, FAMILY>;
-  launch(kernel, dim3((unsigned)h->n_el), dim3(256), lds, stream, a, aa);
-}
-
-// what an action needs beyond the handle's own tables, built on h->stream at first use; true when something was launched
-inline bool apply_prepare(mimi_hip_domain_s* h, double density) {
-  MH_HIP(hipSetDevice(h->device));
-  bool built = false;
-  if (!tensor_usable(h)) {
-    // (the mass term on a flat-table handle fails here like add_mass, before anything is built)
-    if (density != 0.0 && !h->shape_N.ptr) {
-      ensure_shape_values(h);
-      built = true;
-    }
-    if (!h->dN_dX.ptr) built = true;
-    ensure_general_tables(h);
-  }
-  if (!h->adj_ptr.ptr && !h->field_adj_ptr.ptr) built = true;
-  const int64_t* adj_ptr = nullptr;
-  const int32_t* adj = nullptr;
-  form_adjacency(h, adj_ptr, adj);
-  const size_t need = (size_t)h->n_el * h->n_dof * h->dim;
-  if (h->scratch_r.count < need) {
-    MH_HIP(hipStreamSynchronize(h->stream));   // (nothing in flight reads the pieces that are released)
-    h->scratch_r.resize(need);
-  }
-  return built;
-}
-
-inline void apply_check(const mimi_hip_domain_s* h, double stiffness) {
-  if (stiffness != 0.0 && !h->linearized)
-    fail("mimi_hip_domain_apply_tangent with a stiffness coefficient before any mimi_hip_domain_linearize on this handle");
-}
-
-// y += density M x + stiffness K(u_lin) x + viscosity C x on `stream`; x, y on the device; apply_prepare has run
-inline void launch_apply(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, const double* x, double* y,
-                         hipStream_t stream) {
-  h->integrated = false;   // the element pieces of an earlier mimi_hip_domain_integrate are overwritten
-  ApplyArgs aa{};
-  aa.density = density;
-  aa.stiffness = stiffness;
-  aa.viscosity = viscosity;
-  aa.x = x;
-  aa.u_lin = h->lin_u.ptr;
-  aa.rec = h->lin_rec.ptr;
-  aa.pieces = h->scratch_r.ptr;
-  aa.N = h->shape_N.ptr;
-  aa.n_pts = h->n_pts;
-  aa.n_el = h->n_el;
-  const bool recompute = apply_recomputes(h);
-  if (tensor_usable(h)) {
-    const TensorArgs a = tensor_args(h, DomainCall{});
-    by_dim_degree(h, [&](auto D, auto Pd) {
-      constexpr int DIM = decltype(D)::value, P = decltype(Pd)::value;
-      if (recompute) launch_apply_tensor_dp<DIM, P, APPLY_NEOHOOKEAN>(h, a, aa, stream);
-      else launch_apply_tensor_dp<DIM, P, APPLY_RECORD>(h, a, aa, stream);
-    });
-  } else {
-    if (recompute) launch_apply_general<APPLY_NEOHOOKEAN>(h, aa, stream); else launch_apply_general<APPLY_RECORD>(h, aa, stream);
-  }
-  const int64_t* adj_ptr = h->adj_ptr.ptr ? h->adj_ptr.ptr : h->field_adj_ptr.ptr;
-  const int32_t* adj = h->adj_ptr.ptr ? h->adj.ptr : h->field_adj.ptr;
-  const int64_t total = h->n_vdofs;
-  launch(apply_gather_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, h->n_vdofs / h->dim, h->n_dof, h->dim, adj_ptr, adj,
-         (const double*)h->scratch_r.ptr, y);
-  h->apply_family = apply_family_of(h);
-}
-
-inline void run_apply_tangent(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, const double* x, double* y) {
-  MH_HIP(hipSetDevice(h->device));
-  if (!x || !y) fail("null vector argument");
-  apply_check(h, stiffness);
-  apply_prepare(h, density);
-  Mirror<double> mx = Mirror<double>::in(x, h->n_vdofs, h->stage_x, h->stream);
-  Mirror<double> my = Mirror<double>::inout(y, h->n_vdofs, h->stage_r, h->stream);
-  launch_apply(h, density, stiffness, viscosity, mx.dev, my.dev, h->stream);
-  my.finish(h->stream);
-  if (mx.host || my.host) check_status(h);   // synchronous for host-resident arguments
-}
-
-// the snapshot of the tangent at u: committed state, the dt of set_dt; no state changes
-inline void run_linearize(mimi_hip_domain_s* h, const double* u) {
-  MH_HIP(hipSetDevice(h->device));
-  if (!u) fail("null vector argument");
-  // (an action launched by a solver on another stream has ended with its solve: nothing reads what is overwritten here)
-  if (apply_recomputes(h)) {
-    h->lin_u.resize((size_t)h->n_vdofs);
-    MH_HIP(hipMemcpyAsync(h->lin_u.ptr, u, (size_t)h->n_vdofs * sizeof(double), hipMemcpyDefault, h->stream));
-    if (!is_device_pointer(u)) MH_HIP(hipStreamSynchronize(h->stream));   // (the caller may overwrite u on return)
-  } else {
-    Mirror<double> mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
-    const int d4 = h->dim * h->dim * h->dim * h->dim;
-    h->lin_rec.resize((size_t)h->n_pts * d4);
-    ApplyArgs aa{};
-    aa.u_lin = mu.dev;
-    aa.rec = h->lin_rec.ptr;
-    aa.n_pts = h->n_pts;
-    aa.n_el = h->n_el;
-    if (tensor_usable(h)) {
-      const TensorArgs a = tensor_args(h, DomainCall{});
-      by_dim_degree(h, [&](auto D, auto Pd) {
-        by_material_family(h->mat.m.kind, [&](auto K) {
-          launch_apply_tensor_dp<decltype(D)::value, decltype(Pd)::value, APPLY_LINEARIZE, decltype(K)::value>(h, a, aa, h->stream);
-        });
-      });
-    } else {
-      ensure_general_tables(h);
-      by_material_family(h->mat.m.kind, [&](auto K) { launch_apply_general<APPLY_LINEARIZE, decltype(K)::value>(h, aa, h->stream); });
-    }
-    if (mu.host) check_status(h);
-  }
-  if (!h->lin_event) MH_HIP(hipEventCreateWithFlags(&h->lin_event, hipEventDisableTiming));
-  MH_HIP(hipEventRecord(h->lin_event, h->stream));
-  h->linearized = true;
 }
 
 }  // namespace mimi_hip

@@ -23,9 +23,9 @@
 //                       tables to the element's nodes.  At most 64 points per element: one wave per element, four elements
 //                       per 256-thread workgroup; 125 points: two waves per element.  No per-point basis table is read.
 // apply_general_kernel  flat tables and mixed degrees: the same from dN_dX, wdet and the shape values.
-// Both store element pieces [e][a][DIM]; apply_gather_kernel sums them per node over the node -> (element, local node)
-// adjacency in the adjacency's order: every (node, component) is written by exactly one thread, no atomics, equal inputs
-// give equal bytes.
+// Both store element pieces [e][a][DIM]; node_gather_kernel (kernels_fields.hpp) sums them per node over the handle's
+// node -> (element, local node) adjacency in the adjacency's order: every (node, component) is written by exactly one
+// thread, no atomics, equal inputs give equal bytes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -229,7 +229,7 @@ __global__ __launch_bounds__((ApplyShape<DIM, P, MODE>::THREADS)) void apply_ten
   };
   int el[3];
   element_in_box<DIM>(p, e, el);
-  for (int t = tid; t < 3 * 2 * TS; t += NT) tab[t] = element_table_entry<DIM, P>(p, el, t);
+  load_element_tables<DIM, P, NT>(p, el, tid, tab);
   for (int a = tid; a < ND; a += NT) {
     const int64_t node = p.dofs[e * ND + a];
 #pragma unroll
@@ -243,26 +243,8 @@ __global__ __launch_bounds__((ApplyShape<DIM, P, MODE>::THREADS)) void apply_ten
     }
   }
   sync();
-  // T1[c][k][a12][q0] = sum_a0 tab0[k][a0][q0] v_c[a0 + NB a12]                        (k: 0 B, 1 D)
-  for (int t = tid; t < NCF * 2 * NB12 * NQ; t += NT) {
-    const int q0 = t % NQ, a12 = (t / NQ) % NB12, k = (t / (NQ * NB12)) % 2, c = t / (NQ * NB12 * 2);
-    double s = 0.0;
-#pragma unroll
-    for (int a0 = 0; a0 < NB; ++a0) s += tab[(k * NB + a0) * NQ + q0] * ue[c * ND + a0 + NB * a12];
-    X[t] = s;
-  }
-  sync();
-  // T2[c][k][a2][q0 + NQ q1] = sum_a1 tab1[k == 1][a1][q1] T1[c][k == 0][a1 + NB a2][q0]   (k: 0 D0 B1, 1 B0 D1, 2 B0 B1)
-  for (int t = tid; t < NCF * 3 * NBZ * NQ01; t += NT) {
-    const int q01 = t % NQ01, q0 = q01 % NQ, q1 = q01 / NQ, a2 = (t / NQ01) % NBZ, k = (t / (NQ01 * NBZ)) % 3, c = t / (NQ01 * NBZ * 3);
-    const double* t1 = X + ((c * 2 + (k == 0 ? 1 : 0)) * NB12 + NB * a2) * NQ + q0;
-    const double* tb = tab + (2 + (k == 1 ? 1 : 0)) * TS + q1;
-    double s = 0.0;
-#pragma unroll
-    for (int a1 = 0; a1 < NB; ++a1) s += tb[a1 * NQ] * t1[a1 * NQ];
-    Y[t] = s;
-  }
-  sync();
+  // T1 into X, T2 into Y (sum_factor.hpp)
+  forward_stages<DIM, P, NCF, NT>(tab, ue, X, Y, tid, sync);
 
   // ---- quadrature-point stage: lane = point -------------------------------------------------------------------------------
   int status = 0;
@@ -273,22 +255,9 @@ __global__ __launch_bounds__((ApplyShape<DIM, P, MODE>::THREADS)) void apply_ten
     const double wd = geo.wdet();
     double Ji[DD];
     geo.Ji(Ji);
-    // H of component set s (0: x, or u when linearising; 1: u_lin beside x)
-    auto parametric = [&](int set, double* H) {
-#pragma unroll
-      for (int c = 0; c < DIM; ++c)
-#pragma unroll
-        for (int m = 0; m < DIM; ++m) {
-          const double* t2 = Y + (((set * DIM + c) * 3 + (m < 2 ? m : 2)) * NBZ) * NQ01 + q01;
-          const double* tb = tab + (4 + (m == 2 ? 1 : 0)) * TS + q2;
-          double s = 0.0;
-#pragma unroll
-          for (int a2 = 0; a2 < NBZ; ++a2) s += tb[a2 * NQ] * t2[a2 * NQ01];
-          H[c * DIM + m] = s;
-        }
-    };
+    // H of component set 0: x, or u when linearising; set 1: u_lin beside x
     double H[DD];
-    parametric(0, H);
+    parametric_gradient<DIM, P>(tab, Y, 0, q01, q2, H);
     if constexpr (MODE == APPLY_LINEARIZE) {
       double F[DD];
       deformation_gradient<DIM>(H, Ji, F);
@@ -296,17 +265,9 @@ __global__ __launch_bounds__((ApplyShape<DIM, P, MODE>::THREADS)) void apply_ten
     } else {
       double G[DD], F[DD] = {}, xv[DIM];
       physical_gradient<DIM>(H, Ji, G);
-#pragma unroll
-      for (int c = 0; c < DIM; ++c) {
-        const double* t2 = Y + ((c * 3 + 2) * NBZ) * NQ01 + q01;
-        const double* tb = tab + 4 * TS + q2;
-        double s = 0.0;
-#pragma unroll
-        for (int a2 = 0; a2 < NBZ; ++a2) s += tb[a2 * NQ] * t2[a2 * NQ01];
-        xv[c] = s;
-      }
+      point_value<DIM, P>(tab, Y, q01, q2, xv);
       if constexpr (MODE == APPLY_NEOHOOKEAN) {
-        parametric(1, H);
+        parametric_gradient<DIM, P>(tab, Y, 1, q01, q2, H);
         deformation_gradient<DIM>(H, Ji, F);
       }
       double Hp[DD], mv[DIM];
@@ -413,12 +374,8 @@ __global__ __launch_bounds__(256) void apply_general_kernel(GeneralArgs p, Apply
   double* u_e = x_e + n_tdof;
   double* vals = u_e + n_tdof;
   const bool need_u = MODE == APPLY_LINEARIZE || (MODE == APPLY_NEOHOOKEAN && aa.stiffness != 0.0);
-  for (int t = tid; t < n_tdof; t += blockDim.x) {
-    const int a = t % n_dof, i = t / n_dof;
-    const int64_t idx = (int64_t)p.dofs[e * n_dof + a] * DIM + i;
-    if (MODE != APPLY_LINEARIZE) x_e[t] = aa.x[idx];
-    u_e[t] = need_u ? aa.u_lin[idx] : 0.0;
-  }
+  if constexpr (MODE != APPLY_LINEARIZE) gather_element_vector<DIM>(p.dofs, e, n_dof, aa.x, x_e, tid, blockDim.x);
+  gather_element_vector<DIM>(p.dofs, e, n_dof, need_u ? aa.u_lin : nullptr, u_e, tid, blockDim.x);
   __syncthreads();
   int status = 0;
   for (int q = tid; q < n_q; q += blockDim.x) {
@@ -472,25 +429,6 @@ __global__ __launch_bounds__(256) void apply_general_kernel(GeneralArgs p, Apply
       out[t] = s;
     }
   }
-}
-
-// one thread per (node, component): y += the pieces of the elements around the node, in the adjacency's order
-// ((element << 6) | local node, domain_dispatch.hpp)
-__global__ __launch_bounds__(256) void apply_gather_kernel(int64_t n_nodes, int n_dof, int dim, const int64_t* __restrict__ adj_ptr,
-                                                           const int32_t* __restrict__ adj, const double* __restrict__ pieces,
-                                                           double* __restrict__ y) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n_nodes * dim) return;
-  const int64_t node = idx / dim;
-  const int i = (int)(idx % dim);
-  const int64_t a_beg = adj_ptr[node], a_end = adj_ptr[node + 1];
-  if (a_beg == a_end) return;   // no element of this handle touches the node (element boxes)
-  double s = 0.0;
-  for (int64_t t = a_beg; t < a_end; ++t) {
-    const int32_t ea = adj[t];
-    s += pieces[((int64_t)(ea >> 6) * n_dof + (ea & 63)) * dim + i];
-  }
-  y[idx] += s;
 }
 
 }  // namespace mimi_hip

@@ -16,15 +16,16 @@
 //                         shape values N[e][q][a] (the caller's, or expanded from the 1-D tables next to dN_dX).
 // Point form: out[e][q][c], stored through LDS so that a workgroup writes its element's values as one contiguous run.
 // Nodal form, no atomics: the element kernel stores pieces[e][a][ncomp + 1] (the last one is the weight), and
-// field_gather_kernel sums them per node over the node -> (element, local node) adjacency of the general row gather, in
-// the adjacency's order -- every (node, component) is written by exactly one thread, so two calls give the same bytes.
+// node_gather_kernel sums them per node over the handle's node -> (element, local node) adjacency, in the adjacency's
+// order -- every (node, component) is written by exactly one thread, so two calls give the same bytes.  The same gather
+// serves the body force (the weight alone) and the tangent action (kernels_apply.hpp: DIM components, no weight).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include "kernels_general.hpp"
 #include "kernels_setup.hpp"
-#include "patch_index.hpp"
+#include "sum_factor.hpp"
 
 namespace mimi_hip {
 
@@ -161,34 +162,13 @@ __global__ __launch_bounds__((FieldShape<DIM, P>::THREADS)) void field_tensor_ke
   const int64_t e = blockIdx.x;
   int el[3];
   element_in_box<DIM>(p, e, el);
-  // 1-D tables of this element's spans: tab[dir][B, D][a][q]; the direction a 2-D patch lacks is B = 1, D = 0
-  for (int t = tid; t < 3 * 2 * TS; t += NT) tab[t] = element_table_entry<DIM, P>(p, el, t);
+  load_element_tables<DIM, P, NT>(p, el, tid, tab);
   if (fa.need_F) {
     for (int a = tid; a < ND; a += NT) gather_element_u<DIM, ND>(p, e, a, ue);
   }
   __syncthreads();
-  if (fa.need_F) {
-    // T1[c][k][a12][q0] = sum_a0 tab0[k][a0][q0] u_c[a0 + NB a12]                        (k: 0 B, 1 D)
-    for (int t = tid; t < DIM * 2 * NB12 * NQ; t += NT) {
-      const int q0 = t % NQ, a12 = (t / NQ) % NB12, k = (t / (NQ * NB12)) % 2, c = t / (NQ * NB12 * 2);
-      double s = 0.0;
-#pragma unroll
-      for (int a0 = 0; a0 < NB; ++a0) s += tab[(k * NB + a0) * NQ + q0] * ue[c * ND + a0 + NB * a12];
-      X[t] = s;
-    }
-    __syncthreads();
-    // T2[c][k][a2][q0 + NQ q1] = sum_a1 tab1[k == 1][a1][q1] T1[c][k == 0][a1 + NB a2][q0]   (k: 0 D0 B1, 1 B0 D1, 2 B0 B1)
-    for (int t = tid; t < DIM * 3 * NBZ * NQ01; t += NT) {
-      const int q01 = t % NQ01, q0 = q01 % NQ, q1 = q01 / NQ, a2 = (t / NQ01) % NBZ, k = (t / (NQ01 * NBZ)) % 3, c = t / (NQ01 * NBZ * 3);
-      const double* t1 = X + ((c * 2 + (k == 0 ? 1 : 0)) * NB12 + NB * a2) * NQ + q0;
-      const double* tb = tab + (2 + (k == 1 ? 1 : 0)) * TS + q1;
-      double s = 0.0;
-#pragma unroll
-      for (int a1 = 0; a1 < NB; ++a1) s += tb[a1 * NQ] * t1[a1 * NQ];
-      Y[t] = s;
-    }
-    __syncthreads();
-  }
+  // T1 into X, T2 into Y (sum_factor.hpp)
+  if (fa.need_F) forward_stages<DIM, P, DIM, NT>(tab, ue, X, Y, tid, [] { __syncthreads(); });
 
   // ---- quadrature-point stage: lane = point -----------------------------------------------------------------------------
   int status = 0;
@@ -201,17 +181,7 @@ __global__ __launch_bounds__((FieldShape<DIM, P>::THREADS)) void field_tensor_ke
     for (int k = 0; k < DD; ++k) F[k] = 0.0;
     if (fa.need_F) {
       double H[DD];
-#pragma unroll
-      for (int c = 0; c < DIM; ++c)
-#pragma unroll
-        for (int m = 0; m < DIM; ++m) {
-          const double* t2 = Y + ((c * 3 + (m < 2 ? m : 2)) * NBZ) * NQ01 + q01;
-          const double* tb = tab + (4 + (m == 2 ? 1 : 0)) * TS + q2;
-          double s = 0.0;
-#pragma unroll
-          for (int a2 = 0; a2 < NBZ; ++a2) s += tb[a2 * NQ] * t2[a2 * NQ01];
-          H[c * DIM + m] = s;
-        }
+      parametric_gradient<DIM, P>(tab, Y, 0, q01, q2, H);
       double Ji[DD];
       geo.Ji(Ji);
       deformation_gradient<DIM>(H, Ji, F);
@@ -275,12 +245,7 @@ __global__ __launch_bounds__(256) void field_general_kernel(GeneralArgs p, Field
   const int n_dof = p.n_dof, n_q = p.n_q, n_tdof = n_dof * DIM;
   double* u_e = reinterpret_cast<double*>(smem_field);
   double* vals = u_e + n_tdof;
-  if (fa.need_F) {
-    for (int t = tid; t < n_tdof; t += blockDim.x) {
-      const int a = t % n_dof, i = t / n_dof;
-      u_e[t] = p.u[(int64_t)p.dofs[e * n_dof + a] * DIM + i];
-    }
-  }
+  if (fa.need_F) gather_element_vector<DIM>(p.dofs, e, n_dof, p.u, u_e, tid, blockDim.x);
   __syncthreads();
   int status = 0;
   for (int q = tid; q < n_q; q += blockDim.x) {
@@ -311,23 +276,23 @@ __global__ __launch_bounds__(256) void field_general_kernel(GeneralArgs p, Field
   }
 }
 
-// one thread per (node, component; the last component is the weight): the pieces of the elements around the node, in the
-// adjacency's order ((element << 6) | local node, domain_dispatch.hpp)
-__global__ __launch_bounds__(256) void field_gather_kernel(int64_t n_nodes, int n_dof, int ncomp, const int64_t* __restrict__ adj_ptr,
-                                                           const int32_t* __restrict__ adj, const double* __restrict__ pieces,
-                                                           double* __restrict__ sum, double* __restrict__ weight) {
-  const int NC = ncomp + 1;
+// one thread per (node, column < stride) of the element pieces [e][a][stride]: the pieces of the elements around the node,
+// in the adjacency's order ((element << 6) | local node).  Column c < ncomp adds into sum[node][c]; column ncomp (there
+// is one when stride == ncomp + 1) into weight[node], when a weight is given
+__global__ __launch_bounds__(256) void node_gather_kernel(int64_t n_nodes, int n_dof, int stride, int ncomp, const int64_t* __restrict__ adj_ptr,
+                                                          const int32_t* __restrict__ adj, const double* __restrict__ pieces,
+                                                          double* __restrict__ sum, double* __restrict__ weight) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n_nodes * NC) return;
-  const int64_t node = idx / NC;
-  const int c = (int)(idx % NC);
+  if (idx >= n_nodes * stride) return;
+  const int64_t node = idx / stride;
+  const int c = (int)(idx % stride);
   if (c == ncomp && !weight) return;
   const int64_t a_beg = adj_ptr[node], a_end = adj_ptr[node + 1];
   if (a_beg == a_end) return;   // no element of this handle touches the node (element boxes)
   double s = 0.0;
   for (int64_t t = a_beg; t < a_end; ++t) {
     const int32_t ea = adj[t];
-    s += pieces[((int64_t)(ea >> 6) * n_dof + (ea & 63)) * NC + c];
+    s += pieces[((int64_t)(ea >> 6) * n_dof + (ea & 63)) * stride + c];
   }
   if (c < ncomp) sum[node * ncomp + c] += s;
   else weight[node] += s;

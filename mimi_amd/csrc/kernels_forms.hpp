@@ -18,7 +18,7 @@
 //                         node -> (element, local node) adjacency in its order, lanes over the element's nodes b, one image
 //                         of the row in LDS as in general_gather_kernel.
 // The body force is the lumped weight of the nodal field output (kernels_fields.hpp: element pieces of w det N_a, then
-// field_gather_kernel) times b.
+// node_gather_kernel) times b.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -6,11 +6,15 @@ builds of the library (MIMI_HIP_LIBRARY=scratch/lib_parent.so, then the tree's o
   python scratch/dispatch_trace.py --linear > hashes.txt          the linear-solver section alone (a refactor of csrc/krylov.hip)
   rocprofv3 --kernel-trace --output-format csv -d DIR -- python scratch/dispatch_trace.py   (kernel trace alone, no counters)
   python scratch/dispatch_trace.py --compare-hashes A.txt B.txt
-  python scratch/dispatch_trace.py --compare-traces DIR_A DIR_B   (kernel name, grid, workgroup, LDS) in dispatch order
+  python scratch/dispatch_trace.py --compare-traces DIR_A DIR_B   (kernel name, grid, workgroup, LDS) in dispatch order, of the
+                                                                  library's own kernels (namespace mimi_hip); the runtime's
+                                                                  copy and fill kernels are counted, not compared
 
 Entries reached: create from tables and from a B-spline, residual, residual + tangent, from-base in its three residences,
 post-time-advance, integrate + gather over partial windows, phase timing; point and nodal field output (the Cauchy stress,
-and the accumulated plastic strain of a material with state), AddMass, AddDiffusion, AddBodyForce -- on every route: the
+and the accumulated plastic strain of a material with state), AddMass, AddDiffusion, AddBodyForce, and the tangent action
+(Linearize at a seeded u, ApplyTangent with the stiffness alone, all three coefficients and the mass alone, x and a
+pre-filled y on the host and in HBM) -- on every route: the
 cases of the kernel families, the general kernels, flat tables with shape values, node_ids, the cut element box, the
 smallest blocks with p + 2 elements along one direction and fewer than p + 1 along another (a node with full support, a
 node clipped on both sides), one of them as an element box cut on both sides of its long axis, and two patches of
@@ -181,6 +185,20 @@ def run():
         out(case, "diffusion", sha(D))
         out(case, "body force", sha(f))
 
+    def actions(case, G, n_vdofs, mat):
+        """Linearize, then y += (density M + stiffness K + viscosity C) x on a pre-filled y, arrays on the host and in HBM"""
+        G.Linearize(seeded(n_vdofs, 1, 0.05 if mat == "neohook" else 0.02))
+        x = seeded(n_vdofs, 12)
+        for density, stiffness, viscosity in ((0.0, 1.0, 0.0), (0.7, 0.37, 0.11), (1.0, 0.0, 0.0)):
+            what = f"{density:g} {stiffness:g} {viscosity:g}"
+            y = G.ApplyTangent(x, seeded(n_vdofs, 13), stiffness=stiffness, density=density, viscosity=viscosity)
+            out(case, "action " + what, sha(y))
+            y = G.ApplyTangent(torch.from_numpy(x).to(dev), torch.from_numpy(seeded(n_vdofs, 13)).to(dev), stiffness=stiffness,
+                               density=density, viscosity=viscosity)
+            G.Synchronize()
+            out(case, "action hbm " + what, sha(y))
+        out(case, "action family", G.LastActionFamily())
+
     def from_base(case, G, n_vdofs, nnz):
         u, base = seeded(n_vdofs, 1, 0.05), seeded(nnz, 5, 50.0)
         to = lambda a, on_dev: torch.from_numpy(a.copy()).to(dev) if on_dev else a.copy()
@@ -209,6 +227,7 @@ def run():
         patch, pattern, G = handle(n_el, p, mat)
         assemblies(f"bspline {'x'.join(map(str, n_el))} p{p} {mat}", G, patch.n_vdofs, pattern.nnz, mat, fd=len(n_el) == 2 or p == 1)
         fields_and_forms(f"bspline {'x'.join(map(str, n_el))} p{p} {mat}", G, len(n_el), patch.n_vdofs, pattern.nnz, mat)
+        actions(f"bspline {'x'.join(map(str, n_el))} p{p} {mat}", G, patch.n_vdofs, mat)
         if mat == "neohook":
             from_base(f"bspline {'x'.join(map(str, n_el))} p{p} {mat}", G, patch.n_vdofs, pattern.nnz)
     # the general kernels: closed-form and record materials, small and large elements
@@ -218,6 +237,7 @@ def run():
         case = f"general {'x'.join(map(str, n_el))} p{p} {mat}"
         assemblies(case, G, patch.n_vdofs, pattern.nnz, mat, fd=True)
         fields_and_forms(case, G, len(n_el), patch.n_vdofs, pattern.nnz, mat)
+        actions(case, G, patch.n_vdofs, mat)
         if mat == "neohook":
             from_base(case, G, patch.n_vdofs, pattern.nnz)
     # create from flat tables (the oracle's own tables)
@@ -234,6 +254,7 @@ def run():
         case = f"tables {'x'.join(map(str, n_el))} p{p} {mat}"
         assemblies(case, G, P.n_vdofs, D.nnz, mat, fd=True)
         fields_and_forms(case, G, P.dim, P.n_vdofs, D.nnz, mat)
+        actions(case, G, P.n_vdofs, mat)
         from_base(case, G, P.n_vdofs, D.nnz)
     # permuted numbering (node_ids), 3-D degree 2 and 3: the caller's CSR is the lexicographic one renumbered
     for n_el, p in [((5, 4, 4), 2), ((3, 3, 4), 3)]:
@@ -250,6 +271,7 @@ def run():
             G.dt_ = 0.5
             assemblies(f"node_ids {'x'.join(map(str, n_el))} p{p} {mat}", G, patch.n_vdofs, pattern.nnz, mat)
             fields_and_forms(f"node_ids {'x'.join(map(str, n_el))} p{p} {mat}", G, 3, patch.n_vdofs, pattern.nnz, mat)
+            actions(f"node_ids {'x'.join(map(str, n_el))} p{p} {mat}", G, patch.n_vdofs, mat)
     # integrate + gather over partial windows, phase timing on (which event pairs exist is what is printed, not the times)
     for n_el, p, mat in [((5, 7, 4), 2, "neohook"), ((4, 6, 5), 2, "j2"), ((3, 4, 4), 2, "stvk"), ((3, 5, 4), 3, "j2")]:
         patch = mimi_amd.BSplinePatch.block(n_el, p)
@@ -284,6 +306,7 @@ def run():
         patch, pattern, G = handle((5, 6, 8), 2, mat, element_box=([0, 1, 2], [5, 5, 6]))
         assemblies(f"element box 5x6x8 p2 {mat}", G, patch.n_vdofs, pattern.nnz, mat)
         fields_and_forms(f"element box 5x6x8 p2 {mat}", G, 3, patch.n_vdofs, pattern.nnz, mat)
+        actions(f"element box 5x6x8 p2 {mat}", G, patch.n_vdofs, mat)
     # fields and forms on the smallest blocks with an interior node of full support and a node clipped on both sides; the
     # 3-D ones again as an element box cut on both sides of the long axis
     for p in (1, 2, 3):
@@ -293,9 +316,11 @@ def run():
                 case = f"{'general' if env else 'small'} {'x'.join(map(str, n_el))} p{p} j2"
                 G.DomainPostTimeAdvance(seeded(patch.n_vdofs, 4, 0.03))
                 fields_and_forms(case, G, len(n_el), patch.n_vdofs, pattern.nnz, "j2")
+                actions(case, G, patch.n_vdofs, "j2")
         patch, pattern, G = handle((p + 4, p, 2), p, "j2", element_box=([1, 0, 0], [p + 3, p, 2]))
         G.DomainPostTimeAdvance(seeded(patch.n_vdofs, 4, 0.03))
         fields_and_forms(f"cut box {p + 4}x{p}x2 p{p} j2", G, 3, patch.n_vdofs, pattern.nnz, "j2")
+        actions(f"cut box {p + 4}x{p}x2 p{p} j2", G, patch.n_vdofs, "j2")
     # repeated interior knots: the tensor route (small elements) and the general route
     import _patches
     for name in ("rep2d_p2", "rep3d_p2"):
@@ -306,6 +331,7 @@ def run():
         G.dt_ = 0.5
         assemblies(f"patches {name} j2", G, P.n_vdofs, D.nnz, "j2")
         fields_and_forms(f"patches {name} j2", G, P.dim, P.n_vdofs, D.nnz, "j2")
+        actions(f"patches {name} j2", G, P.n_vdofs, "j2")
     # MIMI_HIP_P3_CONTRACT flipped between two calls of one handle
     patch, pattern, G = handle((2, 3, 4), 3, "neohook")
     u = seeded(patch.n_vdofs, 1, 0.05)
@@ -341,8 +367,20 @@ def launches(directory):
              r["Workgroup_Size_Z"], r["LDS_Block_Size"]) for r in rows]
 
 
+def own_launches(directory):
+    """the library's launches, the two gathers of older builds read as the one node gather; the number of other dispatches"""
+    rows = launches(directory)
+    own = []
+    for r in rows:
+        if "mimi_hip" in r[0]:
+            gather = any(k in r[0] for k in ("field_gather_kernel", "apply_gather_kernel", "node_gather_kernel"))
+            own.append((("mimi_hip::node_gather_kernel" if gather else r[0]),) + r[1:])
+    return own, len(rows) - len(own)
+
+
 def compare_traces(a, b):
-    la, lb = launches(a), launches(b)
+    (la, other_a), (lb, other_b) = own_launches(a), own_launches(b)
+    print(f"other dispatches (the runtime's copy and fill kernels): {other_a} / {other_b}")
     bad = [(k, x, y) for k, (x, y) in enumerate(zip(la, lb)) if x != y]
     for k, x, y in bad[:10]:
         print(f"dispatch {k}:\n- {x}\n+ {y}")

@@ -1,9 +1,11 @@
 // TEST HARNESS ONLY: the node side of mimi_amd/csrc/patch_index.hpp -- NodeWindow<P>, what a wave of the row gathers computes
-// for its node -- compiled for the HOST, so that every node of a node window can be checked against a brute-force
-// enumeration without a GPU (tests/test_patch_index_cpu.py).  Nothing in mimi_amd builds or loads this.
+// for its node -- and the forward stages of mimi_amd/csrc/sum_factor.hpp compiled for the HOST, so that every node of a node
+// window can be checked against a brute-force enumeration, and every point's parametric gradient and value against a dense
+// contraction, without a GPU (tests/test_patch_index_cpu.py).  Nothing in mimi_amd builds or loads this.
 #define MH_DEV __host__ __device__ inline
 #include "../mimi_amd/csrc/common.hpp"
 #include "../mimi_amd/csrc/patch_index.hpp"
+#include "../mimi_amd/csrc/sum_factor.hpp"
 
 namespace mimi_hip {
 void set_last_error(const std::string&) {}
@@ -46,6 +48,44 @@ extern "C" int host_node_windows(int P, const int* box_begin, const int* box_n, 
   if (P == 1) fill<1>(p, n_nodes, head, slots);
   else if (P == 2) fill<2>(p, n_nodes, head, slots);
   else if (P == 3) fill<3>(p, n_nodes, head, slots);
+  else return 1;
+  return 0;
+}
+
+// The forward helpers as one thread runs them: NT = 1, tid = 0, an empty barrier; two component sets (NC = 2 DIM).
+// tab_out[3][2][NB][NQ] (the loaded block), H[set][point][DIM DIM], val[point][DIM] (set 0)
+template<int DIM, int P>
+static void forward(const TensorArgs& p, const int (&el)[3], const double* ve, double* tab, double* H, double* val) {
+  using S = ElementShape<DIM, P>;
+  constexpr int NC = 2 * DIM, NQ01 = S::NQ * S::NQ;
+  std::vector<double> X((size_t)NC * 2 * S::NB * S::NBZ * S::NQ), Y((size_t)NC * 3 * S::NBZ * NQ01);
+  load_element_tables<DIM, P, 1>(p, el, 0, tab);
+  forward_stages<DIM, P, NC, 1>(tab, ve, X.data(), Y.data(), 0, [] {});
+  for (int q = 0; q < S::NPT; ++q) {
+    for (int set = 0; set < 2; ++set) parametric_gradient<DIM, P>(tab, Y.data(), set, q % NQ01, q / NQ01, H + ((size_t)set * S::NPT + q) * S::DD);
+    point_value<DIM, P>(tab, Y.data(), q % NQ01, q / NQ01, val + (size_t)q * DIM);
+  }
+}
+
+// tables[dir < dim][B, D][n_spans][P + 1][P + 2]; the element is span box_begin[dir] + el[dir] of each direction
+extern "C" int host_forward_stages(int dim, int P, int n_spans, const int* box_begin, const int* el_in, const double* tables,
+                                   const double* ve, double* tab, double* H, double* val) {
+  TensorArgs p{};
+  const int TS = (P + 1) * (P + 2);
+  int el[3] = {0, 0, 0};
+  for (int d = 0; d < dim; ++d) {
+    p.box_begin[d] = box_begin[d];
+    el[d] = el_in[d];
+    p.tabB[d] = tables + (size_t)(d * 2 + 0) * n_spans * TS;
+    p.tabD[d] = tables + (size_t)(d * 2 + 1) * n_spans * TS;
+  }
+  const int key = dim * 10 + P;
+  if (key == 21) forward<2, 1>(p, el, ve, tab, H, val);
+  else if (key == 22) forward<2, 2>(p, el, ve, tab, H, val);
+  else if (key == 23) forward<2, 3>(p, el, ve, tab, H, val);
+  else if (key == 31) forward<3, 1>(p, el, ve, tab, H, val);
+  else if (key == 32) forward<3, 2>(p, el, ve, tab, H, val);
+  else if (key == 33) forward<3, 3>(p, el, ve, tab, H, val);
   else return 1;
   return 0;
 }

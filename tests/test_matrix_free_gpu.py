@@ -10,7 +10,8 @@ LinearSolver.SetOperator and the facade's "matrix_free" flag.
 (6) solves with the operator on the systems of test_kronecker_gpu.py: the iteration count of the restated GMRES, the solution
     of the extended-precision direct solve; CG on a mass operator;
 (7) the rules of the seam;
-(8) the golden beams through the facade with the flag, and its refusals."""
+(8) the golden beams through the facade with the flag, and its refusals;
+(9) the order of first use on a handle does not matter: assembly, nodal field, mass form and action in either order."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -378,3 +379,72 @@ def test_the_flag_is_refused_where_the_action_does_not_reach():
         prepared(FLAGS, lambda bc: bc.initial.pressure(3, 1.0)).setup(1)
     with pytest.raises(RuntimeError, match="periodic"):
         prepared(FLAGS, lambda bc: bc.initial.periodic(1, 2)).setup(1)
+
+
+
+# ---- (9) ---------------------------------------------------------------------------------------------------------------------
+# What a handle builds at first use (the node adjacency, the longest-row scan, the general tables, the scratch of the
+# two-phase route) is shared by its assemblies, fields, forms and actions: whichever comes first, every call takes the same
+# route and gives the same bytes.
+FIRST_USE = {"small 4x3 p2 neohook": ((4, 3), 2, "neohook", None),
+             "general 3x2x2 p2 j2": ((3, 2, 2), 2, "j2", {"MIMI_HIP_FORCE_GENERAL": "1"}),
+             "tables 2x2 p3 j2": ((2, 2), 3, "j2", "tables")}
+
+
+@pytest.mark.parametrize("name", list(FIRST_USE))
+def test_order_of_first_use_does_not_matter(name, monkeypatch):
+    import mimi_amd
+    from mimi_amd.integrators import CSRPattern, NonlinearSolid
+    n_el, p, matname, how = FIRST_USE[name]
+    dim = len(n_el)
+    if how == "tables":
+        from _cases import oracle_material
+        from oracle import iga, ref_path as rp
+        P = iga.Patch.block(n_el, p)
+        D = rp.DomainOracle(P, oracle_material(matname), n_threads=1)
+        n_nodes, nnz = P.n_nodes, D.nnz
+        tables = dict(dim=dim, n_nodes=n_nodes, dofs=D.conn, dN_dX=D.dN_dX, weight_det=D.weight * D.det, N=np.ascontiguousarray(D.tables["N"]))
+        create = lambda: NonlinearSolid("domain", product_material(matname), CSRPattern(D.rowptr.astype(np.int64), D.col.astype(np.int32), nnz),
+                                        tables=tables)
+    else:
+        patch = mimi_amd.BSplinePatch.block(n_el, p)
+        n_nodes, nnz = patch.n_nodes, CSRPattern.of_bspline_patch(patch).nnz
+        create = lambda: NonlinearSolid("domain", product_material(matname), CSRPattern.of_bspline_patch(patch), patch=patch)
+    for k, v in (how if isinstance(how, dict) else {}).items():
+        monkeypatch.setenv(k, v)
+    rng = np.random.default_rng(97)
+    u, x = 0.02 * rng.standard_normal(n_nodes * dim), rng.standard_normal(n_nodes * dim)
+    r0, A0, M0, y0 = (rng.standard_normal(n) for n in (n_nodes * dim, nnz, nnz, n_nodes * dim))
+    s0, w0 = rng.standard_normal((n_nodes, dim * dim)), rng.standard_normal(n_nodes)
+
+    def assembly(G):
+        r, A = r0.copy(), A0.copy()
+        G.AddDomainResidualAndGrad(u, 0.37, r, A)
+        return dict(r=r, A=A, family=np.array(info(G, 7)))
+
+    def field(G):
+        s, w = s0.copy(), w0.copy()
+        G.NodalField("cauchy_stress", u, s, w)
+        return dict(s=s, w=w)
+
+    def mass(G):
+        return dict(M=G.AddMass(1.3, M0.copy()))
+
+    def act(G):
+        G.Linearize(u)
+        return dict(y=G.ApplyTangent(x, y0.copy(), stiffness=0.37, density=0.7, viscosity=0.11))
+
+    steps = [assembly, field, mass, act]
+    results = []
+    for order in (steps, steps[::-1]):
+        G = create().Prepare()
+        G.dt_ = DT
+        got = {}
+        for step in order:
+            got.update(step(G))
+        results.append(got)
+    first, second = results
+    assert sorted(first) == ["A", "M", "family", "r", "s", "w", "y"]
+    for key in first:
+        assert np.isfinite(first[key]).all() and first[key].tobytes() == second[key].tobytes(), key
+    assert int(first["family"]) == (FAMILY_CODES["tensor_small"] if how is None else FAMILY_CODES["general"])

@@ -1,6 +1,7 @@
 """The index layer of the tensor kernels without a GPU: the node side of mimi_amd/csrc/patch_index.hpp (NodeWindow<P>: the
 elements of a handle's box that contain a node, the node's local index in each, its clipped column window) compiled for
-the host (tests/host_patch_index.hip) against a brute-force enumeration, and every header of mimi_amd/csrc compiled alone."""
+the host (tests/host_patch_index.hip) against a brute-force enumeration, the forward stages of mimi_amd/csrc/sum_factor.hpp
+against a dense contraction, and every header of mimi_amd/csrc compiled alone."""
 import ctypes
 import glob
 import itertools
@@ -100,6 +101,52 @@ def test_node_window_against_brute_force(host_index, P, case):
             assert seen_empty
 
 
+@pytest.mark.parametrize("P", [1, 2, 3])
+@pytest.mark.parametrize("dim", [2, 3])
+def test_forward_stages_against_dense_contraction(host_index, dim, P):
+    """load_element_tables, forward_stages, parametric_gradient and point_value as one thread runs them (NT = 1, tid = 0, an
+    empty barrier), with two component sets, on seeded random table blocks of three spans per direction (the element is not
+    the first one of its box, and the box does not begin the patch) and a random u_e: every point's H of both sets and the
+    value of set 0 against numpy.einsum over the same tables.  The direction a 2-D patch lacks is B = 1, D = 0.
+    Tolerance per entry 2 gamma_n S, n = 3 (P + 1) + 3, gamma_n = n eps / (1 - n eps), S the sum of the absolute products of
+    that entry: the forward error bound of three nested dot products of P + 1 terms, once for each side."""
+    rng = np.random.default_rng(1000 * dim + P)
+    NB, NQ, n_spans = P + 1, P + 2, 3
+    NBZ, NQZ = (NB, NQ) if dim == 3 else (1, 1)
+    ND, NPT, NC = NB * NB * NBZ, NQ * NQ * NQZ, 2 * dim
+    tables = rng.standard_normal((dim, 2, n_spans, NB, NQ))
+    ve = rng.standard_normal((NC, ND))
+    box_begin, el = [1, 0, 1][:dim], [1, 2, 0][:dim]
+    tab = np.full((3, 2, NB, NQ), np.nan)
+    H = np.full((2, NPT, dim, dim), np.nan)
+    val = np.full((NPT, dim), np.nan)
+    ptr = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    rc = host_index.host_forward_stages(dim, P, n_spans, (ctypes.c_int * dim)(*box_begin), (ctypes.c_int * dim)(*el), ptr(tables), ptr(ve),
+                                        ptr(tab), ptr(H), ptr(val))
+    assert rc == 0
+    # the element's block as loaded; the direction a 2-D patch lacks: B = 1 on its one node and point, D = 0
+    for d in range(dim):
+        assert np.array_equal(tab[d], tables[d, :, box_begin[d] + el[d]])
+    if dim == 2:
+        assert tab[2, 0].ravel()[0] == 1.0 and not tab[2, 0].ravel()[1:].any() and not tab[2, 1].any()
+    B = [tab[d, 0] for d in range(dim)] + [np.ones((1, 1))] * (3 - dim)
+    D = [tab[d, 1] for d in range(dim)] + [np.zeros((1, 1))] * (3 - dim)
+    v = ve.reshape(NC, NBZ, NB, NB)                      # [component][a2][a1][a0]
+    dense = lambda t, w: np.einsum("ax,by,cz,ncba->nzyx", t[0], t[1], t[2], w).reshape(len(w), NPT)   # point = q0 + NQ (q1 + NQ q2)
+    n = 3 * (P + 1) + 3
+    eps = np.finfo(np.float64).eps / 2
+    gamma = n * eps / (1 - n * eps)
+    for m in range(dim + 1):                             # m < dim: the derivative along direction m; m == dim: the value
+        t = [D[d] if m < dim and d == m else B[d] for d in range(3)]
+        w = v[:dim] if m == dim else v                   # (the value is taken of component set 0)
+        got = val.T if m == dim else H[..., m].transpose(0, 2, 1).reshape(NC, NPT)
+        assert np.isfinite(got).all()
+        err = np.abs(got - dense(t, w))
+        bound = 2 * gamma * dense([np.abs(x) for x in t], np.abs(w))
+        print(f"dim {dim} P {P} {'value' if m == dim else 'd/dxi_%d' % m}: largest error / bound {float((err / bound).max()):.3f}")
+        assert (err <= bound).all()
+
+
 def test_every_header_compiles_alone():
     """each header of mimi_amd/csrc includes what it uses: host side only, syntax only"""
     if shutil.which("hipcc") is None:
@@ -117,8 +164,8 @@ def test_every_header_compiles_alone():
 
 
 def test_dispatch_headers_include_kernel_headers_never_the_reverse():
-    dispatch = {"domain_dispatch.hpp", "tensor_dispatch.hpp", "domain_create.hpp"}
-    for h in glob.glob(os.path.join(CSRC, "kernels_*.hpp")) + [os.path.join(CSRC, "patch_index.hpp")]:
+    dispatch = {"domain_dispatch.hpp", "domain_dispatch_nodal.hpp", "tensor_dispatch.hpp", "domain_create.hpp"}
+    for h in glob.glob(os.path.join(CSRC, "kernels_*.hpp")) + [os.path.join(CSRC, "patch_index.hpp"), os.path.join(CSRC, "sum_factor.hpp")]:
         text = open(h).read()
         for d in dispatch:
             assert f'#include "{d}"' not in text, (os.path.basename(h), d)

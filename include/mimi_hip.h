@@ -544,6 +544,49 @@ int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const do
  * it must outlive the setting.  domain == NULL clears it. */
 int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, double density, double stiffness, double viscosity);
 
+/* ---- explicit central-difference step with a lumped mass -----------------------------------------------------------
+ * Stands in for the reference's CentralDifference = Newmark(beta = 0, gamma = 1/2) step (solvers/ode.hpp:257,
+ * ode.cpp:229-250), which solves with the consistent mass; here the mass is the vector m and a step is
+ *   predict, the caller's force evaluation at the new x (and the damping force at the new v), correct.
+ * Masks, one byte per dof (NULL: none set): fixed (v = 0, x kept) and prescribed (v = prescribed_velocity, a = 0; wins
+ * where both are set).  The create arguments may be host or device arrays (copied).  Every vector of the other entries
+ * must be device-resident: a host pointer is refused (ode.cpp:229-250 works on the solver's own vectors; a staged copy
+ * per step would defeat the step).  Nothing but mimi_hip_explicit_energies and _synchronize waits for the device. */
+typedef struct mimi_hip_explicit_s* mimi_hip_explicit_t;
+int mimi_hip_explicit_create(int64_t n, const unsigned char* fixed, const unsigned char* prescribed,
+                             const double* prescribed_velocity, int device, mimi_hip_explicit_t* out);
+int mimi_hip_explicit_destroy(mimi_hip_explicit_t h);
+/* NULL = the handle's own stream; MIMI_HIP_STREAM_NULL = the device's null stream.  The launches of one handle must not
+ * overlap: the sums of start / correct share the handle's partial-sum buffers and ticket, so a caller that moves the handle
+ * to another stream orders that stream behind the work already enqueued (one stream per handle is the intended use). */
+int mimi_hip_explicit_set_stream(mimi_hip_explicit_t h, void* stream);
+/* waits for the handle's stream and reads its status word: an error when set_mass saw a non-positive mass on a free or
+ * prescribed dof */
+int mimi_hip_explicit_synchronize(mimi_hip_explicit_t h);
+/* what: 0 n, 1 / 2 the address of the internal / damping force vector of the previous step (the handle keeps the caller's
+ * buffer by pointer: no copy), 3 corrects since start, 8 workgroups of a launch; the shape of the ledger's sums, valid
+ * with h == NULL: 4 threads of a workgroup, 5 most workgroups of a launch, 6 partials a thread of the last workgroup adds,
+ * 7 levels of the two trees.  -1: bad argument. */
+int64_t mimi_hip_explicit_info(mimi_hip_explicit_t h, int what);
+/* the lumped mass (the M of ode.cpp:229-250 as a vector), copied; positive on every free and every prescribed dof (the
+ * latter's enters KE), checked on the device; a fixed dof's is not read */
+int mimi_hip_explicit_set_mass(mimi_hip_explicit_t h, const double* m);
+/* a_0 = ((f - r) - d) / m on free dofs, 0 elsewhere (the initial acceleration of ode.cpp:229-250); the masks are applied
+ * to v; r and d become the previous force vectors; the works are zeroed.  f and d may be NULL (no load / no damping). */
+int mimi_hip_explicit_start(mimi_hip_explicit_t h, double* v, const double* f, const double* r, const double* d);
+/* v <- v + dt/2 a, x <- x + dt v with the masks applied (the predictor of ode.cpp:229-250 at beta = 0, gamma = 1/2) */
+int mimi_hip_explicit_predict(mimi_hip_explicit_t h, double dt, double* x, double* v);
+/* a <- ((f - r) - d) / m on free dofs, v <- v + dt/2 a (the corrector of ode.cpp:229-250 with the mass solve replaced by
+ * the division), and the energy ledger in the same pass (mimi_amd/csrc/explicit.hip).  r: the raw internal force at the
+ * new x, d: the damping force at the predictor velocity (NULL iff it was NULL at start).  r and d are read again by the
+ * next correct, which must be given other buffers: the caller alternates two and leaves the last one untouched. */
+int mimi_hip_explicit_correct(mimi_hip_explicit_t h, double dt, const double* f, const double* r, const double* d, double* v);
+/* a (device, n doubles) <- the current acceleration (the d2x/dt2 ode.cpp:229-250 keeps between steps) */
+int mimi_hip_explicit_acceleration(mimi_hip_explicit_t h, double* a);
+/* out6 (host) = KE, W_int, W_ext, W_damp, Q = dt^2/8 sum m a^2, E* = KE - Q + W_int + W_damp - W_ext: the ledger beside
+ * the step of ode.cpp:229-250 (the reference keeps none).  dt: the step size Q is formed with.  Waits for the stream. */
+int mimi_hip_explicit_energies(mimi_hip_explicit_t h, double dt, double* out6);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,8 @@ from .splines import BSplinePatch
 from . import integrators
 from .integrators import RigidSphere, RigidPlane, RigidSpline, NearestDistanceToSplines, FollowerPressure
 from .solid import NonlinearSolid, Solid, BoundaryConditions, RuntimeCommunication
+from .explicit import ExplicitStepper
 
 __all__ = ["CompressibleOgdenNeoHookean", "J2", "Material", "BSplinePatch", "integrators", "NonlinearSolid",
            "Solid", "BoundaryConditions", "RuntimeCommunication", "RigidSphere", "RigidPlane",
-           "FollowerPressure"]
+           "FollowerPressure", "ExplicitStepper"]

@@ -101,6 +101,9 @@ EXPORTS = [
     "mimi_hip_domain_set_shape_values",
     "mimi_hip_domain_add_mass", "mimi_hip_domain_add_diffusion", "mimi_hip_domain_add_body_force",
     "mimi_hip_domain_linearize", "mimi_hip_domain_apply_tangent", "mimi_hip_linear_set_operator",
+    "mimi_hip_explicit_create", "mimi_hip_explicit_destroy", "mimi_hip_explicit_set_stream", "mimi_hip_explicit_synchronize",
+    "mimi_hip_explicit_info", "mimi_hip_explicit_set_mass", "mimi_hip_explicit_start", "mimi_hip_explicit_predict",
+    "mimi_hip_explicit_correct", "mimi_hip_explicit_acceleration", "mimi_hip_explicit_energies",
 ]
 
 
@@ -244,6 +247,18 @@ def lib():
     L.mimi_hip_linear_set_kronecker.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mimi_hip_linear_set_kronecker_coefficients.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
     L.mimi_hip_linear_apply_preconditioner.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mimi_hip_explicit_create.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.mimi_hip_explicit_destroy.argtypes = [C.c_void_p]
+    L.mimi_hip_explicit_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_explicit_synchronize.argtypes = [C.c_void_p]
+    L.mimi_hip_explicit_info.argtypes = [C.c_void_p, C.c_int]
+    L.mimi_hip_explicit_info.restype = C.c_int64
+    L.mimi_hip_explicit_set_mass.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_explicit_start.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mimi_hip_explicit_predict.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    L.mimi_hip_explicit_correct.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mimi_hip_explicit_acceleration.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_explicit_energies.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
     _lib = L
     return L
 

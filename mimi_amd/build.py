@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libmimi_hip.so")
-SOURCES = ["domain.hip", "tensor_p3.hip", "contact.hip", "krylov.hip", "exchange.hip", "pressure.hip", "fold.hip", "surface.hip"]
+SOURCES = ["domain.hip", "tensor_p3.hip", "contact.hip", "krylov.hip", "exchange.hip", "pressure.hip", "fold.hip", "surface.hip", "explicit.hip"]
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 # the one flag list: objects take it without -shared, the link whole, isa_lint's device-only compiles without -shared / -fPIC
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-munsafe-fp-atomics",

@@ -29,6 +29,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from . import nurbs_mesh, splines
+from .explicit import ExplicitDynamics
 from .integrators import (CouplingSurface, CSRPattern, FollowerPressure, MortarContact,
                           NonlinearSolid as NonlinearSolidIntegrator, PeriodicFold, periodic_node_map)
 from .kronecker import KroneckerOperator, stiffness_coefficients
@@ -333,8 +334,9 @@ def _element_tables(patch, quadrature_order=-1, with_gradients=False, elements=N
     return N, w[None, :] * det, conn
 
 
-class NonlinearSolid(Solid):
-    """PyNonlinearSolid (src/mimi/py/py_nonlinear_solid.cpp:15-387) on top of the HIP integrators."""
+class NonlinearSolid(Solid, ExplicitDynamics):
+    """PyNonlinearSolid (src/mimi/py/py_nonlinear_solid.cpp:15-387) on top of the HIP integrators; with
+    rc.set_int("explicit_dynamics", 1) the explicit central-difference route of mimi_amd/explicit.py."""
 
     def __init__(self, device=0):
         super().__init__()
@@ -357,6 +359,9 @@ class NonlinearSolid(Solid):
             raise RuntimeError("use_kronecker_preconditioner cannot be combined with a periodic boundary "
                                "(boundary_condition.initial.periodic): the folded numbering needs periodic 1-D matrices, "
                                "which the Kronecker preconditioner does not build -- unset one of the two")
+        # "explicit_dynamics": explicit_steps in place of step_time2, no matrix of any kind (mimi_amd/explicit.py)
+        self.explicit_ = self._explicit_flags(rc)
+        self.explicit_consistent_ = self._explicit_consistent_flag(rc, axes)
         # "matrix_free": the Newton solves take the domain integrator's tangent action in place of the assembled Jacobian
         # (LinearSolver.SetOperator); only what the action covers
         if rc is not None and rc.get_int("matrix_free", 0):
@@ -421,6 +426,8 @@ class NonlinearSolid(Solid):
         # (_device_setup, once the integrator and the eliminations exist) unless the host pass is asked for with
         # MIMI_HIP_HOST_SETUP=1 or rc.set_int("host_setup", 1)
         self.host_setup_ = bool(rc.get_int("host_setup", 0)) or os.environ.get("MIMI_HIP_HOST_SETUP", "") == "1"
+        if self.explicit_ and self.host_setup_:
+            raise RuntimeError("explicit_dynamics cannot be combined with the host set-up: the lumped mass is assembled on the device")
         self._mass_host, self._visc_host = None, None
         self.d_mass_, self.d_visc_ = None, None
         self.host_nnz_arrays_ = 0                                    # host arrays of nnz doubles made since setup began
@@ -603,9 +610,13 @@ class NonlinearSolid(Solid):
             self.linear_.SetKronecker(KroneckerOperator(patch, self.dirichlet_, dim))
             self.linear_.preconditioner = "kronecker"
         self.matrix_free_ = bool(rc.get_int("matrix_free", 0))       # (what it needs was checked at the top of setup)
-        if not self.host_setup_:
+        if self.explicit_:
+            self._explicit_setup()
+        elif not self.host_setup_:
             self._device_setup()
         self._to_device()
+        if self.explicit_:
+            self._explicit_make_stepper()
 
     def _folded_dofs(self, nodes, comp):
         """dofs (node, comp) of unwrapped nodes in the solver's numbering (through the periodic node map), unique"""
@@ -654,7 +665,7 @@ class NonlinearSolid(Solid):
             self.d_visc_ = f(self.visc_) if self.visc_ is not None else None
         self.d_rhs_ = f(self.rhs_)
         self._rhs = self.d_rhs_           # what the residual subtracts (_update_rhs)
-        if not self.matrix_free_:
+        if not self.matrix_free_ and not self.explicit_:
             self.d_jac_ = torch.zeros_like(self.d_mass_)
         self.d_dirichlet_ = torch.from_numpy(np.asarray(self.dirichlet_, dtype=np.int64)).to(dev)
         self.d_x_, self.d_v_ = f(self.x), f(self.x_dot)
@@ -662,7 +673,8 @@ class NonlinearSolid(Solid):
             # the integrators' side of the fold: expanded x, unwrapped residual and values
             self.d_xu_ = torch.zeros(self.fold_.n_u_, dtype=torch.float64, device=dev)
             self.d_ru_ = torch.zeros_like(self.d_xu_)
-            self.d_Au_ = torch.zeros(self.fold_.nnz_u_, dtype=torch.float64, device=dev)
+            if not self.explicit_:
+                self.d_Au_ = torch.zeros(self.fold_.nnz_u_, dtype=torch.float64, device=dev)
         if len(self.constant_velocity_dofs_):
             self.d_cv_dofs_ = torch.from_numpy(self.constant_velocity_dofs_).to(dev)
             self.d_cv_values_ = f(self.constant_velocity_values_)
@@ -943,6 +955,7 @@ class NonlinearSolid(Solid):
         Difference from the reference: refused (RuntimeError) while a fixed-point step is open, i.e. after a
         fixed_point_solve2() that no advance_time2() has committed yet; the reference would silently commit that step's
         stale alpha levels."""
+        self._explicit_refuse("step_time2")
         if self._fp_open:
             raise RuntimeError("step_time2() while a fixed-point step is open: finish it with advance_time2() first")
         self._predict()
@@ -960,6 +973,7 @@ class NonlinearSolid(Solid):
 
         Differences from the reference, both RuntimeError where the reference silently commits stale alpha levels:
         advance_time2() without a fixed_point_solve2() in the step, and step_time2() while a fixed-point step is open."""
+        self._explicit_refuse("fixed_point_solve2")
         if not self._fp_open:
             self._predict()
             self._fp_open = True
@@ -971,6 +985,7 @@ class NonlinearSolid(Solid):
         """(x, v), each (n // dim, dim): the end-of-step vectors the current aa gives, after the constant-velocity Restore
         (GeneralizedAlpha2::FixedPointAdvance2, ode.cpp:113-146).  The same two host arrays on every call, updated in place;
         no solver state changes."""
+        self._explicit_refuse("fixed_point_advance2")
         if not self._fp_open:
             raise RuntimeError("FixedPointAdvance2() should be called after FixedPointSolve2()")
         x, v = self.d_x_.clone(), self.d_v_.clone()
@@ -990,6 +1005,7 @@ class NonlinearSolid(Solid):
 
         Difference from the reference: refused (RuntimeError) without a fixed_point_solve2() in the step; the reference
         would silently commit stale alpha levels."""
+        self._explicit_refuse("advance_time2")
         if not self._fp_open:
             raise RuntimeError("advance_time2() without a fixed_point_solve2() in this step: there is no solved step to "
                                "commit")

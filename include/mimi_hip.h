@@ -391,6 +391,22 @@ int mimi_hip_contact_nodal(mimi_hip_contact_t h, int set, double* area, double* 
 int mimi_hip_contact_add_residual_from_nodal(mimi_hip_contact_t h, const double* u, double grad_factor, double* r,
                                              double* A_values);
 
+/* Matrix-free action of the contact tangent: stands in for MortarContact::AddBoundaryResidualAndGrad
+ * (mortar_contact.cpp:353-421) followed by SparseMatrix::Mult on what it assembled.  The tangent is the analytic one with
+ * the nodal pressure frozen (mortar_contact.cpp:263-295), R(a,i) = -w p_q N_a m_i, whatever the tangent mode:
+ *   (K x)(a,i) = sum_q c_q N_a dm_i,  c_q = -w p_q,  dm = dt_1 x t_2 + t_1 x dt_2 (3-D), (dt_y, -dt_x) (2-D),  dt_k = sum_b N_b,k x_b.
+ * linearize = the snapshot at u: pass 1 and the pressure with the handle's current body and penalty (the nodal area / gap /
+ * pressure of the handle are overwritten, the history of the last Add* call is not), then per face point c_q and the
+ * surface tangents t, per face the IsPressureZero flag, in buffers of their own.  The record survives every later call on
+ * the handle (Add* at another u, update_body, gap_norm); no copy of u is kept and no face tangent block is allocated.
+ * apply_tangent: y += factor K(u of linearize) x over the recorded active faces, summed per node in the order of the face
+ * incidences (no atomics: equal inputs give equal bytes); refused before the first linearize.  u, x, y host or device. */
+int mimi_hip_contact_linearize(mimi_hip_contact_t h, const double* u);
+int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const double* x, double* y);
+/* what: 0 bytes of the record (n_faces n_quad (1 + (dim - 1) dim) doubles + n_faces flags; 0 before the first linearize),
+ * 1 whether the face tangent blocks of an assembly are allocated.  -1: bad argument. */
+int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what);
+
 /* ---- follower-pressure boundary integrator (integrators::FollowerPressure) ---------------------------------------
  * The reference stores BCMarker::Pressure(bid, value) (utils/boundary_conditions.cpp:43-50) and never applies it; here it
  * is the follower load t = -p n da on the CURRENT surface x = X + u of a set of faces of one patch:
@@ -436,6 +452,13 @@ int mimi_hip_pressure_add_residual_and_grad(mimi_hip_pressure_t h, const double*
 /* of the latest Add* call (as mimi_hip_contact_last_history for last_area_ / last_force_, mortar_contact.hpp:33-35):
  * out[0] = current area of the faces, out[1..1+dim) = external force -sum p m w; unused entries 0 */
 int mimi_hip_pressure_last_history(mimi_hip_pressure_t h, double* out4);
+/* Matrix-free action of the follower-pressure tangent, the twin of mimi_hip_contact_linearize / _apply_tangent (there:
+ * MortarContact::AddBoundaryResidualAndGrad, mortar_contact.cpp:353-421, followed by SparseMatrix::Mult): c_q = w p_q with
+ * the uniform or nodal pressure the handle holds at linearize; the record survives set_value / set_nodal and every Add*
+ * call.  action_info as mimi_hip_contact_action_info. */
+int mimi_hip_follower_linearize(mimi_hip_pressure_t h, const double* u);
+int mimi_hip_follower_apply_tangent(mimi_hip_pressure_t h, double factor, const double* x, double* y);
+int64_t mimi_hip_follower_action_info(mimi_hip_pressure_t h, int what);
 
 /* ---- coupling surface (partitioned fluid-structure coupling) ---------------------------------------------------------
  * What a fluid partner exchanges with the solid every coupling iteration of the reference's fixed-point loop
@@ -543,6 +566,16 @@ int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const do
  * waits once on the event behind the domain's last linearize.  The domain must be on the solver's device and have its n;
  * it must outlive the setting.  domain == NULL clears it. */
 int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, double density, double stiffness, double viscosity);
+/* A face tangent beside the domain operator: kind 0 = a mimi_hip_contact_t, 1 = a mimi_hip_pressure_t (`handle` must be of
+ * that kind).  With A_values == NULL the product becomes
+ *   y = mask((density M + stiffness K + viscosity C + sum_k factor_k K_face,k) mask x) + x[ess],
+ * the terms added in the order they were set (mimi_hip_contact_apply_tangent / mimi_hip_follower_apply_tangent: stands in
+ * for SparseMatrix::Mult on the matrix MortarContact::AddBoundaryResidualAndGrad, mortar_contact.cpp:353-421, added to).
+ * At most 8 terms; refused without a domain operator, on another device, with another n, beyond the eighth.  Every
+ * mimi_hip_linear_set_operator call (domain NULL or not) drops the terms.  The actions run on the solver's stream; a solve
+ * waits once on the event behind each handle's last linearize, and is refused when a handle has none.  The handles must
+ * outlive the setting. */
+int mimi_hip_linear_add_boundary_operator(mimi_hip_linear_t h, int kind, void* handle, double factor);
 
 /* ---- explicit central-difference step with a lumped mass -----------------------------------------------------------
  * Stands in for the reference's CentralDifference = Newmark(beta = 0, gamma = 1/2) step (solvers/ode.hpp:257,

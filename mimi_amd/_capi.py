@@ -104,6 +104,9 @@ EXPORTS = [
     "mimi_hip_explicit_create", "mimi_hip_explicit_destroy", "mimi_hip_explicit_set_stream", "mimi_hip_explicit_synchronize",
     "mimi_hip_explicit_info", "mimi_hip_explicit_set_mass", "mimi_hip_explicit_start", "mimi_hip_explicit_predict",
     "mimi_hip_explicit_correct", "mimi_hip_explicit_acceleration", "mimi_hip_explicit_energies",
+    "mimi_hip_contact_linearize", "mimi_hip_contact_apply_tangent", "mimi_hip_contact_action_info",
+    "mimi_hip_follower_linearize", "mimi_hip_follower_apply_tangent", "mimi_hip_follower_action_info",
+    "mimi_hip_linear_add_boundary_operator",
 ]
 
 
@@ -259,6 +262,12 @@ def lib():
     L.mimi_hip_explicit_correct.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mimi_hip_explicit_acceleration.argtypes = [C.c_void_p, C.c_void_p]
     L.mimi_hip_explicit_energies.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
+    for kind in ("contact", "follower"):
+        getattr(L, f"mimi_hip_{kind}_linearize").argtypes = [C.c_void_p, C.c_void_p]
+        getattr(L, f"mimi_hip_{kind}_apply_tangent").argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        getattr(L, f"mimi_hip_{kind}_action_info").argtypes = [C.c_void_p, C.c_int]
+        getattr(L, f"mimi_hip_{kind}_action_info").restype = C.c_int64
+    L.mimi_hip_linear_add_boundary_operator.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
     _lib = L
     return L
 

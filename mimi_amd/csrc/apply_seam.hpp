@@ -1,6 +1,8 @@
-// What the Krylov solvers (krylov.hip) see of a domain handle that stands in for the matrix
-// (mimi_hip_linear_set_operator): its size and device, and the tangent action launched on the SOLVER's stream.  Defined in
-// domain.hip; the kernels are kernels_apply.hpp.
+// What the Krylov solvers (krylov.hip) see of the handles that stand in for the matrix: of a domain handle
+// (mimi_hip_linear_set_operator) its size and device and the tangent action launched on the SOLVER's stream -- defined in
+// domain.hip, the kernels are kernels_apply.hpp; of a contact or follower-pressure handle
+// (mimi_hip_linear_add_boundary_operator) the same for the action of its face tangent -- defined in contact.hip and
+// pressure.hip, the kernels are kernels_face_action.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -8,6 +10,8 @@
 #include <cstdint>
 
 struct mimi_hip_domain_s;
+struct mimi_hip_contact_s;
+struct mimi_hip_pressure_s;
 
 namespace mimi_hip {
 
@@ -19,5 +23,17 @@ void operator_begin_solve(mimi_hip_domain_s* h, double density, double stiffness
 // y += density M x + stiffness K x + viscosity C x; x, y on the device, everything on solver_stream
 void operator_add_action(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, const double* x, double* y,
                          hipStream_t solver_stream);
+
+// The boundary twins.  begin_solve: the check of mimi_hip_<kind>_apply_tangent (a linearize came first), the face vector of
+// the action, and one wait of solver_stream on the event recorded behind the handle's last linearize.
+// add_action: y += factor K_face x; x, y on the device, everything on solver_stream.
+int64_t operator_size(const mimi_hip_contact_s* h);
+int operator_device(const mimi_hip_contact_s* h);
+void operator_begin_solve(mimi_hip_contact_s* h, hipStream_t solver_stream);
+void operator_add_action(mimi_hip_contact_s* h, double factor, const double* x, double* y, hipStream_t solver_stream);
+int64_t operator_size(const mimi_hip_pressure_s* h);
+int operator_device(const mimi_hip_pressure_s* h);
+void operator_begin_solve(mimi_hip_pressure_s* h, hipStream_t solver_stream);
+void operator_add_action(mimi_hip_pressure_s* h, double factor, const double* x, double* y, hipStream_t solver_stream);
 
 }  // namespace mimi_hip

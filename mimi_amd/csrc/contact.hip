@@ -17,14 +17,19 @@
 // and summed afterwards in a fixed order through the marked nodes' (face, local node) incidences: no atomics, results
 // bitwise reproducible like the domain paths (round 3; rounds 1-2 used fp64 atomics here).  The face tables, the
 // incidences, the pair positions, the fixed-order sums and the row gather are face_common.hpp's, shared with pressure.hip.
+// The matrix-free action of the frozen-pressure tangent (mimi_hip_contact_linearize / _apply_tangent, and the Krylov
+// solvers' boundary terms through apply_seam.hpp) is kernels_face_action.hpp, shared with pressure.hip as well: it builds
+// no face tangent block.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <memory>
 #include <vector>
 
+#include "apply_seam.hpp"
 #include "common.hpp"
 #include "face_common.hpp"
+#include "kernels_face_action.hpp"
 #include "materials.hpp"
 #include "spline_body.hpp"
 
@@ -476,7 +481,22 @@ struct mimi_hip_contact_s : FaceAssembly {
   DeviceBuffer<double> pt_area, pt_gap, pt_scal;   // per quadrature point: the dense stores of pass 1
   SplineBodyDev spline{};
   DeviceBuffer<double> sb_knots[2], sb_ctrl, sb_sample_xi, sb_sample_x;
+  BoundaryAction action;   // mimi_hip_contact_linearize / _apply_tangent (kernels_face_action.hpp)
 };
+
+// ---- the operator seam of the Krylov solvers (apply_seam.hpp) ----------------------------------------------------------------
+namespace mimi_hip {
+int64_t operator_size(const mimi_hip_contact_s* h) { return h->n_vdofs; }
+int operator_device(const mimi_hip_contact_s* h) { return h->device; }
+void operator_begin_solve(mimi_hip_contact_s* h, hipStream_t solver_stream) {
+  h->action.require("contact");
+  MH_HIP(hipSetDevice(h->device));
+  h->action.begin(*h, solver_stream);
+}
+void operator_add_action(mimi_hip_contact_s* h, double factor, const double* x, double* y, hipStream_t solver_stream) {
+  h->action.add(*h, factor, x, y, solver_stream);
+}
+}  // namespace mimi_hip
 
 // NearestDistanceToSplines::AddSpline / PlantKdTree (nearest_distance.hpp:223-255): (re)upload the rigid spline and the
 // sampled initial guesses.  Called at create time and whenever the caller moved the body and re-planted its tree.
@@ -570,6 +590,23 @@ static void contact_pass1(mimi_hip_contact_s* h, const double* u_dev) {
                      h->n_fnodes, h->n_q, h->n_dof, h->adj_ptr.ptr, h->adj.ptr, h->pt_area.ptr, h->pt_gap.ptr, h->area.ptr, h->gap.ptr);
   hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, npts, 1, 1, h->pt_scal.ptr,
                      (const unsigned char*)nullptr, h->scalars.ptr);
+}
+
+// The snapshot of the frozen-pressure tangent at u: pass 1 and the pressure with the handle's current body and penalty
+// (the history scalars of the last Add* call are left alone), then the record of kernels_face_action.hpp.  It is the
+// analytic tangent whatever the tangent mode says.
+static void contact_linearize(mimi_hip_contact_s* h, const double* u_dev) {
+  const ContactArgs a = contact_args(h, u_dev);
+  const int threads = 128;
+  const int64_t npts = (int64_t)h->n_faces * h->n_q;
+  const unsigned b1 = (unsigned)((npts + threads - 1) / threads);
+  if (h->dim == 2) hipLaunchKernelGGL(contact_gap_area_kernel<2>, dim3(b1), dim3(threads), 0, h->stream, a, 0);
+  else hipLaunchKernelGGL(contact_gap_area_kernel<3>, dim3(b1), dim3(threads), 0, h->stream, a, 0);
+  hipLaunchKernelGGL(contact_nodal_kernel, dim3((unsigned)((h->n_fnodes + 3) / 4)), dim3(256), 0, h->stream,
+                     h->n_fnodes, h->n_q, h->n_dof, h->adj_ptr.ptr, h->adj.ptr, h->pt_area.ptr, h->pt_gap.ptr, h->area.ptr, h->gap.ptr);
+  hipLaunchKernelGGL(contact_pressure_kernel, dim3((unsigned)((h->n_fnodes + threads - 1) / threads)), dim3(threads), 0, h->stream,
+                     h->n_fnodes, h->area.ptr, h->gap.ptr, h->penalty, h->pressure.ptr);
+  h->action.linearize(*h, u_dev, h->pressure.ptr, 0.0, -1.0);
 }
 
 // pressure from the nodal area / gap (mortar_contact.cpp:195-261), then pass 2: face residual vectors (+ tangent blocks)
@@ -669,6 +706,19 @@ int mimi_hip_contact_add_residual_and_grad(mimi_hip_contact_t h, const double* u
     run_contact(h, u, r, A_values, grad_factor, true);
   });
 }
+
+int mimi_hip_contact_linearize(mimi_hip_contact_t h, const double* u) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    h->run(u, nullptr, nullptr, false, [&](const double* u_dev, double*, double*) { contact_linearize(h, u_dev); });
+  });
+}
+
+int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const double* x, double* y) {
+  return guarded([&] { boundary_apply_entry(h, "contact", factor, x, y); });
+}
+
+int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what) { return boundary_action_info(h, what); }
 
 int mimi_hip_contact_gap_norm(mimi_hip_contact_t h, const double* u, double* out) {
   return guarded([&] {

@@ -328,6 +328,16 @@ struct FaceAssembly : FaceSet {
                          fnodes_dev.ptr, adj_ptr.ptr, adj.ptr, 0);
   }
 
+  // y += the node sums of a dense face vector [n_faces][dim][n_dof] over the faces flagged in `active`, on stream s: the
+  // gather above without K, for callers that keep flags and vectors of their own (kernels_face_action.hpp)
+  template<int DIM>
+  void gather_vector(const unsigned char* active, const double* face_vec, double* y, hipStream_t s) {
+    const FaceGatherArgs a{n_dof, rowptr, pair_pos.ptr, active, face_vec, nullptr, y, nullptr, 0.0};
+    const unsigned blocks = (unsigned)(((int64_t)n_fnodes * DIM + kFaceGatherWaves - 1) / kFaceGatherWaves);
+    hipLaunchKernelGGL((face_row_gather_kernel<DIM, 0>), dim3(blocks), dim3(64 * kFaceGatherWaves), 0, s, a, n_fnodes,
+                       fnodes_dev.ptr, adj_ptr.ptr, adj.ptr, 0);
+  }
+
   // One assembly call: u mirrored in, r (when given) and, with_grad, A mirrored in and out around
   // launch(u_dev, r_dev, A_dev); synchronous when any of them lives on the host.
   template<typename Launch>

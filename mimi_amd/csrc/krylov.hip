@@ -378,6 +378,15 @@ struct mimi_hip_linear_s : StreamHandle {
   mimi_hip_domain_s* op_domain = nullptr;
   double op_density = 0.0, op_stiffness = 0.0, op_viscosity = 0.0;
   DeviceBuffer<double> op_x;   // the masked input of the action
+  // mimi_hip_linear_add_boundary_operator: face tangents added to the domain's action, in the order they were set
+  struct BoundaryTerm {
+    int kind;        // 0 contact, 1 pressure
+    void* handle;
+    double factor;
+  };
+  static constexpr int kMaxBoundaryTerms = 8;
+  BoundaryTerm op_terms[kMaxBoundaryTerms];
+  int n_op_terms = 0;
   DeviceBuffer<int> status;                      // one word: what the pattern checks of create found
   double* column_host[2] = {nullptr, nullptr};   // pinned: the Hessenberg column of the step before last and of the last one
   hipEvent_t column_ready[2] = {nullptr, nullptr};
@@ -415,6 +424,13 @@ void by_product_form(const mimi_hip_linear_s* h, F&& f) {
   else f(integral_constant<int, 1>{}, std::false_type{}, h->n, h->col);
 }
 
+// the handle of a boundary term by its kind: the one switch over it.  f(handle)
+template<class F>
+void by_boundary_kind(const mimi_hip_linear_s::BoundaryTerm& t, F&& f) {
+  if (t.kind == 0) f(static_cast<mimi_hip_contact_s*>(t.handle));
+  else f(static_cast<mimi_hip_pressure_s*>(t.handle));
+}
+
 dim3 wave_per_unit(int64_t units) { return dim3((unsigned)((units + 3) / 4)); }   // workgroups of 256: four waves
 
 // y = dinv o (A x), dinv o (b - A x) with b, plain without dinv.  val == nullptr: A is the handle's operator (no dinv then:
@@ -423,6 +439,8 @@ void spmv(mimi_hip_linear_s* h, const double* val, const double* x, const double
   if (!val) {
     launch(kr_operator_mask_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, (const unsigned char*)h->is_ess.ptr, x, h->op_x.ptr, y);
     operator_add_action(h->op_domain, h->op_density, h->op_stiffness, h->op_viscosity, h->op_x.ptr, y, h->stream);
+    for (int k = 0; k < h->n_op_terms; ++k)
+      by_boundary_kind(h->op_terms[k], [&](auto* face) { operator_add_action(face, h->op_terms[k].factor, h->op_x.ptr, y, h->stream); });
     launch(kr_operator_restore_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, (const unsigned char*)h->is_ess.ptr, x, b, y);
     return;
   }
@@ -502,6 +520,8 @@ Mirror<double> solve_matrix(mimi_hip_linear_s* h, const double* A_values, int pr
   if (preconditioner == PRECOND_JACOBI) fail("the Jacobi preconditioner needs the matrix values");
   h->op_x.resize((size_t)h->n);
   operator_begin_solve(h->op_domain, h->op_density, h->op_stiffness, h->stream);
+  for (int k = 0; k < h->n_op_terms; ++k)
+    by_boundary_kind(h->op_terms[k], [&](auto* face) { operator_begin_solve(face, h->stream); });
   MH_HIP(hipSetDevice(h->device));
   return Mirror<double>{};
 }
@@ -846,6 +866,25 @@ int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, 
     h->op_density = density;
     h->op_stiffness = stiffness;
     h->op_viscosity = viscosity;
+    h->n_op_terms = 0;   // the boundary terms belong to the setting they were added to
+  });
+}
+
+int mimi_hip_linear_add_boundary_operator(mimi_hip_linear_t h, int kind, void* handle, double factor) {
+  return guarded([&] {
+    if (!h || !handle) fail("null argument");
+    if (kind != 0 && kind != 1) fail("boundary operator kind %d (0 contact, 1 pressure)", kind);
+    if (!h->op_domain) fail("boundary operator: no domain operator is set (mimi_hip_linear_set_operator comes first)");
+    if (h->n_op_terms >= mimi_hip_linear_s::kMaxBoundaryTerms)
+      fail("boundary operator: at most %d terms", mimi_hip_linear_s::kMaxBoundaryTerms);
+    const mimi_hip_linear_s::BoundaryTerm term{kind, handle, factor};
+    by_boundary_kind(term, [&](auto* face) {
+      if (operator_device(face) != h->device)
+        fail("boundary operator: the handle is on device %d, the solver on device %d", operator_device(face), h->device);
+      if (operator_size(face) != h->n)
+        fail("boundary operator: the handle has %lld dofs, the solver %lld", (long long)operator_size(face), (long long)h->n);
+    });
+    h->op_terms[h->n_op_terms++] = term;
   });
 }
 

@@ -14,6 +14,8 @@
 // vector and tangent block densely (pressure_face_kernel), then the row gather both share (face_common.hpp: one wave per
 // CSR row of a face node walks the node's (face, local node) incidences in a fixed order into an LDS image of the row).
 // No atomics on the assembly path: the same bits every run.
+// The matrix-free action of the tangent (mimi_hip_follower_linearize / _apply_tangent, and the Krylov solvers' boundary
+// terms through apply_seam.hpp) is kernels_face_action.hpp, shared with contact.hip: c_q = w p_q, no face tangent block.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,8 +23,10 @@
 #include <memory>
 #include <vector>
 
+#include "apply_seam.hpp"
 #include "common.hpp"
 #include "face_common.hpp"
+#include "kernels_face_action.hpp"
 
 namespace mimi_hip {
 
@@ -177,7 +181,22 @@ struct mimi_hip_pressure_s : FaceAssembly {
   double value = 0.0;
   bool use_nodal = false;
   DeviceBuffer<double> nodal, scalars;   // nodal: pressure values at fnodes (the order of set_nodal)
+  BoundaryAction action;                 // mimi_hip_follower_linearize / _apply_tangent (kernels_face_action.hpp)
 };
+
+// ---- the operator seam of the Krylov solvers (apply_seam.hpp) ----------------------------------------------------------------
+namespace mimi_hip {
+int64_t operator_size(const mimi_hip_pressure_s* h) { return h->n_vdofs; }
+int operator_device(const mimi_hip_pressure_s* h) { return h->device; }
+void operator_begin_solve(mimi_hip_pressure_s* h, hipStream_t solver_stream) {
+  h->action.require("follower");
+  MH_HIP(hipSetDevice(h->device));
+  h->action.begin(*h, solver_stream);
+}
+void operator_add_action(mimi_hip_pressure_s* h, double factor, const double* x, double* y, hipStream_t solver_stream) {
+  h->action.add(*h, factor, x, y, solver_stream);
+}
+}  // namespace mimi_hip
 
 static PressureArgs pressure_args(mimi_hip_pressure_s* h, const double* u) {
   PressureArgs a{};
@@ -287,6 +306,21 @@ int mimi_hip_pressure_add_residual_and_grad(mimi_hip_pressure_t h, const double*
     run_pressure(h, u, r, A_values, grad_factor, true);
   });
 }
+
+int mimi_hip_follower_linearize(mimi_hip_pressure_t h, const double* u) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    h->run(u, nullptr, nullptr, false, [&](const double* u_dev, double*, double*) {
+      h->action.linearize(*h, u_dev, h->use_nodal ? h->nodal.ptr : nullptr, h->value, 1.0);
+    });
+  });
+}
+
+int mimi_hip_follower_apply_tangent(mimi_hip_pressure_t h, double factor, const double* x, double* y) {
+  return guarded([&] { boundary_apply_entry(h, "follower", factor, x, y); });
+}
+
+int64_t mimi_hip_follower_action_info(mimi_hip_pressure_t h, int what) { return boundary_action_info(h, what); }
 
 int mimi_hip_pressure_last_history(mimi_hip_pressure_t h, double* out4) {
   return guarded([&] {

@@ -469,10 +469,41 @@ class NearestDistanceToSplines:
         return self._rs.c_struct()
 
 
-class MortarContact(NonlinearBase):
+class _FaceTangentAction:
+    """The matrix-free action of a face tangent (include/mimi_hip.h: mimi_hip_contact_linearize / mimi_hip_pressure_linearize
+    and their apply_tangent), the boundary twin of NonlinearSolid.Linearize / ApplyTangent.  `_operator_kind` is the kind of
+    mimi_hip_linear_add_boundary_operator, `_action_prefix` names the C entries (mimi_hip_<_action_prefix>_linearize ...)."""
+
+    def _action_fn(self, name):
+        return getattr(_capi.lib(), f"mimi_hip_{self._action_prefix}_{name}")
+
+    def Linearize(self, u):
+        """the snapshot of the face tangent at u (the handle's current body and penalty, or pressure) that ApplyTangent reads:
+        per face point a coefficient and the surface tangents, per face the active flag.  It survives every later call on
+        the handle.  Stands in, with ApplyTangent, for AddBoundaryResidualAndGrad followed by SparseMatrix::Mult."""
+        self._follow_torch(u)
+        check(self._action_fn("linearize")(self._handle(), fptr(u)))
+
+    def ApplyTangent(self, x, y, factor=1.0):
+        """y += factor K_face(u of Linearize) x, without a matrix.  numpy arrays or torch device tensors."""
+        self._follow_torch(x, y)
+        check(self._action_fn("apply_tangent")(self._handle(), float(factor), fptr(x), fptr(y)))
+        return y
+
+    def LinearizationBytes(self):
+        """bytes of linearisation record the handle holds (0 before the first Linearize)"""
+        return int(self._action_fn("action_info")(self._handle(), 0))
+
+    def HoldsTangentBlocks(self):
+        """whether the per-face tangent blocks of an assembly are allocated"""
+        return bool(self._action_fn("action_info")(self._handle(), 1))
+
+
+class MortarContact(_FaceTangentAction, NonlinearBase):
     """integrators::MortarContact (integrators/mortar_contact.hpp:23-172) against an analytic
     rigid body, on one face of a B-spline patch."""
     _prefix = "contact"
+    _action_prefix, _operator_kind = "contact", 0
 
     def __init__(self, nearest_distance_coeff, name, pattern, patch, axis, side, device=0, quadrature_order=-1,
                  element_box=None):
@@ -579,7 +610,7 @@ class MortarContact(NonlinearBase):
         raise RuntimeError("Currently not implemented, use AddDomainResidualAndGrad")  # mortar_contact.hpp:142-149
 
 
-class FollowerPressure(NonlinearBase):
+class FollowerPressure(_FaceTangentAction, NonlinearBase):
     """Follower pressure t = -p n da on the CURRENT surface of one face of a B-spline patch (include/mimi_hip.h:
     mimi_hip_pressure_*).  The reference's BCMarker::Pressure (utils/boundary_conditions.cpp:43-50) stores the value and
     never applies it; the boundary-integrator surface is MortarContact's (integrators/mortar_contact.hpp:23-172).
@@ -588,6 +619,7 @@ class FollowerPressure(NonlinearBase):
     dm/dx -- exact, not symmetric.  element_box = (begin, end): only the faces of the elements in that box (element slabs:
     every contribution lands in rows of the slab's own elements, no exchange of nodal values is needed)."""
     _prefix = "pressure"
+    _action_prefix, _operator_kind = "follower", 1
 
     def __init__(self, name, pattern, patch, axis, side, device=0, quadrature_order=-1, element_box=None):
         super().__init__(name)

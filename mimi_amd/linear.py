@@ -93,10 +93,19 @@ class LinearSolver(_capi.Handle):
         "kronecker"; "jacobi" needs the matrix values.  Solves that pass values run as ever."""
         check(_capi.lib().mimi_hip_linear_set_operator(self._h, domain._handle(), float(density), float(stiffness), float(viscosity)))
         self._operator = domain          # (the library reads the handle during every solve)
+        self._boundary_operators = []    # every SetOperator drops the boundary terms
+
+    def AddBoundaryOperator(self, integrator, factor):
+        """a MortarContact or FollowerPressure beside the domain of SetOperator: the product gains factor K_face(u of
+        integrator.Linearize).  At most 8 terms, added in this order; SetOperator and ClearOperator drop them."""
+        check(_capi.lib().mimi_hip_linear_add_boundary_operator(self._h, int(integrator._operator_kind), integrator._handle(),
+                                                                float(factor)))
+        self._boundary_operators.append(integrator)   # (the library reads the handle during every solve)
 
     def ClearOperator(self):
         check(_capi.lib().mimi_hip_linear_set_operator(self._h, None, 0.0, 0.0, 0.0))
         self._operator = None
+        self._boundary_operators = []
 
     def Mult(self, A_values, b, x):
         """x = A^-1 b to the configured tolerances (x is overwritten: iterative_mode false); A_values None: the operator of

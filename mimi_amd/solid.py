@@ -364,13 +364,19 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         self.explicit_consistent_ = self._explicit_consistent_flag(rc, axes)
         # "matrix_free": the Newton solves take the domain integrator's tangent action in place of the assembled Jacobian
         # (LinearSolver.SetOperator); only what the action covers
+        # "matrix_free_boundary" beside it: contact and follower-pressure markers are accepted, their face tangents join the
+        # product as actions (LinearSolver.AddBoundaryOperator)
+        boundary_actions = bool(rc is not None and rc.get_int("matrix_free_boundary", 0))
+        if boundary_actions and not rc.get_int("matrix_free", 0):
+            raise RuntimeError("matrix_free_boundary needs matrix_free: it adds the contact and pressure tangents to the "
+                               "matrix-free product")
         if rc is not None and rc.get_int("matrix_free", 0):
             if not (rc.get_int("use_iterative_solver", 0) and rc.get_int("use_kronecker_preconditioner", 0)):
                 raise RuntimeError("matrix_free needs use_iterative_solver and use_kronecker_preconditioner: without matrix values "
                                    "there is neither a direct solve nor a Jacobi preconditioner")
-            if bc.initial.contact_ or bc.current.contact_:
+            if (bc.initial.contact_ or bc.current.contact_) and not boundary_actions:
                 raise RuntimeError("matrix_free cannot be combined with a contact marker: the contact tangent has no matrix-free action")
-            if bc.initial.pressure_:
+            if bc.initial.pressure_ and not boundary_actions:
                 raise RuntimeError("matrix_free cannot be combined with a follower pressure marker: the pressure tangent has no "
                                    "matrix-free action")
             if axes:
@@ -739,12 +745,19 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         self._push(self.domain_)
         if self.matrix_free_:
             # no Jacobian: the residual-only assembly, the snapshot of the tangent at x_t, and the solver's product becomes
-            # rho M + fac0 K(x_t) + fac1 eta C of the domain integrator (no contact, pressure or periodic pair: setup)
+            # rho M + fac0 K(x_t) + fac1 eta C of the domain integrator (no periodic pair: setup); with "matrix_free_boundary"
+            # every contact and pressure integrator adds its residual, is linearised at x_t too and joins the product
             self.domain_.AddDomainResidual(xt, y)
             self.domain_.Linearize(xt)
+            faces = self.contacts_ + self.pressures_
+            for c in faces:
+                c.AddBoundaryResidual(xt, y)
+                c.Linearize(xt)
             eta = getattr(self.material, "viscosity", -1.0)
             self.linear_.SetOperator(self.domain_, self.material.density, self._fac0,
                                      self._fac1 * eta if self.d_visc_ is not None else 0.0)
+            for c in faces:
+                self.linear_.AddBoundaryOperator(c, self._fac0)
             self.linear_.Eliminate(y, None)
             y -= self._rhs
             self.linear_.Eliminate(y, None)

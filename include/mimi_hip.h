@@ -576,6 +576,22 @@ int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, 
  * waits once on the event behind each handle's last linearize, and is refused when a handle has none.  The handles must
  * outlive the setting. */
 int mimi_hip_linear_add_boundary_operator(mimi_hip_linear_t h, int kind, void* handle, double factor);
+/* A periodic fold between the solver and its operator handles: the solver's n is the FOLDED size n_nodes_f dim of `fold`,
+ * the domain handle and every boundary term have the UNWRAPPED size n_nodes_u dim, and with A_values == NULL the product is
+ *   y_f = mask(P^T (density M + stiffness K + viscosity C + sum_k factor_k K_face,k) P (mask x_f)) + x_f[ess]:
+ * the kernel in front of the actions expands the masked input into unwrapped scratch the handle owns, the actions run there
+ * unchanged, and the kernel behind them adds the copies of every folded node in ascending order (the order of
+ * mimi_hip_fold_add's residual, so the bits of folding the unfolded action) -- no pass more than without a fold, no atomics.
+ * Refused when the fold is on another device or its folded size is not the solver's n; a solve without matrix values is
+ * refused when the fold's folded size is not n or a handle has not the unwrapped size.  With a fold set,
+ * mimi_hip_linear_set_operator / _add_boundary_operator expect the unwrapped size.  The fold's tables are read in place: it
+ * must outlive the setting.  It survives mimi_hip_linear_set_operator (which goes on dropping the boundary terms only);
+ * fold == NULL clears it.  Solves that pass matrix values, and the preconditioners, never see it. */
+int mimi_hip_linear_set_operator_fold(mimi_hip_linear_t h, mimi_hip_fold_t fold);
+/* y = the eliminated operator product a solve without matrix values applies, y = mask(A (mask x)) + x[ess], folded or not,
+ * on the solver's stream: the product alone, for checks.  x and y (n doubles each, different vectors) host or device.
+ * Refused without an operator, and where a solve would be (a handle that was never linearised, a wrong size). */
+int mimi_hip_linear_operator_mult(mimi_hip_linear_t h, const double* x, double* y);
 
 /* ---- explicit central-difference step with a lumped mass -----------------------------------------------------------
  * Stands in for the reference's CentralDifference = Newmark(beta = 0, gamma = 1/2) step (solvers/ode.hpp:257,

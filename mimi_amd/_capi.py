@@ -107,6 +107,7 @@ EXPORTS = [
     "mimi_hip_contact_linearize", "mimi_hip_contact_apply_tangent", "mimi_hip_contact_action_info",
     "mimi_hip_follower_linearize", "mimi_hip_follower_apply_tangent", "mimi_hip_follower_action_info",
     "mimi_hip_linear_add_boundary_operator",
+    "mimi_hip_linear_set_operator_fold", "mimi_hip_linear_operator_mult",
 ]
 
 
@@ -268,6 +269,8 @@ def lib():
         getattr(L, f"mimi_hip_{kind}_action_info").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"mimi_hip_{kind}_action_info").restype = C.c_int64
     L.mimi_hip_linear_add_boundary_operator.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
+    L.mimi_hip_linear_set_operator_fold.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_linear_operator_mult.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

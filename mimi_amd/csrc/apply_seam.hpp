@@ -2,7 +2,8 @@
 // (mimi_hip_linear_set_operator) its size and device and the tangent action launched on the SOLVER's stream -- defined in
 // domain.hip, the kernels are kernels_apply.hpp; of a contact or follower-pressure handle
 // (mimi_hip_linear_add_boundary_operator) the same for the action of its face tangent -- defined in contact.hip and
-// pressure.hip, the kernels are kernels_face_action.hpp.
+// pressure.hip, the kernels are kernels_face_action.hpp; of a periodic fold (mimi_hip_linear_set_operator_fold) its node
+// map and copies table -- defined in fold.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -12,6 +13,7 @@
 struct mimi_hip_domain_s;
 struct mimi_hip_contact_s;
 struct mimi_hip_pressure_s;
+struct mimi_hip_fold_s;
 
 namespace mimi_hip {
 
@@ -35,5 +37,18 @@ int64_t operator_size(const mimi_hip_pressure_s* h);
 int operator_device(const mimi_hip_pressure_s* h);
 void operator_begin_solve(mimi_hip_pressure_s* h, hipStream_t solver_stream);
 void operator_add_action(mimi_hip_pressure_s* h, double factor, const double* x, double* y, hipStream_t solver_stream);
+
+// Of a periodic fold (mimi_hip_linear_set_operator_fold) the tables it built at create, read in place by the folded product
+// of krylov.hip -- defined in fold.hip.  node_map[n_nodes_u] -> folded node; the copies of folded node F are
+// copies[copy_ptr[F] .. copy_ptr[F + 1]), ascending: the order in which the fold adds the residual's source rows.
+struct OperatorFold {
+  int dim;
+  int64_t n_nodes_u, n_nodes_f;
+  const int32_t* node_map;
+  const int32_t* copy_ptr;
+  const int32_t* copies;
+};
+int operator_device(const mimi_hip_fold_s* h);
+OperatorFold operator_fold(const mimi_hip_fold_s* h);
 
 }  // namespace mimi_hip

@@ -18,6 +18,7 @@
 #include <memory>
 #include <vector>
 
+#include "apply_seam.hpp"
 #include "common.hpp"
 
 namespace mimi_hip {
@@ -217,6 +218,14 @@ struct mimi_hip_fold_s : StreamHandle {
   DeviceBuffer<unsigned char> serial;
   DeviceBuffer<double> stage_uf, stage_uu, stage_ru, stage_rf, stage_Au, stage_Ab, stage_Af;
 };
+
+// apply_seam.hpp: what the folded product of the Krylov solvers reads of the handle
+namespace mimi_hip {
+int operator_device(const mimi_hip_fold_s* h) { return h->device; }
+OperatorFold operator_fold(const mimi_hip_fold_s* h) {
+  return OperatorFold{h->dim, h->n_nodes_u, h->n_nodes_f, h->node_map.ptr, h->copy_ptr.ptr, h->copies.ptr};
+}
+}  // namespace mimi_hip
 
 extern "C" {
 

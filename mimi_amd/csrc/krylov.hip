@@ -10,7 +10,9 @@
 //       convergence on the preconditioned residual  |s_{i+1}| <= max(rel_tol * ||M r_0||, abs_tol).
 //   Beyond the reference: the matrix may be a domain handle's matrix-free tangent action (mimi_hip_linear_set_operator:
 //       A_values == NULL in a solve), eliminated like the matrix by two vector kernels around it; M may be the Kronecker (fast-diagonalisation) operator of kronecker.hpp instead of Jacobi
-//       (preconditioner id 2 of both solvers); ids 0 and 1 run the kernels and give the bits they always did.
+//       (preconditioner id 2 of both solvers); ids 0 and 1 run the kernels and give the bits they always did.  With a periodic
+//       fold beside the operator (mimi_hip_linear_set_operator_fold) the solver works in the folded numbering and the two
+//       vector kernels also expand the input and fold the output: y_f = mask(P^T A_u P (mask x_f)) + x_f[ess], no extra pass.
 //
 // Everything vector-sized stays in HBM; per Arnoldi step the host sees one Hessenberg column.  Reductions are
 // deterministic: a fixed grid writes per-block partial sums, every consumer adds them in the same order.
@@ -351,6 +353,45 @@ __global__ __launch_bounds__(KR_THREADS) void kr_operator_restore_kernel(int64_t
   }
 }
 
+// The same pair with a periodic fold (mimi_hip_linear_set_operator_fold): x, y and is_ess are in the folded numbering, the
+// actions run between the two kernels in the unwrapped one, y_f = mask(P^T A_u P (mask x_f)) + x_f[ess].
+// Before the actions, per unwrapped dof: xu = (mask x_f)[map], yu = 0 (the folded dof of node n, component c is
+// node_map[n] DIM + c) ...
+template<int DIM>
+__global__ __launch_bounds__(KR_THREADS) void kr_operator_mask_expand_kernel(int64_t n_u, const int32_t* __restrict__ node_map,
+                                                                             const unsigned char* __restrict__ is_ess,
+                                                                             const double* __restrict__ x, double* __restrict__ xu,
+                                                                             double* __restrict__ yu) {
+  for (int64_t i = (int64_t)blockIdx.x * KR_THREADS + threadIdx.x; i < n_u; i += (int64_t)gridDim.x * KR_THREADS) {
+    const int64_t node = i / DIM;
+    const int64_t j = (int64_t)node_map[node] * DIM + (i - node * DIM);
+    xu[i] = is_ess[j] ? 0.0 : x[j];
+    yu[i] = 0.0;
+  }
+}
+
+// ... behind them, per folded dof: the copies of its node added in ascending order from zero (the order and the start of
+// fold.hip's residual fold, so the sum has its bits), y[ess] = x[ess], and y = b - y with b.  One thread writes an entry.
+template<int DIM>
+__global__ __launch_bounds__(KR_THREADS) void kr_operator_fold_restore_kernel(int64_t n_f, const int32_t* __restrict__ copy_ptr,
+                                                                              const int32_t* __restrict__ copies,
+                                                                              const unsigned char* __restrict__ is_ess,
+                                                                              const double* __restrict__ x, const double* __restrict__ b,
+                                                                              const double* __restrict__ yu, double* __restrict__ y) {
+  for (int64_t i = (int64_t)blockIdx.x * KR_THREADS + threadIdx.x; i < n_f; i += (int64_t)gridDim.x * KR_THREADS) {
+    double t;
+    if (is_ess[i]) {
+      t = x[i];
+    } else {
+      const int64_t node = i / DIM;
+      const int c = (int)(i - node * DIM);
+      t = 0.0;
+      for (int k = copy_ptr[node]; k < copy_ptr[node + 1]; ++k) t += yu[(int64_t)copies[k] * DIM + c];
+    }
+    y[i] = b ? b[i] - t : t;
+  }
+}
+
 __global__ void kr_mark_kernel(int64_t n_ess, const int64_t* __restrict__ ess, unsigned char* __restrict__ is_ess) {
   const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k < n_ess) is_ess[ess[k]] = 1;
@@ -387,6 +428,16 @@ struct mimi_hip_linear_s : StreamHandle {
   static constexpr int kMaxBoundaryTerms = 8;
   BoundaryTerm op_terms[kMaxBoundaryTerms];
   int n_op_terms = 0;
+  // mimi_hip_linear_set_operator_fold: the operator handles live in the unwrapped numbering of this fold, the solver in the
+  // folded one; the expanded input and the unwrapped output of the actions
+  mimi_hip_fold_s* op_fold = nullptr;
+  DeviceBuffer<double> op_xu, op_yu;
+  // dofs an operator handle must have: the unwrapped size with a fold, the solver's own without
+  int64_t operator_n() const {
+    if (!op_fold) return n;
+    const OperatorFold f = operator_fold(op_fold);
+    return f.n_nodes_u * f.dim;
+  }
   DeviceBuffer<int> status;                      // one word: what the pattern checks of create found
   double* column_host[2] = {nullptr, nullptr};   // pinned: the Hessenberg column of the step before last and of the last one
   hipEvent_t column_ready[2] = {nullptr, nullptr};
@@ -431,17 +482,46 @@ void by_boundary_kind(const mimi_hip_linear_s::BoundaryTerm& t, F&& f) {
   else f(static_cast<mimi_hip_pressure_s*>(t.handle));
 }
 
+// the components per node of a fold (1 to 3: mimi_hip_fold_create), a compile-time divisor of its two kernels.  f(DIM)
+template<class F>
+void by_fold_dim(int dim, F&& f) {
+  using std::integral_constant;
+  if (dim == 3) f(integral_constant<int, 3>{});
+  else if (dim == 2) f(integral_constant<int, 2>{});
+  else f(integral_constant<int, 1>{});
+}
+
 dim3 wave_per_unit(int64_t units) { return dim3((unsigned)((units + 3) / 4)); }   // workgroups of 256: four waves
 
 // y = dinv o (A x), dinv o (b - A x) with b, plain without dinv.  val == nullptr: A is the handle's operator (no dinv then:
 // Jacobi needs the values), y = mask(A (mask x)) + x[ess]
 void spmv(mimi_hip_linear_s* h, const double* val, const double* x, const double* b, const double* dinv, double* y) {
   if (!val) {
-    launch(kr_operator_mask_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, (const unsigned char*)h->is_ess.ptr, x, h->op_x.ptr, y);
-    operator_add_action(h->op_domain, h->op_density, h->op_stiffness, h->op_viscosity, h->op_x.ptr, y, h->stream);
+    const unsigned char* is_ess = h->is_ess.ptr;
+    // the actions' vectors: the solver's own, or with a fold the unwrapped scratch between the fold's two kernels
+    const double* ax = h->op_fold ? h->op_xu.ptr : h->op_x.ptr;
+    double* ay = h->op_fold ? h->op_yu.ptr : y;
+    OperatorFold f{};
+    if (h->op_fold) {
+      f = operator_fold(h->op_fold);
+      by_fold_dim(f.dim, [&](auto D) {
+        launch(kr_operator_mask_expand_kernel<decltype(D)::value>, KR_GRID, KR_BLOCK, 0, h->stream, f.n_nodes_u * f.dim, f.node_map,
+               is_ess, x, h->op_xu.ptr, h->op_yu.ptr);
+      });
+    } else {
+      launch(kr_operator_mask_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, is_ess, x, h->op_x.ptr, y);
+    }
+    operator_add_action(h->op_domain, h->op_density, h->op_stiffness, h->op_viscosity, ax, ay, h->stream);
     for (int k = 0; k < h->n_op_terms; ++k)
-      by_boundary_kind(h->op_terms[k], [&](auto* face) { operator_add_action(face, h->op_terms[k].factor, h->op_x.ptr, y, h->stream); });
-    launch(kr_operator_restore_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, (const unsigned char*)h->is_ess.ptr, x, b, y);
+      by_boundary_kind(h->op_terms[k], [&](auto* face) { operator_add_action(face, h->op_terms[k].factor, ax, ay, h->stream); });
+    if (h->op_fold) {
+      by_fold_dim(f.dim, [&](auto D) {
+        launch(kr_operator_fold_restore_kernel<decltype(D)::value>, KR_GRID, KR_BLOCK, 0, h->stream, h->n, f.copy_ptr, f.copies, is_ess, x,
+               b, (const double*)h->op_yu.ptr, y);
+      });
+    } else {
+      launch(kr_operator_restore_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, is_ess, x, b, y);
+    }
     return;
   }
   by_product_form(h, [&](auto R, auto NC, int64_t n_units, const int32_t* col) {
@@ -518,7 +598,25 @@ Mirror<double> solve_matrix(mimi_hip_linear_s* h, const double* A_values, int pr
   if (A_values) return Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, h->stream);
   if (!h->op_domain) fail("null argument (no matrix values, and no operator is set: mimi_hip_linear_set_operator)");
   if (preconditioner == PRECOND_JACOBI) fail("the Jacobi preconditioner needs the matrix values");
-  h->op_x.resize((size_t)h->n);
+  if (h->op_fold) {
+    // (set_operator_fold and set_operator checked these against what was set then; either may have changed since)
+    const OperatorFold f = operator_fold(h->op_fold);
+    if (f.n_nodes_f * f.dim != h->n)
+      fail("operator fold: the fold has %lld folded dofs, the solver %lld", (long long)(f.n_nodes_f * f.dim), (long long)h->n);
+    h->op_xu.resize((size_t)(f.n_nodes_u * f.dim));
+    h->op_yu.resize((size_t)(f.n_nodes_u * f.dim));
+  } else {
+    h->op_x.resize((size_t)h->n);
+  }
+  if (operator_size(h->op_domain) != h->operator_n())
+    fail("operator: the domain handle has %lld dofs, the %s %lld", (long long)operator_size(h->op_domain),
+         h->op_fold ? "unwrapped side of the operator fold" : "solver", (long long)h->operator_n());
+  for (int k = 0; k < h->n_op_terms; ++k)
+    by_boundary_kind(h->op_terms[k], [&](auto* face) {
+      if (operator_size(face) != h->operator_n())
+        fail("boundary operator: the handle has %lld dofs, the %s %lld", (long long)operator_size(face),
+             h->op_fold ? "unwrapped side of the operator fold" : "solver", (long long)h->operator_n());
+    });
   operator_begin_solve(h->op_domain, h->op_density, h->op_stiffness, h->stream);
   for (int k = 0; k < h->n_op_terms; ++k)
     by_boundary_kind(h->op_terms[k], [&](auto* face) { operator_begin_solve(face, h->stream); });
@@ -859,8 +957,9 @@ int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, 
     if (domain) {
       if (operator_device(domain) != h->device)
         fail("operator: the domain handle is on device %d, the solver on device %d", operator_device(domain), h->device);
-      if (operator_size(domain) != h->n)
-        fail("operator: the domain handle has %lld dofs, the solver %lld", (long long)operator_size(domain), (long long)h->n);
+      if (operator_size(domain) != h->operator_n())
+        fail("operator: the domain handle has %lld dofs, the %s %lld", (long long)operator_size(domain),
+             h->op_fold ? "unwrapped side of the operator fold" : "solver", (long long)h->operator_n());
     }
     h->op_domain = domain;
     h->op_density = density;
@@ -881,10 +980,49 @@ int mimi_hip_linear_add_boundary_operator(mimi_hip_linear_t h, int kind, void* h
     by_boundary_kind(term, [&](auto* face) {
       if (operator_device(face) != h->device)
         fail("boundary operator: the handle is on device %d, the solver on device %d", operator_device(face), h->device);
-      if (operator_size(face) != h->n)
-        fail("boundary operator: the handle has %lld dofs, the solver %lld", (long long)operator_size(face), (long long)h->n);
+      if (operator_size(face) != h->operator_n())
+        fail("boundary operator: the handle has %lld dofs, the %s %lld", (long long)operator_size(face),
+             h->op_fold ? "unwrapped side of the operator fold" : "solver", (long long)h->operator_n());
     });
     h->op_terms[h->n_op_terms++] = term;
+  });
+}
+
+int mimi_hip_linear_set_operator_fold(mimi_hip_linear_t h, mimi_hip_fold_t fold) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    if (fold) {
+      if (operator_device(fold) != h->device)
+        fail("operator fold: the fold is on device %d, the solver on device %d", operator_device(fold), h->device);
+      const OperatorFold f = operator_fold(fold);
+      if (f.n_nodes_f * f.dim != h->n)
+        fail("operator fold: the fold has %lld folded dofs (%lld nodes x %d), the solver %lld", (long long)(f.n_nodes_f * f.dim),
+             (long long)f.n_nodes_f, f.dim, (long long)h->n);
+    }
+    h->op_fold = fold;   // (the operator and its boundary terms stay: a solve checks their size against the new setting)
+  });
+}
+
+int mimi_hip_linear_operator_mult(mimi_hip_linear_t h, const double* x, double* y) {
+  return guarded([&] {
+    if (!h || !x || !y) fail("null argument");
+    if (x == y) fail("operator product: x and y must be different vectors");
+    MH_HIP(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    solve_matrix(h, nullptr, PRECOND_NONE);
+    Mirror<double> mx = Mirror<double>::in(x, (size_t)h->n, h->stage_x, s);
+    Mirror<double> my;   // written whole: a host y has nothing to upload
+    my.count = (size_t)h->n;
+    if (is_device_pointer(y)) {
+      my.dev = y;
+    } else {
+      h->stage_b.resize((size_t)h->n);
+      my.dev = h->stage_b.ptr;
+      my.host = y;
+    }
+    spmv(h, nullptr, mx.dev, nullptr, nullptr, my.dev);
+    my.finish(s);
+    if (mx.host || my.host) MH_HIP(hipStreamSynchronize(s));
   });
 }
 

@@ -138,7 +138,8 @@ class ExplicitDynamics:
     commit.  x, v, a and the force vectors stay on the device; the host arrays of solution_view are refreshed when
     explicit_steps returns and where the save cadence asks for output.  With rc.set_int("explicit_consistent_mass", 1) beside the
     flag the division by the lumped mass becomes the reference's solve (rho M + dt/2 eta C) a = f - r - eta C v_{n+1/2}, by the
-    operator CG with the Kronecker preconditioner, still without a matrix; that route keeps no ledger."""
+    operator CG with the Kronecker preconditioner, still without a matrix; that route keeps no ledger.  It takes a periodic pair
+    under rc.set_int("periodic_iterative", 1): the CG then runs on the folded dofs, its product through the fold."""
 
     explicit_ = False
     explicit_consistent_ = False
@@ -164,7 +165,7 @@ class ExplicitDynamics:
             return False
         if not rc.get_int("explicit_dynamics", 0):
             raise RuntimeError("explicit_consistent_mass needs explicit_dynamics: it is an option of the explicit route")
-        if axes:
+        if axes and not rc.get_int("periodic_iterative", 0):
             raise RuntimeError("explicit_consistent_mass cannot be combined with a periodic boundary: the operator's action and "
                                "the Kronecker preconditioner run in the unwrapped numbering")
         return True
@@ -218,7 +219,7 @@ class ExplicitDynamics:
         if self.explicit_consistent_:
             # the mass solve's preconditioner, built here: the caller sets no solver flag on this route
             from .kronecker import KroneckerOperator
-            self.linear_.SetKronecker(KroneckerOperator(self.patch_, self.dirichlet_, self._dim))
+            self.linear_.SetKronecker(KroneckerOperator(self.patch_, self.dirichlet_, self._dim, periodic_axes=self.periodic_axes_))
             self.linear_.preconditioner = "kronecker"
             self.use_kronecker_, self._kronecker_pushed = True, None
             self.d_vbar_ = torch.from_numpy(vbar).to(self.d_x_.device)
@@ -347,7 +348,7 @@ class ExplicitDynamics:
                 x.add_(v, alpha=dt)
                 self._consistent_solve(0.5 * dt)
                 v.add_(self._cm_a, alpha=0.5 * dt)
-                self.domain_.DomainPostTimeAdvance(x)
+                self.domain_.DomainPostTimeAdvance(self._expand(x) if self.fold_ is not None else x)
                 self.current_time += dt
                 rc.next_time_step(dt)
                 self._explicit_save()

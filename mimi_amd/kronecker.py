@@ -9,7 +9,9 @@ with the 1-D mass and stiffness matrices M_d, K_d of the patch's own B-spline ba
 of length L_d, the mean length of the control polygons along axis d, and  e_cd = lambda + 2 mu  for d == c, mu otherwise
 (linear elasticity at F = I, the coupling between the components dropped).  What the device needs are the generalised
 eigenpairs  K_d U = M_d U diag(lam),  U^T M_d U = I  per (component, axis): a Dirichlet face removes the boundary function
-of its axis for the components it clamps, so the pairs differ between components.  Nothing here touches the device."""
+of its axis for the components it clamps, so the pairs differ between components.  On a periodic axis (periodic_axes) the
+first and last basis function are one function: the 1-D matrices are the folded P1^T M_d P1, P1^T K_d P1 on n_d - 1 functions,
+and the operator lives on the folded grid of integrators.periodic_node_map.  Nothing here touches the device."""
 import numpy as np
 import scipy.linalg
 
@@ -43,15 +45,40 @@ def axis_lengths(patch):
     return out
 
 
-def removed_functions(patch, essential_dofs, dim):
+def folded_matrices(M, K):
+    """P1^T M P1, P1^T K P1 of a periodic axis: the last basis function is the first one (P1 the n x (n - 1) 0/1 map with
+    P1[n - 1, 0] = 1), so its row and column are added to the first's -- with few spans their cross terms land on the
+    diagonal, which the two additions do by themselves"""
+    out = []
+    for A in (M, K):
+        A = np.array(A, dtype=np.float64)
+        A[0, :] += A[-1, :]
+        A[:, 0] += A[:, -1]
+        out.append(np.ascontiguousarray(A[:-1, :-1]))
+    return out
+
+
+def removed_functions(patch, essential_dofs, dim, periodic_axes=()):
     """kept[c][d]: bool[n_d], False for the boundary function of axis d that component c loses: the one of a face ALL of
-    whose dofs (node, c) are essential.  Essential dofs that do not fill a face remove nothing."""
-    ess = np.zeros(patch.n_nodes * dim, dtype=bool)
+    whose dofs (node, c) are essential.  Essential dofs that do not fill a face remove nothing.  With periodic axes the
+    essential dofs are in the folded numbering (integrators.periodic_node_map): a periodic axis has n_d - 1 functions and no
+    face, and the nodes of the other axes' faces are looked up through the node map."""
+    periodic_axes = sorted(set(int(a) for a in periodic_axes))
+    n_dir = [int(n) - (d in periodic_axes) for d, n in enumerate(patch.n_ctrl)]
+    node_map = None
+    if periodic_axes:
+        from .integrators import periodic_node_map
+        node_map = periodic_node_map(patch.n_ctrl, periodic_axes)
+    ess = np.zeros(int(np.prod(n_dir)) * dim, dtype=bool)
     ess[np.asarray(essential_dofs, dtype=np.int64)] = True
-    kept = [[np.ones(patch.n_ctrl[d], dtype=bool) for d in range(patch.dim)] for _ in range(dim)]
+    kept = [[np.ones(n_dir[d], dtype=bool) for d in range(patch.dim)] for _ in range(dim)]
     for d in range(patch.dim):
+        if d in periodic_axes:
+            continue
         for side in (0, 1):
             nodes = patch.boundary_nodes(d, side)
+            if node_map is not None:
+                nodes = np.unique(node_map[nodes])
             for c in range(dim):
                 if ess[nodes * dim + c].all():
                     kept[c][d][0 if side == 0 else -1] = False
@@ -68,28 +95,36 @@ def stiffness_coefficients(lame_lambda, lame_mu, fac0, fac1=0.0, viscosity=0.0, 
 class KroneckerOperator:
     """The eigen-decompositions of one patch and list of essential dofs (byVDIM numbering, dof = node * dim + c).
 
-    n_dir        nodes per axis
-    lengths      L_d
+    periodic_axes  the axes whose two end faces are joined (boundary_condition.initial.periodic): the first and last basis
+                 function of such an axis are one function, the essential dofs are in the folded numbering of
+                 integrators.periodic_node_map, and everything below lives on the reduced grid
+    n_dir        nodes per axis (n_d - 1 on a periodic axis)
+    lengths      L_d (on a periodic axis the whole unwrapped polygon: the period)
     M, K         the scaled 1-D matrices L_d M^_d and K^_d / L_d, per axis
     kept         kept[c][d], see removed_functions
     U_cd, lam_cd per [c][d]: U (n_d x n_d; zero rows and columns for removed functions) and lam (n_d; -1 marks a removed
                  function, which the device turns into a zero of the scaling)
     U, lam       the same, flattened and concatenated over [component][axis]: the arguments of LinearSolver.SetKronecker"""
 
-    def __init__(self, patch, essential_dofs, dim):
+    def __init__(self, patch, essential_dofs, dim, periodic_axes=()):
         if dim != patch.dim:
             raise RuntimeError(f"Kronecker preconditioner: {dim} components on a {patch.dim}-D patch")
         self.dim = dim
-        self.n_dir = [int(n) for n in patch.n_ctrl]
-        self.n = patch.n_nodes * dim
+        self.periodic_axes = sorted(set(int(a) for a in periodic_axes))
+        if any(a < 0 or a >= patch.dim for a in self.periodic_axes):
+            raise RuntimeError(f"Kronecker preconditioner: periodic axes {self.periodic_axes} on a {patch.dim}-D patch")
+        self.n_dir = [int(n) - (d in self.periodic_axes) for d, n in enumerate(patch.n_ctrl)]
+        self.n = int(np.prod(self.n_dir)) * dim
         self.lengths = axis_lengths(patch)
         self.M, self.K = [], []
         for d in range(patch.dim):
             M, K = matrices_1d(patch.knots[d], patch.degrees[d])
+            if d in self.periodic_axes:
+                M, K = folded_matrices(M, K)
             self.M.append(self.lengths[d] * M)
             self.K.append(K / self.lengths[d])
         self.essential_dofs = np.unique(np.asarray(essential_dofs if essential_dofs is not None else [], dtype=np.int64))
-        self.kept = removed_functions(patch, self.essential_dofs, dim)
+        self.kept = removed_functions(patch, self.essential_dofs, dim, self.periodic_axes)
         self.U_cd, self.lam_cd = [], []
         for c in range(dim):
             Us, lams = [], []

@@ -107,6 +107,19 @@ class LinearSolver(_capi.Handle):
         self._operator = None
         self._boundary_operators = []
 
+    def SetOperatorFold(self, fold):
+        """a mimi_amd.integrators.PeriodicFold between this solver (on the folded pattern) and the handles of SetOperator /
+        AddBoundaryOperator (on the unwrapped one): the product becomes mask(P^T A_u P (mask x)) + x[ess].  Set it before the
+        operator, whose size is checked against it; it survives SetOperator and ClearOperator; None clears it."""
+        check(_capi.lib().mimi_hip_linear_set_operator_fold(self._h, fold._handle() if fold is not None else None))
+        self._operator_fold = fold       # (the library reads its tables during every solve)
+
+    def OperatorMult(self, x, y):
+        """y = the eliminated product Mult(None, ...) / MultCG(None, ...) apply: mask(A (mask x)) + x[ess], folded or not"""
+        self._follow_torch(x, y)
+        check(_capi.lib().mimi_hip_linear_operator_mult(self._h, fptr(x), fptr(y)))
+        return y
+
     def Mult(self, A_values, b, x):
         """x = A^-1 b to the configured tolerances (x is overwritten: iterative_mode false); A_values None: the operator of
         SetOperator"""

@@ -355,7 +355,12 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         bc = self.boundary_condition or BoundaryConditions()
         axes = self._periodic_axes(bc)                               # refusals come before any device work
         rc = self.runtime_communication
-        if axes and rc is not None and rc.get_int("use_iterative_solver", 0) and rc.get_int("use_kronecker_preconditioner", 0):
+        # "periodic_iterative": a periodic pair on the Kronecker, matrix-free and consistent-mass routes -- the preconditioner
+        # from the folded 1-D matrices (KroneckerOperator(periodic_axes=...)), the solver's product through the fold
+        # (LinearSolver.SetOperatorFold).  Without the flag those routes refuse the pair as they always did.
+        periodic_iterative = bool(axes and rc is not None and rc.get_int("periodic_iterative", 0))
+        if (axes and not periodic_iterative and rc is not None and rc.get_int("use_iterative_solver", 0)
+                and rc.get_int("use_kronecker_preconditioner", 0)):
             raise RuntimeError("use_kronecker_preconditioner cannot be combined with a periodic boundary "
                                "(boundary_condition.initial.periodic): the folded numbering needs periodic 1-D matrices, "
                                "which the Kronecker preconditioner does not build -- unset one of the two")
@@ -379,8 +384,9 @@ class NonlinearSolid(Solid, ExplicitDynamics):
             if bc.initial.pressure_ and not boundary_actions:
                 raise RuntimeError("matrix_free cannot be combined with a follower pressure marker: the pressure tangent has no "
                                    "matrix-free action")
-            if axes:
+            if axes and not periodic_iterative:
                 raise RuntimeError("matrix_free cannot be combined with a periodic boundary: the action runs in the unwrapped numbering")
+        self.periodic_axes_ = axes
         self.patch_ = patch = self.patch()
         n = patch.n_vdofs
         # the integrators' pattern: the patch's unwrapped structured one (the tensor kernels' own) -- with periodic
@@ -613,9 +619,13 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         self.use_kronecker_ = self.use_iterative_solver_ and bool(rc.get_int("use_kronecker_preconditioner", 0))
         self._kronecker_pushed = None
         if self.use_kronecker_:
-            self.linear_.SetKronecker(KroneckerOperator(patch, self.dirichlet_, dim))
+            self.linear_.SetKronecker(KroneckerOperator(patch, self.dirichlet_, dim, periodic_axes=self.periodic_axes_))
             self.linear_.preconditioner = "kronecker"
         self.matrix_free_ = bool(rc.get_int("matrix_free", 0))       # (what it needs was checked at the top of setup)
+        if self.fold_ is not None and (self.matrix_free_ or self.explicit_consistent_):
+            # the operator handles stay in the unwrapped numbering: the solver's product expands and folds around them
+            # (set once: it survives every SetOperator)
+            self.linear_.SetOperatorFold(self.fold_)
         if self.explicit_:
             self._explicit_setup()
         elif not self.host_setup_:
@@ -679,7 +689,7 @@ class NonlinearSolid(Solid, ExplicitDynamics):
             # the integrators' side of the fold: expanded x, unwrapped residual and values
             self.d_xu_ = torch.zeros(self.fold_.n_u_, dtype=torch.float64, device=dev)
             self.d_ru_ = torch.zeros_like(self.d_xu_)
-            if not self.explicit_:
+            if not self.explicit_ and not self.matrix_free_:
                 self.d_Au_ = torch.zeros(self.fold_.nnz_u_, dtype=torch.float64, device=dev)
         if len(self.constant_velocity_dofs_):
             self.d_cv_dofs_ = torch.from_numpy(self.constant_velocity_dofs_).to(dev)
@@ -745,14 +755,22 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         self._push(self.domain_)
         if self.matrix_free_:
             # no Jacobian: the residual-only assembly, the snapshot of the tangent at x_t, and the solver's product becomes
-            # rho M + fac0 K(x_t) + fac1 eta C of the domain integrator (no periodic pair: setup); with "matrix_free_boundary"
-            # every contact and pressure integrator adds its residual, is linearised at x_t too and joins the product
-            self.domain_.AddDomainResidual(xt, y)
-            self.domain_.Linearize(xt)
+            # rho M + fac0 K(x_t) + fac1 eta C of the domain integrator; with "matrix_free_boundary"
+            # every contact and pressure integrator adds its residual, is linearised at x_t too and joins the product.
+            # With a periodic pair ("periodic_iterative") x_t is expanded once, every integrator works on the expanded vector
+            # and adds into the unwrapped residual, which is folded once; the product goes through the fold set in setup
+            xp, rp = xt, y
+            if self.fold_ is not None:
+                xp, rp = self._expand(xt), self.d_ru_
+                rp.zero_()
+            self.domain_.AddDomainResidual(xp, rp)
+            self.domain_.Linearize(xp)
             faces = self.contacts_ + self.pressures_
             for c in faces:
-                c.AddBoundaryResidual(xt, y)
-                c.Linearize(xt)
+                c.AddBoundaryResidual(xp, rp)
+                c.Linearize(xp)
+            if self.fold_ is not None:
+                self.fold_.Add(rp, y)
             eta = getattr(self.material, "viscosity", -1.0)
             self.linear_.SetOperator(self.domain_, self.material.density, self._fac0,
                                      self._fac1 * eta if self.d_visc_ is not None else 0.0)

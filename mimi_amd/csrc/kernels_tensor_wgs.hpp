@@ -35,6 +35,7 @@
 #include "materials_other.hpp"
 
 #include "kernels_tensor_2phase.hpp"
+#include "p2_tile_map.hpp"
 
 namespace mimi_hip {
 
@@ -693,6 +694,45 @@ MH_DEV WgsLane wgs_lane_constants(bool for_dump = false) {
   return c;
 }
 
+// Lane constants of the RIDER of a packed b1 (p2_tile_map.hpp): its results lie in accumulator registers 2 and 3 of tile 0
+//   register 2: grp 1, 2, 3 = pairs (0,0) (0,1) (0,2)  (grp 0 is row 8 of the host)      register 3: grp 0 = (1,0), grp 3 = (2,0)
+// and are stored from there (the lanes without an entry: zero constants, dump region); register 3 of grp 1, 2 = pairs (1,1), (1,2)
+// is carried; register 3 of tile 1, grp 0, 1 = pairs (2,1), (2,2) is carried into register 3 of tile 0.
+struct WgsPackLane {
+  bool ok2, ok3;
+  bool take2, wide2;              // the carried value belongs into register 2 (grp 1, 2); transposed rows of 81 (grp 1), not 27
+  int base2, baseT2;              // + a1 243 + b1 9 + j | + b1 (wide2 ? 243 : 81) + a1 9 + i
+  int base3, baseT3;              // + a1 81 + b1 9 + j  | + b1 243 + a1 9 + i
+};
+
+MH_DEV WgsPackLane wgs_pack_lane_constants(const WgsLane& lc) {
+  constexpr int ND = P2Shape::ND, NROW = P2Shape::NROW, NB = P2Shape::NB;
+  WgsPackLane c;
+  const int col = lc.lane & 15, grp = lc.grp;
+  const int a0 = lc.col_ok ? col / NB : 0, b0 = lc.col_ok ? col % NB : 0;
+  c.ok2 = lc.col_ok && grp >= 1;
+  c.ok3 = lc.col_ok && (grp == 0 || grp == 3);
+  c.take2 = grp == 1 || grp == 2;
+  c.wide2 = grp == 1;
+  // register 2: a2 = 0, b2 = grp - 1.  Transposed (a' = b): b2 = 0 -> a2' = 0; b2 >= 1 -> the rows of 27
+  c.base2 = c.ok2 ? a0 * NROW + (grp - 1) * ND + b0 * 3 : 0;
+  c.baseT2 = !c.ok2 ? 0 : grp == 1 ? b0 * NROW + a0 * 3 : 9 * NROW + (b0 + 9 * (grp - 2)) * ND + a0 * 3;
+  // register 3: a2 = 1 (grp 0) or 2 (grp 3), b2 = 0
+  c.base3 = c.ok3 ? 9 * NROW + (a0 + (grp == 3 ? 9 : 0)) * ND + b0 * 3 : 0;
+  c.baseT3 = c.ok3 ? b0 * NROW + (grp == 3 ? 2 : 1) * ND + a0 * 3 : 0;
+  return c;
+}
+
+// dst with its rows N..15 (of the lane quads in BANKS: bit q = rows 4 q .. 4 q + 3) replaced by rows 0..15 - N of src
+// (matrix operand layout: row = lane & 15, one DPP row; v_mov_b32 row_shr:N without bound_ctrl leaves the rows below N alone)
+template<int N, int BANKS>
+MH_DEV double wgs_rows_up(double dst, double src) {
+  const unsigned long long ud = __double_as_longlong(dst), us = __double_as_longlong(src);
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)ud, (int)(unsigned)us, 0x110 + N, 0xf, BANKS, false);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(ud >> 32), (int)(unsigned)(us >> 32), 0x110 + N, 0xf, BANKS, false);
+  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
+}
+
 // One (i, j) block of one element in a contraction wave: S1, then S2 / S3 pipelined over b1, the
 // carry in registers, finished entries into the store-transposition buffer(s).
 // st_n / jn: buffer of piece i and the column component j; st_t / jt: buffer of piece j and i.
@@ -704,11 +744,20 @@ MH_DEV WgsLane wgs_lane_constants(bool for_dump = false) {
 // entry (7 of every 16 columns; for the second register every lane group but 2) store to a 512-double dump region instead
 // (their lane constants are zero, wgs_lane_constants(true)).  Thirty mask regions per element and contraction wave
 // (s_and_saveexec / s_cbranch_execz / s_or: ~90 scalar instructions and as many scheduling boundaries) are gone.
-template<int MODE, bool DUMP = false>
+// PACK = packing level (symmetric-half kernel, with DUMP; p2_b1_packed): the three chains of a packed b1 (p2_tile_map.hpp) go through S3 in two tiles instead
+// of three.  S1 and S2 are untouched; the rider's S3 operand rows are moved into idle rows of the hosts' operands (sixteen
+// v_mov_b32 row_shr per b1 for four matrix instructions less), every result row is the same sum as in a tile of its own, and
+// the rider's results are stored and carried from where they lie (pl; its slot of C holds its pairs (1,1), (1,2); CP, an LDS
+// array [b1][64 lanes] of this wave alone, its pairs (2,1), (2,2): written once and read once per element by the same lane --
+// two LDS instructions instead of two registers of the 256) -- no permlane swap for the rider.
+template<int MODE, bool DUMP = false, int PACK = 0>
 MH_DEV void wgs_contract_block(const WgsLane& lc, const double (&ah)[9], const double (&aS0)[4], const double (&aS2)[4],
                                const double (&uB1)[3][4], const double (&uD1)[3][4], double (&C)[9],
-                               double* st_n, int jn, double* st_t, int jt, double* dump = nullptr) {
+                               double* st_n, int jn, double* st_t, int jt, double* dump = nullptr,
+                               const WgsPackLane* pl = nullptr, double* CP = nullptr) {
   constexpr int NB = P2Shape::NB, NQ = P2Shape::NQ, ND = P2Shape::ND, NROW = P2Shape::NROW;
+  static_assert(!PACK || (DUMP && MODE != 0), "packed tiles: symmetric-half kernel only");
+  static_assert(P2_RIDER == 1 && p2_tile_slot(0, 8).tile == 0 && p2_tile_slot(2, 8).tile == 1, "hosts a1 = 0, 2");
   const mh_d4 zero4 = {0.0, 0.0, 0.0, 0.0};
   const int grp = lc.grp;
   double* const dn0 = lc.col_ok ? st_n : dump;
@@ -726,9 +775,30 @@ MH_DEV void wgs_contract_block(const WgsLane& lc, const double (&ah)[9], const d
   }
   mh_d4 Kt[NB];
   auto carry_and_stage = [&](int b1) {
+    const bool packed = p2_b1_packed(MODE, b1, PACK);
+    if (packed) {
+      // the rider: registers 2, 3 of tile 0 (Kt[0]), register 3 of tile 1 (Kt[2])
+      constexpr int a1 = P2_RIDER;
+      double* const d2n = pl->ok2 ? st_n : dump;
+      double* const d3n = pl->ok3 ? st_n : dump;
+      double* const d2t = pl->ok2 ? st_t : dump;
+      double* const d3t = pl->ok3 ? st_t : dump;
+      // (register 3 takes the whole of CP: rows 14, 15 of tile 1 are sums of zero operand rows)
+      const double out3 = __builtin_fma(CP[b1 * 64 + lc.lane], 1.0, Kt[0][3]);
+      const double out2 = __builtin_fma(pl->take2 ? C[a1 * NB + b1] : 0.0, 1.0, Kt[0][2]);
+      d2n[pl->base2 + a1 * (3 * NROW) + b1 * 9 + jn] = out2;
+      d3n[pl->base3 + a1 * (3 * ND) + b1 * 9 + jn] = out3;
+      if (MODE == 1 || (MODE == 2 && a1 > b1)) {
+        d2t[pl->baseT2 + (pl->wide2 ? b1 * (3 * NROW) : b1 * (3 * ND)) + a1 * 9 + jt] = out2;
+        d3t[pl->baseT3 + b1 * (3 * NROW) + a1 * 9 + jt] = out3;
+      }
+      C[a1 * NB + b1] = out3;
+      CP[b1 * 64 + lc.lane] = Kt[2][3];
+    }
 #pragma unroll
     for (int a1 = 0; a1 < NB; ++a1) {
       if (MODE == 2 && a1 < b1) continue;
+      if (packed && a1 == P2_RIDER) continue;
       const int a1b1 = a1 * NB + b1;
       const double cin = C[a1b1];
       double c_rot, o2_rot;
@@ -792,26 +862,61 @@ MH_DEV void wgs_contract_block(const WgsLane& lc, const double (&ah)[9], const d
 #pragma unroll
       for (int a1 = 0; a1 < NB; ++a1)
         if (!(MODE == 2 && a1 < b1)) WGS_PIN(Ec[g][a1]);
+    const bool packed = p2_b1_packed(MODE, b1, PACK);
+    if (packed) {
+      static_assert(p2_tile_slot(P2_RIDER, 0).row == P2_RIDER_SHIFT_LOW && p2_tile_slot(P2_RIDER, 8).row == 8 + P2_RIDER_SHIFT_HIGH);
+      // rows 9..15 of host 0 <- the rider's pairs 0..6; rows 12..15 of host 2 <- the rider's pairs 7, 8 (and its rows 9, 10: zero)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        Ec[g][0] = wgs_rows_up<P2_RIDER_SHIFT_LOW, 0xf>(Ec[g][0], Ec[g][P2_RIDER]);
+        Ec[g][2] = wgs_rows_up<P2_RIDER_SHIFT_HIGH, 0x8>(Ec[g][2], Ec[g][P2_RIDER]);
+      }
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        WGS_PIN(Ec[g][0]);
+        WGS_PIN(Ec[g][2]);
+      }
+    }
 #pragma unroll
     for (int a1 = 0; a1 < NB; ++a1)
-      if (!(MODE == 2 && a1 < b1)) Kt[a1] = __builtin_amdgcn_mfma_f64_16x16x4f64(Ec[0][a1], aS0[0], zero4, 0, 0, 0);
+      if (!(MODE == 2 && a1 < b1) && !(packed && a1 == P2_RIDER)) Kt[a1] = __builtin_amdgcn_mfma_f64_16x16x4f64(Ec[0][a1], aS0[0], zero4, 0, 0, 0);
 #pragma unroll
     for (int g = 1; g < 4; ++g)
 #pragma unroll
       for (int a1 = 0; a1 < NB; ++a1)
-        if (!(MODE == 2 && a1 < b1)) Kt[a1] = __builtin_amdgcn_mfma_f64_16x16x4f64(Ec[g][a1], aS0[g], Kt[a1], 0, 0, 0);
+        if (!(MODE == 2 && a1 < b1) && !(packed && a1 == P2_RIDER)) Kt[a1] = __builtin_amdgcn_mfma_f64_16x16x4f64(Ec[g][a1], aS0[g], Kt[a1], 0, 0, 0);
   }
   carry_and_stage(NB - 1);
 }
 
 // carried rows of the last element of a column -> the third part of the element block (st_n / st_t: P2Block::carry_of(E, i))
-template<int MODE>
-MH_DEV void wgs_stage_carry(const WgsLane& lc, const double (&C)[9], double* st_n, int jn, double* st_t, int jt) {
-  constexpr int NB = P2Shape::NB;
+// PACK: the rider of a packed b1 holds its pairs (1,1), (1,2) in grp 1, 2 of its slot of C and its pairs (2,1), (2,2) in grp 0, 1
+// of CP[b1][lane] (LDS, wgs_contract_block)
+template<int MODE, int PACK = 0>
+MH_DEV void wgs_stage_carry(const WgsLane& lc, const double (&C)[9], double* st_n, int jn, double* st_t, int jt,
+                            const double* CP = nullptr) {
+  constexpr int NB = P2Shape::NB, ND = P2Shape::ND;
 #pragma unroll
   for (int a1b1 = 0; a1b1 < 9; ++a1b1) {
     const int a1 = a1b1 / NB, b1 = a1b1 % NB;
     if (MODE == 2 && a1 < b1) continue;
+    if (p2_b1_packed(MODE, b1, PACK) && a1 == P2_RIDER) {
+      // as basec / basecT of wgs_lane_constants: (a2 - 1) 9 x 162 + (b2 - 1) 27, transposed (b2 - 1) 9 x 162 + (a2 - 1) 27
+      const int col = lc.lane & 15, grp = lc.grp;
+      const int a0 = lc.col_ok ? col / NB : 0, b0 = lc.col_ok ? col % NB : 0;
+      const int n0 = a0 * 162 + b0 * 3 + a1 * 486 + b1 * 9 + jn, t0 = b0 * 162 + a0 * 3 + b1 * 486 + a1 * 9 + jt;
+      const bool tr = MODE == 1 || (MODE == 2 && a1 > b1);
+      if (lc.col_ok && (grp == 1 || grp == 2)) {          // (1,1), (1,2)
+        st_n[n0 + (grp == 2 ? ND : 0)] = C[a1b1];
+        if (tr) st_t[t0 + (grp == 2 ? 9 * 162 : 0)] = C[a1b1];
+      }
+      if (lc.col_ok && grp < 2) {                         // (2,1), (2,2)
+        const double cp = CP[b1 * 64 + lc.lane];
+        st_n[n0 + 9 * 162 + (grp == 1 ? ND : 0)] = cp;
+        if (tr) st_t[t0 + ND + (grp == 1 ? 9 * 162 : 0)] = cp;
+      }
+      continue;
+    }
     if (lc.col_ok) st_n[lc.basec + a1 * 486 + b1 * 9 + jn] = C[a1b1];
     if ((MODE == 1 || (MODE == 2 && a1 > b1)) && lc.col_ok) st_t[lc.basecT + b1 * 486 + a1 * 9 + jt] = C[a1b1];
   }

@@ -37,6 +37,10 @@ namespace mimi_hip {
 #define WGSYM_MIN_WGS 2048    // ... while at least this many workgroups remain (4 per resident slot)
 #endif
 
+#ifndef WGSYM_PACK
+#define WGSYM_PACK 1   // packing level of the S3 tiles (p2_tile_map.hpp p2_b1_packed): 0 a tile per chain, 1 shipped, 2 all
+#endif
+
 #ifndef WGSYM_DIAG_MODE
 #define WGSYM_DIAG_MODE 2   // 2: contract only the a1 >= b1 chains of a diagonal block; 0: all nine
 #endif
@@ -48,7 +52,9 @@ struct WgsymLds : P2Shape {
   static constexpr int off_ah = off_r + p2_stage_r_size(3);  // [6 blocks (i, j <= i)][9 (m,n)][64]  X -> Y
   static constexpr int off_st = off_ah + 6 * 9 * NQ3;       // [3 i][1216] store transposition      Y
   static constexpr int off_dump = off_st + 3 * WgsLds::st_size;   // where lanes without an entry store (wgs_contract_block)
-  static constexpr int total = off_dump + 512;
+  static constexpr int off_cp = off_dump + 512;   // [3 contraction waves][4][64]: the riders' second carry value (wgs_contract_block)
+  static constexpr int total = off_cp + 3 * 4 * 64;
+  static_assert(2 * total * sizeof(double) <= 160 * 1024, "two workgroups per CU");
   // first Ahat entry of block (i, j), j <= i
   MH_DEV static constexpr int ah_block(int i, int j) { return (i * (i + 1) / 2 + j) * 9; }
 };
@@ -214,6 +220,7 @@ MH_DEV void wgsym_y_loop(const TensorArgs& p, double* lds, int col0, int n_cols)
   // step O blocks: Y0 (1,0), Y1 (2,0), Y2 (2,1)
   constexpr int I1 = W == 0 ? 1 : 2, J1 = W == 2 ? 1 : 0;
   const WgsLane lc = wgs_lane_constants(true);
+  const WgsPackLane pl = wgs_pack_lane_constants(lc);
   const int lane = lc.lane;
   const int n_seq = n_cols * p.seg_len;
   const double* AH0 = lds + L::off_ah + L::ah_block(W, W) * NQ3;
@@ -226,6 +233,12 @@ MH_DEV void wgsym_y_loop(const TensorArgs& p, double* lds, int col0, int n_cols)
   double C0[NB2], C1[NB2];  // packed carries of the two blocks
 #pragma unroll
   for (int k = 0; k < NB2; ++k) C0[k] = C1[k] = 0.0;
+  // the riders' second carry value (packed tiles, p2_tile_map.hpp), one per packed b1, in this lane's own LDS slots: the
+  // diagonal block has one packed b1, the off-diagonal block three
+  double* const CP0 = lds + L::off_cp + W * 4 * 64;
+  double* const CP1 = CP0 + 64;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) CP0[k * 64 + lane] = 0.0;
   double aS0[4], aS2[4];
   double uB1[L::NB][L::NQ], uD1[L::NB][L::NQ];
 
@@ -242,7 +255,8 @@ MH_DEV void wgsym_y_loop(const TensorArgs& p, double* lds, int col0, int n_cols)
       // no barriers around the diagonal block: it reads operands nobody rewrites before O(it)'s first barrier and
       // writes only slots of this wave's own buffer that no other wave touches (the transposed entries other
       // waves add to it during O steps use the other two column components)
-      wgs_contract_block<WGSYM_DIAG_MODE, true>(lc, ah, aS0, aS2, uB1, uD1, C0, st_of(W), W, st_of(W), W, lds + L::off_dump);
+      wgs_contract_block<WGSYM_DIAG_MODE, true, WGSYM_PACK>(lc, ah, aS0, aS2, uB1, uD1, C0, st_of(W), W, st_of(W), W, lds + L::off_dump,
+                                                                   &pl, CP0);
     }
     // ---- O(it), lock step: off-diagonal block, stored as computed and transposed ------------------------------
     {
@@ -250,16 +264,18 @@ MH_DEV void wgsym_y_loop(const TensorArgs& p, double* lds, int col0, int n_cols)
 #pragma unroll
       for (int k = 0; k < 9; ++k) ah[k] = AH1[k * NQ3 + lane];
       wgs_barrier();
-      wgs_contract_block<1, true>(lc, ah, aS0, aS2, uB1, uD1, C1, st_of(I1), J1, st_of(J1), I1, lds + L::off_dump);
+      wgs_contract_block<1, true, WGSYM_PACK>(lc, ah, aS0, aS2, uB1, uD1, C1, st_of(I1), J1, st_of(J1), I1, lds + L::off_dump, &pl, CP1);
       wgs_barrier();
       if (c.pos == p.seg_len - 1) {
         // last element of a unit (column, or column segment): the carried rows have no successor -- straight from the registers into the third
         // part of the pieces (no LDS, no lock step) -- and the next column starts with an empty carry
         double* E = block_at(c.e);
-        wgs_stage_carry<WGSYM_DIAG_MODE>(lc, C0, P2Block::carry_of(E, W), W, P2Block::carry_of(E, W), W);
-        wgs_stage_carry<1>(lc, C1, P2Block::carry_of(E, I1), J1, P2Block::carry_of(E, J1), I1);
+        wgs_stage_carry<WGSYM_DIAG_MODE, WGSYM_PACK>(lc, C0, P2Block::carry_of(E, W), W, P2Block::carry_of(E, W), W, CP0);
+        wgs_stage_carry<1, WGSYM_PACK>(lc, C1, P2Block::carry_of(E, I1), J1, P2Block::carry_of(E, J1), I1, CP1);
 #pragma unroll
         for (int k = 0; k < NB2; ++k) C0[k] = C1[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) CP0[k * 64 + lane] = 0.0;
       }
     }
     e_prev = c.e;

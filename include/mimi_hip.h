@@ -270,7 +270,10 @@ int mimi_hip_domain_phase_ms_detail(mimi_hip_domain_t h, double* prepass_ms, dou
  * 1 two-phase tensor degree 2, 2 two-phase tensor degree 3, 3 small-element tensor, 4 general), 8 whether the handle
  * currently holds per-point gradient tables dN_dX (flat-table handles always; patch handles once a general kernel ran),
  * 9 kernel family of the last tangent action on the handle (the codes of 7), 10 bytes of linearisation record the handle
- * holds (0 before a linearize and on neo-Hookean handles) */
+ * holds (0 before a linearize and on neo-Hookean handles), 11 and 12 the launch geometry of the handle's last assembly on
+ * the symmetric-half degree-2 kernel (neo-Hookean tangent, family 1; 0 before any): 11 elements per unit -- the box's
+ * column length, or the segment length where the columns were cut -- 12 units a workgroup walks back to back (1..4).
+ * Tests assert them; an unknown code returns -1 */
 int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what);
 
 /* ---- structured sparsity: PrecomputedData::PrepareSparsity (precomputed.cpp:151-174) ----

@@ -84,6 +84,15 @@ inline bool env_general_no_mfma() { static const bool on = env_starts("MIMI_HIP_
 inline bool env_force_general() { return env_starts("MIMI_HIP_FORCE_GENERAL", '1'); }
 inline bool env_keep_general() { return env_starts("MIMI_HIP_KEEP_GENERAL", '1'); }
 inline bool env_no_structured() { return env_starts("MIMI_HIP_NO_STRUCTURED", '1'); }
+// a test seam: what stands in for WGSYM_MIN_WGS on the handle (wgsym_geometry.hpp); 0 when unset
+inline int env_wgsym_min_wgs() {
+  const char* v = env_text("MIMI_HIP_WGSYM_MIN_WGS");
+  if (!v) return 0;
+  char* end = nullptr;
+  const long n = strtol(v, &end, 10);
+  if (end == v || *end != '\0' || n < 1 || n > INT32_MAX) fail("MIMI_HIP_WGSYM_MIN_WGS must be a positive integer, got \"%s\"", v);
+  return (int)n;
+}
 // at every launch of the degree-3 contraction
 inline bool env_p3_contract_cxx() {
   const char* v = env_text("MIMI_HIP_P3_CONTRACT");

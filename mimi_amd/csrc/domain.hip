@@ -106,6 +106,7 @@ int mimi_hip_domain_create_bspline(const mimi_hip_bspline_patch* p, const mimi_h
     if (!p || !material || !out) fail("null argument");
     if (p->dim != 2 && p->dim != 3) fail("Unsupported Dim: %d", p->dim);
     auto h = std::make_unique<mimi_hip_domain_s>();
+    h->wgsym_min_wgs = env_wgsym_min_wgs();
     init_common(h.get(), device, material);
     h->dim = p->dim;
     Tables1D t1[3];
@@ -386,6 +387,8 @@ int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what) {
   case 8: return h->dN_dX.ptr ? 1 : 0;
   case 9: return h->apply_family;
   case 10: return (h->linearized && h->lin_rec.ptr) ? h->n_pts * (int64_t)(h->dim * h->dim * h->dim * h->dim) * (int64_t)sizeof(double) : 0;
+  case 11: return h->last_seg_len;
+  case 12: return h->last_cols_per_wg;
   default: return -1;
   }
 }

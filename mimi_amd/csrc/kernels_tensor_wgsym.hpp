@@ -26,16 +26,9 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels_tensor_wgs.hpp"
+#include "wgsym_geometry.hpp"
 
 namespace mimi_hip {
-
-#ifndef WGSYM_SPLIT_BELOW
-#define WGSYM_SPLIT_BELOW 512   // cut the columns into segments while the launch has at most this many workgroups
-#endif
-#ifndef WGSYM_MAX_COLS
-#define WGSYM_MAX_COLS 4      // element columns per workgroup at most
-#define WGSYM_MIN_WGS 2048    // ... while at least this many workgroups remain (4 per resident slot)
-#endif
 
 #ifndef WGSYM_PACK
 #define WGSYM_PACK 1   // packing level of the S3 tiles (p2_tile_map.hpp p2_b1_packed): 0 a tile per chain, 1 shipped, 2 all
@@ -306,21 +299,13 @@ inline void launch_tensor_wgsym(mimi_hip_domain_s* h, const DomainCall& c, Tenso
   a.n_units_u = a.box_n[0];
   a.n_units_v = a.box_n[1];
   const size_t lds = WgsymLds::total * sizeof(double);
-  // several columns per workgroup (the pipeline of the four waves then runs through the column boundaries: one
-  // prologue per workgroup instead of one per column) as long as the grid still fills the chip several times over
-  // few columns (the boundary layers of a multi-GPU slab): each column is cut into segments with their own workgroup, so
-  // that the launch still fills the chip; a segment end stores its carried rows like a column end (phase 2 knows)
-  int nseg = 1;
-  while (a.box_n[0] * a.box_n[1] * nseg * 2 <= WGSYM_SPLIT_BELOW && a.box_n[2] % (nseg * 2) == 0 && a.box_n[2] / (nseg * 2) >= 4) nseg *= 2;
-  a.seg_len = a.box_n[2] / nseg;
-  const int n_cols_all = a.box_n[0] * a.box_n[1] * nseg;
-  a.cols_per_wg = n_cols_all / WGSYM_MIN_WGS < 1 ? 1 : (n_cols_all / WGSYM_MIN_WGS > WGSYM_MAX_COLS ? WGSYM_MAX_COLS : n_cols_all / WGSYM_MIN_WGS);
+  // segments per column, units per workgroup, workgroups: wgsym_geometry.hpp
+  const WgsymGeometry g = wgsym_geometry(a.box_n, h->wgsym_min_wgs ? h->wgsym_min_wgs : WGSYM_MIN_WGS);
+  a.seg_len = h->last_seg_len = g.seg_len;
+  a.cols_per_wg = h->last_cols_per_wg = g.cols_per_wg;
   run_two_phase(
       h, c, false, [] {},
-      [&] {
-        launch(tensor_wgsym_kernel<MIMI_HIP_MAT_NEOHOOKEAN>, dim3((n_cols_all + a.cols_per_wg - 1) / a.cols_per_wg), dim3(256), lds,
-               h->stream, a);
-      },
+      [&] { launch(tensor_wgsym_kernel<MIMI_HIP_MAT_NEOHOOKEAN>, dim3(g.grid), dim3(256), lds, h->stream, a); },
       [&] { launch_tensor_p2(h, a); });
 }
 

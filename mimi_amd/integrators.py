@@ -215,6 +215,13 @@ class NonlinearSolid(NonlinearBase):
         """which kernel family the last assembly on this handle ran on (tests assert it; see mimi_hip_domain_info)"""
         return self.KERNEL_FAMILIES[int(_capi.lib().mimi_hip_domain_info(self._handle(), 7))]
 
+    def LastWalkGeometry(self):
+        """(seg_len, cols_per_wg) of the last launch of the symmetric-half degree-2 kernel on this handle: elements per unit
+        (column or column segment) and units a workgroup walks back to back; (0, 0) before any (mimi_hip_domain_info(h, 11)
+        and (h, 12); tests assert the walk they were written to reach)"""
+        L = _capi.lib()
+        return int(L.mimi_hip_domain_info(self._handle(), 11)), int(L.mimi_hip_domain_info(self._handle(), 12))
+
     def State(self, what):
         # "plastic_strain" = the material's first state matrix (J2 / J2Linear: plastic strain, J2Simo: be_old, J2Log:
         # Fp_inv); "state2" = its second one (J2Linear: beta, J2Simo: F_old)

@@ -17,6 +17,8 @@ above 3100 points); the family is asserted after every call:
   rational             tensor-product weights on a 3-D degree-2 patch (tensor route); weights that do not factorise through
                        flat tables (general route) -- the patches of test_domain_gpu.py::test_tensor_product_nurbs_weights
                        and ::test_rational_weights_general_path
+  walks                WALK_CASES, apart from the above and neo-Hookean only: the multi-unit walks of the symmetric-half degree-2
+                       kernel (tests/test_wgsym_walk_gpu.py), described where they are defined
 Flat tables (dofs, dN/dX, w det) are the reference's own, rounded to double; CSR patterns are the union of the element blocks
 found from the reference's values.
 
@@ -87,6 +89,36 @@ CASES = {
     "nurbs_tp_p2": _uniform_case((2, 2, 2), (4, 3, 3), "tensor_p2_two_phase", weights="tensor", jitter=0.05, seed=5),
     "nurbs_flat_p2": _uniform_case((2, 2, 2), (4, 3, 3), "general", weights="general", jitter=0.05, seed=21, flat=True),
 }
+# The walks of the symmetric-half degree-2 kernel (tests/test_wgsym_walk_gpu.py: a workgroup that walks several units back to
+# back, reached at these sizes through MIMI_HIP_WGSYM_MIN_WGS), neo-Hookean only and apart from CASES, so that the material
+# matrix above does not grow.  Jittered Greville control points as everywhere:
+#   walk335_p2   3 x 3 x 5, non-uniform inner knots on all three axes: nine columns with nine different pairs of x / y tables
+#                (a walk that kept the previous column's tables or spans is wrong in every column); columns of 5 carry the
+#                rider's second value over two steps
+#   walk761_p2   7 x 6 x 1: 42 units of one element, every step a unit end
+#   walk542_p2   5 x 4 x 2 with tensor-product weights (those of nurbs_tp_p2): units of two elements, the one-step carry only
+# and col8_p2 above (4 columns x 2 segments: a workgroup then walks segments of one column back to back).
+WALK_CASES = {
+    "walk335_p2": dict(degrees=(2, 2, 2), inner=([0.7, 1.9], [0.9, 2.6], [0.6, 1.5, 2.7, 3.4]), family="tensor_p2_two_phase",
+                       jitter=0.03, seed=3),
+    "walk761_p2": _uniform_case((2, 2, 2), (7, 6, 1), "tensor_p2_two_phase", seed=4),
+    "walk542_p2": _uniform_case((2, 2, 2), (5, 4, 2), "tensor_p2_two_phase", weights="tensor", jitter=0.05, seed=6),
+}
+WALK_MATERIAL = "neohook"
+WALK_PAIRS = [(c, WALK_MATERIAL) for c in WALK_CASES]
+# (case, element shape, seg_len, [(value of MIMI_HIP_WGSYM_MIN_WGS, cols_per_wg, units of the last workgroup)]); seg_len is the
+# column length except on col8_p2, whose columns of 8 the launcher cuts into two segments of 4
+WALKS = [
+    ("walk335_p2", (3, 3, 5), 5, [(4, 2, 1), (3, 3, 3), (2, 4, 1)]),
+    ("walk761_p2", (7, 6, 1), 1, [(21, 2, 2), (14, 3, 3), (10, 4, 2)]),
+    ("walk542_p2", (5, 4, 2), 2, [(5, 4, 4), (6, 3, 2)]),
+    ("col8_p2", (2, 2, 8), 4, [(2, 4, 4), (4, 2, 2)]),
+]
+# walk335_p2 through two complementary element boxes cut in x (the second one's box_begin[0] != 0 feeds the span arithmetic of
+# the walk) with MIMI_HIP_WGSYM_MIN_WGS = 1: (box, cols_per_wg): 3 units in one workgroup; 6 units, 4 and a tail of 2
+WALK_BOXES = [(([0, 0, 0], [1, 3, 5]), 3), (([1, 0, 0], [3, 3, 5]), 4)]
+WALK_BOX_CASE = "walk335_p2"
+
 # the element boxes of col8_p2: complementary, cutting every column
 BOXES = [([0, 0, 0], [2, 2, 3]), ([0, 0, 3], [2, 2, 8])]
 BOX_CASE = "col8_p2"
@@ -155,7 +187,7 @@ def product_material(matname):
 @functools.lru_cache(maxsize=None)
 def arrays(case):
     """the plain arrays of a case; shared, never modified"""
-    c = CASES[case]
+    c = CASES[case] if case in CASES else WALK_CASES[case]
     degrees = tuple(c["degrees"])
     knots = [_patches.open_knots(p, k) for p, k in zip(degrees, c["inner"])]
     ctrl = _jittered(degrees, knots, c.get("jitter", 0.04), c.get("seed", 1))

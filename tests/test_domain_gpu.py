@@ -332,6 +332,7 @@ def test_many_columns_per_workgroup():
     r_g, A_g = np.zeros(P.n_vdofs), np.zeros(D.nnz)
     D.add_domain_residual_and_grad(u, 1.0, r_o, A_o, rp.TANGENT_EXACT)
     G.AddDomainResidualAndGrad(u, 1.0, r_g, A_g)
+    assert G.LastWalkGeometry() == (2, 2)          # whole columns of 2, two per workgroup (tests/test_wgsym_walk_gpu.py: the other walks)
     assert relmax(r_g, r_o) < 1e-12
     assert relmax(A_g, A_o) < 1e-11
 

@@ -204,7 +204,7 @@ def test_j2linear_point_law(case):
 
 
 # ---- 3. the conditions on the inputs -----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case,matname", dc.PAIRS, ids=lambda v: v)
+@pytest.mark.parametrize("case,matname", dc.PAIRS + dc.WALK_PAIRS, ids=lambda v: v)
 def test_inputs_satisfy_the_conditions(case, matname):
     ref = dc.reference(case, matname)
     bad, fig = dc.conditions(ref)
@@ -254,7 +254,7 @@ def oracle_run(case, matname):
     return P, D, r0, r, [K @ v for v in ref.vectors]
 
 
-@pytest.mark.parametrize("case,matname", dc.PAIRS, ids=lambda v: v)
+@pytest.mark.parametrize("case,matname", dc.PAIRS + dc.WALK_PAIRS, ids=lambda v: v)
 def test_oracle_against_the_reference(case, matname):
     ref = dc.reference(case, matname)
     P, D, r0, r, Kv = oracle_run(case, matname)
@@ -315,6 +315,48 @@ def test_oracle_on_element_boxes():
             mask = dr.in_box(ref.geo.sp, begin, end)
             want = f64(dr.nodal(ref.geo, ref.asm.pt.P, mask))
             assert (np.abs(r - want) / dc.residual_bar(ref, mask)).max() <= MARGIN
+
+
+def test_oracle_on_the_walk_boxes():
+    """the boxes of tests/test_wgsym_walk_gpu.py, cut in x: they partition the points by parameter range, and the oracle on the
+    elements of each agrees with the reference restricted to it"""
+    from oracle import ref_path as rp
+    case, matname = dc.WALK_BOX_CASE, dc.WALK_MATERIAL
+    ref = dc.reference(case, matname)
+    P = dc.oracle_patch(case)
+    ex = P.element_multi_index()[0]
+    total = np.zeros(ref.geo.sp.n_points, dtype=int)
+    for (begin, end), _ in dc.WALK_BOXES:
+        own = np.nonzero((ex >= begin[0]) & (ex < end[0]))[0]
+        assert len(own) == int(np.prod(np.array(end) - np.array(begin)))
+        D = rp.DomainOracle(P, dc.oracle_material(matname), n_threads=2, elements=own)
+        D.set_dt(dc.DT)
+        r = np.zeros(P.n_vdofs)
+        D.add_domain_residual(ref.u, r)
+        mask = dr.in_box(ref.geo.sp, begin, end)
+        total += mask
+        want = f64(dr.nodal(ref.geo, ref.asm.pt.P, mask))
+        assert (np.abs(r - want) / dc.residual_bar(ref, mask)).max() <= MARGIN
+    assert np.all(total == 1)
+
+
+def test_the_walk_cases_are_what_the_walks_need():
+    """the shapes the walks of tests/test_wgsym_walk_gpu.py are written for: element counts, columns with tables of their own
+    on walk335_p2, rational weights on walk542_p2"""
+    for case, n_el, seg_len, walks in dc.WALKS:
+        a = dc.arrays(case)
+        assert tuple(n - 2 for n in a.n_ctrl) == n_el and a.degrees == (2, 2, 2) and a.family == "tensor_p2_two_phase"
+        assert n_el[2] % seg_len == 0
+        units = n_el[0] * n_el[1] * (n_el[2] // seg_len)
+        for value, cols, tail in walks:
+            assert cols == min(4, units // value) > 1
+            assert tail == units - (-(-units // cols) - 1) * cols
+    a = dc.arrays("walk335_p2")
+    for k in a.knots:
+        spans = np.diff(np.unique(k))
+        assert len(set(np.round(spans, 12))) == len(spans)          # no two spans of an axis alike
+    assert dc.arrays("walk542_p2").weights is not None and np.ptp(dc.arrays("walk542_p2").weights) > 0.1
+    assert dc.arrays("walk761_p2").weights is None
 
 
 @pytest.mark.parametrize("case", dc.FORMS_CASES)

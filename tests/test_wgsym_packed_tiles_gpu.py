@@ -3,9 +3,11 @@ rider's rows moved into idle operand rows, its results stored and carried from w
 of the degree-2 parity tests (test_domain_gpu.py: residual 1e-12, analytic tangent 1e-11, relative in the max-norm).
 
 Columns of 1 / 2 / 5 elements: no carry, the one-step carry only, the two-step carry (2,2) -> (1,1) -> (0,0) that the rider's
-pair 8 starts from the second tile.  5 x 4 x 9: columns longer than a segment and more than four columns per workgroup, so the walk
-crosses column boundaries with packed tiles live; cut into the boxes z < 8 and z >= 8 the first box is small enough for the
-segment path (two segments of four elements: a segment end stores the carried rows of hosts and riders)."""
+pair 8 starts from the second tile.  5 x 4 x 9: columns longer than a segment; cut into the boxes z < 8 and z >= 8 the first
+box is small enough for the segment path (two segments of four elements: a segment end stores the carried rows of hosts and
+riders).  Every launch here walks ONE unit per workgroup (20 columns are far below the 4096 at which a workgroup gets a second
+one: asserted through NonlinearSolid.LastWalkGeometry); the walk across unit boundaries with packed tiles live is
+tests/test_wgsym_walk_gpu.py."""
 import numpy as np
 import pytest
 
@@ -57,6 +59,7 @@ def test_parity_with_the_oracle(n_el):
     G = product(n_el, D, "neohook")
     r, A = np.zeros(P.n_vdofs), np.zeros(D.nnz)
     G.AddDomainResidualAndGrad(u, 1.0, r, A)
+    assert G.LastWalkGeometry() == (n_el[2], 1)              # whole columns, one per workgroup
     er, eA = relmax(r, r_o), relmax(A, A_o)
     print(f"{n_el}: residual {er:.2e} tangent {eA:.2e}")
     assert er < 1e-12
@@ -68,8 +71,10 @@ def test_segment_path_on_a_small_box():
     P, D, u, r_o, A_o = oracle(n_el, "neohook")
     r, A = np.zeros(P.n_vdofs), np.zeros(D.nnz)
     # 5 x 4 x 8: 20 columns, cut into two segments of four elements each (WGSYM_SPLIT_BELOW); then the last layer
-    for begin, end in (([0, 0, 0], [5, 4, 8]), ([0, 0, 8], [5, 4, 9])):
-        product(n_el, D, "neohook", element_box=(begin, end)).AddDomainResidualAndGrad(u, 1.0, r, A)
+    for begin, end, seg_len in (([0, 0, 0], [5, 4, 8], 4), ([0, 0, 8], [5, 4, 9], 1)):
+        G = product(n_el, D, "neohook", element_box=(begin, end))
+        G.AddDomainResidualAndGrad(u, 1.0, r, A)
+        assert G.LastWalkGeometry() == (seg_len, 1)
     er, eA = relmax(r, r_o), relmax(A, A_o)
     print(f"boxes of {n_el}: residual {er:.2e} tangent {eA:.2e}")
     assert er < 1e-12
@@ -87,7 +92,9 @@ def test_assembled_matrix_is_symmetric_to_the_bit():
     n_el = (3, 3, 5)
     P, D, u, _, _ = oracle(n_el, "neohook")
     A = np.zeros(D.nnz)
-    product(n_el, D, "neohook").AddDomainResidualAndGrad(u, 1.0, np.zeros(P.n_vdofs), A)
+    G = product(n_el, D, "neohook")
+    G.AddDomainResidualAndGrad(u, 1.0, np.zeros(P.n_vdofs), A)
+    assert G.LastWalkGeometry() == (5, 1)
     n = len(D.rowptr) - 1
     rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(D.rowptr))
     cols = D.col.astype(np.int64)
@@ -113,6 +120,7 @@ def test_nine_block_kernel_j2():
     G = product(n_el, D, "j2")
     r, A = np.zeros(P.n_vdofs), np.zeros(D.nnz)
     G.AddDomainResidualAndGrad(u, 1.0, r, A)
+    assert G.LastKernelFamily() == "tensor_p2_two_phase" and G.LastWalkGeometry() == (0, 0)     # not the symmetric-half kernel
     er, eA = relmax(r, r_o), relmax(A, A_o)
     print(f"j2 {n_el}: residual {er:.2e} tangent {eA:.2e}")
     assert er < 1e-12

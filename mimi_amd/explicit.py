@@ -144,32 +144,6 @@ class ExplicitDynamics:
     explicit_ = False
     explicit_consistent_ = False
 
-    @staticmethod
-    def _explicit_flags(rc):
-        """the flag, with its refusals (before any device work)"""
-        if rc is None or not rc.get_int("explicit_dynamics", 0):
-            return False
-        for other in ("matrix_free", "use_iterative_solver"):
-            if rc.get_int(other, 0):
-                raise RuntimeError(f"explicit_dynamics cannot be combined with {other}: an explicit step has no linear solve "
-                                   "for it to act on -- unset one of the two")
-        if rc.get_int("host_setup", 0):
-            raise RuntimeError("explicit_dynamics cannot be combined with host_setup: the lumped mass is assembled on the device")
-        return True
-
-    @staticmethod
-    def _explicit_consistent_flag(rc, axes):
-        """"explicit_consistent_mass" (beside explicit_dynamics): the reference's CentralDifference step exactly (ode.cpp:229-250),
-        (rho M + dt/2 eta C) a = f - r - eta C v_{n+1/2} by the operator CG with the Kronecker preconditioner"""
-        if rc is None or not rc.get_int("explicit_consistent_mass", 0):
-            return False
-        if not rc.get_int("explicit_dynamics", 0):
-            raise RuntimeError("explicit_consistent_mass needs explicit_dynamics: it is an option of the explicit route")
-        if axes and not rc.get_int("periodic_iterative", 0):
-            raise RuntimeError("explicit_consistent_mass cannot be combined with a periodic boundary: the operator's action and "
-                               "the Kronecker preconditioner run in the unwrapped numbering")
-        return True
-
     def _explicit_require(self):
         if not self.explicit_:
             raise RuntimeError('explicit dynamics is off: call runtime_communication.set_int("explicit_dynamics", 1) before setup()')
@@ -184,19 +158,16 @@ class ExplicitDynamics:
         import torch
         dev = torch.device("cuda", self.device)
         dim = self._dim
-        forms, temporary = self._forms_domain()
-        m_u = torch.zeros(self.patch_.n_vdofs, dtype=torch.float64, device=dev)
-        forms.AddBodyForce(self.material.density * np.ones(dim), m_u)
-        if self.fold_ is not None:
-            m = torch.zeros(self.fold_.n_f_, dtype=torch.float64, device=dev)
-            self.fold_.Add(m_u, m)
-        else:
-            m = m_u
-        self.d_lumped_mass_ = m
-        self.rhs_ = self._load_vector_folded(self._body_force_vector(forms))
-        if temporary:
-            forms.Synchronize()
-            del forms
+        with self._forms_domain() as forms:
+            m_u = torch.zeros(self.patch_.n_vdofs, dtype=torch.float64, device=dev)
+            forms.AddBodyForce(self.material.density * np.ones(dim), m_u)
+            if self.fold_ is not None:
+                m = torch.zeros(self.fold_.n_f_, dtype=torch.float64, device=dev)
+                self.fold_.Add(m_u, m)
+            else:
+                m = m_u
+            self.d_lumped_mass_ = m
+            self.rhs_ = self._load_vector_folded(self._body_force_vector(forms))
 
     def _explicit_make_stepper(self):
         import torch
@@ -218,10 +189,7 @@ class ExplicitDynamics:
         self.explicit_d2h_copies_ = 0                # solution-sized device-to-host copies since setup
         if self.explicit_consistent_:
             # the mass solve's preconditioner, built here: the caller sets no solver flag on this route
-            from .kronecker import KroneckerOperator
-            self.linear_.SetKronecker(KroneckerOperator(self.patch_, self.dirichlet_, self._dim, periodic_axes=self.periodic_axes_))
-            self.linear_.preconditioner = "kronecker"
-            self.use_kronecker_, self._kronecker_pushed = True, None
+            self._set_kronecker()
             self.d_vbar_ = torch.from_numpy(vbar).to(self.d_x_.device)
             self._cm_a, self._cm_rhs = torch.zeros_like(self.d_x_), torch.zeros_like(self.d_x_)
             self.explicit_cg_iterations_ = []        # of every mass solve since setup
@@ -231,30 +199,14 @@ class ExplicitDynamics:
         needs the reactions"""
         out.zero_()
         self._push(self.domain_)
-        if self.fold_ is not None:
-            xu, target = self._expand(x), self.d_ru_
-            target.zero_()
-        else:
-            xu, target = x, out
-        self.domain_.AddDomainResidual(xu, target)
-        for c in self.contacts_:
-            c.AddBoundaryResidual(xu, target)
-        for c in self.pressures_:
-            c.AddBoundaryResidual(xu, target)
-        if self.fold_ is not None:
-            self.fold_.Add(target, out)
+        self._add_residual(x, out)
 
     def _explicit_action(self, z, out, stiffness, viscosity):
         """out = (stiffness K(linearised u) + viscosity C) z of the domain integrator, through the fold when there is one"""
         out.zero_()
-        if self.fold_ is not None:
-            zu, target = self._expand(z), self.d_ru_
-            target.zero_()
-        else:
-            zu, target = z, out
+        zu, target = self._open(z, out)
         self.domain_.ApplyTangent(zu, target, stiffness=stiffness, density=0.0, viscosity=viscosity)
-        if self.fold_ is not None:
-            self.fold_.Add(target, out)
+        self._close(target, out)
         return out
 
     def _consistent_solve(self, fac1):
@@ -295,43 +247,38 @@ class ExplicitDynamics:
         self._ex_started = True
 
     def _explicit_download(self):
+        """x and x_dot into the host arrays, and the boundary integrators' post-advance, which reads the scalars of the latest
+        residual evaluation back: only where the host looks"""
         self.x[:] = self.d_x_.cpu().numpy()
         self.x_dot[:] = self.d_v_.cpu().numpy()
         self.explicit_d2h_copies_ += 2
+        self._post_time_advance(self.d_x_, domain=False)
 
-    def _explicit_boundary_post_advance(self):
-        # (these read the scalars of the latest residual evaluation back: only where the host looks)
-        xp = self._expand(self.d_x_) if self.fold_ is not None else self.d_x_
-        for c in self.contacts_:
-            c.BoundaryPostTimeAdvance(xp)
-        for c in self.pressures_:
-            c.BoundaryPostTimeAdvance(xp)
+    def _lumped_step(self, dt):
+        st, x, v = self.explicit_stepper_, self.d_x_, self.d_v_
+        st.Predict(dt, x, v)
+        k = 1 - self._ex_i
+        r, d = self._ex_r[k], None
+        self._explicit_forces(x, r)
+        if self._ex_d is not None:
+            d = self._explicit_action(v, self._ex_d[k], 0.0, self._ex_eta)
+        st.Correct(dt, self._rhs, r, d, v)
+        self._ex_i = k
 
-    def _explicit_save(self):
-        """the save cadence of RuntimeCommunication after a step: <name>_<steps done>, as step_time2 writes them"""
-        rc = self.runtime_communication
-        from .integrators import NonlinearSolid as Integrator
-        names = [k for k in ("x", "v") + tuple(Integrator.FIELDS) if rc.should_save(k)]
-        if not names:
-            return
-        self._explicit_download()
-        self._explicit_boundary_post_advance()
-        for k in names:
-            if k == "x":
-                rc.save_dynamic_vector("x_", self.in_reference_numbering(self.x))
-            elif k == "v":
-                rc.save_dynamic_vector("v_", self.in_reference_numbering(self.x_dot))
-            else:
-                f = self.field(k)
-                self.explicit_d2h_copies_ += 1
-                rc.save_dynamic_vector(k + "_", self.in_reference_numbering(f, ncomp=f.shape[1]))
+    def _consistent_step(self, dt):
+        # the essential dofs have a = 0 and keep their v, so the masks hold without a kernel of their own
+        x, v = self.d_x_, self.d_v_
+        v.add_(self._cm_a, alpha=0.5 * dt)
+        x.add_(v, alpha=dt)
+        self._consistent_solve(0.5 * dt)
+        v.add_(self._cm_a, alpha=0.5 * dt)
 
     def explicit_steps(self, n):
         """n central-difference steps of time_step_size.  Inside the loop nothing is copied to the host and nothing waits
         for the device, except at the steps where runtime_communication.should_save asks for output (after step k the
-        counter is k: append_should_save("x", 2) writes x_2, x_4, ...).  Afterwards x and x_dot are downloaded once and
-        the status words of the handles are read once: a failed return map raises here.  The state continues on the
-        device, so n steps and n more give the bytes of 2 n steps; explicit_restart() takes up host edits."""
+        counter is k: append_should_save("x", 2) writes x_2, x_4, ..., as step_time2 writes them).  Afterwards x and x_dot are
+        downloaded once and the status words of the handles are read once: a failed return map raises here.  The state
+        continues on the device, so n steps and n more give the bytes of 2 n steps; explicit_restart() takes up host edits."""
         self._explicit_require()
         if not self.time_step_size > 0.0:
             raise RuntimeError(f"explicit_steps needs a positive time_step_size, got {self.time_step_size}")
@@ -339,35 +286,17 @@ class ExplicitDynamics:
             self.explicit_restart()
         else:
             self._update_rhs()
-        st, x, v, rc = self.explicit_stepper_, self.d_x_, self.d_v_, self.runtime_communication
+        step = self._consistent_step if self.explicit_consistent_ else self._lumped_step
         for _ in range(int(n)):
             dt = self.time_step_size
-            if self.explicit_consistent_:
-                # the essential dofs have a = 0 and keep their v, so the masks hold without a kernel of their own
-                v.add_(self._cm_a, alpha=0.5 * dt)
-                x.add_(v, alpha=dt)
-                self._consistent_solve(0.5 * dt)
-                v.add_(self._cm_a, alpha=0.5 * dt)
-                self.domain_.DomainPostTimeAdvance(self._expand(x) if self.fold_ is not None else x)
-                self.current_time += dt
-                rc.next_time_step(dt)
-                self._explicit_save()
-                continue
-            st.Predict(dt, x, v)
-            k = 1 - self._ex_i
-            r, d = self._ex_r[k], None
-            self._explicit_forces(x, r)
-            if self._ex_d is not None:
-                d = self._explicit_action(v, self._ex_d[k], 0.0, self._ex_eta)
-            st.Correct(dt, self._rhs, r, d, v)
-            self._ex_i = k
-            self.domain_.DomainPostTimeAdvance(self._expand(x) if self.fold_ is not None else x)
+            step(dt)
+            self._post_time_advance(self.d_x_, boundaries=False)
             self.current_time += dt
-            rc.next_time_step(dt)
-            self._explicit_save()
+            self.runtime_communication.next_time_step(dt)
+            fields = self._save_cadence(before=self._explicit_download)      # (the download counts its own two copies)
+            self.explicit_d2h_copies_ += fields
         self._explicit_download()
-        self._explicit_boundary_post_advance()
-        for handle in [self.domain_] + self.contacts_ + self.pressures_ + [st]:
+        for handle in self.integrators_ + [self.explicit_stepper_]:
             handle.Synchronize()
 
     def explicit_energies(self):
@@ -399,11 +328,9 @@ class ExplicitDynamics:
         contact lowers the limit further; watch E_star of explicit_energies(), which drifts as soon as a step is too long."""
         self._explicit_require()
         torch = self._torch
-        x = self.d_x_ if u is None else torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64).reshape(-1)).to(self.d_x_.device)
-        if x.numel() != self.d_x_.numel():
-            raise ValueError(f"u has {x.numel()} entries, the displacement has {self.d_x_.numel()}")
+        x = self._displacement(u)
         self._push(self.domain_)
-        self.domain_.Linearize(self._expand(x) if self.fold_ is not None else x)
+        self.domain_.Linearize(self._expand(x))
         z0 = torch.from_numpy(power_start(x.numel())).to(x.device)
         m, free = self.d_lumped_mass_, self.d_free_
         out = torch.empty_like(x)

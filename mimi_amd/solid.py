@@ -21,8 +21,10 @@ NURBS numbering); meshes must be single-cell degree-1 descriptions with unit wei
 the refined control net is the cell's multilinear map at the Greville abscissae), which
 covers every mesh the reference's solver tests use.
 """
+import contextlib
 import os
 import re
+import typing
 
 import numpy as np
 import scipy.sparse as sp
@@ -334,6 +336,68 @@ def _element_tables(patch, quadrature_order=-1, with_gradients=False, elements=N
     return N, w[None, :] * det, conn
 
 
+class Route(typing.NamedTuple):
+    """what setup() builds and the steps run, resolved once from the runtime flags (resolve_route)"""
+    explicit: bool = False              # explicit_steps in place of step_time2, no matrix of any kind (mimi_amd/explicit.py)
+    explicit_consistent: bool = False   # ... with the reference's consistent-mass solve in place of the lumped division
+    iterative: bool = False             # GMRES / CG on the device in place of the host's sparse direct solve
+    kronecker: bool = False             # ... with the fast-diagonalisation preconditioner in place of Jacobi
+    matrix_free: bool = False           # the domain integrator's tangent action in place of the assembled Jacobian
+    boundary_actions: bool = False      # ... with the contact and pressure tangents as actions beside it
+    periodic_iterative: bool = False    # a periodic pair on the Kronecker, matrix-free and consistent-mass routes
+    host_setup: bool = False            # mass, damping and right-hand side in numpy on the host
+
+
+def resolve_route(rc, bc, axes):
+    """The Route of the flags of `rc` (a RuntimeCommunication or None), the markers of `bc` and the periodic `axes`, or the
+    RuntimeError of the first rule the combination breaks.  No device work; the only place that reads these flags."""
+    flag = lambda key: bool(rc is not None and rc.get_int(key, 0))
+    # "periodic_iterative": the preconditioner from the folded 1-D matrices (KroneckerOperator(periodic_axes=...)), the solver's
+    # product through the fold (LinearSolver.SetOperatorFold).  Without the flag those routes refuse the pair as they always did.
+    periodic_iterative = bool(axes) and flag("periodic_iterative")
+    # (the first rule asks for its flags itself, ahead of the others: tests/test_periodic_kronecker_cpu.py steps past it by
+    # answering that question alone)
+    if axes and not periodic_iterative and flag("use_iterative_solver") and flag("use_kronecker_preconditioner"):
+        raise RuntimeError("use_kronecker_preconditioner cannot be combined with a periodic boundary "
+                           "(boundary_condition.initial.periodic): the folded numbering needs periodic 1-D matrices, "
+                           "which the Kronecker preconditioner does not build -- unset one of the two")
+    explicit, consistent = flag("explicit_dynamics"), flag("explicit_consistent_mass")
+    iterative, kronecker = flag("use_iterative_solver"), flag("use_kronecker_preconditioner")
+    matrix_free, boundary_actions = flag("matrix_free"), flag("matrix_free_boundary")
+    host_setup = flag("host_setup")
+    if explicit:
+        for other, on in (("matrix_free", matrix_free), ("use_iterative_solver", iterative)):
+            if on:
+                raise RuntimeError(f"explicit_dynamics cannot be combined with {other}: an explicit step has no linear solve "
+                                   "for it to act on -- unset one of the two")
+        if host_setup:
+            raise RuntimeError("explicit_dynamics cannot be combined with host_setup: the lumped mass is assembled on the device")
+    if consistent:
+        if not explicit:
+            raise RuntimeError("explicit_consistent_mass needs explicit_dynamics: it is an option of the explicit route")
+        if axes and not periodic_iterative:
+            raise RuntimeError("explicit_consistent_mass cannot be combined with a periodic boundary: the operator's action and "
+                               "the Kronecker preconditioner run in the unwrapped numbering")
+    if boundary_actions and not matrix_free:
+        raise RuntimeError("matrix_free_boundary needs matrix_free: it adds the contact and pressure tangents to the "
+                           "matrix-free product")
+    if matrix_free:                                                  # only what the action covers
+        if not (iterative and kronecker):
+            raise RuntimeError("matrix_free needs use_iterative_solver and use_kronecker_preconditioner: without matrix values "
+                               "there is neither a direct solve nor a Jacobi preconditioner")
+        if (bc.initial.contact_ or bc.current.contact_) and not boundary_actions:
+            raise RuntimeError("matrix_free cannot be combined with a contact marker: the contact tangent has no matrix-free action")
+        if bc.initial.pressure_ and not boundary_actions:
+            raise RuntimeError("matrix_free cannot be combined with a follower pressure marker: the pressure tangent has no "
+                               "matrix-free action")
+        if axes and not periodic_iterative:
+            raise RuntimeError("matrix_free cannot be combined with a periodic boundary: the action runs in the unwrapped numbering")
+    host_setup = host_setup or os.environ.get("MIMI_HIP_HOST_SETUP", "") == "1"
+    if explicit and host_setup:
+        raise RuntimeError("explicit_dynamics cannot be combined with the host set-up: the lumped mass is assembled on the device")
+    return Route(explicit, consistent, iterative, iterative and kronecker, matrix_free, boundary_actions, periodic_iterative, host_setup)
+
+
 class NonlinearSolid(Solid, ExplicitDynamics):
     """PyNonlinearSolid (src/mimi/py/py_nonlinear_solid.cpp:15-387) on top of the HIP integrators; with
     rc.set_int("explicit_dynamics", 1) the explicit central-difference route of mimi_amd/explicit.py."""
@@ -354,38 +418,9 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         dim = self._dim
         bc = self.boundary_condition or BoundaryConditions()
         axes = self._periodic_axes(bc)                               # refusals come before any device work
-        rc = self.runtime_communication
-        # "periodic_iterative": a periodic pair on the Kronecker, matrix-free and consistent-mass routes -- the preconditioner
-        # from the folded 1-D matrices (KroneckerOperator(periodic_axes=...)), the solver's product through the fold
-        # (LinearSolver.SetOperatorFold).  Without the flag those routes refuse the pair as they always did.
-        periodic_iterative = bool(axes and rc is not None and rc.get_int("periodic_iterative", 0))
-        if (axes and not periodic_iterative and rc is not None and rc.get_int("use_iterative_solver", 0)
-                and rc.get_int("use_kronecker_preconditioner", 0)):
-            raise RuntimeError("use_kronecker_preconditioner cannot be combined with a periodic boundary "
-                               "(boundary_condition.initial.periodic): the folded numbering needs periodic 1-D matrices, "
-                               "which the Kronecker preconditioner does not build -- unset one of the two")
-        # "explicit_dynamics": explicit_steps in place of step_time2, no matrix of any kind (mimi_amd/explicit.py)
-        self.explicit_ = self._explicit_flags(rc)
-        self.explicit_consistent_ = self._explicit_consistent_flag(rc, axes)
-        # "matrix_free": the Newton solves take the domain integrator's tangent action in place of the assembled Jacobian
-        # (LinearSolver.SetOperator); only what the action covers
-        # "matrix_free_boundary" beside it: contact and follower-pressure markers are accepted, their face tangents join the
-        # product as actions (LinearSolver.AddBoundaryOperator)
-        boundary_actions = bool(rc is not None and rc.get_int("matrix_free_boundary", 0))
-        if boundary_actions and not rc.get_int("matrix_free", 0):
-            raise RuntimeError("matrix_free_boundary needs matrix_free: it adds the contact and pressure tangents to the "
-                               "matrix-free product")
-        if rc is not None and rc.get_int("matrix_free", 0):
-            if not (rc.get_int("use_iterative_solver", 0) and rc.get_int("use_kronecker_preconditioner", 0)):
-                raise RuntimeError("matrix_free needs use_iterative_solver and use_kronecker_preconditioner: without matrix values "
-                                   "there is neither a direct solve nor a Jacobi preconditioner")
-            if (bc.initial.contact_ or bc.current.contact_) and not boundary_actions:
-                raise RuntimeError("matrix_free cannot be combined with a contact marker: the contact tangent has no matrix-free action")
-            if bc.initial.pressure_ and not boundary_actions:
-                raise RuntimeError("matrix_free cannot be combined with a follower pressure marker: the pressure tangent has no "
-                                   "matrix-free action")
-            if axes and not periodic_iterative:
-                raise RuntimeError("matrix_free cannot be combined with a periodic boundary: the action runs in the unwrapped numbering")
+        # the route and its refusals (resolve_route) come before any device work too
+        self.route_ = route = resolve_route(self.runtime_communication, bc, axes)
+        self.explicit_, self.explicit_consistent_ = route.explicit, route.explicit_consistent
         self.periodic_axes_ = axes
         self.patch_ = patch = self.patch()
         n = patch.n_vdofs
@@ -437,31 +472,26 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         # here and no reference fixture sets a viscosity: parity unpinned) and rhs (:221-283): on the device
         # (_device_setup, once the integrator and the eliminations exist) unless the host pass is asked for with
         # MIMI_HIP_HOST_SETUP=1 or rc.set_int("host_setup", 1)
-        self.host_setup_ = bool(rc.get_int("host_setup", 0)) or os.environ.get("MIMI_HIP_HOST_SETUP", "") == "1"
-        if self.explicit_ and self.host_setup_:
-            raise RuntimeError("explicit_dynamics cannot be combined with the host set-up: the lumped mass is assembled on the device")
+        self.host_setup_ = route.host_setup
         self._mass_host, self._visc_host = None, None
         self.d_mass_, self.d_visc_ = None, None
         self.host_nnz_arrays_ = 0                                    # host arrays of nnz doubles made since setup began
         if self.host_setup_:
-            self._host_setup(patch, bc, rowptr, col, n)
+            self._host_setup(patch, bc, rowptr, col)
         # integrators (py_nonlinear_solid.cpp:197-218, 286-326)
         q_order = rc.get_int("nonlinear_solid_quadrature_order", -1)
         self.domain_ = self._make_domain(q_order)
         self.domain_.SetTangentMode(self.tangent_mode)
         self._finish_setup(patch, bc, rc, q_order)
 
-    def _host_setup(self, patch, bc, rowptr, col, n):
+    def _host_setup(self, patch, bc, rowptr, col):
         """mass, damping and right-hand side in numpy on the host"""
         viscosity = getattr(self.material, "viscosity", -1.0)
         mass, visc, rhs = _assemble_mass_viscosity_rhs(patch, self.pattern_u_.rowptr, self.material.density, viscosity,
                                                        bc.initial.body_force_)
+        rhs = self._load_vector_folded(rhs)
         if self.fold_ is not None:
             # assembled on the unwrapped pattern as without periodicity, folded once by the device pass
-            rhs = _load_vector(patch, self._faces, bc.initial.traction_, rhs, np.zeros(0, dtype=np.int64))
-            rhs_f = np.zeros(n)
-            self.fold_.Add(rhs, rhs_f)
-            rhs = rhs_f
             mass_f = np.empty(self.pattern_.nnz)
             self.fold_.Add(None, None, mass, None, mass_f)
             mass = mass_f
@@ -475,7 +505,7 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         self.visc_ = visc
         if visc is not None:
             _eliminate_row_col(rowptr, col, self.visc_, self.dirichlet_)
-        self.rhs_ = _load_vector(patch, self._faces, bc.initial.traction_ if self.fold_ is None else {}, rhs, self.dirichlet_)
+        self.rhs_ = rhs
 
     def _make_domain(self, q_order):
         """the domain integrator of the patch with the rule of `q_order`"""
@@ -494,13 +524,17 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         return NonlinearSolidIntegrator("nonlinear_solid", self.material, self.pattern_u_, tables=tables,
                                         device=self.device).Prepare()
 
+    @contextlib.contextmanager
     def _forms_domain(self):
-        """(integrator, temporary) the mass, damping and body-force forms are assembled with: they use the default rule,
-        which is the domain integrator's unless nonlinear_solid_quadrature_order is set -- then a handle of its own, which
-        the caller drops"""
+        """the integrator the mass, damping and body-force forms are assembled with: they use the default rule, which is the
+        domain integrator's unless nonlinear_solid_quadrature_order is set -- then a handle of its own, dropped on exit"""
         if self.runtime_communication.get_int("nonlinear_solid_quadrature_order", -1) < 0:
-            return self.domain_, False
-        return self._make_domain(-1), True
+            yield self.domain_
+            return
+        forms = self._make_domain(-1)
+        yield forms
+        forms.Synchronize()
+        del forms
 
     def _body_force_vector(self, forms):
         """the body-force vector of the unwrapped patch, assembled on the device: n_vdofs doubles on the host"""
@@ -514,7 +548,7 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         return r_u.cpu().numpy()
 
     def _load_vector_folded(self, rhs):
-        """body force `rhs` (unwrapped, modified) + traction, folded, zero on the Dirichlet dofs: what _host_setup does"""
+        """body force `rhs` (unwrapped, modified) + traction, folded, zero on the Dirichlet dofs"""
         patch, bc = self.patch_, self.bc_
         if self.fold_ is None:
             return _load_vector(patch, self._faces, bc.initial.traction_, rhs, self.dirichlet_)
@@ -529,7 +563,6 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         array of nnz doubles exists on the host or crosses PCIe.  The traction stays on the host (face work)."""
         import torch
         dev = torch.device("cuda", self.device)
-        forms, temporary = self._forms_domain()
 
         def assembled(add, factor):
             a = torch.zeros(self.pattern_u_.nnz, dtype=torch.float64, device=dev)
@@ -541,13 +574,11 @@ class NonlinearSolid(Solid, ExplicitDynamics):
             self.linear_.Eliminate(None, a)
             return a
 
-        self.d_mass_ = assembled(forms.AddMass, self.material.density)
-        viscosity = getattr(self.material, "viscosity", -1.0)
-        self.d_visc_ = assembled(forms.AddDiffusion, viscosity) if viscosity > 0.0 else None
-        self.rhs_ = self._load_vector_folded(self._body_force_vector(forms))
-        if temporary:
-            forms.Synchronize()
-            del forms
+        with self._forms_domain() as forms:
+            self.d_mass_ = assembled(forms.AddMass, self.material.density)
+            viscosity = getattr(self.material, "viscosity", -1.0)
+            self.d_visc_ = assembled(forms.AddDiffusion, viscosity) if viscosity > 0.0 else None
+            self.rhs_ = self._load_vector_folded(self._body_force_vector(forms))
 
     # mass_ / visc_: the host copies of d_mass_ / d_visc_, downloaded on first read (the direct-solve route and _csr read
     # them; the iterative route never does)
@@ -578,11 +609,9 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         assembled again on the device and rhs_ rebuilt IN PLACE -- body force + traction, zero on the Dirichlet dofs --
         so the array linear_form_view2("rhs") handed out stays the one in use; takes effect from the next solve"""
         self.bc_.initial.body_force_[dim] = value
-        forms, temporary = self._forms_domain()
-        self.rhs_[:] = self._load_vector_folded(self._body_force_vector(forms))
-        if temporary:
-            forms.Synchronize()
-            del forms
+        with self._forms_domain() as forms:
+            self.rhs_[:] = self._load_vector_folded(self._body_force_vector(forms))
+        del forms                                    # (a temporary handle goes here, not at the return)
         self.has_rhs_ = True
         self.d_rhs_.copy_(self._torch.from_numpy(self.rhs_))
 
@@ -613,15 +642,13 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         # linear solver (py_nonlinear_solid.cpp:327-343): "use_iterative_solver" -> GMRES + Jacobi on the device
         # (mimi_amd/linear.py); else a sparse direct solve on the host (UMFPack in the reference, SuperLU here)
         self.linear_ = LinearSolver(self.pattern_, self.dirichlet_, device=self.device)
-        self.use_iterative_solver_ = bool(rc.get_int("use_iterative_solver", 0))
+        route = self.route_
+        self.use_iterative_solver_, self.matrix_free_ = route.iterative, route.matrix_free
         # "use_kronecker_preconditioner" (with the iterative solver only): the fast-diagonalisation operator of
         # mimi_amd/kronecker.py in place of Jacobi, for the Newton solves and the explicit mass solve
-        self.use_kronecker_ = self.use_iterative_solver_ and bool(rc.get_int("use_kronecker_preconditioner", 0))
-        self._kronecker_pushed = None
-        if self.use_kronecker_:
-            self.linear_.SetKronecker(KroneckerOperator(patch, self.dirichlet_, dim, periodic_axes=self.periodic_axes_))
-            self.linear_.preconditioner = "kronecker"
-        self.matrix_free_ = bool(rc.get_int("matrix_free", 0))       # (what it needs was checked at the top of setup)
+        self.use_kronecker_, self._kronecker_pushed = False, None
+        if route.kronecker:
+            self._set_kronecker()
         if self.fold_ is not None and (self.matrix_free_ or self.explicit_consistent_):
             # the operator handles stay in the unwrapped numbering: the solver's product expands and folds around them
             # (set once: it survives every SetOperator)
@@ -633,6 +660,12 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         self._to_device()
         if self.explicit_:
             self._explicit_make_stepper()
+
+    def _set_kronecker(self):
+        """the Kronecker preconditioner of the patch on the solver: the implicit routes and the consistent-mass solve"""
+        self.linear_.SetKronecker(KroneckerOperator(self.patch_, self.dirichlet_, self._dim, periodic_axes=self.periodic_axes_))
+        self.linear_.preconditioner = "kronecker"
+        self.use_kronecker_, self._kronecker_pushed = True, None
 
     def _folded_dofs(self, nodes, comp):
         """dofs (node, comp) of unwrapped nodes in the solver's numbering (through the periodic node map), unique"""
@@ -703,30 +736,89 @@ class NonlinearSolid(Solid, ExplicitDynamics):
     def _push(self, integ):
         integ.dt_, integ.first_effective_dt_, integ.second_effective_dt_ = self.time_step_size, self._fac0, self._fac1
 
+    # ---- the seam: what the integrators see -------------------------------------------------------------
+    # The integrators work in the patch's unwrapped numbering, the solver in the folded one.  Every assembly and every step
+    # goes through these entries, the only ones that ask whether there is a fold and the only ones that walk the integrators.
+    @property
+    def boundaries_(self):
+        """the boundary integrators in assembly order: contacts, then pressures (the domain comes before them)"""
+        return self.contacts_ + self.pressures_
+
+    @property
+    def integrators_(self):
+        """every integrator in assembly order: the domain, then the boundaries"""
+        return [self.domain_] + self.boundaries_
+
     def _expand(self, x):
-        """the unwrapped vector the integrators read (periodic route)"""
-        return self.fold_.Expand(x, self.d_xu_)
+        """the vector the integrators read for the solver's x: x through the fold, x itself without one"""
+        return x if self.fold_ is None else self.fold_.Expand(x, self.d_xu_)
+
+    def _open(self, x, y):
+        """(xu, target): the expanded x and the zeroed unwrapped residual the integrators add into -- x and y themselves
+        without a fold; _close(target, y) finishes"""
+        if self.fold_ is None:
+            return x, y
+        xu = self._expand(x)
+        self.d_ru_.zero_()
+        return xu, self.d_ru_
+
+    def _close(self, target, y):
+        """y += the fold of target (nothing without a fold: the integrators wrote into y)"""
+        if self.fold_ is not None:
+            self.fold_.Add(target, y)
+
+    def _add_residual(self, x, y, linearize=False):
+        """y += the residual of every integrator at x; linearize: each one also takes the snapshot of its tangent action there"""
+        xu, target = self._open(x, y)
+        self.domain_.AddDomainResidual(xu, target)
+        if linearize:
+            self.domain_.Linearize(xu)
+        for c in self.boundaries_:
+            c.AddBoundaryResidual(xu, target)
+            if linearize:
+                c.Linearize(xu)
+        self._close(target, y)
+
+    def _add_residual_and_grad(self, x, y):
+        """y += the residual, d_jac_ = d_mass_ + fac0 K of every integrator at x.  Without a fold the domain integrator writes
+        J = M + fac0 K in one pass where "+=" would read J (std::copy_n(mass_A_, ...) followed by AddMultGrad:
+        mimi_hip_domain_add_residual_and_grad_from -- no 2 x nnz copy, and the domain integrator of a single-patch solid
+        touches every row); with one everything goes into the zeroed unwrapped r_u / A_u and ONE fold forms
+        y += P^T r_u, J = M + P^T A_u P"""
+        xu, r = self._open(x, y)
+        if self.fold_ is None:
+            A = self.d_jac_
+            self.domain_.AddDomainResidualAndGradFrom(xu, self._fac0, r, self.d_mass_, A)
+        else:
+            A = self.d_Au_
+            A.zero_()
+            self.domain_.AddDomainResidualAndGrad(xu, self._fac0, r, A)
+        for c in self.boundaries_:
+            c.AddBoundaryResidualAndGrad(xu, self._fac0, r, A)
+        if self.fold_ is not None:
+            self.fold_.Add(r, y, A, self.d_mass_, self.d_jac_)
+
+    def _post_time_advance(self, x, domain=True, boundaries=True):
+        """PostTimeAdvance at the solver's x of the chosen integrators (the boundary ones read the scalars of the latest
+        residual evaluation back: an explicit step leaves them to the next download)"""
+        xp = self._expand(x)
+        if domain:
+            self.domain_.DomainPostTimeAdvance(xp)
+        for c in self.boundaries_ if boundaries else ():
+            c.BoundaryPostTimeAdvance(xp)
+
+    def _displacement(self, u):
+        """the current displacement (u None) or the host vector u in this facade's numbering, as a device vector"""
+        if u is None:
+            return self.d_x_
+        x = self._torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64).reshape(-1)).to(self.d_x_.device)
+        if x.numel() != self.d_x_.numel():
+            raise ValueError(f"u has {x.numel()} entries, the displacement has {self.d_x_.numel()}")
+        return x
 
     def _add_mult(self, xt, y):                       # forms/nonlinear.hpp:53-81
-        if self.fold_ is not None:
-            # expand, every integrator into the unwrapped residual, one fold into y
-            xu, ru = self._expand(xt), self.d_ru_
-            ru.zero_()
-            self._push(self.domain_)
-            self.domain_.AddDomainResidual(xu, ru)
-            for c in self.contacts_:
-                c.AddBoundaryResidual(xu, ru)
-            for c in self.pressures_:
-                c.AddBoundaryResidual(xu, ru)
-            self.fold_.Add(ru, y)
-            self.linear_.Eliminate(y, None)
-            return
         self._push(self.domain_)
-        self.domain_.AddDomainResidual(xt, y)
-        for c in self.contacts_:
-            c.AddBoundaryResidual(xt, y)
-        for c in self.pressures_:
-            c.AddBoundaryResidual(xt, y)
+        self._add_residual(xt, y)
         self.linear_.Eliminate(y, None)               # y[ess] = 0
 
     def _linear_part(self, a, y):
@@ -749,55 +841,23 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         xt = self._xa + self._fac0 * a
         y = self._torch.empty_like(a)
         self._linear_part(a, y)
-        # std::copy_n(mass_A_, ...) followed by AddMultGrad, as one pass: J = M + fac0 K with the row gathers reading M
-        # where "+=" would read J (mimi_hip_domain_add_residual_and_grad_from) -- no 2 x nnz copy, and the domain
-        # integrator of a single-patch solid touches every row
         self._push(self.domain_)
         if self.matrix_free_:
             # no Jacobian: the residual-only assembly, the snapshot of the tangent at x_t, and the solver's product becomes
             # rho M + fac0 K(x_t) + fac1 eta C of the domain integrator; with "matrix_free_boundary"
             # every contact and pressure integrator adds its residual, is linearised at x_t too and joins the product.
-            # With a periodic pair ("periodic_iterative") x_t is expanded once, every integrator works on the expanded vector
-            # and adds into the unwrapped residual, which is folded once; the product goes through the fold set in setup
-            xp, rp = xt, y
-            if self.fold_ is not None:
-                xp, rp = self._expand(xt), self.d_ru_
-                rp.zero_()
-            self.domain_.AddDomainResidual(xp, rp)
-            self.domain_.Linearize(xp)
-            faces = self.contacts_ + self.pressures_
-            for c in faces:
-                c.AddBoundaryResidual(xp, rp)
-                c.Linearize(xp)
-            if self.fold_ is not None:
-                self.fold_.Add(rp, y)
+            # With a periodic pair ("periodic_iterative") the product goes through the fold set in setup
+            self._add_residual(xt, y, linearize=True)
             eta = getattr(self.material, "viscosity", -1.0)
             self.linear_.SetOperator(self.domain_, self.material.density, self._fac0,
                                      self._fac1 * eta if self.d_visc_ is not None else 0.0)
-            for c in faces:
+            for c in self.boundaries_:
                 self.linear_.AddBoundaryOperator(c, self._fac0)
             self.linear_.Eliminate(y, None)
             y -= self._rhs
             self.linear_.Eliminate(y, None)
             return y, None
-        if self.fold_ is not None:
-            # periodic route: expand x_t, every integrator into the zeroed unwrapped r_u / A_u, then ONE fold
-            # y += P^T r_u, J = M + P^T A_u P in place of the from-base pass
-            xu, ru, Au = self._expand(xt), self.d_ru_, self.d_Au_
-            ru.zero_()
-            Au.zero_()
-            self.domain_.AddDomainResidualAndGrad(xu, self._fac0, ru, Au)
-            for c in self.contacts_:
-                c.AddBoundaryResidualAndGrad(xu, self._fac0, ru, Au)
-            for c in self.pressures_:
-                c.AddBoundaryResidualAndGrad(xu, self._fac0, ru, Au)
-            self.fold_.Add(ru, y, Au, self.d_mass_, self.d_jac_)
-        else:
-            self.domain_.AddDomainResidualAndGradFrom(xt, self._fac0, y, self.d_mass_, self.d_jac_)
-            for c in self.contacts_:
-                c.AddBoundaryResidualAndGrad(xt, self._fac0, y, self.d_jac_)
-            for c in self.pressures_:
-                c.AddBoundaryResidualAndGrad(xt, self._fac0, y, self.d_jac_)
+        self._add_residual_and_grad(xt, y)
         self.linear_.Eliminate(y, self.d_jac_)        # forms/nonlinear.hpp:76-80,112-115
         if self.d_visc_ is not None:
             self.d_jac_.add_(self.d_visc_, alpha=self._fac1)     # jacobian_->Add(fac1_, viscosity_->SpMat())
@@ -954,31 +1014,34 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         if self._saved_x is not None:
             self._a[self.d_cv_dofs_] = 0.0
         # PostTimeAdvance (operators/nonlinear_solid.cpp:285-292)
-        xp = self._expand(x) if self.fold_ is not None else x
         self._push(self.domain_)
-        self.domain_.DomainPostTimeAdvance(xp)
-        for c in self.contacts_:
-            c.BoundaryPostTimeAdvance(xp)
-        for c in self.pressures_:
-            c.BoundaryPostTimeAdvance(xp)
+        self._post_time_advance(x)
         self.current_time += dt
         # the arrays solution_view handed out (zero-copy views of the reference: py_solid.cpp:379-388)
         self.x[:] = x.cpu().numpy()
         self.x_dot[:] = v.cpu().numpy()
-        x, v = self.x, self.x_dot
-        # PySolid::StepTime2 (py_solid.cpp:433-440): save cadence, in the reference's (MFEM's) dof numbering
         rc = self.runtime_communication
         if rc is not None:
-            if rc.should_save("x"):
-                rc.save_dynamic_vector("x_", self.in_reference_numbering(x))
-            if rc.should_save("v"):
-                rc.save_dynamic_vector("v_", self.in_reference_numbering(v))
-            # nodal fields (beyond the reference, which saves x_ / v_ only): <field name>_<step>, in its node order
-            for name in NonlinearSolidIntegrator.FIELDS:
-                if rc.should_save(name):
-                    f = self.field(name)
-                    rc.save_dynamic_vector(name + "_", self.in_reference_numbering(f, ncomp=f.shape[1]))
+            self._save_cadence()
             rc.next_time_step(dt)
+
+    def _save_cadence(self, before=None):
+        """PySolid::StepTime2 (py_solid.cpp:433-440): x_<step> and v_<step> from the host arrays where the save cadence asks,
+        in the reference's (MFEM's) dof numbering; beyond the reference the nodal fields, <field name>_<step>, in its node
+        order.  before(): runs once if anything is due, ahead of the first write.  Returns the number of fields saved."""
+        rc = self.runtime_communication
+        names = [k for k in ("x", "v") + tuple(NonlinearSolidIntegrator.FIELDS) if rc.should_save(k)]
+        if names and before is not None:
+            before()
+        for k in names:
+            if k == "x":
+                rc.save_dynamic_vector("x_", self.in_reference_numbering(self.x))
+            elif k == "v":
+                rc.save_dynamic_vector("v_", self.in_reference_numbering(self.x_dot))
+            else:
+                f = self.field(k)
+                rc.save_dynamic_vector(k + "_", self.in_reference_numbering(f, ncomp=f.shape[1]))
+        return len([k for k in names if k not in ("x", "v")])
 
     def step_time2(self):
         """PySolid::StepTime2 (py_solid.cpp:425-441).
@@ -1125,10 +1188,8 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         if getattr(self, "domain_", None) is None:
             raise RuntimeError("field() needs setup()")
         torch = self._torch
-        x = self.d_x_ if u is None else torch.from_numpy(np.ascontiguousarray(u, dtype=np.float64).reshape(-1)).to(self.d_x_.device)
-        if x.numel() != self.d_x_.numel():
-            raise ValueError(f"u has {x.numel()} entries, the displacement has {self.d_x_.numel()}")
-        xu = self._expand(x) if self.fold_ is not None else x
+        x = self._displacement(u)
+        xu = self._expand(x)
         self.domain_.dt_ = self.time_step_size      # (the effective dts do not reach the material)
         ncomp = self.domain_.FieldComponents(name)
         if where == "points":

@@ -4,7 +4,11 @@ cubic Bezier punch that first descends, then slides sideways) on mimi_amd, print
 The punch is handed over as any object with `degrees`, `knot_vectors`, `control_points` (a splinepy spline qualifies);
 a SimpleNamespace is enough.
 
-    python examples/nl_contact.py [--steps 30]
+    python examples/nl_contact.py [--steps 30] [--friction MU]
+
+--friction MU puts Coulomb friction on the punch (the reference has none): the tangential penalty is the scene's
+coefficient, and the punch's displacement of the step is handed over as step_displacement, so that only the relative slip
+of the surface against the punch loads the block.  The default, 0, prints what the frictionless run prints.
 """
 import argparse
 import os
@@ -43,6 +47,7 @@ def make_punch():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--friction", type=float, default=0.0, metavar="MU", help="friction coefficient of the punch (default 0)")
     args = ap.parse_args()
 
     block, punch = make_block(), make_punch()
@@ -59,17 +64,22 @@ def main():
     block.configure_newton("nonlinear_solid", 1e-10, 1e-8, 100, False)
     block.time_step_size = 0.001
     rigid_scene.coefficient = 1e11                           # stiffer penalty once everything is set up
+    rigid_scene.friction = args.friction
 
     disp = block.solution_view("displacement", "x").reshape(-1, block.mesh_dim())
     for k in range(args.steps):
         shift = [0.0, -PUNCH_SPEED] if k < DESCEND_STEPS else [-PUNCH_SPEED, 0.0]
         punch.control_points += shift
         rigid_scene.plant_kd_tree(10000, 4)                  # the moved body reaches the device handles here
+        rigid_scene.step_displacement = shift                # (read by the friction law only)
         block.step_time2()
         info = block.newton_history[-1]
-        force = block.contacts_[0].last_force_
+        contact = block.contacts_[0]
+        rubbing = ""
+        if args.friction > 0.0:
+            rubbing = f"  friction force {contact.last_friction_force_}  stick {contact.n_stick_} slip {contact.n_slip_}"
         print(f"step {k:3d}  Newton iterations {info['iterations']:2d}  converged {info['converged']}  "
-              f"|u|max = {np.abs(disp).max():.3e}  contact force {force}")
+              f"|u|max = {np.abs(disp).max():.3e}  contact force {contact.last_force_}{rubbing}")
 
 
 if __name__ == "__main__":

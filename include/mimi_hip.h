@@ -410,6 +410,31 @@ int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const do
  * 1 whether the face tangent blocks of an assembly are allocated.  -1: bad argument. */
 int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what);
 
+/* Coulomb friction (the reference has none; model and layout: DESIGN.md "Coulomb friction").  At a face point with
+ * p_N = -p_h > 0 that was in contact at the last commit: a = xi + x_q - xbar - d, s = (I - n n^T) a on the deformable
+ * surface's own normal; stick (eps_t |s| <= mu p_N): t = eps_t s, xi' = s; slip: t = mu p_N s / |s|, xi' = t / eps_t;
+ * r(a,i) += sum_q w |m| N_a t_i, exact tangent with the nodal pressures, the state, d and the branch frozen.  A point that
+ * is new in contact carries no traction in that step.  Every Add* call writes a TRIAL state; only post_time_advance
+ * commits.  mu = 0 (the default): launches and bytes of every other entry are those of a handle without friction.
+ *   set_friction        mu >= 0, eps_t > 0 (with mu > 0); the first mu > 0 allocates the state (xi = 0, no point in contact).
+ *                       Refused in the reference-FD tangent mode; with mu > 0 set_tangent_mode(REFERENCE_FD), linearize and
+ *                       apply_tangent (and a Krylov operator built on the handle) are refused.
+ *   set_body_increment  d[dim]: the rigid body's displacement over the current step (NULL: zero)
+ *   post_time_advance   u != NULL: an evaluation at u (pass 1, pressure, pass 2 without the gather: the history scalars are
+ *                       those of u), then commit.  u == NULL: commit the trial state of the latest evaluation on the
+ *                       handle's stream -- nothing is recomputed and nothing waits for the device.
+ *   reset_friction      xi = 0, no point in contact, no trial state
+ *   friction_history    of the latest evaluation: out[0..3) = sum da t (friction force on the body), out[3] = sum da |t|,
+ *                       out[4] = sticking points, out[5] = slipping points
+ *   friction_state      the committed state to the host: xi, xbar [n_faces][n_quad][dim], c [n_faces][n_quad] (each may
+ *                       be NULL) */
+int mimi_hip_contact_set_friction(mimi_hip_contact_t h, double mu, double eps_t);
+int mimi_hip_contact_set_body_increment(mimi_hip_contact_t h, const double* d);
+int mimi_hip_contact_post_time_advance(mimi_hip_contact_t h, const double* u);
+int mimi_hip_contact_reset_friction(mimi_hip_contact_t h);
+int mimi_hip_contact_friction_history(mimi_hip_contact_t h, double* out6);
+int mimi_hip_contact_friction_state(mimi_hip_contact_t h, double* xi, double* xbar, unsigned char* c);
+
 /* ---- follower-pressure boundary integrator (integrators::FollowerPressure) ---------------------------------------
  * The reference stores BCMarker::Pressure(bid, value) (utils/boundary_conditions.cpp:43-50) and never applies it; here it
  * is the follower load t = -p n da on the CURRENT surface x = X + u of a set of faces of one patch:

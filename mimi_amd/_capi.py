@@ -108,6 +108,8 @@ EXPORTS = [
     "mimi_hip_follower_linearize", "mimi_hip_follower_apply_tangent", "mimi_hip_follower_action_info",
     "mimi_hip_linear_add_boundary_operator",
     "mimi_hip_linear_set_operator_fold", "mimi_hip_linear_operator_mult",
+    "mimi_hip_contact_set_friction", "mimi_hip_contact_set_body_increment", "mimi_hip_contact_post_time_advance",
+    "mimi_hip_contact_reset_friction", "mimi_hip_contact_friction_history", "mimi_hip_contact_friction_state",
 ]
 
 
@@ -210,6 +212,12 @@ def lib():
     L.mimi_hip_contact_marked_nodes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.mimi_hip_contact_nodal.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.mimi_hip_contact_add_residual_from_nodal.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+    L.mimi_hip_contact_set_friction.argtypes = [C.c_void_p, C.c_double, C.c_double]
+    L.mimi_hip_contact_set_body_increment.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_contact_post_time_advance.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_contact_reset_friction.argtypes = [C.c_void_p]
+    L.mimi_hip_contact_friction_history.argtypes = [C.c_void_p, C.c_void_p]
+    L.mimi_hip_contact_friction_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.mimi_hip_pressure_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     L.mimi_hip_pressure_destroy.argtypes = [C.c_void_p]
     L.mimi_hip_pressure_set_stream.argtypes = [C.c_void_p, C.c_void_p]

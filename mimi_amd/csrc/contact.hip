@@ -30,6 +30,7 @@
 #include "common.hpp"
 #include "face_common.hpp"
 #include "kernels_face_action.hpp"
+#include "kernels_face_friction.hpp"
 #include "materials.hpp"
 #include "spline_body.hpp"
 
@@ -482,13 +483,80 @@ struct mimi_hip_contact_s : FaceAssembly {
   SplineBodyDev spline{};
   DeviceBuffer<double> sb_knots[2], sb_ctrl, sb_sample_xi, sb_sample_x;
   BoundaryAction action;   // mimi_hip_contact_linearize / _apply_tangent (kernels_face_action.hpp)
+  // Coulomb friction (kernels_face_friction.hpp); mu == 0: none of it is allocated or launched
+  double mu = 0.0, eps_t = 0.0, body_inc[3] = {0.0, 0.0, 0.0};
+  DeviceBuffer<double> fr_xi, fr_xbar, fr_xi_t, fr_xbar_t, fr_face, fr_scalars;
+  DeviceBuffer<unsigned char> fr_c, fr_c_t;
+  bool fr_trial = false;   // an evaluation has written the trial state since create / reset
 };
+
+// the friction state of a handle: allocated and zeroed by the first set_friction with mu > 0
+static void friction_reset(mimi_hip_contact_s* h) {
+  const size_t npts = (size_t)h->n_faces * h->n_q, ns = npts * h->dim;
+  h->fr_xi.resize(ns);
+  h->fr_xbar.resize(ns);
+  h->fr_xi_t.resize(ns);
+  h->fr_xbar_t.resize(ns);
+  h->fr_c.resize(npts);
+  h->fr_c_t.resize(npts);
+  h->fr_face.resize((size_t)h->n_faces * kFrictionScalars);
+  h->fr_scalars.resize(kFrictionScalars);
+  for (DeviceBuffer<double>* b : {&h->fr_xi, &h->fr_xbar, &h->fr_xi_t, &h->fr_xbar_t})
+    MH_HIP(hipMemsetAsync(b->ptr, 0, ns * sizeof(double), h->stream));
+  MH_HIP(hipMemsetAsync(h->fr_c.ptr, 0, npts, h->stream));
+  MH_HIP(hipMemsetAsync(h->fr_c_t.ptr, 0, npts, h->stream));
+  MH_HIP(hipMemsetAsync(h->fr_scalars.ptr, 0, kFrictionScalars * sizeof(double), h->stream));
+  h->fr_trial = false;
+}
+
+static FrictionArgs friction_args(const mimi_hip_contact_s* h, const ContactArgs& c) {
+  FrictionArgs a{};
+  a.n_faces = c.n_faces;
+  a.n_dof = c.n_dof;
+  a.n_q = c.n_q;
+  a.dofs = c.dofs;
+  a.local = c.local;
+  a.N = c.N;
+  a.dN = c.dN;
+  a.weight = c.weight;
+  a.x_ref = c.x_ref;
+  a.u = c.u;
+  a.pressure = c.pressure;
+  a.face_r = c.face_r;
+  a.face_k = c.face_k;
+  a.mu = h->mu;
+  a.eps_t = h->eps_t;
+  for (int i = 0; i < 3; ++i) a.d[i] = h->body_inc[i];
+  a.xi = h->fr_xi.ptr;
+  a.xbar = h->fr_xbar.ptr;
+  a.c = h->fr_c.ptr;
+  a.xi_t = h->fr_xi_t.ptr;
+  a.xbar_t = h->fr_xbar_t.ptr;
+  a.c_t = h->fr_c_t.ptr;
+  a.face_fr = h->fr_face.ptr;
+  return a;
+}
+
+// the trial state over the committed one, on the handle's stream; nothing waits
+static void friction_commit(mimi_hip_contact_s* h) {
+  const int64_t npts = (int64_t)h->n_faces * h->n_q, ns = npts * h->dim;
+  hipLaunchKernelGGL(contact_friction_commit_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, h->stream, ns, npts,
+                     h->fr_xi_t.ptr, h->fr_xbar_t.ptr, h->fr_c_t.ptr, h->fr_xi.ptr, h->fr_xbar.ptr, h->fr_c.ptr);
+  MH_HIP(hipGetLastError());
+}
+
+static void refuse_friction(const mimi_hip_contact_s* h, const char* what) {
+  if (h->mu > 0.0)
+    fail("%s is not available on a contact handle with friction (mu = %g): the friction tangent is assembled only "
+         "(set_friction(h, 0, 0) removes it)", what, h->mu);
+}
 
 // ---- the operator seam of the Krylov solvers (apply_seam.hpp) ----------------------------------------------------------------
 namespace mimi_hip {
 int64_t operator_size(const mimi_hip_contact_s* h) { return h->n_vdofs; }
 int operator_device(const mimi_hip_contact_s* h) { return h->device; }
 void operator_begin_solve(mimi_hip_contact_s* h, hipStream_t solver_stream) {
+  refuse_friction(h, "the matrix-free tangent action");
   h->action.require("contact");
   MH_HIP(hipSetDevice(h->device));
   h->action.begin(*h, solver_stream);
@@ -610,7 +678,8 @@ static void contact_linearize(mimi_hip_contact_s* h, const double* u_dev) {
 }
 
 // pressure from the nodal area / gap (mortar_contact.cpp:195-261), then pass 2: face residual vectors (+ tangent blocks)
-// and their row gather
+// and their row gather (r_dev null: everything but the gather -- the evaluation of mimi_hip_contact_post_time_advance).
+// With mu > 0 the friction kernels add to the face stores behind the frictionless ones and write the trial state.
 static void contact_pass2(mimi_hip_contact_s* h, const double* u_dev, double* r_dev, double* A_dev, double gf, bool with_grad) {
   if (with_grad) h->reserve_face_k();
   ContactArgs a = contact_args(h, u_dev);
@@ -633,9 +702,23 @@ static void contact_pass2(mimi_hip_contact_s* h, const double* u_dev, double* r_
     if (h->dim == 2) hipLaunchKernelGGL(contact_tangent_kernel<2>, dim3(b4), dim3(256), 0, h->stream, a);
     else hipLaunchKernelGGL(contact_tangent_kernel<3>, dim3(b4), dim3(256), 0, h->stream, a);
   }
+  if (h->mu > 0.0) {
+    if (h->mode == MIMI_HIP_TANGENT_REFERENCE_FD) fail("friction has no reference-FD tangent");   // (refused where either is set)
+    const FrictionArgs fa = friction_args(h, a);
+    if (h->dim == 2) hipLaunchKernelGGL(contact_friction_kernel<2>, dim3(b3w), dim3(256), 0, h->stream, fa);
+    else hipLaunchKernelGGL(contact_friction_kernel<3>, dim3(b3w), dim3(256), 0, h->stream, fa);
+    if (with_grad) {
+      if (h->dim == 2) hipLaunchKernelGGL(contact_friction_tangent_kernel<2>, dim3(b3w), dim3(256), 0, h->stream, fa);
+      else hipLaunchKernelGGL(contact_friction_tangent_kernel<3>, dim3(b3w), dim3(256), 0, h->stream, fa);
+    }
+    hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, kFrictionScalars, kFrictionScalars,
+                       h->fr_face.ptr, (const unsigned char*)nullptr, h->fr_scalars.ptr);
+    h->fr_trial = true;
+  }
   // pressure integral and force of the active faces (last_pressure_ / last_force_), in a fixed order
   hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, 1 + h->dim, 1 + h->dim,
                      h->face_scal.ptr, h->face_active.ptr, h->scalars.ptr + 1);
+  if (!r_dev) return;
   if (h->dim == 2) h->gather<2>(r_dev, A_dev, gf, with_grad);
   else h->gather<3>(r_dev, A_dev, gf, with_grad);
 }
@@ -685,6 +768,7 @@ int mimi_hip_contact_set_tangent_mode(mimi_hip_contact_t h, int mode) {
   return guarded([&] {
     if (!h) fail("null handle");
     if (mode != MIMI_HIP_TANGENT_ANALYTIC && mode != MIMI_HIP_TANGENT_REFERENCE_FD) fail("bad tangent mode %d", mode);
+    if (mode == MIMI_HIP_TANGENT_REFERENCE_FD) refuse_friction(h, "the reference-FD tangent mode");
     h->mode = mode;
   });
 }
@@ -710,12 +794,16 @@ int mimi_hip_contact_add_residual_and_grad(mimi_hip_contact_t h, const double* u
 int mimi_hip_contact_linearize(mimi_hip_contact_t h, const double* u) {
   return guarded([&] {
     if (!h) fail("null handle");
+    refuse_friction(h, "mimi_hip_contact_linearize");
     h->run(u, nullptr, nullptr, false, [&](const double* u_dev, double*, double*) { contact_linearize(h, u_dev); });
   });
 }
 
 int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const double* x, double* y) {
-  return guarded([&] { boundary_apply_entry(h, "contact", factor, x, y); });
+  return guarded([&] {
+    if (h) refuse_friction(h, "mimi_hip_contact_apply_tangent");
+    boundary_apply_entry(h, "contact", factor, x, y);
+  });
 }
 
 int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what) { return boundary_action_info(h, what); }
@@ -813,6 +901,93 @@ int mimi_hip_contact_get_pressure(mimi_hip_contact_t h, double* out, int64_t cap
     MH_HIP(hipSetDevice(h->device));
     MH_HIP(hipMemcpyAsync(out, h->pressure.ptr, h->n_fnodes * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     MH_HIP(hipStreamSynchronize(h->stream));
+  });
+}
+
+// ---- Coulomb friction (kernels_face_friction.hpp) ------------------------------------------------------------------------
+int mimi_hip_contact_set_friction(mimi_hip_contact_t h, double mu, double eps_t) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    if (!(mu >= 0.0)) fail("friction coefficient %g: must be >= 0", mu);
+    if (mu > 0.0 && !(eps_t > 0.0)) fail("tangential penalty %g: must be > 0 with friction", eps_t);
+    if (mu > 0.0 && h->mode == MIMI_HIP_TANGENT_REFERENCE_FD)
+      fail("friction (mu = %g) is not available in the reference-FD tangent mode: its tangent is the analytic one", mu);
+    MH_HIP(hipSetDevice(h->device));
+    if (mu > 0.0 && !h->fr_xi.ptr) friction_reset(h);
+    h->mu = mu;
+    h->eps_t = eps_t;
+  });
+}
+
+int mimi_hip_contact_set_body_increment(mimi_hip_contact_t h, const double* d) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    for (int i = 0; i < 3; ++i) h->body_inc[i] = (d && i < h->dim) ? d[i] : 0.0;
+  });
+}
+
+int mimi_hip_contact_post_time_advance(mimi_hip_contact_t h, const double* u) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    if (!(h->mu > 0.0)) fail("mimi_hip_contact_post_time_advance: the handle has no friction (set_friction with mu > 0 first)");
+    MH_HIP(hipSetDevice(h->device));
+    if (!u) {
+      if (!h->fr_trial) fail("mimi_hip_contact_post_time_advance(h, NULL): no evaluation since create / reset_friction to commit");
+      friction_commit(h);
+      return;
+    }
+    h->run(u, nullptr, nullptr, false, [&](const double* u_dev, double*, double*) {
+      contact_pass1(h, u_dev);
+      contact_pass2(h, u_dev, nullptr, nullptr, 0.0, false);
+      friction_commit(h);
+    });
+  });
+}
+
+int mimi_hip_contact_reset_friction(mimi_hip_contact_t h) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    MH_HIP(hipSetDevice(h->device));
+    if (h->fr_xi.ptr) friction_reset(h);
+  });
+}
+
+int mimi_hip_contact_friction_history(mimi_hip_contact_t h, double* out6) {
+  return guarded([&] {
+    if (!h || !out6) fail("null argument");
+    for (int i = 0; i < kFrictionScalars; ++i) out6[i] = 0.0;
+    if (!h->fr_scalars.ptr) return;
+    MH_HIP(hipSetDevice(h->device));
+    MH_HIP(hipMemcpyAsync(out6, h->fr_scalars.ptr, kFrictionScalars * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MH_HIP(hipStreamSynchronize(h->stream));
+  });
+}
+
+int mimi_hip_contact_friction_state(mimi_hip_contact_t h, double* xi, double* xbar, unsigned char* c) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    const size_t n_q = h->n_q, dim = h->dim, npts = (size_t)h->n_faces * n_q;
+    if (!h->fr_xi.ptr) {   // never had friction: the initial state
+      for (size_t k = 0; k < npts * dim; ++k) {
+        if (xi) xi[k] = 0.0;
+        if (xbar) xbar[k] = 0.0;
+      }
+      for (size_t k = 0; c && k < npts; ++k) c[k] = 0;
+      return;
+    }
+    MH_HIP(hipSetDevice(h->device));
+    std::vector<double> a(npts * dim), b(npts * dim);
+    MH_HIP(hipMemcpyAsync(a.data(), h->fr_xi.ptr, a.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MH_HIP(hipMemcpyAsync(b.data(), h->fr_xbar.ptr, b.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (c) MH_HIP(hipMemcpyAsync(c, h->fr_c.ptr, npts, hipMemcpyDeviceToHost, h->stream));
+    MH_HIP(hipStreamSynchronize(h->stream));
+    // device [face][i][q] -> caller [face][q][i]
+    for (size_t f = 0; f < (size_t)h->n_faces; ++f)
+      for (size_t i = 0; i < dim; ++i)
+        for (size_t q = 0; q < n_q; ++q) {
+          if (xi) xi[(f * n_q + q) * dim + i] = a[(f * dim + i) * n_q + q];
+          if (xbar) xbar[(f * n_q + q) * dim + i] = b[(f * dim + i) * n_q + q];
+        }
   });
 }
 

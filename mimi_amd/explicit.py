@@ -252,7 +252,7 @@ class ExplicitDynamics:
         self.x[:] = self.d_x_.cpu().numpy()
         self.x_dot[:] = self.d_v_.cpu().numpy()
         self.explicit_d2h_copies_ += 2
-        self._post_time_advance(self.d_x_, domain=False)
+        self._post_time_advance(self.d_x_, domain=False, commit=False)
 
     def _lumped_step(self, dt):
         st, x, v = self.explicit_stepper_, self.d_x_, self.d_v_
@@ -291,6 +291,9 @@ class ExplicitDynamics:
             dt = self.time_step_size
             step(dt)
             self._post_time_advance(self.d_x_, boundaries=False)
+            for c in self.contacts_:                 # friction: the state of the step's force evaluation, on the device
+                if c.friction_ > 0.0:
+                    c.CommitFriction()
             self.current_time += dt
             self.runtime_communication.next_time_step(dt)
             fields = self._save_cadence(before=self._explicit_download)      # (the download counts its own two copies)

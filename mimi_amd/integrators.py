@@ -8,6 +8,7 @@ Method names, argument meaning and accumulate-into semantics are the reference's
 torch tensors on the handle's device (used in place, call is asynchronous on the stream).
 """
 import ctypes as C
+import weakref
 
 import numpy as np
 
@@ -365,38 +366,85 @@ class NonlinearSolid(NonlinearBase):
     domain_post_time_advance = DomainPostTimeAdvance
 
 
-class RigidSphere:
+class _Frictional:
+    """Coulomb friction of a rigid body (include/mimi_hip.h: mimi_hip_contact_set_friction; the reference has none):
+    friction = mu (0: none), tangential_coefficient = the tangential penalty (None: the body's coefficient),
+    step_displacement = the body's displacement over the current step (None: zero).  A change reaches the MortarContact
+    integrators built on the body, as a change of NearestDistanceToSplines.coefficient does."""
+
+    def _init_friction(self, friction=0.0, tangential_coefficient=None, step_displacement=None):
+        self._friction_handles = weakref.WeakSet()      # MortarContact integrators built on this body
+        self._friction, self._tangential = float(friction), tangential_coefficient
+        self._step = None if step_displacement is None else [float(v) for v in np.ravel(step_displacement)]
+
+    def _push_friction(self):
+        for c in list(self.__dict__.get("_friction_handles", ())):
+            c._apply_friction()
+
+    @property
+    def friction(self):
+        return self.__dict__.get("_friction", 0.0)
+
+    @friction.setter
+    def friction(self, value):
+        self._friction = float(value)
+        self._push_friction()
+
+    @property
+    def tangential_coefficient(self):
+        t = self.__dict__.get("_tangential")
+        return self.coefficient if t is None else float(t)
+
+    @tangential_coefficient.setter
+    def tangential_coefficient(self, value):
+        self._tangential = value
+        self._push_friction()
+
+    @property
+    def step_displacement(self):
+        return self.__dict__.get("_step")
+
+    @step_displacement.setter
+    def step_displacement(self, value):
+        self._step = None if value is None else [float(v) for v in np.ravel(value)]
+        self._push_friction()
+
+
+class RigidSphere(_Frictional):
     """Analytic rigid body standing in for NearestDistanceToSplines
     (coefficients/nearest_distance.hpp:215-288; splinepy's proximity query is not available)."""
     kind = 0
 
-    def __init__(self, center, radius, coefficient=1.0e4):
+    def __init__(self, center, radius, coefficient=1.0e4, friction=0.0, tangential_coefficient=None, step_displacement=None):
         self.center, self.radius = [float(c) for c in center], float(radius)
         self.coefficient = float(coefficient)   # NearestDistanceBase::coefficient_ (nearest_distance.hpp:18)
+        self._init_friction(friction, tangential_coefficient, step_displacement)
 
     def params(self, dim):
         return self.center + [0.0] * (3 - dim) + [self.radius]
 
 
-class RigidPlane:
+class RigidPlane(_Frictional):
     kind = 1
 
-    def __init__(self, point, normal, coefficient=1.0e4):
+    def __init__(self, point, normal, coefficient=1.0e4, friction=0.0, tangential_coefficient=None, step_displacement=None):
         n = np.asarray(normal, dtype=np.float64)
         self.point, self.normal = [float(c) for c in point], list(n / np.linalg.norm(n))
         self.coefficient = float(coefficient)
+        self._init_friction(friction, tangential_coefficient, step_displacement)
 
     def params(self, dim):
         return self.point + [0.0] * (3 - dim) + self.normal + [0.0] * (3 - dim)
 
 
-class RigidSpline:
+class RigidSpline(_Frictional):
     """One rigid boundary spline (curve in 2-D, surface in 3-D): what NearestDistanceToSplines holds
     (coefficients/nearest_distance.hpp:215-288).  Orientation: the normal (t_y, -t_x) / S_u x S_v must point out of the
     rigid body (nearest_distance.hpp:139-184)."""
     kind = 2
 
-    def __init__(self, degrees, knots, control_points, weights=None, resolution=100, coefficient=1.0e4, max_iterations=-1):
+    def __init__(self, degrees, knots, control_points, weights=None, resolution=100, coefficient=1.0e4, max_iterations=-1,
+                 friction=0.0, tangential_coefficient=None, step_displacement=None):
         self.degrees = [int(p) for p in degrees]
         self.knots = [np.ascontiguousarray(k, dtype=np.float64) for k in knots]
         n = int(np.prod([len(k) - p - 1 for k, p in zip(self.knots, self.degrees)]))
@@ -404,6 +452,7 @@ class RigidSpline:
         self.weights = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(n)
         self.resolution, self.max_iterations = int(resolution), int(max_iterations)
         self.coefficient = float(coefficient)
+        self._init_friction(friction, tangential_coefficient, step_displacement)
 
     def params(self, dim):
         return []
@@ -420,7 +469,7 @@ class RigidSpline:
         return s
 
 
-class NearestDistanceToSplines:
+class NearestDistanceToSplines(_Frictional):
     """coefficients::NearestDistanceToSplines as bound in py/py_nearest_distance.cpp: add_spline / plant_kd_tree /
     coefficient.  `spline` is anything with the attributes degrees, knot_vectors, control_points and (optionally)
     weights -- a splinepy spline has them."""
@@ -431,6 +480,7 @@ class NearestDistanceToSplines:
         self.tolerance = 1.0e-24        # nearest_distance.hpp:20 (the search here stops on the step size)
         self._splines, self._resolution = [], 100
         self._attached = []             # MortarContact integrators built on this scene
+        self._init_friction()
 
     @property
     def coefficient(self):
@@ -442,6 +492,7 @@ class NearestDistanceToSplines:
         self._coefficient = float(value)
         for c in getattr(self, "_attached", []):
             c.UpdateBody(penalty=self._coefficient)
+        self._push_friction()           # (the tangential penalty defaults to the coefficient)
 
     def add_spline(self, spline):
         self._splines.append(spline)
@@ -523,6 +574,10 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
         self.last_area_ = 0.0
         self.last_pressure_ = 0.0
         self.last_force_ = np.zeros(patch.dim)
+        self.friction_, self._has_increment = 0.0, False
+        self.last_friction_force_ = np.zeros(patch.dim)
+        self.last_friction_traction_ = 0.0
+        self.n_stick_ = self.n_slip_ = 0
 
     def Prepare(self):
         L = _capi.lib()
@@ -547,7 +602,70 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
         check(L.mimi_hip_contact_create(C.byref(t), self.device_, C.byref(h)))
         self._h = h
         self.n_marked_boundaries_ = int(t.n_faces)
+        self.n_q_ = int(t.n_quad)
+        if hasattr(body, "_friction_handles"):
+            body._friction_handles.add(self)
+        self._apply_friction()
         return self
+
+    # -- Coulomb friction (include/mimi_hip.h: mimi_hip_contact_set_friction ...) ------------------------------------
+    def _apply_friction(self):
+        """the body's friction, tangential_coefficient and step_displacement onto the handle; a body that never had
+        friction makes no call at all"""
+        if getattr(self, "_h", None) is None:
+            return
+        body = self.nearest_distance_coeff_
+        mu = float(getattr(body, "friction", 0.0))
+        if mu > 0.0 and getattr(self, "sharded_", False):
+            raise RuntimeError(f"friction (mu = {mu:g}) on the body of a ShardedContact is not supported")
+        if mu > 0.0 or self.friction_ > 0.0:
+            self.SetFriction(mu, float(getattr(body, "tangential_coefficient", body.coefficient)))
+        d = getattr(body, "step_displacement", None)
+        if d is not None or self._has_increment:
+            self.SetBodyIncrement(d)
+
+    def SetFriction(self, mu, tangential_coefficient=None):
+        """mu >= 0 and the tangential penalty (None: the body's coefficient); mu = 0 switches friction off"""
+        eps_t = self.nearest_distance_coeff_.coefficient if tangential_coefficient is None else tangential_coefficient
+        check(_capi.lib().mimi_hip_contact_set_friction(self._handle(), float(mu), float(eps_t)))
+        self.friction_ = float(mu)
+
+    def SetBodyIncrement(self, d=None):
+        """the rigid body's displacement over the current step (dim numbers; None: zero)"""
+        dim = self.patch_.dim
+        v = np.zeros(dim) if d is None else np.ascontiguousarray(np.asarray(d, dtype=np.float64).ravel())
+        if v.size != dim:
+            raise ValueError(f"step displacement must have {dim} components, got {v.size}")
+        check(_capi.lib().mimi_hip_contact_set_body_increment(self._handle(), ptr(v)))
+        self._has_increment = d is not None
+
+    def ResetFriction(self):
+        """elastic slip zero, no point in contact, no trial state"""
+        check(_capi.lib().mimi_hip_contact_reset_friction(self._handle()))
+
+    def CommitFriction(self):
+        """commit the trial state of the latest evaluation, on the device: nothing is recomputed, nothing waits"""
+        check(_capi.lib().mimi_hip_contact_post_time_advance(self._handle(), None))
+
+    def FrictionState(self):
+        """the committed state: (xi [n_faces, n_q, dim], xbar [n_faces, n_q, dim], c [n_faces, n_q] uint8)"""
+        shape = (self.n_marked_boundaries_, self.n_q_, self.patch_.dim)
+        xi, xbar, c = np.zeros(shape), np.zeros(shape), np.zeros(shape[:2], dtype=np.uint8)
+        check(_capi.lib().mimi_hip_contact_friction_state(self._handle(), ptr(xi), ptr(xbar), c.ctypes.data_as(C.c_void_p)))
+        return xi, xbar, c
+
+    def _refuse_friction(self, what):
+        if self.friction_ > 0.0:
+            raise RuntimeError(f"{what} is not available on a contact with friction (mu = {self.friction_:g}): the friction "
+                               "tangent is assembled only")
+
+    def Linearize(self, u):
+        self._refuse_friction("the matrix-free tangent action (Linearize)")
+        return super().Linearize(u)
+
+    def ApplyTangent(self, x, y, factor=1.0):
+        self._refuse_friction("the matrix-free tangent action (ApplyTangent)")
+        return super().ApplyTangent(x, y, factor)
 
     def UpdateBody(self, spline=False, penalty=-1.0):
         """the rigid body moved (spline=True: re-read it from nearest_distance_coeff_) and / or the penalty changed"""
@@ -581,6 +699,8 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
                                                                    fptr(residual), fptr(grad)))
 
     def SetTangentMode(self, mode):
+        if mode == TANGENT_REFERENCE_FD:
+            self._refuse_friction("the reference-FD tangent mode")
         check(_capi.lib().mimi_hip_contact_set_tangent_mode(self._handle(), mode))
 
     def _history(self):
@@ -588,6 +708,12 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
         check(_capi.lib().mimi_hip_contact_last_history(self._handle(), ptr(out)))
         self.last_area_, self.last_pressure_ = out[0], out[1]
         self.last_force_ = out[2:2 + self.patch_.dim].copy()
+        if self.friction_ > 0.0:
+            out = np.zeros(6)
+            check(_capi.lib().mimi_hip_contact_friction_history(self._handle(), ptr(out)))
+            self.last_friction_force_ = out[:self.patch_.dim].copy()
+            self.last_friction_traction_ = float(out[3])
+            self.n_stick_, self.n_slip_ = int(out[4]), int(out[5])
 
     # mortar_contact.cpp:297-351
     def AddBoundaryResidual(self, current_u, residual):
@@ -606,8 +732,12 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
         check(_capi.lib().mimi_hip_contact_gap_norm(self._handle(), ptr(test_u), C.byref(out)))
         return out.value
 
-    # mortar_contact.cpp:469-488: record last_area_, last_force_, last_pressure_
+    # mortar_contact.cpp:469-488: record last_area_, last_force_, last_pressure_.  With friction: first the evaluation at
+    # converged_u and the commit of its state (the history is then that of converged_u)
     def BoundaryPostTimeAdvance(self, converged_u):
+        if self.friction_ > 0.0:
+            self._follow_torch(converged_u)
+            check(_capi.lib().mimi_hip_contact_post_time_advance(self._handle(), fptr(converged_u)))
         self._history()
 
     def AveragePressure(self):

@@ -479,6 +479,9 @@ class ShardedContact:
     then travel with the domain integrator's InterfaceExchange like any other contribution."""
 
     def __init__(self, shard, body, pattern, axis, side, device=0, quadrature_order=-1, name="contact", loopback=False):
+        if float(getattr(body, "friction", 0.0)) > 0.0:
+            raise RuntimeError(f"ShardedContact: a body with friction (mu = {body.friction:g}) is not supported -- the friction "
+                               "state is kept per handle and its commit has no sharded form; use friction = 0 or one device")
         import torch
         import torch.distributed as dist
         from .integrators import MortarContact
@@ -494,6 +497,7 @@ class ShardedContact:
             if has_face:
                 self.contact = MortarContact(body, name, pattern, patch, axis, side, device=device,
                                              quadrature_order=quadrature_order, element_box=shard.element_box).Prepare()
+                self.contact.sharded_ = True       # (friction set on the body later is refused there)
         except RuntimeError as e:                      # this slab does not touch the contact face
             if "no marked boundary faces" not in str(e):
                 raise

@@ -390,6 +390,10 @@ def resolve_route(rc, bc, axes):
         if bc.initial.pressure_ and not boundary_actions:
             raise RuntimeError("matrix_free cannot be combined with a follower pressure marker: the pressure tangent has no "
                                "matrix-free action")
+        rough = [b for b in bc.current.contact_.values() if float(getattr(b, "friction", 0.0)) > 0.0]
+        if rough:
+            raise RuntimeError(f"matrix_free_boundary cannot be combined with a contact body with friction (mu = "
+                               f"{rough[0].friction:g}): the friction tangent has no matrix-free action")
         if axes and not periodic_iterative:
             raise RuntimeError("matrix_free cannot be combined with a periodic boundary: the action runs in the unwrapped numbering")
     host_setup = host_setup or os.environ.get("MIMI_HIP_HOST_SETUP", "") == "1"
@@ -798,14 +802,18 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         if self.fold_ is not None:
             self.fold_.Add(r, y, A, self.d_mass_, self.d_jac_)
 
-    def _post_time_advance(self, x, domain=True, boundaries=True):
+    def _post_time_advance(self, x, domain=True, boundaries=True, commit=True):
         """PostTimeAdvance at the solver's x of the chosen integrators (the boundary ones read the scalars of the latest
-        residual evaluation back: an explicit step leaves them to the next download)"""
+        residual evaluation back: an explicit step leaves them to the next download; a contact with friction first evaluates
+        and commits its state at x).  commit=False: the scalars only -- the explicit loop has committed on the device"""
         xp = self._expand(x)
         if domain:
             self.domain_.DomainPostTimeAdvance(xp)
         for c in self.boundaries_ if boundaries else ():
-            c.BoundaryPostTimeAdvance(xp)
+            if commit:
+                c.BoundaryPostTimeAdvance(xp)
+            else:
+                c._history()
 
     def _displacement(self, u):
         """the current displacement (u None) or the host vector u in this facade's numbering, as a device vector"""

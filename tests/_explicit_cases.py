@@ -204,9 +204,10 @@ E_CASE, E_STEPS, E_DT, E_V_SCALE, E_EVERY = "cube_p2", 200, 1e-3, 2.0, 20
 E_VISCOSITY, E_PENALTY, E_GAP, E_CV, E_PRESSURE = 0.05, 1.0e4, 0.002, 0.4, 60.0
 E_RUNS = {"neohook": ("neohook", None, "clamped"), "j2": ("j2", None, "clamped"), "j2_viscous": ("j2", E_VISCOSITY, "clamped"),
           "contact": ("neohook", None, "contact"), "pressure": ("neohook", None, "pressure"),
-          "constant_velocity": ("neohook", None, "cv")}
+          "constant_velocity": ("neohook", None, "cv"), "friction": ("neohook", None, "contact")}
+E_FRICTION = {"friction": 0.3}              # run -> mu on the plane of the contact run (the tangential penalty: E_PENALTY)
 E_DRIFT_MEASURED = {"neohook": 2.66e-15, "j2": 1.78e-15, "j2_viscous": 1.78e-15, "contact": 1.78e-15, "pressure": 2.66e-15,
-                    "constant_velocity": 5.33e-15}
+                    "constant_velocity": 5.33e-15, "friction": 4.44e-15}
 
 
 def e_plane(P):
@@ -225,7 +226,8 @@ def e_configure(run):
             bc.initial.dirichlet(0, c)
         if what == "contact":
             b = e_plane(oracle_patch(E_CASE))
-            bc.current.contact(1, RigidPlane(b["point"], b["normal"], E_PENALTY))
+            kw = dict(friction=E_FRICTION[run]) if run in E_FRICTION else {}
+            bc.current.contact(1, RigidPlane(b["point"], b["normal"], E_PENALTY, **kw))
         if what == "cv":
             bc.initial.constant_velocity(1, 2, E_CV)
         if what == "pressure":
@@ -243,7 +245,9 @@ def e_initial_velocity(P, run):
 @functools.lru_cache(maxsize=None)
 def e_reference(run):
     """the E* series of the float64 restatement at steps 0, E_EVERY, 2 E_EVERY, ..., its energies at the end, the largest
-    |E*_n - E*_0| over ALL steps (drift) and the largest |(KE + W_int - W_ext)_n - (KE + W_int - W_ext)_0| over all steps (band)"""
+    |E*_n - E*_0| over ALL steps (drift) and the largest |(KE + W_int - W_ext)_n - (KE + W_int - W_ext)_0| over all steps (band);
+    for a run of E_FRICTION also `counts`, (sticking points, slipping points, kink margin) of the force evaluation at the
+    sampled steps, and `rough`, the contact with its evaluation log"""
     import scipy.sparse as sp
     from oracle import harness as hz, ref_path as rp
     matname, viscosity, what = E_RUNS[run]
@@ -252,6 +256,12 @@ def e_reference(run):
     D.set_dt(E_DT)
     n = P.n_vdofs
     contact = rp.ContactOracle(P, P.dim - 1, 1, e_plane(P), penalty=E_PENALTY) if what == "contact" else None
+    rough = None
+    if run in E_FRICTION:
+        # domain + RoughContact (tests/_friction_stepping.py: long double, rounded to float64 on output), committed with the
+        # domain after every step and not at the start, as explicit_steps does
+        import _friction_stepping as fs
+        contact = rough = fs.RoughContact(P, P.dim - 1, 1, e_plane(P), E_PENALTY, E_FRICTION[run], E_PENALTY)
 
     face = None
     if what == "pressure":
@@ -279,8 +289,14 @@ def e_reference(run):
         pres, vbar = np.zeros(n, dtype=bool), np.zeros(n)
         top = P.boundary_nodes(P.dim - 1, 1) * P.dim + (P.dim - 1)
         pres[top], vbar[top] = True, E_CV
+    def commit(x):
+        D.domain_post_time_advance(x)
+        if rough is not None:
+            rough.post_time_advance(x)
+
     s = er.Stepper(lumped_mass(P, D), fixed, pres, vbar).start(np.zeros(n), e_initial_velocity(P, run), None, force, damping,
-                                                              commit=D.domain_post_time_advance)
+                                                              commit=commit)
+    counts = []
     e0 = s.energies(E_DT)
     series, worst, scale = [e0["E_star"]], 0.0, abs(e0["KE"])
     total = lambda en: en["KE"] + en["W_int"] - en["W_ext"]
@@ -293,8 +309,11 @@ def e_reference(run):
         scale = max(scale, abs(e["KE"]), abs(e["W_int"]), abs(e["W_ext"]), abs(e["W_damp"]))
         if k % E_EVERY == 0:
             series.append(e["E_star"])
+            if rough is not None:
+                # (stick, slip, kink margin) of the step's evaluation
+                counts.append((rough.n_stick, rough.n_slip, rough.log[-1]["kink"]))
     return types.SimpleNamespace(series=np.array(series), last=e, first=e0, drift=worst, scale=scale, eqps_max=float(D.eqps.max()),
-                                 x=s.x.copy(), band=band)
+                                 x=s.x.copy(), band=band, counts=counts, rough=rough)
 
 
 # ---- examples/explicit_impact.py: the float64 restatement on the example's input ---------------------------------------------

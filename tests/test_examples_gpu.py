@@ -31,6 +31,18 @@ def test_example_nl_contact():
     assert "contact force [0. 0.]" not in lines[-1]      # the curve has reached the body by then
 
 
+def test_example_nl_contact_with_friction():
+    """the same 25 steps with --friction 0.3: every step converges, and once the punch touches, points stick or slip"""
+    text = run("nl_contact.py", "--steps", "25", "--friction", "0.3")
+    lines = [l for l in text.splitlines() if l.startswith("step")]
+    assert len(lines) == 25 and all("converged True" in l for l in lines)
+    touching = [k for k, l in enumerate(lines) if "contact force [0. 0.]" not in l]
+    rubbing = [int(l.split(" stick ")[1].split()[0]) + int(l.split(" slip ")[1].split()[0]) for l in lines]
+    assert touching and "contact force [0. 0.]" not in lines[-1]
+    assert all(n == 0 for n in rubbing[:touching[0]])             # nothing rubs before the punch touches
+    assert any(n > 0 for n in rubbing[touching[0]:])              # (contact is new in its first step: no traction yet)
+
+
 def test_example_toy_problem():
     """viscous strip pulled through a channel of two rigid B-spline curves: the mesh file of the reference, viscosity,
     a prescribed edge, contact on two boundaries"""

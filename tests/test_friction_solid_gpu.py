@@ -1,7 +1,10 @@
 """Friction through NonlinearSolid: a 2-D block of 4 x 2 elements (degree 2) on a RigidPlane(friction=0.3), its top edge
 driven down and then sideways by constant_velocity (implicit route), and the contact run of tests/test_explicit_gpu.py
 with friction on the plane (explicit route).  The state is committed by _post_time_advance on step_time2 / advance_time2,
-never by fixed_point_solve2, and by the null form of the commit inside explicit_steps."""
+never by fixed_point_solve2, and by the null form of the commit inside explicit_steps.  The explicit run is held to the float64
+restatement of tests/_explicit_cases.py (run "friction": domain + RoughContact of tests/_friction_stepping.py, committed after
+every step).  Measured on an MI355X: KE, W_int at the end equal to the restatement's in all 13 digits printed (bar 1e-6 of
+the scale 5.96), the stick / slip counts at the ten samples the restatement's, (4, 60) ... (12, 52) ... (0, 0)."""
 import numpy as np
 import pytest
 
@@ -127,19 +130,31 @@ def test_explicit_route():
     """E* is conserved by the scheme whatever the force law: the bar is the one tests/test_explicit_gpu.py holds its
     contact run to, 8 x the drift of the float64 restatement of that run"""
     bar = 8.0 * ec.e_reference("contact").drift
+    ref = ec.e_reference("friction")
     nl = rough(MU)
     c = nl.contacts_[0]
-    series, rubbed, touched = [nl.explicit_energies()], 0, False
+    series, rubbed, touched, counts = [nl.explicit_energies()], 0, False, []
     for _ in range(ec.E_STEPS // ec.E_EVERY):
         nl.explicit_steps(ec.E_EVERY)
         series.append(nl.explicit_energies())
         rubbed += c.n_stick_ + c.n_slip_
+        counts.append((c.n_stick_, c.n_slip_))
         touched = touched or np.abs(c.last_force_).max() > 0.0
     star = np.array([e["E_star"] for e in series])
     drift = np.abs(star - star[0]).max()
     print(f"explicit with friction: E* drift {drift:.2e} (bar {bar:.2e}); points with a traction at the samples: {rubbed}")
     assert touched and rubbed > 0                                 # the plane was reached, and it rubbed
     assert drift <= bar
+    # the run is the one the restatement made (E* holds whatever the force law; the works and the branches do not): the
+    # line tests/test_explicit_gpu.py has for its contact run, against domain + RoughContact committed after every step,
+    # and the restatement's stick / slip counts at the sampled steps (their kink margins: tests/test_friction_stepping_cpu.py)
+    last = series[-1]
+    print("   at the end: " + " ".join(f"{k} {last[k]:.12e} (restated {float(ref.last[k]):.12e})" for k in ("KE", "W_int", "W_ext"))
+          + f"; scale {ref.scale:.3e}; stick / slip at the samples {counts}")
+    for k in ("KE", "W_int", "W_ext"):
+        assert abs(last[k] - float(ref.last[k])) <= 1e-6 * ref.scale, k
+    assert all(kink >= 1e-9 for _, _, kink in ref.counts)
+    assert counts == [(a, b) for a, b, _ in ref.counts]
     # the same run without friction copies as often to the host, and differs
     plain = rough(None)
     plain.explicit_steps(ec.E_STEPS)

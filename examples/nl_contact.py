@@ -4,11 +4,15 @@ cubic Bezier punch that first descends, then slides sideways) on mimi_amd, print
 The punch is handed over as any object with `degrees`, `knot_vectors`, `control_points` (a splinepy spline qualifies);
 a SimpleNamespace is enough.
 
-    python examples/nl_contact.py [--steps 30] [--friction MU]
+    python examples/nl_contact.py [--steps 30] [--friction MU] [--consistent-tangent]
 
 --friction MU puts Coulomb friction on the punch (the reference has none): the tangential penalty is the scene's
 coefficient, and the punch's displacement of the step is handed over as step_displacement, so that only the relative slip
 of the surface against the punch loads the block.  The default, 0, prints what the frictionless run prints.
+
+--consistent-tangent solves the Newton steps matrix-free (GMRES with the Kronecker preconditioner, the domain and contact
+tangents as actions) and lets the contact action carry the derivative of the nodal pressure, which the reference's Jacobian
+freezes: rc.set_int("contact_consistent_tangent", 1).  Not with --friction.
 """
 import argparse
 import os
@@ -48,7 +52,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--friction", type=float, default=0.0, metavar="MU", help="friction coefficient of the punch (default 0)")
+    ap.add_argument("--consistent-tangent", action="store_true",
+                    help="matrix-free Newton solves with the consistent contact tangent (not with --friction)")
     args = ap.parse_args()
+    if args.consistent_tangent and args.friction > 0.0:
+        ap.error("--consistent-tangent cannot be combined with --friction: the friction tangent is assembled only")
 
     block, punch = make_block(), make_punch()
     rigid_scene = mimi.NearestDistanceToSplines()
@@ -60,6 +68,12 @@ def main():
     conditions.initial.dirichlet(0, 0).dirichlet(0, 1)       # bottom edge clamped
     conditions.current.contact(1, rigid_scene)               # top edge may touch the punch
     block.boundary_condition = conditions
+    if args.consistent_tangent:
+        flags = mimi.RuntimeCommunication()
+        for key in ("use_iterative_solver", "use_kronecker_preconditioner", "matrix_free", "matrix_free_boundary",
+                    "contact_consistent_tangent"):
+            flags.set_int(key, 1)
+        block.runtime_communication = flags
     block.setup(4)
     block.configure_newton("nonlinear_solid", 1e-10, 1e-8, 100, False)
     block.time_step_size = 0.001

@@ -406,9 +406,25 @@ int mimi_hip_contact_add_residual_from_nodal(mimi_hip_contact_t h, const double*
  * incidences (no atomics: equal inputs give equal bytes); refused before the first linearize.  u, x, y host or device. */
 int mimi_hip_contact_linearize(mimi_hip_contact_t h, const double* u);
 int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const double* x, double* y);
-/* what: 0 bytes of the record (n_faces n_quad (1 + (dim - 1) dim) doubles + n_faces flags; 0 before the first linearize),
- * 1 whether the face tangent blocks of an assembly are allocated.  -1: bad argument. */
+/* what: 0 bytes of the record (n_faces n_quad (1 + (dim - 1) dim) doubles + n_faces flags; 0 before the first linearize; a
+ * consistent record: n_faces n_quad (2 + dim + (dim - 1) dim) doubles + 2 n_marked doubles + n_faces flags),
+ * 1 whether the face tangent blocks of an assembly are allocated, 2 whether the current record is a consistent one
+ * (mimi_hip_contact_set_consistent_tangent).  -1: bad argument. */
 int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what);
+
+/* The consistent contact tangent as an action (the reference has none: its Jacobian freezes the nodal pressure,
+ * mortar_contact.cpp:281-294, so Newton is a fixed-point iteration in p_i = eps G_i / A_i).  on != 0: the NEXT linearize
+ * records, on top of the frozen record, per face point the gap g_q and chi_q nu_q (chi_q = [g_q != 0], nu_q the body's unit
+ * normal at the closest point), per marked node copies of A_i and p_i, and the penalty; apply_tangent (and a Krylov operator
+ * built on the handle) then adds
+ *   -sum_q w dp_q N_a m_i,  dp_q = sum_i N_i dp_i,  dp_i = (eps dG_i - p_i dA_i) / A_i,
+ *   dA_i = sum_q w (n.dm) N_i,  dG_i = sum_q w ((n.dm) g_q + |m| chi_q nu_q.dx_q) N_i,  dx_q = sum_b N_b x_b
+ * to the frozen action: the exact derivative of the residual with the active set frozen.  The term couples nodes up to
+ * 2 p basis functions apart, outside the CSR pattern: it cannot be assembled, add_residual_and_grad is unchanged.  The
+ * nodal sums run over the handle's own faces.  Takes effect at the next linearize and never touches an existing record;
+ * on == 0 (the default): launches and bytes of every entry are those of a handle that never saw this call.  Refused with
+ * friction (mu > 0). */
+int mimi_hip_contact_set_consistent_tangent(mimi_hip_contact_t h, int on);
 
 /* Coulomb friction (the reference has none; model and layout: DESIGN.md "Coulomb friction").  At a face point with
  * p_N = -p_h > 0 that was in contact at the last commit: a = xi + x_q - xbar - d, s = (I - n n^T) a on the deformable

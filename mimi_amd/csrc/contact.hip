@@ -19,7 +19,8 @@
 // incidences, the pair positions, the fixed-order sums and the row gather are face_common.hpp's, shared with pressure.hip.
 // The matrix-free action of the frozen-pressure tangent (mimi_hip_contact_linearize / _apply_tangent, and the Krylov
 // solvers' boundary terms through apply_seam.hpp) is kernels_face_action.hpp, shared with pressure.hip as well: it builds
-// no face tangent block.
+// no face tangent block.  The consistent tangent -- the frozen one plus the derivative of the nodal pressure, which leaves the
+// CSR pattern -- exists as such an action only (mimi_hip_contact_set_consistent_tangent, kernels_face_consistent.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +31,7 @@
 #include "common.hpp"
 #include "face_common.hpp"
 #include "kernels_face_action.hpp"
+#include "kernels_face_consistent.hpp"
 #include "kernels_face_friction.hpp"
 #include "materials.hpp"
 #include "spline_body.hpp"
@@ -104,6 +106,42 @@ MH_DEV void nearest_body(const ContactArgs& p, const double* xq, double& true_g,
     distance = sqrt(dist);
   }
 }
+
+// nearest_body with the body's unit normal at the closest point, the gradient of the gap (kernels_face_consistent.hpp)
+template<int DIM>
+MH_DEV void nearest_body_normal(const ContactArgs& p, const double* xq, double& true_g, double& distance, double* nu) {
+  if (p.body_kind == MIMI_HIP_BODY_SPLINE) {
+    double n[3];
+    sb_nearest(p.spline, xq, true_g, distance, n);
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) nu[i] = n[i];
+    return;
+  }
+  nearest_body<DIM>(p, xq, true_g, distance);
+  if (p.body_kind == MIMI_HIP_BODY_SPHERE) {
+    double nrm = 0;
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) {
+      nu[i] = xq[i] - p.body[i];
+      nrm += nu[i] * nu[i];
+    }
+    nrm = sqrt(nrm);
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) nu[i] /= nrm;
+  } else {
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) nu[i] = p.body[3 + i];
+  }
+}
+
+// the Body of contact_consistent_record_kernel
+struct ContactBodyQuery {
+  ContactArgs a;
+  template<int DIM>
+  MH_DEV void nearest(const double* xq, double& true_g, double& distance, double* nu) const {
+    nearest_body_normal<DIM>(a, xq, true_g, distance, nu);
+  }
+};
 
 // J = x_e^T dN_dxi (integrator_utils.cpp:101-105); returns |J| (DenseMatrix::Weight) and the
 // NON-normalised normal m (ComputeUnitNormal before the division, integrator_utils.hpp:216-251)
@@ -482,7 +520,8 @@ struct mimi_hip_contact_s : FaceAssembly {
   DeviceBuffer<double> pt_area, pt_gap, pt_scal;   // per quadrature point: the dense stores of pass 1
   SplineBodyDev spline{};
   DeviceBuffer<double> sb_knots[2], sb_ctrl, sb_sample_xi, sb_sample_x;
-  BoundaryAction action;   // mimi_hip_contact_linearize / _apply_tangent (kernels_face_action.hpp)
+  ContactAction action;    // mimi_hip_contact_linearize / _apply_tangent (kernels_face_action.hpp, kernels_face_consistent.hpp)
+  bool consistent_tangent = false;   // what the NEXT linearize records (mimi_hip_contact_set_consistent_tangent)
   // Coulomb friction (kernels_face_friction.hpp); mu == 0: none of it is allocated or launched
   double mu = 0.0, eps_t = 0.0, body_inc[3] = {0.0, 0.0, 0.0};
   DeviceBuffer<double> fr_xi, fr_xbar, fr_xi_t, fr_xbar_t, fr_face, fr_scalars;
@@ -661,8 +700,9 @@ static void contact_pass1(mimi_hip_contact_s* h, const double* u_dev) {
 }
 
 // The snapshot of the frozen-pressure tangent at u: pass 1 and the pressure with the handle's current body and penalty
-// (the history scalars of the last Add* call are left alone), then the record of kernels_face_action.hpp.  It is the
-// analytic tangent whatever the tangent mode says.
+// (the history scalars of the last Add* call are left alone), then the record of kernels_face_action.hpp -- with the
+// consistent part of kernels_face_consistent.hpp when the handle is set to it.  It is the analytic tangent whatever the
+// tangent mode says.
 static void contact_linearize(mimi_hip_contact_s* h, const double* u_dev) {
   const ContactArgs a = contact_args(h, u_dev);
   const int threads = 128;
@@ -674,7 +714,7 @@ static void contact_linearize(mimi_hip_contact_s* h, const double* u_dev) {
                      h->n_fnodes, h->n_q, h->n_dof, h->adj_ptr.ptr, h->adj.ptr, h->pt_area.ptr, h->pt_gap.ptr, h->area.ptr, h->gap.ptr);
   hipLaunchKernelGGL(contact_pressure_kernel, dim3((unsigned)((h->n_fnodes + threads - 1) / threads)), dim3(threads), 0, h->stream,
                      h->n_fnodes, h->area.ptr, h->gap.ptr, h->penalty, h->pressure.ptr);
-  h->action.linearize(*h, u_dev, h->pressure.ptr, 0.0, -1.0);
+  h->action.linearize(*h, u_dev, h->area.ptr, h->pressure.ptr, h->penalty, h->consistent_tangent, ContactBodyQuery{a});
 }
 
 // pressure from the nodal area / gap (mortar_contact.cpp:195-261), then pass 2: face residual vectors (+ tangent blocks)
@@ -806,7 +846,18 @@ int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const do
   });
 }
 
-int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what) { return boundary_action_info(h, what); }
+int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what) {
+  if (h && what == 2) return h->action.linearized && h->action.consistent ? 1 : 0;
+  return boundary_action_info(h, what);
+}
+
+int mimi_hip_contact_set_consistent_tangent(mimi_hip_contact_t h, int on) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    if (on) refuse_friction(h, "the consistent tangent");
+    h->consistent_tangent = on != 0;
+  });
+}
 
 int mimi_hip_contact_gap_norm(mimi_hip_contact_t h, const double* u, double* out) {
   return guarded([&] {

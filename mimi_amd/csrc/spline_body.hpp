@@ -276,10 +276,10 @@ SB_HD void sb_closest_point(const SplineBodyDev& b, const double* xq, double* xi
 }
 
 // NearestDistance + Results::ComputeNormal<true> + NormalGap (nearest_distance.hpp:139-193) for the spline body
-SB_HD void sb_nearest(const SplineBodyDev& b, const double* xq, double& true_g, double& distance) {
+// (n[3]: the unit normal at the closest point, the gradient of the gap)
+SB_HD void sb_nearest(const SplineBodyDev& b, const double* xq, double& true_g, double& distance, double* n) {
   double xi[2], S[3], S1[6];
   sb_closest_point(b, xq, xi, S, S1);
-  double n[3];
   if (b.dim == 2) {
     const double d0 = S1[0], d1 = S1[1];
     const double inv = 1.0 / sqrt(d0 * d0 + d1 * d1);
@@ -301,6 +301,11 @@ SB_HD void sb_nearest(const SplineBodyDev& b, const double* xq, double& true_g, 
   }
   true_g = g;
   distance = sqrt(d2);
+}
+
+SB_HD void sb_nearest(const SplineBodyDev& b, const double* xq, double& true_g, double& distance) {
+  double n[3];
+  sb_nearest(b, xq, true_g, distance, n);
 }
 
 // ---- host only: what NearestDistanceToSplines::AddSpline / PlantKdTree (nearest_distance.hpp:223-255) prepare -----------

@@ -575,6 +575,7 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
         self.last_pressure_ = 0.0
         self.last_force_ = np.zeros(patch.dim)
         self.friction_, self._has_increment = 0.0, False
+        self.consistent_tangent_ = False
         self.last_friction_force_ = np.zeros(patch.dim)
         self.last_friction_traction_ = 0.0
         self.n_stick_ = self.n_slip_ = 0
@@ -666,6 +667,24 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
     def ApplyTangent(self, x, y, factor=1.0):
         self._refuse_friction("the matrix-free tangent action (ApplyTangent)")
         return super().ApplyTangent(x, y, factor)
+
+    def SetConsistentTangent(self, on=True):
+        """The next Linearize records the consistent tangent (include/mimi_hip.h: mimi_hip_contact_set_consistent_tangent):
+        ApplyTangent then adds the derivative of the nodal pressure p_i = eps G_i / A_i to the frozen-pressure action.  The
+        term reaches past the CSR pattern, so it exists as an action only; AddBoundaryResidualAndGrad is unchanged.  An
+        existing record is not touched.  On a handle built from an element box the nodal sums are those of its own faces,
+        so the handles of a ShardedContact are refused."""
+        if on and getattr(self, "sharded_", False):
+            raise RuntimeError("the consistent tangent on a ShardedContact is not supported: the nodal sums of a handle run "
+                               "over its own faces")
+        if on:
+            self._refuse_friction("the consistent tangent")
+        check(_capi.lib().mimi_hip_contact_set_consistent_tangent(self._handle(), 1 if on else 0))
+        self.consistent_tangent_ = bool(on)
+
+    def HoldsConsistentRecord(self):
+        """whether the record of the last Linearize is a consistent one"""
+        return bool(self._action_fn("action_info")(self._handle(), 2))
 
     def UpdateBody(self, spline=False, penalty=-1.0):
         """the rigid body moved (spline=True: re-read it from nearest_distance_coeff_) and / or the penalty changed"""

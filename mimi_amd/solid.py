@@ -346,6 +346,7 @@ class Route(typing.NamedTuple):
     boundary_actions: bool = False      # ... with the contact and pressure tangents as actions beside it
     periodic_iterative: bool = False    # a periodic pair on the Kronecker, matrix-free and consistent-mass routes
     host_setup: bool = False            # mass, damping and right-hand side in numpy on the host
+    consistent_contact: bool = False    # the contact actions carry the derivative of the nodal pressure as well
 
 
 def resolve_route(rc, bc, axes):
@@ -365,6 +366,14 @@ def resolve_route(rc, bc, axes):
     iterative, kronecker = flag("use_iterative_solver"), flag("use_kronecker_preconditioner")
     matrix_free, boundary_actions = flag("matrix_free"), flag("matrix_free_boundary")
     host_setup = flag("host_setup")
+    consistent_contact = flag("contact_consistent_tangent")
+    if consistent_contact and explicit:
+        raise RuntimeError("contact_consistent_tangent cannot be combined with explicit_dynamics: an explicit step has no "
+                           "tangent for it to act on -- unset one of the two")
+    if consistent_contact and not boundary_actions:
+        raise RuntimeError("contact_consistent_tangent needs matrix_free_boundary: the derivative of the nodal pressure "
+                           "couples nodes up to 2 p basis functions apart, which leaves the CSR pattern -- it exists as a "
+                           "matrix-free action only")
     if explicit:
         for other, on in (("matrix_free", matrix_free), ("use_iterative_solver", iterative)):
             if on:
@@ -399,7 +408,8 @@ def resolve_route(rc, bc, axes):
     host_setup = host_setup or os.environ.get("MIMI_HIP_HOST_SETUP", "") == "1"
     if explicit and host_setup:
         raise RuntimeError("explicit_dynamics cannot be combined with the host set-up: the lumped mass is assembled on the device")
-    return Route(explicit, consistent, iterative, iterative and kronecker, matrix_free, boundary_actions, periodic_iterative, host_setup)
+    return Route(explicit, consistent, iterative, iterative and kronecker, matrix_free, boundary_actions, periodic_iterative, host_setup,
+                 consistent_contact)
 
 
 class NonlinearSolid(Solid, ExplicitDynamics):
@@ -626,6 +636,8 @@ class NonlinearSolid(Solid, ExplicitDynamics):
             axis, side = self._faces[bid + 1]
             self.contacts_.append(MortarContact(body, "contact", self.pattern_u_, patch, axis, side, device=self.device,
                                                 quadrature_order=rc.get_int("contact_quadrature_order", -1)).Prepare())
+            if self.route_.consistent_contact:
+                self.contacts_[-1].SetConsistentTangent(True)
         # follower pressure (the reference stores BCMarker::pressure_ and never applies it): one device integrator per bid
         self.pressures_, self._pressure_by_bid = [], {}
         for bid, value in bc.initial.pressure_.items():

@@ -4,7 +4,7 @@ cubic Bezier punch that first descends, then slides sideways) on mimi_amd, print
 The punch is handed over as any object with `degrees`, `knot_vectors`, `control_points` (a splinepy spline qualifies);
 a SimpleNamespace is enough.
 
-    python examples/nl_contact.py [--steps 30] [--friction MU] [--consistent-tangent]
+    python examples/nl_contact.py [--steps 30] [--friction MU] [--matrix-free] [--consistent-tangent]
 
 --friction MU puts Coulomb friction on the punch (the reference has none): the tangential penalty is the scene's
 coefficient, and the punch's displacement of the step is handed over as step_displacement, so that only the relative slip
@@ -12,7 +12,11 @@ of the surface against the punch loads the block.  The default, 0, prints what t
 
 --consistent-tangent solves the Newton steps matrix-free (GMRES with the Kronecker preconditioner, the domain and contact
 tangents as actions) and lets the contact action carry the derivative of the nodal pressure, which the reference's Jacobian
-freezes: rc.set_int("contact_consistent_tangent", 1).  Not with --friction.
+freezes: rc.set_int("contact_consistent_tangent", 1).  With --friction it needs --matrix-free.
+
+--matrix-free solves the Newton steps matrix-free with the frozen-pressure contact action; with --friction the friction
+tangent joins that action, rc.set_int("friction_matrix_free", 1), and --consistent-tangent may stand beside it: in slip
+the traction is mu p_N s / |s|, so the consistent action then carries the pressure's derivative of the friction residual too.
 """
 import argparse
 import os
@@ -53,10 +57,13 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--friction", type=float, default=0.0, metavar="MU", help="friction coefficient of the punch (default 0)")
     ap.add_argument("--consistent-tangent", action="store_true",
-                    help="matrix-free Newton solves with the consistent contact tangent (not with --friction)")
+                    help="matrix-free Newton solves with the consistent contact tangent (with --friction: needs --matrix-free)")
+    ap.add_argument("--matrix-free", action="store_true",
+                    help="matrix-free Newton solves; with --friction the friction tangent as a part of the contact action")
     args = ap.parse_args()
-    if args.consistent_tangent and args.friction > 0.0:
-        ap.error("--consistent-tangent cannot be combined with --friction: the friction tangent is assembled only")
+    if args.consistent_tangent and args.friction > 0.0 and not args.matrix_free:
+        ap.error("--consistent-tangent cannot be combined with --friction: the friction tangent is assembled only "
+                 "(--matrix-free makes it an action)")
 
     block, punch = make_block(), make_punch()
     rigid_scene = mimi.NearestDistanceToSplines()
@@ -68,11 +75,14 @@ def main():
     conditions.initial.dirichlet(0, 0).dirichlet(0, 1)       # bottom edge clamped
     conditions.current.contact(1, rigid_scene)               # top edge may touch the punch
     block.boundary_condition = conditions
-    if args.consistent_tangent:
+    if args.consistent_tangent or args.matrix_free:
         flags = mimi.RuntimeCommunication()
-        for key in ("use_iterative_solver", "use_kronecker_preconditioner", "matrix_free", "matrix_free_boundary",
-                    "contact_consistent_tangent"):
+        for key in ("use_iterative_solver", "use_kronecker_preconditioner", "matrix_free", "matrix_free_boundary"):
             flags.set_int(key, 1)
+        if args.consistent_tangent:
+            flags.set_int("contact_consistent_tangent", 1)
+        if args.matrix_free and args.friction > 0.0:
+            flags.set_int("friction_matrix_free", 1)
         block.runtime_communication = flags
     block.setup(4)
     block.configure_newton("nonlinear_solid", 1e-10, 1e-8, 100, False)

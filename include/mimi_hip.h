@@ -409,7 +409,8 @@ int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const do
 /* what: 0 bytes of the record (n_faces n_quad (1 + (dim - 1) dim) doubles + n_faces flags; 0 before the first linearize; a
  * consistent record: n_faces n_quad (2 + dim + (dim - 1) dim) doubles + 2 n_marked doubles + n_faces flags),
  * 1 whether the face tangent blocks of an assembly are allocated, 2 whether the current record is a consistent one
- * (mimi_hip_contact_set_consistent_tangent).  -1: bad argument. */
+ * (mimi_hip_contact_set_consistent_tangent), 3 whether it carries friction (mimi_hip_contact_set_friction_action; what 0
+ * then includes n_faces n_quad (8 (dim + 1) + 1) + 8 bytes more).  -1: bad argument. */
 int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what);
 
 /* The consistent contact tangent as an action (the reference has none: its Jacobian freezes the nodal pressure,
@@ -423,7 +424,7 @@ int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what);
  * 2 p basis functions apart, outside the CSR pattern: it cannot be assembled, add_residual_and_grad is unchanged.  The
  * nodal sums run over the handle's own faces.  Takes effect at the next linearize and never touches an existing record;
  * on == 0 (the default): launches and bytes of every entry are those of a handle that never saw this call.  Refused with
- * friction (mu > 0). */
+ * friction (mu > 0) unless mimi_hip_contact_set_friction_action is on. */
 int mimi_hip_contact_set_consistent_tangent(mimi_hip_contact_t h, int on);
 
 /* Coulomb friction (the reference has none; model and layout: DESIGN.md "Coulomb friction").  At a face point with
@@ -434,7 +435,8 @@ int mimi_hip_contact_set_consistent_tangent(mimi_hip_contact_t h, int on);
  * commits.  mu = 0 (the default): launches and bytes of every other entry are those of a handle without friction.
  *   set_friction        mu >= 0, eps_t > 0 (with mu > 0); the first mu > 0 allocates the state (xi = 0, no point in contact).
  *                       Refused in the reference-FD tangent mode; with mu > 0 set_tangent_mode(REFERENCE_FD), linearize and
- *                       apply_tangent (and a Krylov operator built on the handle) are refused.
+ *                       apply_tangent (and a Krylov operator built on the handle) are refused -- the last three only until
+ *                       mimi_hip_contact_set_friction_action(h, 1), below.
  *   set_body_increment  d[dim]: the rigid body's displacement over the current step (NULL: zero)
  *   post_time_advance   u != NULL: an evaluation at u (pass 1, pressure, pass 2 without the gather: the history scalars are
  *                       those of u), then commit.  u == NULL: commit the trial state of the latest evaluation on the
@@ -450,6 +452,23 @@ int mimi_hip_contact_post_time_advance(mimi_hip_contact_t h, const double* u);
 int mimi_hip_contact_reset_friction(mimi_hip_contact_t h);
 int mimi_hip_contact_friction_history(mimi_hip_contact_t h, double* out6);
 int mimi_hip_contact_friction_state(mimi_hip_contact_t h, double* xi, double* xbar, unsigned char* c);
+
+/* Friction on the matrix-free route (csrc/kernels_face_friction_action.hpp).  on == 0 (the default): every refusal above
+ * stands, no buffer is allocated and no launch changes.  on != 0: linearize, apply_tangent, a Krylov operator built on the
+ * handle and set_consistent_tangent accept a handle with mu > 0; the reference-FD tangent mode stays refused.  A linearize
+ * with mu > 0 then records, on top of the frozen (and, when set, the consistent) record, per face point
+ * a_q = xi + x_q - xbar - d (dim doubles), coef_q (eps_t in stick, mu p_N / |s| in slip, 0 where the point carries no
+ * traction) and the branch (one byte), and mu: n_faces n_quad (8 (dim + 1) + 1) + 8 bytes.  It reads the COMMITTED state, d,
+ * mu and eps_t of that moment and the nodal pressure at u; it writes neither the trial state nor the history scalars.
+ * The record is a snapshot: set_friction, set_body_increment, post_time_advance, reset_friction, update_body and any
+ * evaluation leave it alone, only the next linearize replaces it.  apply_tangent then adds, with tau the traction,
+ *   sum_q w N_a (tau_i nD + |m| dtau_i),  nD = n.dm,  dn = (dm - n nD) / |m|,  ds = (I - n n^T) dx_q - dn (n.a) - n (dn.a),
+ *   dtau = coef (ds - [slip] sh (sh.ds))     (the assembled friction tangent applied to x)
+ * and, on a consistent record, -mu dp_q sh to dtau at slipping points: there tau = mu p_N sh, so the frozen-pressure tangent
+ * drops a first-order term of the friction residual itself.  One face kernel takes the place of the frictionless one:
+ * friction adds no launch to a product.  With mu == 0 at the linearize the record and the launches are the frictionless
+ * ones. */
+int mimi_hip_contact_set_friction_action(mimi_hip_contact_t h, int on);
 
 /* ---- follower-pressure boundary integrator (integrators::FollowerPressure) ---------------------------------------
  * The reference stores BCMarker::Pressure(bid, value) (utils/boundary_conditions.cpp:43-50) and never applies it; here it

@@ -110,7 +110,7 @@ EXPORTS = [
     "mimi_hip_linear_set_operator_fold", "mimi_hip_linear_operator_mult",
     "mimi_hip_contact_set_friction", "mimi_hip_contact_set_body_increment", "mimi_hip_contact_post_time_advance",
     "mimi_hip_contact_reset_friction", "mimi_hip_contact_friction_history", "mimi_hip_contact_friction_state",
-    "mimi_hip_contact_set_consistent_tangent",
+    "mimi_hip_contact_set_consistent_tangent", "mimi_hip_contact_set_friction_action",
 ]
 
 
@@ -278,6 +278,7 @@ def lib():
         getattr(L, f"mimi_hip_{kind}_action_info").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"mimi_hip_{kind}_action_info").restype = C.c_int64
     L.mimi_hip_contact_set_consistent_tangent.argtypes = [C.c_void_p, C.c_int]
+    L.mimi_hip_contact_set_friction_action.argtypes = [C.c_void_p, C.c_int]
     L.mimi_hip_linear_add_boundary_operator.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
     L.mimi_hip_linear_set_operator_fold.argtypes = [C.c_void_p, C.c_void_p]
     L.mimi_hip_linear_operator_mult.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]

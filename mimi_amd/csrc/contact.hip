@@ -21,6 +21,8 @@
 // solvers' boundary terms through apply_seam.hpp) is kernels_face_action.hpp, shared with pressure.hip as well: it builds
 // no face tangent block.  The consistent tangent -- the frozen one plus the derivative of the nodal pressure, which leaves the
 // CSR pattern -- exists as such an action only (mimi_hip_contact_set_consistent_tangent, kernels_face_consistent.hpp).
+// Friction joins either action when the handle is set to it (mimi_hip_contact_set_friction_action,
+// kernels_face_friction_action.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -33,6 +35,7 @@
 #include "kernels_face_action.hpp"
 #include "kernels_face_consistent.hpp"
 #include "kernels_face_friction.hpp"
+#include "kernels_face_friction_action.hpp"
 #include "materials.hpp"
 #include "spline_body.hpp"
 
@@ -520,8 +523,10 @@ struct mimi_hip_contact_s : FaceAssembly {
   DeviceBuffer<double> pt_area, pt_gap, pt_scal;   // per quadrature point: the dense stores of pass 1
   SplineBodyDev spline{};
   DeviceBuffer<double> sb_knots[2], sb_ctrl, sb_sample_xi, sb_sample_x;
-  ContactAction action;    // mimi_hip_contact_linearize / _apply_tangent (kernels_face_action.hpp, kernels_face_consistent.hpp)
+  // mimi_hip_contact_linearize / _apply_tangent (kernels_face_action.hpp, kernels_face_consistent.hpp, kernels_face_friction_action.hpp)
+  FrictionContactAction action;
   bool consistent_tangent = false;   // what the NEXT linearize records (mimi_hip_contact_set_consistent_tangent)
+  bool friction_action = false;      // friction has a matrix-free action (mimi_hip_contact_set_friction_action)
   // Coulomb friction (kernels_face_friction.hpp); mu == 0: none of it is allocated or launched
   double mu = 0.0, eps_t = 0.0, body_inc[3] = {0.0, 0.0, 0.0};
   DeviceBuffer<double> fr_xi, fr_xbar, fr_xi_t, fr_xbar_t, fr_face, fr_scalars;
@@ -584,8 +589,9 @@ static void friction_commit(mimi_hip_contact_s* h) {
   MH_HIP(hipGetLastError());
 }
 
-static void refuse_friction(const mimi_hip_contact_s* h, const char* what) {
-  if (h->mu > 0.0)
+// (lifted: what mimi_hip_contact_set_friction_action(h, 1) makes available)
+static void refuse_friction(const mimi_hip_contact_s* h, const char* what, bool lifted = false) {
+  if (h->mu > 0.0 && !lifted)
     fail("%s is not available on a contact handle with friction (mu = %g): the friction tangent is assembled only "
          "(set_friction(h, 0, 0) removes it)", what, h->mu);
 }
@@ -595,7 +601,7 @@ namespace mimi_hip {
 int64_t operator_size(const mimi_hip_contact_s* h) { return h->n_vdofs; }
 int operator_device(const mimi_hip_contact_s* h) { return h->device; }
 void operator_begin_solve(mimi_hip_contact_s* h, hipStream_t solver_stream) {
-  refuse_friction(h, "the matrix-free tangent action");
+  refuse_friction(h, "the matrix-free tangent action", h->friction_action);
   h->action.require("contact");
   MH_HIP(hipSetDevice(h->device));
   h->action.begin(*h, solver_stream);
@@ -701,8 +707,9 @@ static void contact_pass1(mimi_hip_contact_s* h, const double* u_dev) {
 
 // The snapshot of the frozen-pressure tangent at u: pass 1 and the pressure with the handle's current body and penalty
 // (the history scalars of the last Add* call are left alone), then the record of kernels_face_action.hpp -- with the
-// consistent part of kernels_face_consistent.hpp when the handle is set to it.  It is the analytic tangent whatever the
-// tangent mode says.
+// consistent part of kernels_face_consistent.hpp when the handle is set to it, and with the friction part of
+// kernels_face_friction_action.hpp when the friction action is on and mu > 0: the committed friction state is read, no trial
+// state is written.  It is the analytic tangent whatever the tangent mode says.
 static void contact_linearize(mimi_hip_contact_s* h, const double* u_dev) {
   const ContactArgs a = contact_args(h, u_dev);
   const int threads = 128;
@@ -714,7 +721,10 @@ static void contact_linearize(mimi_hip_contact_s* h, const double* u_dev) {
                      h->n_fnodes, h->n_q, h->n_dof, h->adj_ptr.ptr, h->adj.ptr, h->pt_area.ptr, h->pt_gap.ptr, h->area.ptr, h->gap.ptr);
   hipLaunchKernelGGL(contact_pressure_kernel, dim3((unsigned)((h->n_fnodes + threads - 1) / threads)), dim3(threads), 0, h->stream,
                      h->n_fnodes, h->area.ptr, h->gap.ptr, h->penalty, h->pressure.ptr);
-  h->action.linearize(*h, u_dev, h->area.ptr, h->pressure.ptr, h->penalty, h->consistent_tangent, ContactBodyQuery{a});
+  const bool rough = h->friction_action && h->mu > 0.0;
+  const FrictionArgs fa = rough ? friction_args(h, a) : FrictionArgs{};
+  h->action.linearize(*h, u_dev, h->area.ptr, h->pressure.ptr, h->penalty, h->consistent_tangent, ContactBodyQuery{a},
+                      rough ? &fa : nullptr);
 }
 
 // pressure from the nodal area / gap (mortar_contact.cpp:195-261), then pass 2: face residual vectors (+ tangent blocks)
@@ -834,28 +844,36 @@ int mimi_hip_contact_add_residual_and_grad(mimi_hip_contact_t h, const double* u
 int mimi_hip_contact_linearize(mimi_hip_contact_t h, const double* u) {
   return guarded([&] {
     if (!h) fail("null handle");
-    refuse_friction(h, "mimi_hip_contact_linearize");
+    refuse_friction(h, "mimi_hip_contact_linearize", h->friction_action);
     h->run(u, nullptr, nullptr, false, [&](const double* u_dev, double*, double*) { contact_linearize(h, u_dev); });
   });
 }
 
 int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const double* x, double* y) {
   return guarded([&] {
-    if (h) refuse_friction(h, "mimi_hip_contact_apply_tangent");
+    if (h) refuse_friction(h, "mimi_hip_contact_apply_tangent", h->friction_action);
     boundary_apply_entry(h, "contact", factor, x, y);
   });
 }
 
 int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what) {
   if (h && what == 2) return h->action.linearized && h->action.consistent ? 1 : 0;
+  if (h && what == 3) return h->action.linearized && h->action.friction ? 1 : 0;
   return boundary_action_info(h, what);
 }
 
 int mimi_hip_contact_set_consistent_tangent(mimi_hip_contact_t h, int on) {
   return guarded([&] {
     if (!h) fail("null handle");
-    if (on) refuse_friction(h, "the consistent tangent");
+    if (on) refuse_friction(h, "the consistent tangent", h->friction_action);
     h->consistent_tangent = on != 0;
+  });
+}
+
+int mimi_hip_contact_set_friction_action(mimi_hip_contact_t h, int on) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    h->friction_action = on != 0;
   });
 }
 

@@ -329,12 +329,8 @@ struct ContactAction : BoundaryAction {
     dp.resize((size_t)h.n_fnodes);
   }
 
-  // y += factor K x over the recorded active faces, K the frozen or the consistent tangent as the record says
-  void add(FaceAssembly& h, double factor, const double* x, double* y, hipStream_t s) {
-    if (!consistent) {
-      BoundaryAction::add(h, factor, x, y, s);
-      return;
-    }
+  // dp [n_marked] of the direction x: the face rates and the nodal sums (a consistent record)
+  void nodal_rates(FaceAssembly& h, const double* x, hipStream_t s) {
     const dim3 grid((unsigned)((h.n_faces + 3) / 4));
     const ConsistentRatesArgs r{h.n_faces, h.n_dof,   h.n_q,      h.dofs.ptr, h.N.ptr, h.dN.ptr,    h.weight.ptr,
                                 tang.ptr,  gq.ptr,    chinu.ptr,  active.ptr, x,       face_dA.ptr, face_dG.ptr};
@@ -342,6 +338,16 @@ struct ContactAction : BoundaryAction {
     else launch(contact_consistent_rates_kernel<3>, grid, dim3(256), 0, s, r);
     launch(contact_consistent_nodal_kernel, dim3((unsigned)((h.n_fnodes + 255) / 256)), dim3(256), 0, s, h.n_fnodes, h.n_dof,
            h.adj_ptr.ptr, h.adj.ptr, active.ptr, face_dA.ptr, face_dG.ptr, area.ptr, pressure.ptr, penalty, dp.ptr);
+  }
+
+  // y += factor K x over the recorded active faces, K the frozen or the consistent tangent as the record says
+  void add(FaceAssembly& h, double factor, const double* x, double* y, hipStream_t s) {
+    if (!consistent) {
+      BoundaryAction::add(h, factor, x, y, s);
+      return;
+    }
+    nodal_rates(h, x, s);
+    const dim3 grid((unsigned)((h.n_faces + 3) / 4));
     const ConsistentActionArgs a{h.n_faces, h.n_dof,  h.n_q,      h.dofs.ptr, h.local.ptr, h.N.ptr, h.dN.ptr,   h.weight.ptr,
                                  coef.ptr,  tang.ptr, active.ptr, dp.ptr,     factor,      x,       face_y.ptr};
     if (h.dim == 2) launch(contact_consistent_action_kernel<2>, grid, dim3(256), 0, s, a);

@@ -576,6 +576,7 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
         self.last_force_ = np.zeros(patch.dim)
         self.friction_, self._has_increment = 0.0, False
         self.consistent_tangent_ = False
+        self.friction_action_ = False
         self.last_friction_force_ = np.zeros(patch.dim)
         self.last_friction_traction_ = 0.0
         self.n_stick_ = self.n_slip_ = 0
@@ -655,17 +656,36 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
         check(_capi.lib().mimi_hip_contact_friction_state(self._handle(), ptr(xi), ptr(xbar), c.ctypes.data_as(C.c_void_p)))
         return xi, xbar, c
 
-    def _refuse_friction(self, what):
-        if self.friction_ > 0.0:
+    def _refuse_friction(self, what, lifted=False):
+        """(lifted: what SetFrictionAction(True) makes available)"""
+        if self.friction_ > 0.0 and not lifted:
             raise RuntimeError(f"{what} is not available on a contact with friction (mu = {self.friction_:g}): the friction "
                                "tangent is assembled only")
 
+    def SetFrictionAction(self, on=True):
+        """Friction on the matrix-free route (include/mimi_hip.h: mimi_hip_contact_set_friction_action): with it Linearize,
+        ApplyTangent, a Krylov operator built on the handle and SetConsistentTangent accept a contact with friction.  A
+        Linearize with mu > 0 then records, per face point, a = xi + x_q - xbar - d, the traction's coefficient and the
+        branch, from the COMMITTED friction state -- a snapshot like the rest of the record, which no later SetFriction,
+        SetBodyIncrement, CommitFriction, ResetFriction, UpdateBody or evaluation touches; it writes no trial state.
+        ApplyTangent adds the assembled friction tangent's action and, on a consistent record, the derivative of the slip
+        limit mu p_N by the nodal pressure.  Off (the default): every refusal stands.  The reference-FD tangent mode stays
+        refused, and so do the handles of a ShardedContact."""
+        if on and getattr(self, "sharded_", False):
+            raise RuntimeError("the friction action on a ShardedContact is not supported: friction itself is refused there")
+        check(_capi.lib().mimi_hip_contact_set_friction_action(self._handle(), 1 if on else 0))
+        self.friction_action_ = bool(on)
+
+    def HoldsFrictionRecord(self):
+        """whether the record of the last Linearize carries friction"""
+        return bool(self._action_fn("action_info")(self._handle(), 3))
+
     def Linearize(self, u):
-        self._refuse_friction("the matrix-free tangent action (Linearize)")
+        self._refuse_friction("the matrix-free tangent action (Linearize)", self.friction_action_)
         return super().Linearize(u)
 
     def ApplyTangent(self, x, y, factor=1.0):
-        self._refuse_friction("the matrix-free tangent action (ApplyTangent)")
+        self._refuse_friction("the matrix-free tangent action (ApplyTangent)", self.friction_action_)
         return super().ApplyTangent(x, y, factor)
 
     def SetConsistentTangent(self, on=True):
@@ -678,7 +698,7 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
             raise RuntimeError("the consistent tangent on a ShardedContact is not supported: the nodal sums of a handle run "
                                "over its own faces")
         if on:
-            self._refuse_friction("the consistent tangent")
+            self._refuse_friction("the consistent tangent", self.friction_action_)
         check(_capi.lib().mimi_hip_contact_set_consistent_tangent(self._handle(), 1 if on else 0))
         self.consistent_tangent_ = bool(on)
 

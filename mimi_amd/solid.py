@@ -347,6 +347,7 @@ class Route(typing.NamedTuple):
     periodic_iterative: bool = False    # a periodic pair on the Kronecker, matrix-free and consistent-mass routes
     host_setup: bool = False            # mass, damping and right-hand side in numpy on the host
     consistent_contact: bool = False    # the contact actions carry the derivative of the nodal pressure as well
+    friction_actions: bool = False      # ... and Coulomb friction, which is assembled only without it
 
 
 def resolve_route(rc, bc, axes):
@@ -374,6 +375,15 @@ def resolve_route(rc, bc, axes):
         raise RuntimeError("contact_consistent_tangent needs matrix_free_boundary: the derivative of the nodal pressure "
                            "couples nodes up to 2 p basis functions apart, which leaves the CSR pattern -- it exists as a "
                            "matrix-free action only")
+    # "friction_matrix_free": the friction tangent as a part of the contact action (MortarContact.SetFrictionAction).  Without
+    # the flag matrix_free_boundary refuses a body with friction as it always did.
+    friction_actions = flag("friction_matrix_free")
+    if friction_actions and explicit:
+        raise RuntimeError("friction_matrix_free cannot be combined with explicit_dynamics: an explicit step has no "
+                           "tangent for it to act on -- unset one of the two")
+    if friction_actions and not boundary_actions:
+        raise RuntimeError("friction_matrix_free needs matrix_free_boundary: it adds the friction tangent to the contact "
+                           "action of the matrix-free product")
     if explicit:
         for other, on in (("matrix_free", matrix_free), ("use_iterative_solver", iterative)):
             if on:
@@ -400,7 +410,7 @@ def resolve_route(rc, bc, axes):
             raise RuntimeError("matrix_free cannot be combined with a follower pressure marker: the pressure tangent has no "
                                "matrix-free action")
         rough = [b for b in bc.current.contact_.values() if float(getattr(b, "friction", 0.0)) > 0.0]
-        if rough:
+        if rough and not friction_actions:
             raise RuntimeError(f"matrix_free_boundary cannot be combined with a contact body with friction (mu = "
                                f"{rough[0].friction:g}): the friction tangent has no matrix-free action")
         if axes and not periodic_iterative:
@@ -409,7 +419,7 @@ def resolve_route(rc, bc, axes):
     if explicit and host_setup:
         raise RuntimeError("explicit_dynamics cannot be combined with the host set-up: the lumped mass is assembled on the device")
     return Route(explicit, consistent, iterative, iterative and kronecker, matrix_free, boundary_actions, periodic_iterative, host_setup,
-                 consistent_contact)
+                 consistent_contact, friction_actions)
 
 
 class NonlinearSolid(Solid, ExplicitDynamics):
@@ -636,6 +646,8 @@ class NonlinearSolid(Solid, ExplicitDynamics):
             axis, side = self._faces[bid + 1]
             self.contacts_.append(MortarContact(body, "contact", self.pattern_u_, patch, axis, side, device=self.device,
                                                 quadrature_order=rc.get_int("contact_quadrature_order", -1)).Prepare())
+            if self.route_.friction_actions:
+                self.contacts_[-1].SetFrictionAction(True)
             if self.route_.consistent_contact:
                 self.contacts_[-1].SetConsistentTangent(True)
         # follower pressure (the reference stores BCMarker::pressure_ and never applies it): one device integrator per bid

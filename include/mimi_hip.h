@@ -246,6 +246,19 @@ int mimi_hip_domain_linearize(mimi_hip_domain_t h, const double* u);
  * matrix forms::Nonlinear::AddMultGrad assembled. */
 int mimi_hip_domain_apply_tangent(mimi_hip_domain_t h, double density, double stiffness, double viscosity,
                                   const double* x, double* y);
+/* ---- tangent diagonal: the node-block diagonal of the operator apply_tangent applies, without the matrix.  For a control
+ * point A with local index a in element e
+ *   D[A][i][j] = sum_{e of A} sum_q w_q det_q [ (density N_a^2 + viscosity |grad_X N_a|^2) delta_ij
+ *                                               + stiffness d_J N_a (dP_iJ / dF_jL)(q) d_L N_a ],
+ * the (A,i),(A,j) entries of what add_mass, add_diffusion and add_residual_and_grad(grad_factor = stiffness) assemble.
+ * d += ...: block == 0 the diagonal, n_nodes dim doubles in byVDIM order; block != 0 the node blocks, n_nodes dim dim doubles
+ * [A][i][j] row-major.  The entries i == j of the blocks are the diagonal to the bit (the same instructions compute both).
+ * d host or device.  stiffness != 0 needs a linearize() first, the mass term on a flat-table handle
+ * mimi_hip_domain_set_shape_values, as apply_tangent.  Reads the snapshot only: a later commit, set_dt, or an overwritten u
+ * changes nothing.  No essential dofs (the caller eliminates).  Element boxes compose by addition.  No atomics: equal inputs
+ * give equal bytes.  What mfem::DSmoother reads off the assembled matrix (py_nonlinear_solid.cpp:329-339), without it. */
+int mimi_hip_domain_tangent_diagonal(mimi_hip_domain_t h, double density, double stiffness, double viscosity, int32_t block,
+                                     double* d);
 /* The two-step form of mimi_hip_domain_add_residual_and_grad, for a caller that needs some rows before the others (the
  * rows a neighbour rank is waiting for: mimi_amd/parallel.py, bench.py): integrate() runs the integration kernels of the
  * whole handle -- element row pieces and element residual pieces into the handle's scratch, nothing into r / A_values --
@@ -594,7 +607,8 @@ int mimi_hip_linear_add_mult(mimi_hip_linear_t h, const double* A_values, const 
  * rel 1e-8, abs 1e-12, 300 iterations; kdim <= 0 = mfem's default 50): x = 0 start, left-preconditioned restarted
  * GMRES, modified Gram-Schmidt, stops when the preconditioned residual estimate <= max(rel_tol * ||M b||, abs_tol).
  * preconditioner: 1 = the reference's Jacobi, 0 = none, 2 = the Kronecker operator below (needs set_kronecker and
- * set_kronecker_coefficients first; an error otherwise).  A_values / b / x host or device. */
+ * set_kronecker_coefficients first; an error otherwise), 3 = the node-block Jacobi below (needs set_node_block first).
+ * A_values / b / x host or device. */
 int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol,
                           double abs_tol, int max_iter, int kdim, int preconditioner, int32_t* iterations,
                           double* final_norm, int32_t* converged);
@@ -618,14 +632,15 @@ int mimi_hip_linear_set_kronecker(mimi_hip_linear_t h, int32_t dim, const int32_
                                   const double* lambda);
 /* mass and stiff[c * dim + d] (host) of the operator above; the scaling array is rebuilt on the device */
 int mimi_hip_linear_set_kronecker_coefficients(mimi_hip_linear_t h, double mass_coef, const double* stiff_coef);
-/* z = M r with the preconditioner the solvers apply: kind 1 Jacobi (z = r / diag(A); needs A_values), 2 Kronecker
- * (A_values may be NULL).  Host or device arrays; z == r is allowed. */
+/* z = M r with the preconditioner the solvers apply: kind 1 Jacobi (z = r / diag(A); needs A_values, or NULL with
+ * set_operator_diagonal armed and an operator set), 2 Kronecker (A_values may be NULL), 3 node-block Jacobi (A_values, or
+ * NULL: the blocks of the operator).  Host or device arrays; z == r is allowed. */
 int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const double* A_values, const double* r, double* z);
 /* A domain handle in place of the matrix: with an operator set, A_values == NULL in mimi_hip_linear_gmres / _cg means
  * "the product is density M + stiffness K(u_lin) + viscosity C of `domain`" (mimi_hip_domain_apply_tangent), eliminated
  * like the matrix: y = mask(A (mask x)) + x[ess].  Stands in for SparseMatrix::Mult on the matrix
- * forms::Nonlinear::AddMultGrad assembled.  A non-null A_values takes the CSR kernels as ever.  Preconditioner ids 0 and
- * 2 work with the operator, id 1 (Jacobi) needs the matrix values.  The action runs on the solver's stream; a solve
+ * forms::Nonlinear::AddMultGrad assembled.  A non-null A_values takes the CSR kernels as ever.  Preconditioner ids 0, 2
+ * and 3 work with the operator, id 1 (Jacobi) needs the matrix values unless mimi_hip_linear_set_operator_diagonal armed it.  The action runs on the solver's stream; a solve
  * waits once on the event behind the domain's last linearize.  The domain must be on the solver's device and have its n;
  * it must outlive the setting.  domain == NULL clears it. */
 int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, double density, double stiffness, double viscosity);
@@ -655,6 +670,30 @@ int mimi_hip_linear_set_operator_fold(mimi_hip_linear_t h, mimi_hip_fold_t fold)
  * on the solver's stream: the product alone, for checks.  x and y (n doubles each, different vectors) host or device.
  * Refused without an operator, and where a solve would be (a handle that was never linearised, a wrong size). */
 int mimi_hip_linear_operator_mult(mimi_hip_linear_t h, const double* x, double* y);
+/* Node-block Jacobi, preconditioner id 3 of mimi_hip_linear_gmres / _cg / _apply_preconditioner (no reference counterpart:
+ * the reference has the scalar Jacobi only): z_A = B_A^-1 r_A with B_A the dim x dim block (A,i),(A,j) of node A, which carries
+ * the coupling between the components of a control point.  set_node_block says that the handle's n is n_nodes dim in byVDIM
+ * order (dim 1 to 3); refused when n % dim != 0.  Id 3 needs it.  With matrix values the blocks are read out of the CSR
+ * (positions searched once per pattern; an (A,i),(A,j) entry the pattern lacks counts as zero); with A_values == NULL they come
+ * from mimi_hip_domain_tangent_diagonal(block = 1) of the operator's domain with the coefficients of set_operator (the domain's
+ * dim must be the block's).  Either way the blocks are eliminated like the matrix (row and column of an essential dof zero,
+ * its diagonal 1), inverted per node in closed form on the device once per solve, and applied behind the product.  A block
+ * whose determinant is zero or not finite fails the solve; the error names the node. */
+int mimi_hip_linear_set_node_block(mimi_hip_linear_t h, int32_t dim);
+/* Arms preconditioner id 1 (Jacobi) for solves WITHOUT matrix values: 1 / diag then comes from
+ * mimi_hip_domain_tangent_diagonal(block = 0) of the operator's domain with the coefficients of set_operator, essential dofs 1,
+ * built once per solve on the solver's stream behind the event wait of the product, and applied inside the kernel behind the
+ * actions.  A free dof whose diagonal entry is zero or not finite fails the solve; the error names the dof.  What
+ * mfem::DSmoother reads off the assembled matrix (py_nonlinear_solid.cpp:329-339), without it.  Off by default:
+ * id 1 with A_values == NULL is then refused ("needs the matrix values").  Solves that pass values never see the setting.
+ * With an operator fold the unwrapped diagonal (or, id 3, the unwrapped blocks) is summed over the copies of each folded node
+ * in the fold's ascending order: the diagonal of P^T A P whenever no element holds both copies of a node, i.e. when the
+ * periodic axis has at least two knot spans; with a single span the cross blocks between the copies are left out.
+ * Boundary terms (mimi_hip_linear_add_boundary_operator) contribute nothing to the diagonal or the blocks: for frozen contact
+ * and follower pressure the scalar diagonal is identically zero (d m_i / d x_a,i = (e_i x t)_i = 0 in 3-D; m = (t_y, -t_x) in
+ * 2-D), so id 1 is exactly the assembled route's Jacobi there; their skew node blocks, the friction action and the
+ * consistent-tangent terms are not carried.  Solves converge to the same solution; the preconditioner is weaker. */
+int mimi_hip_linear_set_operator_diagonal(mimi_hip_linear_t h, int32_t on);
 
 /* ---- explicit central-difference step with a lumped mass -----------------------------------------------------------
  * Stands in for the reference's CentralDifference = Newmark(beta = 0, gamma = 1/2) step (solvers/ode.hpp:257,

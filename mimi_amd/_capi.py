@@ -111,6 +111,7 @@ EXPORTS = [
     "mimi_hip_contact_set_friction", "mimi_hip_contact_set_body_increment", "mimi_hip_contact_post_time_advance",
     "mimi_hip_contact_reset_friction", "mimi_hip_contact_friction_history", "mimi_hip_contact_friction_state",
     "mimi_hip_contact_set_consistent_tangent", "mimi_hip_contact_set_friction_action",
+    "mimi_hip_domain_tangent_diagonal", "mimi_hip_linear_set_node_block", "mimi_hip_linear_set_operator_diagonal",
 ]
 
 
@@ -282,6 +283,9 @@ def lib():
     L.mimi_hip_linear_add_boundary_operator.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
     L.mimi_hip_linear_set_operator_fold.argtypes = [C.c_void_p, C.c_void_p]
     L.mimi_hip_linear_operator_mult.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.mimi_hip_domain_tangent_diagonal.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_void_p]
+    L.mimi_hip_linear_set_node_block.argtypes = [C.c_void_p, C.c_int32]
+    L.mimi_hip_linear_set_operator_diagonal.argtypes = [C.c_void_p, C.c_int32]
     _lib = L
     return L
 

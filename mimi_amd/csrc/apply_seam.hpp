@@ -26,6 +26,14 @@ void operator_begin_solve(mimi_hip_domain_s* h, double density, double stiffness
 void operator_add_action(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, const double* x, double* y,
                          hipStream_t solver_stream);
 
+// The diagonal of the same operator (mimi_hip_domain_tangent_diagonal).  begin_diagonal, once per solve behind begin_solve:
+// the checks and what the diagonal kernels build on first use (the element pieces of `block`); add_diagonal: d += the diagonal
+// (block == 0: [A][i]) or the node blocks (block != 0: [A][i][j]); d on the device, everything on solver_stream.
+int operator_dim(const mimi_hip_domain_s* h);
+void operator_begin_diagonal(mimi_hip_domain_s* h, double density, double stiffness, int block, hipStream_t solver_stream);
+void operator_add_diagonal(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, int block, double* d,
+                           hipStream_t solver_stream);
+
 // The boundary twins.  begin_solve: the check of mimi_hip_<kind>_apply_tangent (a linearize came first), the face vector of
 // the action, and one wait of solver_stream on the event recorded behind the handle's last linearize.
 // add_action: y += factor K_face x; x, y on the device, everything on solver_stream.

@@ -39,6 +39,19 @@ void operator_add_action(mimi_hip_domain_s* h, double density, double stiffness,
   launch_apply(h, density, stiffness, viscosity, x, y, solver_stream);
 }
 
+int operator_dim(const mimi_hip_domain_s* h) { return h->dim; }
+
+void operator_begin_diagonal(mimi_hip_domain_s* h, double density, double stiffness, int block, hipStream_t solver_stream) {
+  apply_check(h, stiffness, "mimi_hip_domain_tangent_diagonal");
+  if (diagonal_prepare(h, density, block)) MH_HIP(hipStreamSynchronize(h->stream));
+  if (h->lin_event && stiffness != 0.0) MH_HIP(hipStreamWaitEvent(solver_stream, h->lin_event, 0));
+}
+
+void operator_add_diagonal(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, int block, double* d,
+                           hipStream_t solver_stream) {
+  launch_diagonal(h, density, stiffness, viscosity, block, d, solver_stream);
+}
+
 }  // namespace mimi_hip
 
 using namespace mimi_hip;
@@ -310,6 +323,13 @@ int mimi_hip_domain_apply_tangent(mimi_hip_domain_t h, double density, double st
   return guarded([&] {
     if (!h) fail("null handle");
     run_apply_tangent(h, density, stiffness, viscosity, x, y);
+  });
+}
+
+int mimi_hip_domain_tangent_diagonal(mimi_hip_domain_t h, double density, double stiffness, double viscosity, int32_t block, double* d) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    run_tangent_diagonal(h, density, stiffness, viscosity, block, d);
   });
 }
 

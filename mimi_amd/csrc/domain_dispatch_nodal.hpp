@@ -4,6 +4,7 @@
 #pragma once
 
 #include "domain_dispatch.hpp"
+#include "kernels_diagonal.hpp"
 
 namespace mimi_hip {
 
@@ -267,9 +268,9 @@ inline bool apply_prepare(mimi_hip_domain_s* h, double density) {
   return built;
 }
 
-inline void apply_check(const mimi_hip_domain_s* h, double stiffness) {
+inline void apply_check(const mimi_hip_domain_s* h, double stiffness, const char* who = "mimi_hip_domain_apply_tangent") {
   if (stiffness != 0.0 && !h->linearized)
-    fail("mimi_hip_domain_apply_tangent with a stiffness coefficient before any mimi_hip_domain_linearize on this handle");
+    fail("%s with a stiffness coefficient before any mimi_hip_domain_linearize on this handle", who);
 }
 
 // y += density M x + stiffness K(u_lin) x + viscosity C x on `stream`; x, y on the device; apply_prepare has run
@@ -305,6 +306,74 @@ inline void run_apply_tangent(mimi_hip_domain_s* h, double density, double stiff
   launch_apply(h, density, stiffness, viscosity, mx.dev, my.dev, h->stream);
   my.finish(h->stream);
   if (mx.host || my.host) check_status(h);   // synchronous for host-resident arguments
+}
+
+// ---- tangent diagonal (kernels_diagonal.hpp) -----------------------------------------------------------------------------
+
+// apply_prepare, and the element pieces [n_el][n_dof][ncomp]; true when something was launched
+inline bool diagonal_prepare(mimi_hip_domain_s* h, double density, int block) {
+  const bool built = apply_prepare(h, density);
+  const size_t need = (size_t)h->n_el * h->n_dof * (block ? h->dim * h->dim : h->dim);
+  if (h->scratch_r.count < need) {
+    MH_HIP(hipStreamSynchronize(h->stream));   // (nothing in flight reads the pieces that are released)
+    h->scratch_r.resize(need);
+  }
+  return built;
+}
+
+// d += the diagonal (block == 0: [A][i]) or the node blocks (block != 0: [A][i][j]) of density M + stiffness K(u_lin) +
+// viscosity C on `stream`; d on the device; diagonal_prepare has run
+inline void launch_diagonal(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, int block, double* d,
+                            hipStream_t stream) {
+  h->integrated = false;   // the element pieces of an earlier mimi_hip_domain_integrate are overwritten
+  DiagonalArgs da{};
+  da.density = density;
+  da.stiffness = stiffness;
+  da.viscosity = viscosity;
+  da.u_lin = h->lin_u.ptr;
+  da.rec = h->lin_rec.ptr;
+  da.pieces = h->scratch_r.ptr;
+  da.N = h->shape_N.ptr;
+  da.n_pts = h->n_pts;
+  da.n_el = h->n_el;
+  da.block = block ? 1 : 0;
+  const bool recompute = apply_recomputes(h);
+  if (tensor_usable(h)) {
+    const TensorArgs a = tensor_args(h, DomainCall{});
+    by_dim_degree(h, [&](auto D, auto Pd) {
+      constexpr int DIM = decltype(D)::value, P = decltype(Pd)::value;
+      auto go = [&](auto M) {
+        using S = DiagonalShape<DIM, P, decltype(M)::value>;
+        launch(diagonal_tensor_kernel<DIM, P, decltype(M)::value>, dim3((unsigned)((h->n_el + S::EPW - 1) / S::EPW)), dim3(S::THREADS),
+               (size_t)S::total * S::EPW * sizeof(double), stream, a, da);
+      };
+      if (recompute) go(std::integral_constant<int, APPLY_NEOHOOKEAN>{}); else go(std::integral_constant<int, APPLY_RECORD>{});
+    });
+  } else {
+    const GeneralArgs a = general_args(h, DomainCall{});
+    // (the record route keeps nothing per point in LDS)
+    const size_t lds = ((size_t)h->n_dof * h->dim + (recompute ? (size_t)(h->dim * h->dim + 1) * h->n_q : 0)) * sizeof(double);
+    if (lds > 64 * 1024)
+      fail("tangent diagonal: an element of %d nodes and %d points needs %zu bytes of LDS, a workgroup has 65536", h->n_dof, h->n_q, lds);
+    by_dim(h, [&](auto D) {
+      constexpr int DIM = decltype(D)::value;
+      launch(recompute ? diagonal_general_kernel<DIM, APPLY_NEOHOOKEAN> : diagonal_general_kernel<DIM, APPLY_RECORD>, dim3((unsigned)h->n_el),
+             dim3(256), lds, stream, a, da);
+    });
+  }
+  const int ncomp = block ? h->dim * h->dim : h->dim;
+  launch_node_gather(h, ncomp, ncomp, h->scratch_r.ptr, d, nullptr, stream);
+}
+
+inline void run_tangent_diagonal(mimi_hip_domain_s* h, double density, double stiffness, double viscosity, int block, double* d) {
+  MH_HIP(hipSetDevice(h->device));
+  if (!d) fail("null vector argument");
+  apply_check(h, stiffness, "mimi_hip_domain_tangent_diagonal");
+  diagonal_prepare(h, density, block);
+  Mirror<double> md = Mirror<double>::inout(d, (size_t)h->n_vdofs * (block ? h->dim : 1), h->stage_f, h->stream);
+  launch_diagonal(h, density, stiffness, viscosity, block, md.dev, h->stream);
+  md.finish(h->stream);
+  if (md.host) check_status(h);   // synchronous for host-resident arguments
 }
 
 // the snapshot of the tangent at u: committed state, the dt of set_dt; no state changes

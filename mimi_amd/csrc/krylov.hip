@@ -10,7 +10,20 @@
 //       convergence on the preconditioned residual  |s_{i+1}| <= max(rel_tol * ||M r_0||, abs_tol).
 //   Beyond the reference: the matrix may be a domain handle's matrix-free tangent action (mimi_hip_linear_set_operator:
 //       A_values == NULL in a solve), eliminated like the matrix by two vector kernels around it; M may be the Kronecker (fast-diagonalisation) operator of kronecker.hpp instead of Jacobi
-//       (preconditioner id 2 of both solvers); ids 0 and 1 run the kernels and give the bits they always did.  With a periodic
+//       (preconditioner id 2 of both solvers); ids 0 and 1 run the kernels and give the bits they always did.
+//       Jacobi without the matrix: with mimi_hip_linear_set_operator_diagonal armed, id 1 of a solve without values takes
+//       1 / diag from the operator's domain (mimi_hip_domain_tangent_diagonal, kernels_diagonal.hpp), built once per solve on
+//       the solver's stream behind the event wait of the product, essential dofs 1, fused into the kernel behind the actions.
+//       Node-block Jacobi (id 3, mimi_hip_linear_set_node_block): z_A = B_A^-1 r_A with B_A the dim x dim block of node A --
+//       read out of the CSR values (a missing entry is zero) or taken from the operator's domain (block mode) -- eliminated
+//       like the matrix and inverted per node in closed form, once per solve.
+//       With an operator fold the unwrapped diagonal or blocks are summed over the copies of each folded node in the fold's
+//       ascending order.  That is the diagonal of P^T A P whenever no element holds both copies of a node, i.e. when the
+//       periodic axis has at least two knot spans; with a single span the cross blocks between the two copies are left out.
+//       Boundary terms (mimi_hip_linear_add_boundary_operator) contribute nothing to either: for frozen contact and follower
+//       pressure the scalar diagonal is identically zero (d m_i / d x_a,i = (e_i x t)_i = 0 in 3-D, m = (t_y, -t_x) in 2-D), so
+//       id 1 is exactly the assembled route's Jacobi there; their skew node blocks, the friction action and the
+//       consistent-tangent terms are not carried -- the solution is the same, the preconditioner weaker.  With a periodic
 //       fold beside the operator (mimi_hip_linear_set_operator_fold) the solver works in the folded numbering and the two
 //       vector kernels also expand the input and fold the output: y_f = mask(P^T A_u P (mask x_f)) + x_f[ess], no extra pass.
 //
@@ -343,13 +356,14 @@ __global__ __launch_bounds__(KR_THREADS) void kr_operator_mask_kernel(int64_t n,
   }
 }
 
-// ... behind it y[ess] = x[ess], and y = b - y with b
+// ... behind it y[ess] = x[ess], y = b - y with b, and y = dinv o y with dinv (Jacobi from the operator's diagonal)
 __global__ __launch_bounds__(KR_THREADS) void kr_operator_restore_kernel(int64_t n, const unsigned char* __restrict__ is_ess,
                                                                          const double* __restrict__ x, const double* __restrict__ b,
-                                                                         double* __restrict__ y) {
+                                                                         const double* __restrict__ dinv, double* __restrict__ y) {
   for (int64_t i = (int64_t)blockIdx.x * KR_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * KR_THREADS) {
-    const double t = is_ess[i] ? x[i] : y[i];
-    y[i] = b ? b[i] - t : t;
+    double t = is_ess[i] ? x[i] : y[i];
+    if (b) t = b[i] - t;
+    y[i] = dinv ? dinv[i] * t : t;
   }
 }
 
@@ -377,6 +391,7 @@ __global__ __launch_bounds__(KR_THREADS) void kr_operator_fold_restore_kernel(in
                                                                               const int32_t* __restrict__ copies,
                                                                               const unsigned char* __restrict__ is_ess,
                                                                               const double* __restrict__ x, const double* __restrict__ b,
+                                                                              const double* __restrict__ dinv,
                                                                               const double* __restrict__ yu, double* __restrict__ y) {
   for (int64_t i = (int64_t)blockIdx.x * KR_THREADS + threadIdx.x; i < n_f; i += (int64_t)gridDim.x * KR_THREADS) {
     double t;
@@ -388,8 +403,132 @@ __global__ __launch_bounds__(KR_THREADS) void kr_operator_fold_restore_kernel(in
       t = 0.0;
       for (int k = copy_ptr[node]; k < copy_ptr[node + 1]; ++k) t += yu[(int64_t)copies[k] * DIM + c];
     }
-    y[i] = b ? b[i] - t : t;
+    if (b) t = b[i] - t;
+    y[i] = dinv ? dinv[i] * t : t;
   }
+}
+
+// ---- Jacobi from the operator's diagonal, node-block Jacobi ---------------------------------------------------------------
+
+// d[F][c] = the sum of du[copy][c] over the copies of folded node F, ascending from zero (the order of the folded product);
+// nc values per node
+__global__ void kr_fold_sum_kernel(int64_t n_nodes_f, int nc, const int32_t* __restrict__ copy_ptr, const int32_t* __restrict__ copies,
+                                   const double* __restrict__ du, double* __restrict__ d) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n_nodes_f * nc) return;
+  const int64_t node = idx / nc;
+  const int c = (int)(idx - node * nc);
+  double t = 0.0;
+  for (int k = copy_ptr[node]; k < copy_ptr[node + 1]; ++k) t += du[(int64_t)copies[k] * nc + c];
+  d[idx] = t;
+}
+
+// dinv = 1 / d, 1 on the essential dofs (the diagonal EliminateRowCol(DIAG_ONE) leaves), in place; a free dof whose
+// diagonal is zero or not finite leaves the smallest such dof in *bad
+__global__ void kr_operator_dinv_kernel(int64_t n, const unsigned char* __restrict__ is_ess, double* __restrict__ d,
+                                        unsigned long long* __restrict__ bad) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (is_ess[i]) {
+    d[i] = 1.0;
+    return;
+  }
+  const double v = d[i];
+  if (!(v != 0.0) || !isfinite(v)) atomicMin(bad, (unsigned long long)i);
+  d[i] = 1.0 / v;
+}
+
+// pos[row][j] = where column (node of row) dim + j stands in the row, -1 when the pattern lacks it (as kr_diag_pos_kernel)
+__global__ void kr_block_pos_kernel(int64_t n, int dim, const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                    int64_t* __restrict__ pos) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * dim) return;
+  const int64_t row = idx / dim;
+  const int64_t want = (row / dim) * dim + (idx - row * dim);
+  int64_t lo = rowptr[row], hi = rowptr[row + 1];
+  const int64_t base = lo, end = hi;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (col[mid] < want) lo = mid + 1; else hi = mid;
+  }
+  pos[idx] = (lo < end && col[lo] == want) ? lo - base : -1;
+}
+
+// B[A][i][j] = A((A, i), (A, j)), zero where the pattern has no such entry
+__global__ void kr_block_values_kernel(int64_t n, int dim, const int64_t* __restrict__ rowptr, const int64_t* __restrict__ pos,
+                                       const double* __restrict__ val, double* __restrict__ B) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= n * dim) return;
+  B[idx] = pos[idx] >= 0 ? val[rowptr[idx / dim] + pos[idx]] : 0.0;
+}
+
+// B_A <- (the block eliminated like the matrix: row and column of an essential dof zero, its diagonal 1)^-1 in closed form;
+// a determinant that is zero or not finite leaves the smallest such node in *bad
+template<int DIM>
+__global__ void kr_block_invert_kernel(int64_t n_nodes, const unsigned char* __restrict__ is_ess, double* __restrict__ B,
+                                       unsigned long long* __restrict__ bad) {
+  const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (node >= n_nodes) return;
+  double m[DIM][DIM], inv[DIM][DIM];
+  bool e[DIM];
+#pragma unroll
+  for (int i = 0; i < DIM; ++i) e[i] = is_ess[node * DIM + i] != 0;
+#pragma unroll
+  for (int i = 0; i < DIM; ++i)
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) m[i][j] = (e[i] || e[j]) ? (i == j ? 1.0 : 0.0) : B[(node * DIM + i) * DIM + j];
+  double det;
+  if constexpr (DIM == 1) {
+    det = m[0][0];
+    inv[0][0] = 1.0;
+  } else if constexpr (DIM == 2) {
+    det = m[0][0] * m[1][1] - m[0][1] * m[1][0];
+    inv[0][0] = m[1][1], inv[0][1] = -m[0][1], inv[1][0] = -m[1][0], inv[1][1] = m[0][0];
+  } else {
+    inv[0][0] = m[1][1] * m[2][2] - m[1][2] * m[2][1];
+    inv[0][1] = m[0][2] * m[2][1] - m[0][1] * m[2][2];
+    inv[0][2] = m[0][1] * m[1][2] - m[0][2] * m[1][1];
+    inv[1][0] = m[1][2] * m[2][0] - m[1][0] * m[2][2];
+    inv[1][1] = m[0][0] * m[2][2] - m[0][2] * m[2][0];
+    inv[1][2] = m[0][2] * m[1][0] - m[0][0] * m[1][2];
+    inv[2][0] = m[1][0] * m[2][1] - m[1][1] * m[2][0];
+    inv[2][1] = m[0][1] * m[2][0] - m[0][0] * m[2][1];
+    inv[2][2] = m[0][0] * m[1][1] - m[0][1] * m[1][0];
+    det = m[0][0] * inv[0][0] + m[0][1] * inv[1][0] + m[0][2] * inv[2][0];
+  }
+  if (!(det != 0.0) || !isfinite(det)) {
+    atomicMin(bad, (unsigned long long)node);
+    return;
+  }
+  const double over = 1.0 / det;
+#pragma unroll
+  for (int i = 0; i < DIM; ++i)
+#pragma unroll
+    for (int j = 0; j < DIM; ++j)   // (row and column of an essential dof: the identity's, without the rounding of det / det)
+      B[(node * DIM + i) * DIM + j] = (e[i] || e[j]) ? (i == j ? 1.0 : 0.0) : inv[i][j] * over;
+}
+
+// z_A = Binv_A r_A (z == r allowed: a thread reads its node's r before it writes), partial_out = partial sums of r . z
+template<int DIM>
+__global__ __launch_bounds__(KR_THREADS) void kr_block_apply_kernel(int64_t n_nodes, const double* __restrict__ binv, const double* r,
+                                                                    double* z, double* __restrict__ partial_out) {
+  __shared__ double sh[KR_THREADS / 64];
+  double acc = 0.0;
+  for (int64_t node = (int64_t)blockIdx.x * KR_THREADS + threadIdx.x; node < n_nodes; node += (int64_t)KR_BLOCKS * KR_THREADS) {
+    double rv[DIM];
+#pragma unroll
+    for (int j = 0; j < DIM; ++j) rv[j] = r[node * DIM + j];
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < DIM; ++j) s += binv[(node * DIM + i) * DIM + j] * rv[j];
+      z[node * DIM + i] = s;
+      acc += rv[i] * s;
+    }
+  }
+  const double t = kr_block_sum(acc, sh);
+  if (threadIdx.x == 0 && partial_out) partial_out[blockIdx.x] = t;
 }
 
 __global__ void kr_mark_kernel(int64_t n_ess, const int64_t* __restrict__ ess, unsigned char* __restrict__ is_ess) {
@@ -432,6 +571,15 @@ struct mimi_hip_linear_s : StreamHandle {
   // folded one; the expanded input and the unwrapped output of the actions
   mimi_hip_fold_s* op_fold = nullptr;
   DeviceBuffer<double> op_xu, op_yu;
+  // mimi_hip_linear_set_operator_diagonal: id 1 of a solve without values takes its diagonal from the operator's domain
+  bool op_diagonal = false;
+  DeviceBuffer<double> op_du;   // with a fold: the unwrapped diagonal or blocks, before the copies are summed
+  // mimi_hip_linear_set_node_block: the handle's n is n_nodes * node_block in byVDIM order (0: not set); preconditioner id 3
+  int node_block = 0;
+  DeviceBuffer<int64_t> block_pos;     // [n][node_block]: where the block's entries stand in their CSR rows, found at first use
+  bool have_block_pos = false;
+  DeviceBuffer<double> binv;           // [n_nodes][node_block][node_block]: the inverted blocks of this solve
+  DeviceBuffer<unsigned long long> bad_node;
   // dofs an operator handle must have: the unwrapped size with a fold, the solver's own without
   int64_t operator_n() const {
     if (!op_fold) return n;
@@ -493,8 +641,8 @@ void by_fold_dim(int dim, F&& f) {
 
 dim3 wave_per_unit(int64_t units) { return dim3((unsigned)((units + 3) / 4)); }   // workgroups of 256: four waves
 
-// y = dinv o (A x), dinv o (b - A x) with b, plain without dinv.  val == nullptr: A is the handle's operator (no dinv then:
-// Jacobi needs the values), y = mask(A (mask x)) + x[ess]
+// y = dinv o (A x), dinv o (b - A x) with b, plain without dinv.  val == nullptr: A is the handle's operator,
+// y = mask(A (mask x)) + x[ess] (dinv then comes from the operator's diagonal)
 void spmv(mimi_hip_linear_s* h, const double* val, const double* x, const double* b, const double* dinv, double* y) {
   if (!val) {
     const unsigned char* is_ess = h->is_ess.ptr;
@@ -517,10 +665,10 @@ void spmv(mimi_hip_linear_s* h, const double* val, const double* x, const double
     if (h->op_fold) {
       by_fold_dim(f.dim, [&](auto D) {
         launch(kr_operator_fold_restore_kernel<decltype(D)::value>, KR_GRID, KR_BLOCK, 0, h->stream, h->n, f.copy_ptr, f.copies, is_ess, x,
-               b, (const double*)h->op_yu.ptr, y);
+               b, dinv, (const double*)h->op_yu.ptr, y);
       });
     } else {
-      launch(kr_operator_restore_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, is_ess, x, b, y);
+      launch(kr_operator_restore_kernel, KR_GRID, KR_BLOCK, 0, h->stream, h->n, is_ess, x, b, dinv, y);
     }
     return;
   }
@@ -545,37 +693,126 @@ double total_to_host(mimi_hip_linear_s* h) {
 }
 
 // the preconditioner ids of mimi_hip_linear_gmres / _cg / _apply_preconditioner
-enum { PRECOND_NONE = 0, PRECOND_JACOBI = 1, PRECOND_KRONECKER = 2 };
+enum { PRECOND_NONE = 0, PRECOND_JACOBI = 1, PRECOND_KRONECKER = 2, PRECOND_BLOCK_JACOBI = 3 };
+
+// d = the diagonal (block == 0: n doubles) or the node blocks (block != 0: n dim doubles) of the handle's operator in the
+// solver's numbering, on the solver's stream; solve_matrix has run.  The boundary terms contribute nothing (header comment).
+void operator_diagonal(mimi_hip_linear_s* h, int block, double* d) {
+  const int dim = operator_dim(h->op_domain);
+  const int nc = block ? dim * dim : dim;
+  operator_begin_diagonal(h->op_domain, h->op_density, h->op_stiffness, block, h->stream);
+  MH_HIP(hipSetDevice(h->device));
+  if (h->op_fold) {
+    const OperatorFold f = operator_fold(h->op_fold);
+    if (f.dim != dim) fail("operator diagonal: the fold has %d components per node, the domain handle %d", f.dim, dim);
+    const size_t n_u = (size_t)f.n_nodes_u * nc;
+    h->op_du.resize(n_u);
+    MH_HIP(hipMemsetAsync(h->op_du.ptr, 0, n_u * sizeof(double), h->stream));
+    operator_add_diagonal(h->op_domain, h->op_density, h->op_stiffness, h->op_viscosity, block, h->op_du.ptr, h->stream);
+    launch(kr_fold_sum_kernel, dim3((unsigned)((f.n_nodes_f * nc + 255) / 256)), dim3(256), 0, h->stream, f.n_nodes_f, nc, f.copy_ptr,
+           f.copies, (const double*)h->op_du.ptr, d);
+  } else {
+    MH_HIP(hipMemsetAsync(d, 0, (size_t)(h->n / dim) * nc * sizeof(double), h->stream));
+    operator_add_diagonal(h->op_domain, h->op_density, h->op_stiffness, h->op_viscosity, block, d, h->stream);
+  }
+}
 
 // M of one solve: the identity, 1 / diag(A) of THIS solve's values (mfem::DSmoother; the values change between Newton
-// iterations, so nothing of it outlives the solve), or the Kronecker operator the handle holds.  Which kernels apply M is
-// decided here and nowhere else.
+// iterations, so nothing of it outlives the solve) or of the operator (armed, no values), the Kronecker operator the handle
+// holds, or the inverted node blocks of this solve's values or operator.  Which kernels apply M is decided here and nowhere
+// else.
 struct Preconditioner {
   mimi_hip_linear_s* h;
   int id;
   const double* dinv = nullptr;   // Jacobi; fused into the kernels that take it
 
   Preconditioner(mimi_hip_linear_s* h_, int id_, const double* val) : h(h_), id(id_) {
-    if (id < PRECOND_NONE || id > PRECOND_KRONECKER) fail("unknown preconditioner id %d (0 none, 1 Jacobi, 2 Kronecker)", id);
+    if (id < PRECOND_NONE || id > PRECOND_BLOCK_JACOBI)
+      fail("unknown preconditioner id %d (0 none, 1 Jacobi, 2 Kronecker, 3 node-block Jacobi)", id);
     if (id == PRECOND_KRONECKER) {
       if (!h->kron.set) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker first");
       if (!h->kron.have_coefficients) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker_coefficients first");
     } else if (id == PRECOND_JACOBI) {
-      if (!val) fail("the Jacobi preconditioner needs the matrix values");
+      if (!val && !(h->op_diagonal && h->op_domain)) fail("the Jacobi preconditioner needs the matrix values");
       h->dinv.resize((size_t)h->n);
-      launch(kr_diag_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, h->stream, h->n, h->rowptr, h->diag_pos.ptr, val,
-             h->dinv.ptr);
+      const dim3 grid((unsigned)((h->n + 255) / 256));
+      if (val) {
+        launch(kr_diag_kernel, grid, dim3(256), 0, h->stream, h->n, h->rowptr, h->diag_pos.ptr, val, h->dinv.ptr);
+      } else {
+        operator_diagonal(h, 0, h->dinv.ptr);
+        reset_bad();
+        launch(kr_operator_dinv_kernel, grid, dim3(256), 0, h->stream, h->n, (const unsigned char*)h->is_ess.ptr, h->dinv.ptr,
+               h->bad_node.ptr);
+        const unsigned long long bad = read_bad();
+        if (bad != ~0ull)
+          fail("Jacobi from the operator's diagonal: the diagonal entry of dof %llu is zero or not finite", bad);
+      }
       dinv = h->dinv.ptr;
+    } else if (id == PRECOND_BLOCK_JACOBI) {
+      build_blocks(val);
     }
+  }
+
+  // the one word a build of M reports its first bad node or dof in: all ones before, read back once per solve
+  void reset_bad() const {
+    h->bad_node.resize(1);
+    MH_HIP(hipMemsetAsync(h->bad_node.ptr, 0xff, sizeof(unsigned long long), h->stream));
+  }
+  unsigned long long read_bad() const {
+    unsigned long long bad = 0;
+    MH_HIP(hipMemcpyAsync(&bad, h->bad_node.ptr, sizeof(bad), hipMemcpyDeviceToHost, h->stream));
+    MH_HIP(hipStreamSynchronize(h->stream));
+    return bad;
+  }
+
+  // the inverted node blocks of this solve into h->binv
+  void build_blocks(const double* val) const {
+    const int dim = h->node_block;
+    if (!dim) fail("preconditioner id 3 (node-block Jacobi) needs mimi_hip_linear_set_node_block first");
+    const int64_t n_nodes = h->n / dim;
+    const dim3 grid((unsigned)((h->n * dim + 255) / 256));
+    h->binv.resize((size_t)h->n * dim);
+    if (val) {
+      if (!h->have_block_pos) {
+        h->block_pos.resize((size_t)h->n * dim);
+        launch(kr_block_pos_kernel, grid, dim3(256), 0, h->stream, h->n, dim, h->rowptr, h->col, h->block_pos.ptr);
+        h->have_block_pos = true;
+      }
+      launch(kr_block_values_kernel, grid, dim3(256), 0, h->stream, h->n, dim, h->rowptr, (const int64_t*)h->block_pos.ptr, val,
+             h->binv.ptr);
+    } else {
+      if (!h->op_domain) fail("the node-block Jacobi preconditioner needs the matrix values or an operator");
+      if (operator_dim(h->op_domain) != dim)
+        fail("node-block Jacobi: the operator's domain has %d components per node, mimi_hip_linear_set_node_block gave %d",
+             operator_dim(h->op_domain), dim);
+      operator_diagonal(h, 1, h->binv.ptr);
+    }
+    reset_bad();
+    by_fold_dim(dim, [&](auto D) {
+      launch(kr_block_invert_kernel<decltype(D)::value>, dim3((unsigned)((n_nodes + 255) / 256)), dim3(256), 0, h->stream, n_nodes,
+             (const unsigned char*)h->is_ess.ptr, h->binv.ptr, h->bad_node.ptr);
+    });
+    const unsigned long long bad = read_bad();
+    if (bad != ~0ull) fail("node-block Jacobi: the block of node %llu is singular or not finite", bad);
+  }
+
+  // z_A = B_A^-1 r_A  (z == r allowed)
+  void blocks(const double* r, double* z, double* partial_rz) const {
+    by_fold_dim(h->node_block, [&](auto D) {
+      launch(kr_block_apply_kernel<decltype(D)::value>, KR_GRID, KR_BLOCK, 0, h->stream, h->n / h->node_block, (const double*)h->binv.ptr, r,
+             z, partial_rz);
+    });
   }
 
   // z = P^-1 r, z[ess] = r[ess]  (z == r allowed)
   void kronecker(const double* r, double* z) const { h->kron.apply(r, z, h->n_ess > 0 ? h->is_ess.ptr : nullptr, h->stream); }
 
-  // y = M (b - A x), or M A x without b: Jacobi inside the product, the Kronecker operator in place behind a plain one
+  // y = M (b - A x), or M A x without b: Jacobi inside the product, the Kronecker operator or the node blocks in place
+  // behind a plain one
   void product(const double* val, const double* x, const double* b, double* y) const {
     spmv(h, val, x, b, dinv, y);
     if (id == PRECOND_KRONECKER) kronecker(y, y);
+    else if (id == PRECOND_BLOCK_JACOBI) blocks(y, y, nullptr);
   }
 
   // z = M r, and the partial sums of r . z into partial_rz when the caller wants them
@@ -583,6 +820,10 @@ struct Preconditioner {
     if (id == PRECOND_KRONECKER) {
       kronecker(r, z);
       if (partial_rz) dot(h, z, r, partial_rz);
+      return;
+    }
+    if (id == PRECOND_BLOCK_JACOBI) {
+      blocks(r, z, partial_rz);
       return;
     }
     if (!partial_rz) {   // (the fused kernel writes them always)
@@ -597,7 +838,7 @@ struct Preconditioner {
 Mirror<double> solve_matrix(mimi_hip_linear_s* h, const double* A_values, int preconditioner) {
   if (A_values) return Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, h->stream);
   if (!h->op_domain) fail("null argument (no matrix values, and no operator is set: mimi_hip_linear_set_operator)");
-  if (preconditioner == PRECOND_JACOBI) fail("the Jacobi preconditioner needs the matrix values");
+  if (preconditioner == PRECOND_JACOBI && !h->op_diagonal) fail("the Jacobi preconditioner needs the matrix values");
   if (h->op_fold) {
     // (set_operator_fold and set_operator checked these against what was set then; either may have changed since)
     const OperatorFold f = operator_fold(h->op_fold);
@@ -1003,6 +1244,23 @@ int mimi_hip_linear_set_operator_fold(mimi_hip_linear_t h, mimi_hip_fold_t fold)
   });
 }
 
+int mimi_hip_linear_set_node_block(mimi_hip_linear_t h, int32_t dim) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    if (dim < 1 || dim > 3) fail("node block: dim %d (1 to 3)", dim);
+    if (h->n % dim != 0) fail("node block: the handle's %lld dofs are no multiple of dim %d", (long long)h->n, dim);
+    if (h->node_block != dim) h->have_block_pos = false;
+    h->node_block = dim;
+  });
+}
+
+int mimi_hip_linear_set_operator_diagonal(mimi_hip_linear_t h, int32_t on) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    h->op_diagonal = on != 0;
+  });
+}
+
 int mimi_hip_linear_operator_mult(mimi_hip_linear_t h, const double* x, double* y) {
   return guarded([&] {
     if (!h || !x || !y) fail("null argument");
@@ -1029,13 +1287,16 @@ int mimi_hip_linear_operator_mult(mimi_hip_linear_t h, const double* x, double* 
 int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const double* A_values, const double* r, double* z) {
   return guarded([&] {
     if (!h || !r || !z) fail("null argument");
-    if (kind != PRECOND_JACOBI && kind != PRECOND_KRONECKER) fail("preconditioner kind %d (1 Jacobi, 2 Kronecker)", kind);
+    if (kind < PRECOND_JACOBI || kind > PRECOND_BLOCK_JACOBI) fail("preconditioner kind %d (1 Jacobi, 2 Kronecker, 3 node-block Jacobi)", kind);
     MH_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     Mirror<double> mr = Mirror<double>::in(r, (size_t)h->n, h->stage_b, s);
     Mirror<double> mz = Mirror<double>::inout(z, (size_t)h->n, h->stage_x, s);
-    Mirror<double> mA;   // the values: Jacobi alone reads them
-    if (kind == PRECOND_JACOBI && A_values) mA = Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, s);
+    Mirror<double> mA;   // the values: the two Jacobis alone read them; without them theirs is the operator's diagonal
+    if (kind != PRECOND_KRONECKER) {
+      if (A_values) mA = Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, s);
+      else if (h->op_domain && (kind == PRECOND_BLOCK_JACOBI || h->op_diagonal)) solve_matrix(h, nullptr, kind);
+    }
     const Preconditioner M(h, kind, mA.dev);
     M.apply(mr.dev, mz.dev, nullptr);
     mz.finish(s);

@@ -329,6 +329,16 @@ class NonlinearSolid(NonlinearBase):
                                                         fptr(x), fptr(y)))
         return y
 
+    def TangentDiagonal(self, out, stiffness=1.0, density=0.0, viscosity=0.0, block=False):
+        """out += the diagonal of density M + stiffness K(u of Linearize) + viscosity C, the operator ApplyTangent applies,
+        without a matrix (mimi_hip.h: "tangent diagonal").  block=False: n_nodes * dim values in byVDIM order; block=True: the
+        node blocks [A][i][j], n_nodes * dim * dim values, whose entries i == j are the diagonal to the bit.  No essential dofs.
+        What mfem::DSmoother reads off the assembled matrix.  numpy array or torch device tensor."""
+        self._follow_torch(out)
+        check(_capi.lib().mimi_hip_domain_tangent_diagonal(self._handle(), float(density), float(stiffness), float(viscosity),
+                                                           1 if block else 0, fptr(out)))
+        return out
+
     def LastActionFamily(self):
         """which kernel family the last ApplyTangent on this handle ran on (mimi_hip_domain_info(h, 9))"""
         return self.KERNEL_FAMILIES[int(_capi.lib().mimi_hip_domain_info(self._handle(), 9))]

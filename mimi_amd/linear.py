@@ -19,9 +19,10 @@ class LinearSolver(_capi.Handle):
     abs_tol = 1e-12
     max_iter = 300
     kdim = 50
-    # "jacobi": mfem::DSmoother, the reference's; "kronecker": the fast-diagonalisation operator of SetKronecker; "none"
+    # "jacobi": mfem::DSmoother, the reference's; "kronecker": the fast-diagonalisation operator of SetKronecker;
+    # "block_jacobi": the inverted dim x dim node blocks (SetNodeBlock); "none"
     preconditioner = "jacobi"
-    _PRECONDITIONER_IDS = {"none": 0, "jacobi": 1, "kronecker": 2}
+    _PRECONDITIONER_IDS = {"none": 0, "jacobi": 1, "kronecker": 2, "block_jacobi": 3}
 
     @property
     def use_jacobi(self):
@@ -81,16 +82,27 @@ class LinearSolver(_capi.Handle):
         check(_capi.lib().mimi_hip_linear_set_kronecker_coefficients(self._h, float(mass), fptr(stiff)))
 
     def ApplyPreconditioner(self, kind, A_values, r, z):
-        """z = M r as the solvers apply it: kind "jacobi" / 1 (needs A_values) or "kronecker" / 2 (A_values may be None)"""
+        """z = M r as the solvers apply it: kind "jacobi" / 1 (needs A_values, or None with SetOperatorDiagonal armed),
+        "kronecker" / 2 (A_values may be None) or "block_jacobi" / 3 (A_values, or None: the blocks of the operator)"""
         kind = self._PRECONDITIONER_IDS.get(kind, kind)
         self._follow_torch(A_values, r, z)
         check(_capi.lib().mimi_hip_linear_apply_preconditioner(self._h, int(kind), fptr(A_values), fptr(r), fptr(z)))
         return z
 
+    def SetNodeBlock(self, dim):
+        """the handle's n is n_nodes * dim in byVDIM order: what "block_jacobi" needs.  Refused when n % dim != 0."""
+        check(_capi.lib().mimi_hip_linear_set_node_block(self._h, int(dim)))
+
+    def SetOperatorDiagonal(self, on):
+        """arms "jacobi" for solves without matrix values: 1 / diag then comes from the operator's domain
+        (NonlinearSolid.TangentDiagonal), once per solve.  Off by default: "jacobi" with None values is refused."""
+        check(_capi.lib().mimi_hip_linear_set_operator_diagonal(self._h, 1 if on else 0))
+
     def SetOperator(self, domain, density, stiffness, viscosity):
         """a domain integrator in place of the matrix: Mult(None, b, x) / MultCG(None, b, x) then solve with the product
-        density M + stiffness K(u of domain.Linearize) + viscosity C, eliminated like the matrix.  Preconditioners "none" and
-        "kronecker"; "jacobi" needs the matrix values.  Solves that pass values run as ever."""
+        density M + stiffness K(u of domain.Linearize) + viscosity C, eliminated like the matrix.  Preconditioners "none",
+        "kronecker" and "block_jacobi"; "jacobi" needs the matrix values unless SetOperatorDiagonal armed it.  Solves that pass
+        values run as ever."""
         check(_capi.lib().mimi_hip_linear_set_operator(self._h, domain._handle(), float(density), float(stiffness), float(viscosity)))
         self._operator = domain          # (the library reads the handle during every solve)
         self._boundary_operators = []    # every SetOperator drops the boundary terms

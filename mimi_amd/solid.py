@@ -348,6 +348,8 @@ class Route(typing.NamedTuple):
     host_setup: bool = False            # mass, damping and right-hand side in numpy on the host
     consistent_contact: bool = False    # the contact actions carry the derivative of the nodal pressure as well
     friction_actions: bool = False      # ... and Coulomb friction, which is assembled only without it
+    operator_jacobi: bool = False       # matrix-free: the reference's Jacobi from the diagonal of the operator itself
+    block_jacobi: bool = False          # node-block (dim x dim per control point) Jacobi, assembled or matrix-free
 
 
 def resolve_route(rc, bc, axes):
@@ -367,6 +369,24 @@ def resolve_route(rc, bc, axes):
     iterative, kronecker = flag("use_iterative_solver"), flag("use_kronecker_preconditioner")
     matrix_free, boundary_actions = flag("matrix_free"), flag("matrix_free_boundary")
     host_setup = flag("host_setup")
+    # "matrix_free_jacobi": mfem::DSmoother without the matrix, 1 / diag from the domain integrator (TangentDiagonal);
+    # "use_block_jacobi_preconditioner": the inverted node blocks, out of the CSR values or from the domain integrator
+    operator_jacobi, block_jacobi = flag("matrix_free_jacobi"), flag("use_block_jacobi_preconditioner")
+    if operator_jacobi and block_jacobi:
+        raise RuntimeError("matrix_free_jacobi cannot be combined with use_block_jacobi_preconditioner: a solve has one "
+                           "preconditioner -- unset one of the two")
+    for name, on in (("matrix_free_jacobi", operator_jacobi), ("use_block_jacobi_preconditioner", block_jacobi)):
+        if on and kronecker:
+            raise RuntimeError(f"{name} cannot be combined with use_kronecker_preconditioner: a solve has one "
+                               "preconditioner -- unset one of the two")
+        if on and explicit:
+            raise RuntimeError(f"{name} cannot be combined with explicit_dynamics: an explicit step has no linear solve for "
+                               "it to act on -- unset one of the two")
+    if operator_jacobi and not matrix_free:
+        raise RuntimeError("matrix_free_jacobi needs matrix_free: with matrix values the Jacobi preconditioner reads the "
+                           "diagonal off them (use_iterative_solver alone)")
+    if block_jacobi and not iterative:
+        raise RuntimeError("use_block_jacobi_preconditioner needs use_iterative_solver: it preconditions the device GMRES")
     consistent_contact = flag("contact_consistent_tangent")
     if consistent_contact and explicit:
         raise RuntimeError("contact_consistent_tangent cannot be combined with explicit_dynamics: an explicit step has no "
@@ -401,9 +421,10 @@ def resolve_route(rc, bc, axes):
         raise RuntimeError("matrix_free_boundary needs matrix_free: it adds the contact and pressure tangents to the "
                            "matrix-free product")
     if matrix_free:                                                  # only what the action covers
-        if not (iterative and kronecker):
-            raise RuntimeError("matrix_free needs use_iterative_solver and use_kronecker_preconditioner: without matrix values "
-                               "there is neither a direct solve nor a Jacobi preconditioner")
+        if not (iterative and (kronecker or operator_jacobi or block_jacobi)):
+            raise RuntimeError("matrix_free needs use_iterative_solver and use_kronecker_preconditioner (or matrix_free_jacobi, "
+                               "or use_block_jacobi_preconditioner): without matrix values there is neither a direct solve nor "
+                               "a diagonal to read off them")
         if (bc.initial.contact_ or bc.current.contact_) and not boundary_actions:
             raise RuntimeError("matrix_free cannot be combined with a contact marker: the contact tangent has no matrix-free action")
         if bc.initial.pressure_ and not boundary_actions:
@@ -419,7 +440,7 @@ def resolve_route(rc, bc, axes):
     if explicit and host_setup:
         raise RuntimeError("explicit_dynamics cannot be combined with the host set-up: the lumped mass is assembled on the device")
     return Route(explicit, consistent, iterative, iterative and kronecker, matrix_free, boundary_actions, periodic_iterative, host_setup,
-                 consistent_contact, friction_actions)
+                 consistent_contact, friction_actions, operator_jacobi, block_jacobi)
 
 
 class NonlinearSolid(Solid, ExplicitDynamics):
@@ -677,6 +698,11 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         self.use_kronecker_, self._kronecker_pushed = False, None
         if route.kronecker:
             self._set_kronecker()
+        if route.block_jacobi:
+            self.linear_.SetNodeBlock(dim)
+            self.linear_.preconditioner = "block_jacobi"
+        if route.operator_jacobi:
+            self.linear_.SetOperatorDiagonal(True)    # ("jacobi" stays the solver's preconditioner)
         if self.fold_ is not None and (self.matrix_free_ or self.explicit_consistent_):
             # the operator handles stay in the unwrapped numbering: the solver's product expands and folds around them
             # (set once: it survives every SetOperator)

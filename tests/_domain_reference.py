@@ -28,17 +28,34 @@ imported (they are independent already).
                              inc = phi / (3 G + H_kin + H_iso), s <- s - sqrt(6) G inc eta / |eta|; committed eqps + inc,
                              eps_p + sqrt(3/2) inc eta / |eta|, beta + sqrt(2/3) H_kin inc eta / |eta|
                              (materials.hpp:187-236)
+                   j2log     F_e = F Fp_inv, E_e = 1/2 log(F_e^T F_e) (through `sym_eig`), p = K tr E_e, s = 2 G dev_dim E_e,
+                             q = sqrt(3/2) |s|, the scalar equation, root and radial return of j2, P = det F (s + p / det F I)
+                             F^-T; committed eqps + d, Fp_inv exp(-d N_p), the temperature untouched
+                             (materials.hpp:636-735, material_utils.hpp:91-114, materials.cpp:60-71, 221-241)
+                   j2simo    f_bar = (F_old F^-1)^-1 cbrt(det .) (multiplied, as written), be = f_bar be_old f_bar^T,
+                             s = G dev_dim be, N_p = sqrt(3/2) s / |s| (sqrt(1/2) I where |s| < DBL_EPSILON), s_eff = N_p : s,
+                             R(d) = s_eff - G tr(be) d - H(eqps + d) rate(d / dt) thermo(T), the root in
+                             [0, (s_eff - H(eqps) thermo) / (G tr be)] by the same bisection, be <- be - 2/3 d tr(be) N_p,
+                             P = (G dev_dim be + K/2 (det F^2 - 1) I) F^-T; committed eqps + d, T + chi s_eff d / (rho c)
+                             (temperature-dependent law), and, yielding or not, F_old = F, be_old = be
+                             (materials.hpp:455-564, materials.cpp:184-203)
                  dP/dF : dF by hand for the hyperelastic laws; for the J2 laws by implicit differentiation of the scalar
-                 equation, d delta = dq / (3 G + (H' rate + H rate' / dt) thermo) -- no difference quotient anywhere.
+                 equation, d delta = dq / (3 G + (H' rate + H rate' / dt) thermo) -- no difference quotient anywhere.  j2log:
+                 d E_e = Q ((Q^T dC Q) o Gamma) Q^T with Gamma_ab the divided differences of 1/2 log on the eigenvalues,
+                 (log a - log b) / (a - b) = 2 atanh(z) / (z (a + b)), z = (a - b) / (a + b), atanh(z) / z by its series where
+                 |z| < 1e-3: accurate where eigenvalues are close or equal, and Q need not be well determined there because
+                 Gamma is then constant to the same order.  j2simo: the product rule through f_bar, be, N_p, and
+                 d delta = (d s_eff - G delta d tr be) / (G tr be + (H' rate + H rate' / dt) thermo).
+    symmetric    `sym_eig`: cyclic Jacobi in long double, vectorised over the points (2 x 2 and 3 x 3), rotations skipped
+    functions    where the off-diagonal entry is exactly 0; `sym_fun` = Q f(lam) Q^T for 1/2 log and exp.
     sums         r_(A,i) = sum_q w det P_iJ dN_A/dX_J;  (K v)_(A,i) = sum_q w det dN_A/dX_J (dP/dF : dF_q(v))_iJ with
                  dF_q(v) = sum_B v_B (x) dN_B/dX;  the committed state per point;  and the three linear forms of
                  kernels_forms.hpp applied to a vector: mass rho sum w det N_A N_B v_(B,i), viscosity nu sum w det
                  (dN_A/dX . dN_B/dX) v_(B,i), body force b_i sum w det N_A.
 
-J2Simo and J2Log are not here: there is no long-double eigen-solver.  They stay pinned at 50 digits under homogeneous
-deformation (tests/test_finite_strain_*.py) and against the oracle elsewhere.
-
-Vectors are [n_nodes * dim], node-major (entry A * dim + i).  State matrices are [q, i, J]."""
+Vectors are [n_nodes * dim], node-major (entry A * dim + i).  State matrices are [q, i, J]; the state of the finite-strain laws
+is named as mimi_hip_domain_get_state orders it: eqps, temperature, the first matrix (Fp_inv | be_old), the second (F_old,
+j2simo only)."""
 import functools
 import types
 
@@ -49,6 +66,8 @@ from _cases import HARDENING_LAWS, POISSON, YOUNG, thermal_of
 
 LD = np.longdouble
 BISECTIONS = 100
+DBL_EPSILON = LD(2.220446049250313e-16)                 # AlmostZero (material_utils.hpp:14-17)
+SOLVER_LAWS = ("j2", "j2log", "j2simo")                 # the laws with a hardening law and a scalar equation
 
 
 # ---- points --------------------------------------------------------------------------------------------------------------
@@ -168,6 +187,62 @@ def eye(dim):
     return np.eye(dim, dtype=LD)
 
 
+def dev(A):
+    return A - tr(A)[..., None, None] / A.shape[-1] * eye(A.shape[-1])
+
+
+def sym_eig(A, sweeps=30):
+    """(lam [n, d], Q [n, d, d]) with A = Q diag(lam) Q^T for symmetric A [n, d, d]: cyclic Jacobi, every point rotated in
+    every step (by the identity where its off-diagonal entry is exactly 0), until every off-diagonal entry is below
+    1e-25 of the largest diagonal one"""
+    A = np.array(A, dtype=LD)
+    A = (A + T(A)) / 2
+    n, d = A.shape[0], A.shape[-1]
+    Q = np.broadcast_to(eye(d), A.shape).copy()
+    off = ~np.eye(d, dtype=bool)
+    for _ in range(sweeps):
+        if np.abs(A[:, off]).max(initial=0) <= LD(1e-25) * np.abs(A[:, ~off]).max(initial=0):
+            break
+        for p in range(d):
+            for q in range(p + 1, d):
+                apq = A[:, p, q]
+                on = apq != 0
+                tau = (A[:, q, q] - A[:, p, p]) / (2 * np.where(on, apq, LD(1)))
+                t = np.where(on, np.where(tau >= 0, LD(1), LD(-1)) / (np.abs(tau) + np.sqrt(1 + tau * tau)), LD(0))
+                c = 1 / np.sqrt(1 + t * t)
+                sn = t * c
+                R = np.broadcast_to(eye(d), A.shape).copy()
+                R[:, p, p], R[:, q, q], R[:, p, q], R[:, q, p] = c, c, sn, -sn
+                A = mm(mm(T(R), A), R)
+                A = (A + T(A)) / 2
+                A[:, p, q] = A[:, q, p] = 0
+                Q = mm(Q, R)
+    else:
+        raise AssertionError("the Jacobi sweeps do not converge")
+    return np.einsum("nii->ni", A).copy(), Q
+
+
+def spectral(Q, f):
+    """Q diag(f) Q^T"""
+    return np.einsum("nia,na,nja->nij", Q, f, Q)
+
+
+def sym_fun(A, f):
+    lam, Q = sym_eig(A)
+    return spectral(Q, f(lam))
+
+
+def half_log_differences(lam):
+    """Gamma[n, a, b] = (1/2 log lam_a - 1/2 log lam_b) / (lam_a - lam_b), 1 / (2 lam_a) on the diagonal"""
+    a, b = lam[:, :, None], lam[:, None, :]
+    z = (a - b) / (a + b)
+    z2 = z * z
+    series = 1 + z2 * (LD(1) / 3 + z2 * (LD(1) / 5 + z2 * (LD(1) / 7 + z2 * (LD(1) / 9 + z2 / 11))))
+    small = np.abs(z) < LD(1e-3)
+    zs = np.where(small, LD(0.5), z)
+    return np.where(small, series, np.arctanh(zs) / zs) / (a + b)
+
+
 # ---- geometry ------------------------------------------------------------------------------------------------------------
 def geometry(sp, X):
     """dX/dxi [q, I, d], its determinant (positive), w det, and dN_A/dX_J [q, A, J] on the control points X [n_nodes, dim]"""
@@ -258,9 +333,9 @@ class Hardening:
 
 def material(name, law=None, **thermal):
     """'neohook' | 'stvk' | 'j2' (law: a name of HARDENING_LAWS, the default JohnsonCookTempRate = _cases.JC_TEST) |
-    'j2linear' (the constants of _cases.oracle_material / product_material)"""
-    m = types.SimpleNamespace(name=name, stateful=name in ("j2", "j2linear"))
-    if name == "j2":
+    'j2log' | 'j2simo' (law: the same) | 'j2linear' (the constants of _cases.oracle_material / product_material)"""
+    m = types.SimpleNamespace(name=name, stateful=name in SOLVER_LAWS + ("j2linear",), solver=name in SOLVER_LAWS)
+    if m.solver:
         m.hardening = Hardening(law or "JohnsonCookTempRate", **thermal)
         m.density = LD(1)
     if name == "j2linear":
@@ -269,9 +344,18 @@ def material(name, law=None, **thermal):
 
 
 def virgin_state(mat, n, dim):
-    """eqps, plastic strain, temperature (j2), back stress (j2linear) of n points; None for the stateless laws"""
+    """eqps, plastic strain, temperature (j2), back stress (j2linear) of n points; eqps, temperature, Fp_inv = I (j2log);
+    eqps, temperature, be_old = F_old = I (j2simo); None for the stateless laws"""
     if not mat.stateful:
         return None
+    if mat.name in ("j2log", "j2simo"):
+        st = types.SimpleNamespace(eqps=np.zeros(n, dtype=LD), temperature=np.full(n, mat.hardening.thermal["initial_temperature"], dtype=LD))
+        one = np.broadcast_to(eye(dim), (n, dim, dim))
+        if mat.name == "j2log":
+            st.Fp_inv = one.copy()
+        else:
+            st.be_old, st.F_old = one.copy(), one.copy()
+        return st
     st = types.SimpleNamespace(eqps=np.zeros(n, dtype=LD), plastic_strain=np.zeros((n, dim, dim), dtype=LD))
     if mat.name == "j2":
         st.temperature = np.full(n, mat.hardening.thermal["initial_temperature"], dtype=LD)
@@ -294,13 +378,123 @@ def _pk1_from_cauchy(F, sigma, dsigmas, dFs):
     return P, dPs, frob(J[:, None, None] * FiT)
 
 
-def point_law(mat, F, state=None, dt=1.0, dFs=()):
+def _root(R, plastic, upper, scale):
+    """the root of the decreasing R in [0, upper] at the points of `plastic` (0 elsewhere) by plain bisection"""
+    lo, hi = np.zeros(len(upper), dtype=LD), np.where(plastic, upper, LD(0))
+    assert np.all(R(lo)[plastic] > 0) and np.all(R(hi)[plastic] <= 1e-15 * scale[plastic]), "the root is not bracketed"
+    for _ in range(BISECTIONS):
+        mid = (lo + hi) / 2
+        up = R(mid) > 0
+        lo, hi = np.where(up, mid, lo), np.where(up, hi, mid)
+    return np.where(plastic, (lo + hi) / 2, LD(0))
+
+
+def _finite_strain_law(mat, F, state, dt, dFs, delta=None):
+    """j2log and j2simo (module docstring).  Beyond what point_law returns for j2: slope0 [q] (the coefficient of d in the
+    scalar equation: 3 G | G tr be), stress_scale [q] (|dP| / |d delta| of the one-step bar derived in
+    tests/_finite_strain_return.py: 2 G sqrt(3/2) |det F F^-T|_F | G 2/3 tr(be) sqrt(3/2) |F^-T|_F), spectrum [q, dim] (the
+    eigenvalues of C_e | of the trial be), and cond [q] = cond(C_e) (j2log) or fbar2 [q] = |f_bar|_2^2 and tr_be [q] = tr of the
+    trial be (j2simo)"""
+    n, dim = F.shape[0], F.shape[-1]
+    I = eye(dim)
+    _, _, K, G = constants()
+    h = mat.hardening
+    J, Fi = det(F), inverse(F)
+    FiT = T(Fi)
+    dJs = [J * tr(mm(Fi, dF)) for dF in dFs]
+    thermo, e0 = h.thermo(state.temperature), state.eqps
+    r32 = np.sqrt(LD(3) / 2)
+    out = types.SimpleNamespace()
+    if mat.name == "j2log":
+        Fe = mm(F, state.Fp_inv)
+        lam, Q = sym_eig(mm(T(Fe), Fe))
+        E = spectral(Q, np.log(lam) / 2)
+        p, s = K * tr(E), 2 * G * dev(E)
+        q = r32 * frob(s)
+        slope0 = np.full(n, 3 * G, dtype=LD)
+        out.spectrum, out.cond = lam, lam.max(axis=1) / lam.min(axis=1)
+    else:
+        f0 = inverse(mm(state.F_old, Fi))
+        c = np.cbrt(det(f0))
+        fb = f0 * c[:, None, None]
+        be = mm(mm(fb, state.be_old), T(fb))
+        s = G * dev(be)
+        sn = frob(s)
+        small = sn < DBL_EPSILON
+        sns = np.where(small, LD(1), sn)
+        Np = np.where(small[:, None, None], np.sqrt(LD(1) / 2) * I, (r32 / sns)[:, None, None] * s)
+        q = ddot(Np, s)                                                          # s_effective
+        tr_be = tr(be)
+        slope0 = G * tr_be
+        out.tr_be, out.fbar2, out.spectrum = tr_be, sym_eig(mm(T(fb), fb))[0].max(axis=1), sym_eig(be)[0]
+    margin = q - h.H(e0) * thermo
+    plastic = margin > 0
+    if delta is None:
+        delta = _root(lambda d: q - slope0 * d - h.H(e0 + d) * h.rate(d / dt) * thermo, plastic, margin / slope0, q)
+    e1 = e0 + delta
+    slope = slope0 + (h.dH(e1) * h.rate(delta / dt) + h.H(e1) * h.drate(delta / dt) / dt) * thermo
+    new = types.SimpleNamespace(eqps=e1, temperature=state.temperature.copy())
+    if mat.name == "j2log":
+        qs = np.where(q > 0, q, LD(1))
+        Np = (LD(1.5) / qs)[:, None, None] * s
+        shrink = 1 - 3 * G * delta / qs                                          # s_new = s - 2 G delta N_p = s shrink
+        sigma = shrink[:, None, None] * s + (p / J)[:, None, None] * I
+        new.Fp_inv = mm(state.Fp_inv, sym_fun(-delta[:, None, None] * Np, np.exp))
+        Gamma = half_log_differences(lam)
+        dsigmas = []
+        for dF, dJ in zip(dFs, dJs):
+            dFe = mm(dF, state.Fp_inv)
+            dC = mm(T(dFe), Fe) + mm(T(Fe), dFe)
+            dE = mm(mm(Q, mm(mm(T(Q), dC), Q) * Gamma), T(Q))
+            dp, ds = K * tr(dE), 2 * G * dev(dE)
+            dq = LD(1.5) * ddot(s, ds) / qs
+            dd = np.where(plastic, dq / slope, LD(0))
+            dsn = shrink[:, None, None] * ds - (3 * G * (dd / qs - delta * dq / (qs * qs)))[:, None, None] * s
+            dsigmas.append(dsn + (dp / J - p * dJ / (J * J))[:, None, None] * I)
+        out.P, out.dP, out.JFinvT_norm = _pk1_from_cauchy(F, sigma, dsigmas, dFs)
+        out.stress_scale = 2 * G * r32 * out.JFinvT_norm
+    else:
+        flow = LD(2) / 3 * delta * tr_be
+        be_new = be - flow[:, None, None] * Np
+        tau = G * dev(be_new) + (K / 2 * (J * J - 1))[:, None, None] * I
+        out.P = mm(tau, FiT)
+        if h.temperature_dependent:
+            new.temperature = state.temperature + h.thermal["heat_fraction"] * q * delta / (mat.density * h.thermal["specific_heat"])
+        new.be_old, new.F_old = be_new, F.copy()
+        f0i = inverse(f0)
+        out.dP = []
+        for dF, dJ in zip(dFs, dJs):
+            dFi = -mm(mm(Fi, dF), Fi)
+            df0 = -mm(mm(f0, mm(state.F_old, dFi)), f0)
+            dc = c / 3 * tr(mm(f0i, df0))
+            dfb = df0 * c[:, None, None] + f0 * dc[:, None, None]
+            dbe = mm(mm(dfb, state.be_old), T(fb)) + mm(mm(fb, state.be_old), T(dfb))
+            ds = G * dev(dbe)
+            dn = ddot(s, ds) / sns
+            dq = np.where(small, LD(0), r32 * dn)
+            dNp = np.where(small[:, None, None], LD(0), r32 * (ds / sns[:, None, None] - (dn / (sns * sns))[:, None, None] * s))
+            dtr = tr(dbe)
+            dd = np.where(plastic, (dq - G * delta * dtr) / slope, LD(0))
+            dflow = LD(2) / 3 * (dd * tr_be + delta * dtr)
+            dbe_new = dbe - dflow[:, None, None] * Np - flow[:, None, None] * dNp
+            dtau = G * dev(dbe_new) + (K * J * dJ)[:, None, None] * I
+            out.dP.append(mm(dtau, FiT) + mm(tau, T(dFi)))
+        out.stress_scale = G * LD(2) / 3 * tr_be * r32 * frob(FiT)
+    out.new, out.plastic, out.margin, out.delta, out.q, out.slope0 = new, plastic, margin, delta, q, slope0
+    return out
+
+
+def point_law(mat, F, state=None, dt=1.0, dFs=(), delta=None):
     """the law at the points F [q, i, J] from `state`: a namespace with P [q, i, J], dP (one [q, i, J] per direction of
     dFs), and for the stateful laws the committed state `new`, plastic [q], margin [q] (the yield function of the trial
-    state), delta [q], q [q], JFinvT_norm [q]"""
+    state), delta [q], q [q] (the trial q | s_eff), JFinvT_norm [q]; more for j2log and j2simo (_finite_strain_law).
+    delta [q]: take this increment at the plastic points instead of the root (to see what a root that is off does to the
+    result: _domain_cases.root_shift; never as an answer)"""
     F = np.asarray(F, dtype=LD)
     dFs = [np.asarray(d, dtype=LD) for d in dFs]
     n, dim = F.shape[0], F.shape[-1]
+    if mat.name in ("j2log", "j2simo"):
+        return _finite_strain_law(mat, F, virgin_state(mat, n, dim) if state is None else state, LD(dt), dFs, delta)
     I = eye(dim)
     lam, mu, K, G = constants()
     out = types.SimpleNamespace(new=None)
@@ -343,13 +537,9 @@ def point_law(mat, F, state=None, dt=1.0, dFs=()):
             return q - 3 * G * d - h.H(e0 + d) * h.rate(d / dt) * thermo
 
         plastic = margin > 0
-        lo, hi = np.zeros(n, dtype=LD), np.where(plastic, margin / (3 * G), LD(0))
-        assert np.all(R(lo)[plastic] > 0) and np.all(R(hi)[plastic] <= 1e-15 * q[plastic]), "the root is not bracketed"
-        for _ in range(BISECTIONS):
-            mid = (lo + hi) / 2
-            up = R(mid) > 0
-            lo, hi = np.where(up, mid, lo), np.where(up, hi, mid)
-        delta = np.where(plastic, (lo + hi) / 2, LD(0))
+        if delta is None:
+            delta = _root(R, plastic, margin / (3 * G), q)
+        out.slope0 = np.full(n, 3 * G, dtype=LD)
         qs = np.where(q > 0, q, LD(1))
         Np = (LD(1.5) / qs)[:, None, None] * s
         sigma = s - (2 * G * delta)[:, None, None] * Np + p[:, None, None] * I

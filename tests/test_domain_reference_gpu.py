@@ -3,17 +3,24 @@ against the long-double reference of tests/_domain_reference.py under INHOMOGENE
 inputs and bars: tests/_domain_cases.py; the reference itself and the inputs are checked without a GPU in
 tests/test_domain_reference_cpu.py.
 
+Materials: neo-Hookean, StVK, J2 (three laws), J2Linear, and J2Log and J2Simo (default law, PowerLaw, and an [elastic] variant at
+a tenth of the displacements in which no point yields while the lanes still diverge in the eigen-solver) -- dc.FINITE_PAIRS.
+
 Per (case, material): DomainPostTimeAdvance(u0) where the law has state and State(...) per point (sorted values first, so that
 a misread layout shows as a layout error, then point by point through the (element, point) layout of include/mimi_hip.h);
 AddDomainResidual, then AddDomainResidualAndGrad twice, in accumulate form on random r0 / A0 with grad_factor 0.37: the
 residual increments entrywise, the increment of A times a random, a smooth and a single-node vector against the reference's
 K v row by row, and for the hyperelastic laws the symmetry of the increment (the symmetric-half kernel assumes it).  Every
 assembly asserts its kernel family.  Element boxes: each handle against the reference restricted to its parameter range, and
-their sum against the whole.  Linear forms: body force entrywise, mass and viscosity through the three vectors.
+their sum against the whole.  A second step on dc.SECOND_PAIRS: a second commit at u, the state again, the assemblies at a
+third field from it (J2Log's Fp_inv is non-symmetric only then).  Linear forms: body force entrywise, mass and viscosity through the three vectors.
 
 Bars: residual 1e-12 and tangent 1e-11 of the largest reference entry; J2 residual per row the derived
 _domain_cases.residual_bar, J2 tangent + _domain_cases.J2_TANGENT_BAR (measured on the CPU on the oracle, never here), J2 state
 2 x SOLVER_XTOL (eqps), sqrt(3/2) x (plastic strain), chi q / (rho c) x (temperature); linear forms 1e-13; symmetry 1e-12.
+J2Log and J2Simo: the residual bar carries an earlier commit's error with the point's own `carry` (dc.stress_bar_points), the
+state bars are derived in dc.state_bars (both steps), the tangent + dc.FINITE_TANGENT_BAR; the [elastic] variants are held to
+the plain 1e-12 / 1e-11 and their state to 1e-12 of the largest entry.
 
 Measured on the MI355X (worst per family; test_report prints this table): residual relative to max |r| (and as a share of
 its row bar), K v relative to max |K v|, asymmetry, state as a share of its bar
@@ -25,7 +32,16 @@ its row bar), K v relative to max |K v|, asymmetry, state as a share of its bar
   asymmetry of the hyperelastic increments <= 7.3e-16 (bar 1e-12); the J2 tangent figures are the oracle's own to two digits
   (_domain_cases.J2_TANGENT_MEASURED: the solver's root, not rounding), bar 1e-8 (Johnson-Cook laws) and 1.8e-11 (PowerLaw)
   linear forms         body force <= 1.1e-15, mass <= 2.3e-15, viscosity <= 9.7e-15 (nonuni3d_p2), bar 1e-13
-The whole module takes 12 s."""
+  the finite-strain laws: residual relative (share of its row bar), K v, state (second commit) as a share of its bar
+  family               J2Log                                   J2Simo                                  [PowerLaw] Log | Simo: K v
+  tensor_small         1.6e-11 (1.9e-2), 3.3e-10, 0.21 (0.015)  1.9e-12 (4.1e-4), 2.3e-12, 0.007 (0.015)
+  tensor_p2_two_phase  8.0e-12 (1.1e-3), 7.4e-9,  0.37          2.6e-11 (1.8e-3), 3.4e-10, 0.39         5.8e-13 | 4.5e-13
+  tensor_p3_two_phase  5.0e-12 (7.2e-4), 4.8e-13, 0.25 (0.081)  3.6e-12 (3.5e-4), 1.1e-10, 0.12 (0.040)  1.0e-12 | 6.8e-13
+  general              2.6e-12 (1.4e-3), 1.7e-9,  0.11          3.5e-12 (5.2e-4), 4.4e-10, 0.37
+  the tangent figures are again the solver's root (dc.root_shift gives them from the reference alone): bars 1e-8 (J2Log),
+  4.4e-9 (J2Simo), 2e-11 (PowerLaw); the [elastic] variants: residual <= 4.4e-14, K v <= 3.1e-15, J2Simo's state (be_old,
+  F_old) <= 2.8e-3 of 1e-12, J2Log's equal to the bit
+The whole module takes 22 s, 9 s of them the finite-strain laws."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -40,7 +56,7 @@ WORST = {}          # (family, material class) -> {figure: worst}, for test_repo
 
 
 def note(family, matname, **fig):
-    cls = "j2" if dc.is_j2(matname) else matname
+    cls = "j2" if dc.is_j2(matname) else matname          # (the finite-strain laws: a class per model and law)
     w = WORST.setdefault((family, cls), {})
     for k, v in fig.items():
         w[k] = max(w.get(k, 0.0), float(v))
@@ -72,23 +88,24 @@ def csr(case, values):
     return sp.csr_matrix((values, col, rowptr), shape=(n, n))
 
 
-def check_assemblies(G, ref, family, label, mask=None):
-    """the three assemblies in accumulate form against the reference (restricted to the points of `mask`); returns the
-    increments (r, A) of the tangent call"""
+def check_assemblies(G, ref, family, label, mask=None, step=1):
+    """the three assemblies in accumulate form against the reference (restricted to the points of `mask`) at u (step 1) or at
+    u2 of the second step; returns the increments (r, A) of the tangent call"""
     case, matname, geo = ref.case, ref.matname, ref.geo
-    want_r = f64(ref.asm.r if mask is None else dr.nodal(geo, ref.asm.pt.P, mask))
-    want_Kv = [f64(k) if mask is None else f64(dr.nodal(geo, dP, mask)) for k, dP in zip(ref.asm.Kv, ref.asm.pt.dP)]
-    bar_r = dc.residual_bar(ref, mask)
+    asm, u = dc.steps_of(ref, step)[0], (ref.u if step == 1 else ref.second.u)
+    want_r = f64(asm.r if mask is None else dr.nodal(geo, asm.pt.P, mask))
+    want_Kv = [f64(k) if mask is None else f64(dr.nodal(geo, dP, mask)) for k, dP in zip(asm.Kv, asm.pt.dP)]
+    bar_r = dc.residual_bar(ref, mask, step)
     n, nnz = want_r.size, len(dc.pattern(case)[1])
     r0 = np.random.default_rng(3).standard_normal(n)
     A0 = np.random.default_rng(4).standard_normal(nnz)
     r_g = r0.copy()
-    G.AddDomainResidual(ref.u, r_g)
+    G.AddDomainResidual(u, r_g)
     assert G.LastKernelFamily() == family
     fig = dict(residual_only=(np.abs((r_g - r0) - want_r) / bar_r).max())
     for k in range(2):
         r_g, A_g = r0.copy(), A0.copy()
-        G.AddDomainResidualAndGrad(ref.u, GRAD_FACTOR, r_g, A_g)
+        G.AddDomainResidualAndGrad(u, GRAD_FACTOR, r_g, A_g)
         assert G.LastKernelFamily() == family
         dr_, dA = r_g - r0, A_g - A0
         fig["residual"] = max(fig.get("residual", 0.0), (np.abs(dr_ - want_r) / bar_r).max())
@@ -121,8 +138,21 @@ def test_kernels_against_the_reference(case, matname):
     check_assemblies(G, ref, family, case)
 
 
+@pytest.mark.parametrize("case,matname", dc.SECOND_PAIRS, ids=lambda v: v)
+def test_second_step_against_the_reference(case, matname):
+    """commit at u0, commit at u, the state again, then the assemblies at u2 from it: J2Log's Fp_inv is no longer symmetric
+    (dc.conditions: beyond 1e4 bars at >= 5 % of the points), so a stored symmetrised or transposed matrix fails here"""
+    ref = dc.reference(case, matname)
+    family = dc.arrays(case).family
+    G = handle(case, matname)
+    G.DomainPostTimeAdvance(ref.u0)
+    G.DomainPostTimeAdvance(ref.u)
+    note(family, matname, state_2=dc.compare_state(ref, G.State, dr.layout(ref.geo.sp), f"{case} {matname} second commit", step=2))
+    check_assemblies(G, ref, family, f"{case} second step", step=2)
+
+
 # ---- element boxes ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("matname", ["neohook", "stvk", "j2"])
+@pytest.mark.parametrize("matname", ["neohook", "stvk", "j2", "j2log", "j2simo"])
 def test_element_boxes_match_their_parameter_range(matname):
     case = dc.BOX_CASE
     ref = dc.reference(case, matname)

@@ -1,5 +1,6 @@
 """Field output on the device (include/mimi_hip.h, "field output") against the numpy yardstick of tests/_fields.py on the
-oracle, against closed forms, and its properties: range, reproducibility, composition over element boxes, numbering,
+oracle, for J2Log and J2Simo against the long-double reference of tests/_domain_reference.py on inhomogeneous fields (1b),
+against closed forms, and its properties: range, reproducibility, composition over element boxes, numbering,
 storage, no table materialisation on the tensor route, errors, and the facade (field(), save cadence, periodic fold, example).
 
 Bars.  Parity: relmax = max|a - b| / max|b| <= 1e-11, the project's tangent bar (the residual's 1e-12 is a bar on sums of
@@ -98,6 +99,45 @@ def test_parity_with_the_yardstick(shape, matname):
     if creator == "bspline":
         assert holds_tables(G) == 0
         assert G.LastKernelFamily() != "general"
+
+
+# ---- 1b. the finite-strain laws against the long-double reference ---------------------------------------------------------------
+@pytest.mark.parametrize("model", ["j2log", "j2simo"])
+@pytest.mark.parametrize("case", ["rep2d_p3", "col5_p3"])
+def test_finite_strain_point_fields_against_the_reference(case, model):
+    """After the commit at u0, the point fields at u on the inhomogeneous inputs of tests/_domain_cases.py against
+    tests/_domain_reference.py: sigma = P F^T / det F (column-major), its von Mises value sqrt(3/2) |dev_dim sigma|; eqps and
+    temperature equal to the bit to State(...).  Bar per point: the parity bar 1e-11 of the largest entry, plus the derived
+    stress bar of the point (dc.stress_bar_points: the solver's 1e-10 at the points that are or were plastic) divided by
+    det F |F^-T|_F -- P = det F sigma F^-T, so that is the bound on |d sigma|_F behind the bar on P; sqrt(3/2) times it for the
+    von Mises value (|dq| <= sqrt(3/2) |d dev sigma|_F)."""
+    import _domain_cases as dc
+    import _domain_reference as dr
+    from test_domain_reference_gpu import handle
+    ref = dc.reference(case, model)
+    dim = ref.geo.sp.dim
+    G = handle(case, model)
+    G.DomainPostTimeAdvance(ref.u0)
+    grid = dr.layout(ref.geo.sp)
+    F = dr.deformation_gradient(ref.geo, ref.u)
+    J = dr.det(F)
+    sigma = dr.mm(ref.asm.pt.P, dr.T(F)) / J[:, None, None]
+    q = np.sqrt(dc.LD(3) / 2) * dr.frob(dr.dev(sigma))
+    solver = dc.stress_bar_points(ref) / dc.f64(J * dr.frob(dr.T(dr.inverse(F))))
+    want = {"cauchy_stress": (dc.f64(np.swapaxes(sigma, 1, 2).reshape(len(J), -1)), solver),
+            "von_mises_stress": (dc.f64(q)[:, None], np.sqrt(1.5) * solver)}
+    for name, (w, extra) in want.items():
+        got = G.PointField(name, ref.u)
+        assert got.shape == grid.shape + (w.shape[1],)
+        bar = 1e-11 * np.abs(w).max() + extra[grid]
+        err = np.abs(got - w[grid]) / bar[..., None]
+        print(f"{case} {model} {name}: {err.max():.2e} of the bar, {relmax(got, w[grid]):.2e} relative")
+        assert err.max() <= 1.0
+    assert (solver > 0).mean() > 0.3 and (solver == 0).mean() > 0.05          # both kinds of points are there
+    for name in ("accumulated_plastic_strain", "temperature"):
+        a = G.PointField(name, None)
+        assert a.shape == grid.shape + (1,) and np.array_equal(a[..., 0], G.State(name))
+        assert np.array_equal(G.PointField(name, ref.u), a)
 
 
 # ---- 2. closed form, no oracle -------------------------------------------------------------------------------------------------

@@ -1,10 +1,12 @@
 """The matrix-free tangent action (csrc/kernels_apply.hpp) through the C ABI: NonlinearSolid.Linearize / ApplyTangent,
 LinearSolver.SetOperator and the facade's "matrix_free" flag.
 
-(1) the stiffness action on every (case, material) of tests/_domain_cases.py against the long-double reference's K v, within
-    the bar the assembled tangent is held to (dc.tangent_bar, relative to max |K v|); the kernel family and the bytes of record;
+(1) the stiffness action on every (case, material) of tests/_domain_cases.py -- J2Log and J2Simo with their three laws among
+    them (dc.FINITE_PAIRS) -- against the long-double reference's K v, within the bar the assembled tangent is held to
+    (dc.tangent_bar, relative to max |K v|); the kernel family and the bytes of record;
 (2) the mass and viscosity terms against dr.mass_times / dr.diffusion_times within dc.FORMS_BAR, and their sum in one call;
-(3) J2Simo and J2Log (no long-double reference) against the handle's own assembled tangent within dc.TANGENT_BAR;
+(3) J2Simo and J2Log against the handle's own assembled tangent within dc.TANGENT_BAR, and on the same cases against the
+    reference's K v within dc.tangent_bar: a tangent record that is wrong in the assembly and the action alike fails the second;
 (4) element boxes: the sum of the boxes' actions is the whole;
 (5) semantics: equal bytes, the snapshot, the refusal, host and device arguments, symmetry;
 (6) solves with the operator on the systems of test_kronecker_gpu.py: the iteration count of the restated GMRES, the solution
@@ -133,6 +135,12 @@ def test_finite_strain_laws_against_the_assembled_tangent(case, model):
     assert worst <= dc.TANGENT_BAR
     assert info(G, 9) == FAMILY_CODES[a.family]
     assert info(G, 10) == G.n_elements_ * G.n_quad_ * a.dim ** 4 * 8
+    # independently: the same model at its own inputs (dc.SEEDS) against the long-double reference's K v
+    G, r = linearized(case, model)
+    worst = max(relmax(action(G, v), Kv) for v, Kv in zip(r.vectors, r.asm.Kv))
+    print(f"{case} {model} [{a.family}]: action deviates {worst:.2e} from the reference's K v (bar {dc.tangent_bar(model):.2e})")
+    assert worst <= dc.tangent_bar(model)
+    assert info(G, 9) == FAMILY_CODES[a.family]
 
 
 # ---- (4) ---------------------------------------------------------------------------------------------------------------------

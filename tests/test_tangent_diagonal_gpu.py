@@ -5,22 +5,19 @@ NonlinearSolid.TangentDiagonal.
     against the long-double tangent of tests/_domain_reference.py -- dP/dF at every point from the unit directions e_j (x) e_L,
     the node blocks sum_q w det d_J N_A (dP_iJ/dF_jL) d_L N_A cut out in numpy -- within dc.tangent_bar, relative to the
     largest entry (the normalisation of test_matrix_free_gpu.py::test_stiffness_action_against_the_reference);
-(2) J2Simo and J2Log (no long-double reference) against the node blocks of the handle's own assembled tangent within
-    dc.TANGENT_BAR;
+(2) J2Simo and J2Log against the node blocks of the handle's own assembled tangent within dc.TANGENT_BAR, and on the same
+    cases against the long-double node blocks of (1) within dc.tangent_bar;
 (3) the mass and viscosity terms against the node blocks of the device-assembled AddMass / AddDiffusion within dc.FORMS_BAR;
 (4) against the action itself, no matrix anywhere: column j of block A is rows (A, .) of ApplyTangent(e_(A, j));
 (5) symmetry of the hyperelastic blocks within dc.SYMMETRY_BAR;
 (6) the contract: += into a prefilled array, equal bytes from two calls and from a device tensor, block=False equal TO THE
     BIT to the diagonal of block=True (both modes run one instruction stream per component), element boxes add up, the
     snapshot survives a commit, another dt and an overwritten u, the two refusals."""
-import functools
-
 import numpy as np
 import pytest
 import scipy.sparse as sp
 
 import _domain_cases as dc
-import _domain_reference as dr
 from _cases import product_material
 from _domain_cases import DT, f64
 from test_matrix_free_gpu import action, handle, linearized, relmax
@@ -38,24 +35,7 @@ CASES = ["one2d_p1", "one3d_p2",      # single element, no neighbour sums
 MATERIALS = ["neohook", "stvk", "j2"]
 
 
-@functools.lru_cache(maxsize=None)
-def reference_blocks(case, matname):
-    """D[A, i, j] of the stiffness term in long double, from the inputs and the state of dc.reference(case, matname)"""
-    r = dc.reference(case, matname)
-    geo, dim = r.geo, r.geo.sp.dim
-    n = len(geo.wdet)
-    units = []
-    for j in range(dim):
-        for L in range(dim):
-            E = np.zeros((n, dim, dim), dtype=dc.LD)
-            E[:, j, L] = 1
-            units.append(E)
-    pt = dr.point_law(r.mat, dr.deformation_gradient(geo, r.u), r.state, DT, units)
-    C = np.stack(pt.dP, axis=-1).reshape(n, dim, dim, dim, dim)                 # [q, i, J, j, L]
-    half = np.einsum("qAJ,qiJjL->qAijL", geo.dNdX, C)
-    D = np.einsum("q,qAijL,qAL->Aij", geo.wdet, half, geo.dNdX)
-    D.setflags(write=False)
-    return D
+reference_blocks = dc.reference_blocks          # D[A, i, j] of the stiffness term in long double (tests/_domain_cases.py)
 
 
 def diagonal(G, n_nodes, dim, block, **coefficients):
@@ -104,6 +84,13 @@ def test_finite_strain_laws_against_the_assembled_tangent(case, model):
     dev = relmax(diagonal(G, a.n_nodes, a.dim, True), want)
     print(f"\n{case} {model} [{a.family}]: blocks deviate {dev:.2e} from the assembled tangent's (bar {dc.TANGENT_BAR:.2e})")
     assert dev <= dc.TANGENT_BAR
+    # independently: the same model at its own inputs (dc.SEEDS) against the long-double node blocks
+    G, r = linearized(case, model)
+    want = reference_blocks(case, model)
+    dev_b = relmax(diagonal(G, a.n_nodes, a.dim, True), want)
+    dev_d = relmax(diagonal(G, a.n_nodes, a.dim, False), np.einsum("Aii->Ai", want))
+    print(f"{case} {model} [{a.family}]: blocks deviate {dev_b:.2e}, diagonal {dev_d:.2e} from the reference's (bar {dc.tangent_bar(model):.2e})")
+    assert dev_b <= dc.tangent_bar(model) and dev_d <= dc.tangent_bar(model)
 
 
 # ---- (3) ---------------------------------------------------------------------------------------------------------------------

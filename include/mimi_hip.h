@@ -25,6 +25,15 @@
  *    the message the reference would have thrown as std::runtime_error
  *    (utils/print.hpp:47-56).  Not re-entrant per handle (like the reference:
  *    mutable work data, nonlinear_solid.hpp:42).
+ *  - KERNEL-RAISED ERRORS (a return map whose ScalarSolve finds its root not bracketed or does not converge, where the
+ *    reference throws from inside the evaluation) are raised on the device into a status word of the handle.  With a HOST
+ *    argument the call is synchronous and reports the error itself.  With DEVICE arguments only the call has merely
+ *    enqueued: it returns 0, and the error is reported by the next mimi_hip_domain_synchronize on the handle, or by the
+ *    next call on it that waits (any call with a host argument) -- whichever comes first, and possibly a call that did
+ *    nothing wrong itself.  A caller that keeps everything on the device therefore synchronises the handle wherever the
+ *    reference's throw has to surface: after an evaluation whose result it is about to use, and after
+ *    mimi_hip_domain_post_time_advance.  The error is reported ONCE: reading the word clears it, and the handle stays
+ *    usable (the failed kernel ran to its end: a point whose return map failed took no plastic step).
  */
 #ifndef MIMI_HIP_H
 #define MIMI_HIP_H

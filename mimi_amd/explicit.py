@@ -237,13 +237,15 @@ class ExplicitDynamics:
         if self.explicit_consistent_:
             self.d_v_.mul_(self.d_free_).add_(self.d_vbar_)          # v = 0 on fixed dofs, the prescribed value on the others
             self._consistent_solve(0.0)                              # rho M a_0 = f - r_0 - eta C v_0
-            self._ex_started = True
-            return
-        r, d = self._ex_r[0], None
-        self._explicit_forces(self.d_x_, r)
-        if self._ex_d is not None:
-            d = self._explicit_action(self.d_v_, self._ex_d[0], 0.0, self._ex_eta)
-        self.explicit_stepper_.Start(self.d_v_, self._rhs, r, d)
+        else:
+            r, d = self._ex_r[0], None
+            self._explicit_forces(self.d_x_, r)
+            if self._ex_d is not None:
+                d = self._explicit_action(self.d_v_, self._ex_d[0], 0.0, self._ex_eta)
+            self.explicit_stepper_.Start(self.d_v_, self._rhs, r, d)
+        # outside the step loop a wait costs nothing: a return map that fails at the start displacement raises here, before a
+        # step is taken or anything is committed (inside the loop the words are read once per explicit_steps call)
+        self._raise_device_errors()
         self._ex_started = True
 
     def _explicit_download(self):

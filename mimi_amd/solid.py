@@ -865,6 +865,15 @@ class NonlinearSolid(Solid, ExplicitDynamics):
             else:
                 c._history()
 
+    def _raise_device_errors(self):
+        """The integrators get device tensors, so their calls only enqueue and an error raised by a kernel -- a return map
+        that cannot solve its scalar equation, where the reference throws out of the evaluation -- waits in the handle's status
+        word (include/mimi_hip.h: "kernel-raised errors").  Read the words: called where the host has just waited for the
+        stream anyway, so it costs one 4-byte copy per integrator.  Raises the reference's RuntimeError; the words are cleared
+        and the integrators stay usable."""
+        for integ in self.integrators_:
+            integ.Synchronize()
+
     def _displacement(self, u):
         """the current displacement (u None) or the host vector u in this facade's numbering, as a device vector"""
         if u is None:
@@ -946,7 +955,14 @@ class NonlinearSolid(Solid, ExplicitDynamics):
     def _newton_solve(self, x0):                      # solvers/newton.cpp:10-218
         torch = self._torch
         o = self._newton
-        nrm = lambda t: float(torch.linalg.vector_norm(t))
+
+        def nrm(t):
+            """the norm of a residual on the host, and with it whether the evaluation behind it failed on the device: a step
+            whose return map fails raises here, before anything is committed, as the reference throws out of StepTime2"""
+            value = float(torch.linalg.vector_norm(t))
+            self._raise_device_errors()
+            return value
+
         x = x0.clone() if o["iterative_mode"] else torch.zeros_like(x0)
         improved, i_improved = [True] * 5, 0
         best_res, best_x = np.finfo(float).max, x.clone()
@@ -1034,6 +1050,7 @@ class NonlinearSolid(Solid, ExplicitDynamics):
                 self._a = self.linear_.MultCG(self.d_mass_, z, torch.zeros_like(z))
             else:
                 self._a = torch.from_numpy(spla.splu(self._csr(self.mass_).tocsc()).solve(z.cpu().numpy())).to(x.device)
+            self._raise_device_errors()                # (the evaluation at the initial x)
             self._aa = torch.zeros_like(x)
             self._nstate = 1
         a = self._a
@@ -1074,6 +1091,7 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         # PostTimeAdvance (operators/nonlinear_solid.cpp:285-292)
         self._push(self.domain_)
         self._post_time_advance(x)
+        self._raise_device_errors()                    # (the commit runs the return map once more: before the time moves on)
         self.current_time += dt
         # the arrays solution_view handed out (zero-copy views of the reference: py_solid.cpp:379-388)
         self.x[:] = x.cpu().numpy()

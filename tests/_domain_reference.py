@@ -276,8 +276,8 @@ def constants():
 class Hardening:
     """a law of _cases.HARDENING_LAWS in long double, vectorised: H, H', rate, rate', thermo (material_hardening.hpp:79-346)"""
 
-    def __init__(self, law, **thermal):
-        oracle, _, attrs = HARDENING_LAWS[law]
+    def __init__(self, law, table=None, **thermal):
+        oracle, _, attrs = (HARDENING_LAWS if table is None else table)[law]
         self.law, self.kind = law, oracle["kind"]
         self.a = {k: LD(float(v)) for k, v in attrs.items()}
         self.a.setdefault("C", LD(0))                     # (JohnsonCookRateDependentHardening::C_ unset: the fixtures' 0)
@@ -331,12 +331,13 @@ class Hardening:
         return np.ones_like(temp)
 
 
-def material(name, law=None, **thermal):
+def material(name, law=None, table=None, **thermal):
     """'neohook' | 'stvk' | 'j2' (law: a name of HARDENING_LAWS, the default JohnsonCookTempRate = _cases.JC_TEST) |
-    'j2log' | 'j2simo' (law: the same) | 'j2linear' (the constants of _cases.oracle_material / product_material)"""
+    'j2log' | 'j2simo' (law: the same) | 'j2linear' (the constants of _cases.oracle_material / product_material);
+    table: a dict in the format of HARDENING_LAWS to take the law from instead (tests/_status_cases.py)"""
     m = types.SimpleNamespace(name=name, stateful=name in SOLVER_LAWS + ("j2linear",), solver=name in SOLVER_LAWS)
     if m.solver:
-        m.hardening = Hardening(law or "JohnsonCookTempRate", **thermal)
+        m.hardening = Hardening(law or "JohnsonCookTempRate", table, **thermal)
         m.density = LD(1)
     if name == "j2linear":
         m.h_iso, m.h_kin, m.sigma_y = LD(40.0), LD(25.0), LD(70.0)
@@ -389,6 +390,52 @@ def _root(R, plastic, upper, scale):
     return np.where(plastic, (lo + hi) / 2, LD(0))
 
 
+def trial_state(mat, F, state):
+    """the trial state of a law with a scalar equation (j2, j2log, j2simo) at the points F [q, i, J] from `state`, before any
+    root is sought: q [q] (the trial q | s_eff) and limit [q] = H(eqps) thermo(T), the yield stress the trial q is held
+    against (sigma_y thermo on the virgin state) -- a point yields where q > limit -- with the pieces the law goes on with
+    (p, s, thermo, and for the finite-strain laws slope0 and their kinematics).  point_law and _finite_strain_law start from
+    it; tests/_status_cases.py takes its predicate "this point yields" from it"""
+    F = np.asarray(F, dtype=LD)
+    dim = F.shape[-1]
+    I = eye(dim)
+    _, _, K, G = constants()
+    h = mat.hardening
+    r32 = np.sqrt(LD(3) / 2)
+    thermo = h.thermo(state.temperature)
+    t = types.SimpleNamespace(thermo=thermo, limit=h.H(state.eqps) * thermo, r32=r32)
+    if mat.name == "j2":
+        eps = (F + T(F)) / 2 - I - state.plastic_strain
+        t.p = K * tr(eps)
+        t.s = 2 * G * (eps - tr(eps)[:, None, None] / dim * I)
+        t.q = r32 * frob(t.s)
+        return t
+    n = F.shape[0]
+    t.J, t.Fi = det(F), inverse(F)
+    t.FiT = T(t.Fi)
+    if mat.name == "j2log":
+        t.Fe = mm(F, state.Fp_inv)
+        t.lam, t.Q = sym_eig(mm(T(t.Fe), t.Fe))
+        E = spectral(t.Q, np.log(t.lam) / 2)
+        t.p, t.s = K * tr(E), 2 * G * dev(E)
+        t.q = r32 * frob(t.s)
+        t.slope0 = np.full(n, 3 * G, dtype=LD)
+    else:
+        t.f0 = inverse(mm(state.F_old, t.Fi))
+        t.c = np.cbrt(det(t.f0))
+        t.fb = t.f0 * t.c[:, None, None]
+        t.be = mm(mm(t.fb, state.be_old), T(t.fb))
+        t.s = G * dev(t.be)
+        t.sn = frob(t.s)
+        t.small = t.sn < DBL_EPSILON
+        t.sns = np.where(t.small, LD(1), t.sn)
+        t.Np = np.where(t.small[:, None, None], np.sqrt(LD(1) / 2) * I, (r32 / t.sns)[:, None, None] * t.s)
+        t.q = ddot(t.Np, t.s)                                                    # s_effective
+        t.tr_be = tr(t.be)
+        t.slope0 = G * t.tr_be
+    return t
+
+
 def _finite_strain_law(mat, F, state, dt, dFs, delta=None):
     """j2log and j2simo (module docstring).  Beyond what point_law returns for j2: slope0 [q] (the coefficient of d in the
     scalar equation: 3 G | G tr be), stress_scale [q] (|dP| / |d delta| of the one-step bar derived in
@@ -399,35 +446,17 @@ def _finite_strain_law(mat, F, state, dt, dFs, delta=None):
     I = eye(dim)
     _, _, K, G = constants()
     h = mat.hardening
-    J, Fi = det(F), inverse(F)
-    FiT = T(Fi)
+    t = trial_state(mat, F, state)
+    J, Fi, FiT, thermo, e0, r32, q, slope0, s = t.J, t.Fi, t.FiT, t.thermo, state.eqps, t.r32, t.q, t.slope0, t.s
     dJs = [J * tr(mm(Fi, dF)) for dF in dFs]
-    thermo, e0 = h.thermo(state.temperature), state.eqps
-    r32 = np.sqrt(LD(3) / 2)
     out = types.SimpleNamespace()
     if mat.name == "j2log":
-        Fe = mm(F, state.Fp_inv)
-        lam, Q = sym_eig(mm(T(Fe), Fe))
-        E = spectral(Q, np.log(lam) / 2)
-        p, s = K * tr(E), 2 * G * dev(E)
-        q = r32 * frob(s)
-        slope0 = np.full(n, 3 * G, dtype=LD)
+        Fe, lam, Q, p = t.Fe, t.lam, t.Q, t.p
         out.spectrum, out.cond = lam, lam.max(axis=1) / lam.min(axis=1)
     else:
-        f0 = inverse(mm(state.F_old, Fi))
-        c = np.cbrt(det(f0))
-        fb = f0 * c[:, None, None]
-        be = mm(mm(fb, state.be_old), T(fb))
-        s = G * dev(be)
-        sn = frob(s)
-        small = sn < DBL_EPSILON
-        sns = np.where(small, LD(1), sn)
-        Np = np.where(small[:, None, None], np.sqrt(LD(1) / 2) * I, (r32 / sns)[:, None, None] * s)
-        q = ddot(Np, s)                                                          # s_effective
-        tr_be = tr(be)
-        slope0 = G * tr_be
+        f0, c, fb, be, sn, small, sns, Np, tr_be = t.f0, t.c, t.fb, t.be, t.sn, t.small, t.sns, t.Np, t.tr_be
         out.tr_be, out.fbar2, out.spectrum = tr_be, sym_eig(mm(T(fb), fb))[0].max(axis=1), sym_eig(be)[0]
-    margin = q - h.H(e0) * thermo
+    margin = q - t.limit
     plastic = margin > 0
     if delta is None:
         delta = _root(lambda d: q - slope0 * d - h.H(e0 + d) * h.rate(d / dt) * thermo, plastic, margin / slope0, q)
@@ -519,19 +548,22 @@ def point_law(mat, F, state=None, dt=1.0, dFs=(), delta=None):
         return out
     state = virgin_state(mat, n, dim) if state is None else state
     dt = LD(dt)
-    eps = (F + T(F)) / 2 - I - state.plastic_strain
-    p = K * tr(eps)
-    s = 2 * G * (eps - tr(eps)[:, None, None] / dim * I)
+    if mat.name == "j2":
+        t = trial_state(mat, F, state)
+        p, s = t.p, t.s
+    else:
+        eps = (F + T(F)) / 2 - I - state.plastic_strain
+        p = K * tr(eps)
+        s = 2 * G * (eps - tr(eps)[:, None, None] / dim * I)
     deps = [(dF + T(dF)) / 2 for dF in dFs]
     dp = [K * tr(de) for de in deps]
     ds = [2 * G * (de - tr(de)[:, None, None] / dim * I) for de in deps]
     r32 = np.sqrt(LD(3) / 2)
     if mat.name == "j2":
         h = mat.hardening
-        q = r32 * frob(s)
-        thermo = h.thermo(state.temperature)
+        q, thermo = t.q, t.thermo
         e0 = state.eqps
-        margin = q - h.H(e0) * thermo
+        margin = q - t.limit
 
         def R(d):
             return q - 3 * G * d - h.H(e0 + d) * h.rate(d / dt) * thermo

@@ -81,8 +81,9 @@ def material_pair(matname):
     return oracle_material(matname), product_material(matname)
 
 
-def facade(case, matname, flags=(("explicit_dynamics", 1),), configure=None, setup=True, viscosity=None):
-    """the NonlinearSolid of a case, the bottom clamped unless `configure(bc)` says otherwise; setup=False: no device work"""
+def facade(case, matname, flags=(("explicit_dynamics", 1),), configure=None, setup=True, viscosity=None, material=None):
+    """the NonlinearSolid of a case, the bottom clamped unless `configure(bc)` says otherwise; setup=False: no device work;
+    material: this product material instead of matname's"""
     import mimi_amd as mimi
     mesh, elevate, subdivide, _ = CASES[case]
     nl = mimi.NonlinearSolid()
@@ -92,7 +93,7 @@ def facade(case, matname, flags=(("explicit_dynamics", 1),), configure=None, set
     if case in NAMED:
         B = _dc.product_patch(case)
         nl.patch = lambda: B
-    mat = material_pair(matname)[1]
+    mat = material_pair(matname)[1] if material is None else material
     if viscosity is not None:
         mat.viscosity = viscosity
     nl.set_material(mat)

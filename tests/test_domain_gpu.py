@@ -173,7 +173,10 @@ def test_structured_sparsity_matches_oracle():
 
 
 def test_errors_surface_as_runtime_error():
-    """ScalarSolve's throw paths / bad input arrive as RuntimeError (utils/print.hpp:47-56)."""
+    """Bad input at Prepare() arrives as RuntimeError (utils/print.hpp:47-56): a J2 material without a hardening law, refused on
+    the host, and a CSR pattern without an element's block, raised by a kernel through the status word.  ScalarSolve's throw
+    paths -- the status word raised by a return map on every kernel family, and the inverted geometry map -- are in
+    tests/test_status_gpu.py."""
     import mimi_amd
     from mimi_amd.integrators import CSRPattern, NonlinearSolid
     patch = mimi_amd.BSplinePatch.block((2, 2), 2)

@@ -16,7 +16,9 @@
 // densely -- per quadrature point the nodal area / gap shares, per face the residual vector and the tangent block --
 // and summed afterwards in a fixed order through the marked nodes' (face, local node) incidences: no atomics, results
 // bitwise reproducible like the domain paths (round 3; rounds 1-2 used fp64 atomics here).  The face tables, the
-// incidences, the pair positions, the fixed-order sums and the row gather are face_common.hpp's, shared with pressure.hip.
+// incidences, the pair positions, the fixed-order sums and the row gather are face_common.hpp's, shared with pressure.hip;
+// the stages of the wave-per-face kernels (wave index, node load, point stage, normals, point scatter, node-pair loop) are
+// face_wave.hpp's, shared with the action and friction kernels (contact_residual_wave_kernel has them in its own text).
 // The matrix-free action of the frozen-pressure tangent (mimi_hip_contact_linearize / _apply_tangent, and the Krylov
 // solvers' boundary terms through apply_seam.hpp) is kernels_face_action.hpp, shared with pressure.hip as well: it builds
 // no face tangent block.  The consistent tangent -- the frozen one plus the derivative of the nodal pressure, which leaves the
@@ -43,13 +45,7 @@ namespace mimi_hip {
 
 struct ContactArgs {
   SplineBodyDev spline;      // body_kind == MIMI_HIP_BODY_SPLINE
-  int dim, n_faces, n_dof, n_q;
-  const int32_t* dofs;       // [n_faces][n_dof] global node ids
-  const int32_t* local;      // [n_faces][n_dof] index into the nodal arrays
-  const double* N;           // [n_faces][n_q][n_dof]
-  const double* dN;          // [n_faces][n_q][dim-1][n_dof]
-  const double* weight;      // [n_faces][n_q]
-  const double* x_ref;       // [n_nodes][dim]
+  FaceView v;
   int body_kind;
   double body[8];
   double penalty;
@@ -159,25 +155,16 @@ MH_DEV double surface_normal(int n_dof, const double* x_e /*[DIM][n_dof]*/, cons
       for (int a = 0; a < n_dof; ++a) s += x_e[i * n_dof + a] * dN[k * n_dof + a];
       t[k * DIM + i] = s;
     }
-  if constexpr (DIM == 2) {
-    m[0] = t[1];
-    m[1] = -t[0];
-    return sqrt(m[0] * m[0] + m[1] * m[1]);
-  } else {
-    m[0] = t[1] * t[5] - t[2] * t[4];
-    m[1] = t[2] * t[3] - t[0] * t[5];
-    m[2] = t[0] * t[4] - t[1] * t[3];
-    return sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
-  }
+  return face_normal_len<DIM>(t, m);
 }
 
 template<int DIM>
 MH_DEV void gather_x(const ContactArgs& p, int f, double* x_e) {
   // integrator_utils.cpp:80-89: x_e = u[v_dofs] + X_ref
-  for (int a = 0; a < p.n_dof; ++a) {
-    const int64_t node = p.dofs[(int64_t)f * p.n_dof + a];
+  for (int a = 0; a < p.v.n_dof; ++a) {
+    const int64_t node = p.v.dofs[(int64_t)f * p.v.n_dof + a];
 #pragma unroll
-    for (int i = 0; i < DIM; ++i) x_e[i * p.n_dof + a] = p.u[node * DIM + i] + p.x_ref[node * DIM + i];
+    for (int i = 0; i < DIM; ++i) x_e[i * p.v.n_dof + a] = p.u[node * DIM + i] + p.v.x_ref[node * DIM + i];
   }
 }
 
@@ -185,26 +172,26 @@ MH_DEV void gather_x(const ContactArgs& p, int f, double* x_e) {
 template<int DIM>
 __global__ void contact_gap_area_kernel(ContactArgs p, int gap_norm_only) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= (int64_t)p.n_faces * p.n_q) return;
-  const int f = idx / p.n_q;
+  if (idx >= (int64_t)p.v.n_faces * p.v.n_q) return;
+  const int f = idx / p.v.n_q;
   const int64_t pt = idx;
   // x_e = u[v_dofs] + X_ref (integrator_utils.cpp:80-89) is used node by node as it arrives: the point's position and the
   // two tangents J = x_e^T dN_dxi (integrator_utils.cpp:101-105) in one pass, no private array
-  const double* N = p.N + pt * p.n_dof;
-  const double* dN = p.dN + pt * p.n_dof * (DIM - 1);
+  const double* N = p.v.N + pt * p.v.n_dof;
+  const double* dN = p.v.dN + pt * p.v.n_dof * (DIM - 1);
   double xq[DIM], t[(DIM - 1) * DIM];
 #pragma unroll
   for (int i = 0; i < DIM; ++i) xq[i] = 0.0;
 #pragma unroll
   for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = 0.0;
-  for (int a = 0; a < p.n_dof; ++a) {
-    const int64_t node = p.dofs[(int64_t)f * p.n_dof + a];
+  for (int a = 0; a < p.v.n_dof; ++a) {
+    const int64_t node = p.v.dofs[(int64_t)f * p.v.n_dof + a];
 #pragma unroll
     for (int i = 0; i < DIM; ++i) {
-      const double x = p.u[node * DIM + i] + p.x_ref[node * DIM + i];
+      const double x = p.u[node * DIM + i] + p.v.x_ref[node * DIM + i];
       xq[i] = __builtin_fma(x, N[a], xq[i]);
 #pragma unroll
-      for (int k = 0; k < DIM - 1; ++k) t[k * DIM + i] = __builtin_fma(x, dN[k * p.n_dof + a], t[k * DIM + i]);
+      for (int k = 0; k < DIM - 1; ++k) t[k * DIM + i] = __builtin_fma(x, dN[k * p.v.n_dof + a], t[k * DIM + i]);
     }
   }
   double true_g, distance;
@@ -215,7 +202,7 @@ __global__ void contact_gap_area_kernel(ContactArgs p, int gap_norm_only) {
     return;
   }
   double g = true_g < 0. ? true_g : 0.;
-  // |J| (DenseMatrix::Weight) from the non-normalised normal (integrator_utils.hpp:216-251)
+  // |J| (DenseMatrix::Weight) from the non-normalised normal (integrator_utils.hpp:216-251); this kernel keeps its own text
   double detJ;
   if constexpr (DIM == 2) {
     detJ = sqrt(t[1] * t[1] + t[0] * t[0]);
@@ -223,14 +210,14 @@ __global__ void contact_gap_area_kernel(ContactArgs p, int gap_norm_only) {
     const double m0 = t[1] * t[5] - t[2] * t[4], m1 = t[2] * t[3] - t[0] * t[5], m2 = t[0] * t[4] - t[1] * t[3];
     detJ = sqrt(m0 * m0 + m1 * m1 + m2 * m2);
   }
-  const double fac = p.weight[pt] * detJ;
+  const double fac = p.v.weight[pt] * detJ;
   p.pt_scal[pt] = fac;
   const double ratio = fabs(true_g) / distance;
   if (acos(ratio < 1. ? ratio : 1.) > 1.e-5) g = 0.0;  // angle tolerance, mortar_contact.cpp:172-181
   const double fac_g = fac * g;
-  for (int a = 0; a < p.n_dof; ++a) {
-    p.pt_area[pt * p.n_dof + a] = fac * N[a];
-    p.pt_gap[pt * p.n_dof + a] = fac_g * N[a];
+  for (int a = 0; a < p.v.n_dof; ++a) {
+    p.pt_area[pt * p.v.n_dof + a] = fac * N[a];
+    p.pt_gap[pt * p.v.n_dof + a] = fac_g * N[a];
   }
 }
 
@@ -272,19 +259,19 @@ __global__ void contact_pressure_kernel(int n, const double* area, const double*
 template<int DIM>
 MH_DEV void face_residual(const ContactArgs& p, int f, const double* x_e, const double* p_e, double* R_e,
                           double* force, double* pint) {
-  for (int k = 0; k < p.n_dof * DIM; ++k) R_e[k] = 0.0;
-  for (int q = 0; q < p.n_q; ++q) {
-    const int64_t pt = (int64_t)f * p.n_q + q;
-    const double* N = p.N + pt * p.n_dof;
+  for (int k = 0; k < p.v.n_dof * DIM; ++k) R_e[k] = 0.0;
+  for (int q = 0; q < p.v.n_q; ++q) {
+    const int64_t pt = (int64_t)f * p.v.n_q + q;
+    const double* N = p.v.N + pt * p.v.n_dof;
     double pq = 0;
-    for (int a = 0; a < p.n_dof; ++a) pq += N[a] * p_e[a];
+    for (int a = 0; a < p.v.n_dof; ++a) pq += N[a] * p_e[a];
     double m[DIM], t[(DIM - 1) * DIM];
-    const double detJ = surface_normal<DIM>(p.n_dof, x_e, p.dN + pt * p.n_dof * (DIM - 1), m, t);
-    const double fac = p.weight[pt] * detJ * pq;
+    const double detJ = surface_normal<DIM>(p.v.n_dof, x_e, p.v.dN + pt * p.v.n_dof * (DIM - 1), m, t);
+    const double fac = p.v.weight[pt] * detJ * pq;
 #pragma unroll
     for (int i = 0; i < DIM; ++i) {
       const double aw = (m[i] / detJ) * (-fac);
-      for (int a = 0; a < p.n_dof; ++a) R_e[i * p.n_dof + a] += aw * N[a];
+      for (int a = 0; a < p.v.n_dof; ++a) R_e[i * p.v.n_dof + a] += aw * N[a];
       if (force) force[i] += fac * (m[i] / detJ);
     }
     if (pint) *pint += fac;
@@ -296,18 +283,18 @@ MH_DEV void face_residual(const ContactArgs& p, int f, const double* x_e, const 
 template<int DIM>
 __global__ void contact_residual_kernel(ContactArgs p, int with_grad) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= p.n_faces) return;
+  if (f >= p.v.n_faces) return;
   double p_e[kFaceMaxDof];
   bool any = false;
-  for (int a = 0; a < p.n_dof; ++a) {
-    p_e[a] = p.pressure[p.local[(int64_t)f * p.n_dof + a]];
+  for (int a = 0; a < p.v.n_dof; ++a) {
+    p_e[a] = p.pressure[p.v.local[(int64_t)f * p.v.n_dof + a]];
     any = any || (p_e[a] != 0.0);
   }
   if (!any) return;  // IsPressureZero (integrator_utils.cpp:112-119)
   double x_e[DIM * kFaceMaxDof], R_e[DIM * kFaceMaxDof];
   gather_x<DIM>(p, f, x_e);
   face_residual<DIM>(p, f, x_e, p_e, R_e, nullptr, nullptr);
-  const int NT = p.n_dof * DIM;
+  const int NT = p.v.n_dof * DIM;
   // (the face residual, pressure integral and force are stored by contact_residual_wave_kernel in every mode, so that
   // the history scalars do not depend on the tangent mode to the last bit; this kernel adds the difference tangent)
   if (!with_grad) return;
@@ -321,31 +308,32 @@ __global__ void contact_residual_kernel(ContactArgs p, int with_grad) {
     x_e[c] = orig + step;
     face_residual<DIM>(p, f, x_e, p_e, fwd, nullptr, nullptr);
     x_e[c] = orig;
-    const int b = c % p.n_dof, j = c / p.n_dof;
-    for (int a = 0; a < p.n_dof; ++a)
+    const int b = c % p.v.n_dof, j = c / p.v.n_dof;
+    for (int a = 0; a < p.v.n_dof; ++a)
 #pragma unroll
       for (int i = 0; i < DIM; ++i)
-        Kf[(a * DIM + i) * NT + j * p.n_dof + b] = (fwd[i * p.n_dof + a] - R_e[i * p.n_dof + a]) * step_inv;
+        Kf[(a * DIM + i) * NT + j * p.v.n_dof + b] = (fwd[i * p.v.n_dof + a] - R_e[i * p.v.n_dof + a]) * step_inv;
   }
 }
 
 // pass 2 without the reference-FD tangent, one WAVE per face: lane = quadrature point for pressure, normal and weights,
 // then lane = (i, a) for the residual entries -- summed over the points in the order of the one-thread form above, so
 // the two give the same bits (that form left 9 216 faces to 144 waves: 0.19 ms of latency at configuration 4)
+// (The kernel keeps its own stage text: on face_wave.hpp's helpers it computed the same bytes with 2 to 5 instructions more.)
 template<int DIM>
-__global__ __launch_bounds__(256) void contact_residual_wave_kernel(ContactArgs p) {
+__global__ __launch_bounds__(kFaceWaveThreads) void contact_residual_wave_kernel(ContactArgs p) {
   const int lane = threadIdx.x & 63;
   const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;
-  const int n_dof = p.n_dof, n_q = p.n_q, NT = n_dof * DIM;
+  if (f >= p.v.n_faces) return;
+  const int n_dof = p.v.n_dof, n_q = p.v.n_q, NT = n_dof * DIM;
   double pc = 0.0, xc[DIM];
 #pragma unroll
   for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
   if (lane < n_dof) {
-    pc = p.pressure[p.local[(int64_t)f * n_dof + lane]];
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
+    pc = p.pressure[p.v.local[(int64_t)f * n_dof + lane]];
+    const int64_t node = p.v.dofs[(int64_t)f * n_dof + lane];
 #pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = p.u[node * DIM + i] + p.x_ref[node * DIM + i];
+    for (int i = 0; i < DIM; ++i) xc[i] = p.u[node * DIM + i] + p.v.x_ref[node * DIM + i];
   }
   const bool any = __ballot(pc != 0.0) != 0;
   if (lane == 0) p.face_active[f] = any ? 1 : 0;
@@ -357,8 +345,8 @@ __global__ __launch_bounds__(256) void contact_residual_wave_kernel(ContactArgs 
   {
     const int q = lane < n_q ? lane : 0;
     const int64_t pt = (int64_t)f * n_q + q;
-    const double* N = p.N + pt * n_dof;
-    const double* dN = p.dN + pt * n_dof * (DIM - 1);
+    const double* N = p.v.N + pt * n_dof;
+    const double* dN = p.v.dN + pt * n_dof * (DIM - 1);
     double pq = 0.0, t[(DIM - 1) * DIM];
 #pragma unroll
     for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = 0.0;
@@ -382,7 +370,7 @@ __global__ __launch_bounds__(256) void contact_residual_wave_kernel(ContactArgs 
       m[2] = t[0] * t[4] - t[1] * t[3];
       detJ = sqrt(m[0] * m[0] + m[1] * m[1] + m[2] * m[2]);
     }
-    fac = p.weight[pt] * detJ * pq;
+    fac = p.v.weight[pt] * detJ * pq;
 #pragma unroll
     for (int i = 0; i < DIM; ++i) nq[i] = m[i] / detJ;
   }
@@ -398,7 +386,7 @@ __global__ __launch_bounds__(256) void contact_residual_wave_kernel(ContactArgs 
         const double v = face_lane_read(nq[ii], q) * mf;
         aw = i == ii ? v : aw;
       }
-      R += aw * p.N[((int64_t)f * n_q + q) * n_dof + a];
+      R += aw * p.v.N[((int64_t)f * n_q + q) * n_dof + a];
     }
     if (lane < NT) p.face_r[(int64_t)f * NT + lane] = R;      // [i][a]
   }
@@ -427,86 +415,35 @@ __global__ __launch_bounds__(256) void contact_residual_wave_kernel(ContactArgs 
 // registers, the point's seven numbers read from the lane that computed them.  (Before: every pair lane recomputed
 // pressure and tangents of every point from private arrays -- 0.44 ms for the 9 216 faces of configuration 4.)
 template<int DIM>
-__global__ __launch_bounds__(256) void contact_tangent_kernel(ContactArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;
-  const int n_dof = p.n_dof, n_q = p.n_q;   // (<= 16 nodes; <= 64 points: checked at create)
-  // lane c < n_dof: node c of the face
-  double pc = 0.0, xc[DIM];
-#pragma unroll
-  for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
-  if (lane < n_dof) {
-    pc = p.pressure[p.local[(int64_t)f * n_dof + lane]];
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = p.u[node * DIM + i] + p.x_ref[node * DIM + i];   // integrator_utils.cpp:80-89
-  }
+__global__ __launch_bounds__(kFaceWaveThreads) void contact_tangent_kernel(ContactArgs p) {
+  int lane, f;
+  if (!face_wave_index(p.v, lane, f)) return;
+  const int n_dof = p.v.n_dof, n_q = p.v.n_q;   // (<= 16 nodes; <= 64 points: checked at create)
+  double xc[DIM];
+  const double pc = face_load_nodes<DIM, true, kNodal>(p.v, f, lane, p.u, xc, p.pressure);
   if (__ballot(pc != 0.0) == 0) return;  // IsPressureZero (integrator_utils.cpp:112-119)
   // stage 1: lane q < n_q
-  double wq = 0.0, tq[(DIM - 1) * DIM];
-#pragma unroll
-  for (int k = 0; k < (DIM - 1) * DIM; ++k) tq[k] = 0.0;
-  {
-    const int q = lane < n_q ? lane : 0;
-    const int64_t pt = (int64_t)f * n_q + q;
-    const double* N = p.N + pt * n_dof;
-    const double* dN = p.dN + pt * n_dof * (DIM - 1);
-    double pq = 0.0;
-    for (int c = 0; c < n_dof; ++c) {
-      pq = __builtin_fma(N[c], face_lane_read(pc, c), pq);
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) {
-        const double x = face_lane_read(xc[i], c);
-#pragma unroll
-        for (int k = 0; k < DIM - 1; ++k) tq[k * DIM + i] = __builtin_fma(x, dN[k * n_dof + c], tq[k * DIM + i]);
-      }
-    }
-    wq = -p.weight[pt] * pq;
-  }
-  const int n_pairs = n_dof * n_dof, NT = n_dof * DIM;
-  double* Kf = p.face_k + (int64_t)f * NT * NT;
-  for (int pair0 = 0; pair0 < n_pairs; pair0 += 64) {
-    const int pair = pair0 + lane;
-    const bool on = pair < n_pairs;
-    const int a = on ? pair / n_dof : 0, b = on ? pair % n_dof : 0;
-    double acc[DIM * DIM];
-#pragma unroll
-    for (int k = 0; k < DIM * DIM; ++k) acc[k] = 0.0;
+  const int64_t pt_q = face_lane_point(p.v, f, lane);
+  double pq, tq[(DIM - 1) * DIM];
+  face_point_stage<DIM, true, false, true>(p.v, pt_q, pc, xc, &pq, nullptr, tq);
+  const double wq = -p.v.weight[pt_q] * pq;
+  face_pair_loop<DIM, false>(n_dof, lane, p.face_k + (int64_t)f * (n_dof * DIM) * (n_dof * DIM), [&](int a, int b, double* acc) {
     for (int q = 0; q < n_q; ++q) {
       const int64_t pt = (int64_t)f * n_q + q;
-      const double wpn = face_lane_read(wq, q) * p.N[pt * n_dof + a];
-      const double* dN = p.dN + pt * n_dof * (DIM - 1);
+      const double wpn = face_lane_read(wq, q) * p.v.N[pt * n_dof + a];
+      const double* dN = p.v.dN + pt * n_dof * (DIM - 1);
       double t[(DIM - 1) * DIM];
 #pragma unroll
       for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = face_lane_read(tq[k], q);
 #pragma unroll
       for (int j = 0; j < DIM; ++j) {
         double dm[DIM];
-        if constexpr (DIM == 2) {
-          dm[0] = (j == 1) ? dN[b] : 0.0;
-          dm[1] = (j == 0) ? -dN[b] : 0.0;
-        } else {
-          double e[3] = {0, 0, 0};
-          e[j] = 1.0;
-          const double* t1 = t;
-          const double* t2 = t + 3;
-          const double d1 = dN[b], d2 = dN[n_dof + b];
-          dm[0] = d1 * (e[1] * t2[2] - e[2] * t2[1]) + d2 * (t1[1] * e[2] - t1[2] * e[1]);
-          dm[1] = d1 * (e[2] * t2[0] - e[0] * t2[2]) + d2 * (t1[2] * e[0] - t1[0] * e[2]);
-          dm[2] = d1 * (e[0] * t2[1] - e[1] * t2[0]) + d2 * (t1[0] * e[1] - t1[1] * e[0]);
-        }
+        face_normal_column<DIM>(t, dN, n_dof, b, j, dm);
 #pragma unroll
         for (int i = 0; i < DIM; ++i) acc[i * DIM + j] += wpn * dm[i];
       }
     }
-    if (on) {
-#pragma unroll
-      for (int i = 0; i < DIM; ++i)
-#pragma unroll
-        for (int j = 0; j < DIM; ++j) Kf[(a * DIM + i) * NT + j * n_dof + b] = acc[i * DIM + j];
-    }
-  }
+  });
 }
 
 }  // namespace mimi_hip
@@ -553,40 +490,17 @@ static void friction_reset(mimi_hip_contact_s* h) {
   h->fr_trial = false;
 }
 
+// the face tables, u and the stores of this evaluation (c), and the handle's friction state
 static FrictionArgs friction_args(const mimi_hip_contact_s* h, const ContactArgs& c) {
-  FrictionArgs a{};
-  a.n_faces = c.n_faces;
-  a.n_dof = c.n_dof;
-  a.n_q = c.n_q;
-  a.dofs = c.dofs;
-  a.local = c.local;
-  a.N = c.N;
-  a.dN = c.dN;
-  a.weight = c.weight;
-  a.x_ref = c.x_ref;
-  a.u = c.u;
-  a.pressure = c.pressure;
-  a.face_r = c.face_r;
-  a.face_k = c.face_k;
-  a.mu = h->mu;
-  a.eps_t = h->eps_t;
-  for (int i = 0; i < 3; ++i) a.d[i] = h->body_inc[i];
-  a.xi = h->fr_xi.ptr;
-  a.xbar = h->fr_xbar.ptr;
-  a.c = h->fr_c.ptr;
-  a.xi_t = h->fr_xi_t.ptr;
-  a.xbar_t = h->fr_xbar_t.ptr;
-  a.c_t = h->fr_c_t.ptr;
-  a.face_fr = h->fr_face.ptr;
-  return a;
+  return {c.v, c.u, c.pressure, c.face_r, c.face_k, h->mu, h->eps_t, {h->body_inc[0], h->body_inc[1], h->body_inc[2]},
+          h->fr_xi.ptr, h->fr_xbar.ptr, h->fr_c.ptr, h->fr_xi_t.ptr, h->fr_xbar_t.ptr, h->fr_c_t.ptr, h->fr_face.ptr};
 }
 
 // the trial state over the committed one, on the handle's stream; nothing waits
 static void friction_commit(mimi_hip_contact_s* h) {
   const int64_t npts = (int64_t)h->n_faces * h->n_q, ns = npts * h->dim;
-  hipLaunchKernelGGL(contact_friction_commit_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, h->stream, ns, npts,
-                     h->fr_xi_t.ptr, h->fr_xbar_t.ptr, h->fr_c_t.ptr, h->fr_xi.ptr, h->fr_xbar.ptr, h->fr_c.ptr);
-  MH_HIP(hipGetLastError());
+  launch(contact_friction_commit_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, h->stream, ns, npts, h->fr_xi_t.ptr,
+         h->fr_xbar_t.ptr, h->fr_c_t.ptr, h->fr_xi.ptr, h->fr_xbar.ptr, h->fr_c.ptr);
 }
 
 // (lifted: what mimi_hip_contact_set_friction_action(h, 1) makes available)
@@ -659,18 +573,9 @@ static void upload_spline_body(mimi_hip_contact_s* h, const mimi_hip_spline_body
 
 static ContactArgs contact_args(mimi_hip_contact_s* h, const double* u) {
   ContactArgs a{};
-  a.dim = h->dim;
-  a.n_faces = h->n_faces;
-  a.n_dof = h->n_dof;
-  a.n_q = h->n_q;
-  a.dofs = h->dofs.ptr;
-  a.local = h->local.ptr;
-  a.N = h->N.ptr;
-  a.dN = h->dN.ptr;
-  a.weight = h->weight.ptr;
-  a.x_ref = h->x_ref.ptr;
-  a.body_kind = h->body_kind;
   a.spline = h->spline;
+  a.v = h->view();
+  a.body_kind = h->body_kind;
   for (int i = 0; i < 8; ++i) a.body[i] = h->body[i];
   a.penalty = h->penalty;
   a.u = u;
@@ -689,20 +594,38 @@ static ContactArgs contact_args(mimi_hip_contact_s* h, const double* u) {
   return a;
 }
 
+constexpr int kContactThreads = 128;   // of the one-thread-per-point and per-node kernels
+
+// The kernels of pass 1 (mortar_contact.cpp:148-193), the one place that launches them: the points' gap and area shares, then
+// their nodal sums and the area scalar -- or, gap_norm_only, the points' min(g, 0)^2 and their sum into the gap-norm scalar
+static void contact_pass1_kernels(mimi_hip_contact_s* h, const ContactArgs& a, int gap_norm_only) {
+  const int64_t npts = (int64_t)h->n_faces * h->n_q;
+  const dim3 grid((unsigned)((npts + kContactThreads - 1) / kContactThreads));
+  face_dispatch_dim(h->dim, [&](auto D) {
+    launch(contact_gap_area_kernel<decltype(D)::value>, grid, dim3(kContactThreads), 0, h->stream, a, gap_norm_only);
+  });
+  if (!gap_norm_only)
+    launch(contact_nodal_kernel, dim3((unsigned)((h->n_fnodes + 3) / 4)), dim3(256), 0, h->stream, h->n_fnodes, h->n_q, h->n_dof,
+           h->adj_ptr.ptr, h->adj.ptr, h->pt_area.ptr, h->pt_gap.ptr, h->area.ptr, h->gap.ptr);   // (a wave per marked node, four per workgroup)
+}
+
+// the sum of pass 1's point scalars into the history scalar `slot`
+static void contact_sum_points(mimi_hip_contact_s* h, int slot) {
+  launch(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces * h->n_q, 1, 1, h->pt_scal.ptr,
+         (const unsigned char*)nullptr, h->scalars.ptr + slot);
+}
+
+static void contact_pressure(mimi_hip_contact_s* h) {   // mortar_contact.cpp:253-257
+  launch(contact_pressure_kernel, dim3((unsigned)((h->n_fnodes + kContactThreads - 1) / kContactThreads)), dim3(kContactThreads), 0,
+         h->stream, h->n_fnodes, h->area.ptr, h->gap.ptr, h->penalty, h->pressure.ptr);
+}
+
 // pass 1 (mortar_contact.cpp:148-193): nodal area / gap of this handle's faces; pressure not formed yet
 static void contact_pass1(mimi_hip_contact_s* h, const double* u_dev) {
-  ContactArgs a = contact_args(h, u_dev);
   // InitializeGapAreaPressure + last_* reset (mortar_contact.cpp:135-146,302-306)
   MH_HIP(hipMemsetAsync(h->scalars.ptr, 0, 6 * sizeof(double), h->stream));
-  const int threads = 128;
-  const int64_t npts = (int64_t)h->n_faces * h->n_q;
-  const unsigned b1 = (unsigned)((npts + threads - 1) / threads);
-  if (h->dim == 2) hipLaunchKernelGGL(contact_gap_area_kernel<2>, dim3(b1), dim3(threads), 0, h->stream, a, 0);
-  else hipLaunchKernelGGL(contact_gap_area_kernel<3>, dim3(b1), dim3(threads), 0, h->stream, a, 0);
-  hipLaunchKernelGGL(contact_nodal_kernel, dim3((unsigned)((h->n_fnodes + 3) / 4)), dim3(256), 0, h->stream,
-                     h->n_fnodes, h->n_q, h->n_dof, h->adj_ptr.ptr, h->adj.ptr, h->pt_area.ptr, h->pt_gap.ptr, h->area.ptr, h->gap.ptr);
-  hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, npts, 1, 1, h->pt_scal.ptr,
-                     (const unsigned char*)nullptr, h->scalars.ptr);
+  contact_pass1_kernels(h, contact_args(h, u_dev), 0);
+  contact_sum_points(h, 0);
 }
 
 // The snapshot of the frozen-pressure tangent at u: pass 1 and the pressure with the handle's current body and penalty
@@ -712,15 +635,8 @@ static void contact_pass1(mimi_hip_contact_s* h, const double* u_dev) {
 // state is written.  It is the analytic tangent whatever the tangent mode says.
 static void contact_linearize(mimi_hip_contact_s* h, const double* u_dev) {
   const ContactArgs a = contact_args(h, u_dev);
-  const int threads = 128;
-  const int64_t npts = (int64_t)h->n_faces * h->n_q;
-  const unsigned b1 = (unsigned)((npts + threads - 1) / threads);
-  if (h->dim == 2) hipLaunchKernelGGL(contact_gap_area_kernel<2>, dim3(b1), dim3(threads), 0, h->stream, a, 0);
-  else hipLaunchKernelGGL(contact_gap_area_kernel<3>, dim3(b1), dim3(threads), 0, h->stream, a, 0);
-  hipLaunchKernelGGL(contact_nodal_kernel, dim3((unsigned)((h->n_fnodes + 3) / 4)), dim3(256), 0, h->stream,
-                     h->n_fnodes, h->n_q, h->n_dof, h->adj_ptr.ptr, h->adj.ptr, h->pt_area.ptr, h->pt_gap.ptr, h->area.ptr, h->gap.ptr);
-  hipLaunchKernelGGL(contact_pressure_kernel, dim3((unsigned)((h->n_fnodes + threads - 1) / threads)), dim3(threads), 0, h->stream,
-                     h->n_fnodes, h->area.ptr, h->gap.ptr, h->penalty, h->pressure.ptr);
+  contact_pass1_kernels(h, a, 0);
+  contact_pressure(h);
   const bool rough = h->friction_action && h->mu > 0.0;
   const FrictionArgs fa = rough ? friction_args(h, a) : FrictionArgs{};
   h->action.linearize(*h, u_dev, h->area.ptr, h->pressure.ptr, h->penalty, h->consistent_tangent, ContactBodyQuery{a},
@@ -732,45 +648,32 @@ static void contact_linearize(mimi_hip_contact_s* h, const double* u_dev) {
 // With mu > 0 the friction kernels add to the face stores behind the frictionless ones and write the trial state.
 static void contact_pass2(mimi_hip_contact_s* h, const double* u_dev, double* r_dev, double* A_dev, double gf, bool with_grad) {
   if (with_grad) h->reserve_face_k();
-  ContactArgs a = contact_args(h, u_dev);
-  const int threads = 128;
-  const unsigned b2 = (unsigned)((h->n_fnodes + threads - 1) / threads);
-  const unsigned b3 = (unsigned)((h->n_faces + 63) / 64);
-  hipLaunchKernelGGL(contact_pressure_kernel, dim3(b2), dim3(threads), 0, h->stream, h->n_fnodes, h->area.ptr, h->gap.ptr, h->penalty, h->pressure.ptr);
-  // analytic tangent: the residual by the face-per-thread kernel, the tangent by one wave per face
-  const bool wave_tangent = with_grad && h->mode != MIMI_HIP_TANGENT_REFERENCE_FD;
-  const int grad_flag = (with_grad && !wave_tangent) ? 1 : 0;
-  const unsigned b3w = (unsigned)((h->n_faces + 3) / 4);
-  if (h->dim == 2) hipLaunchKernelGGL(contact_residual_wave_kernel<2>, dim3(b3w), dim3(256), 0, h->stream, a);
-  else hipLaunchKernelGGL(contact_residual_wave_kernel<3>, dim3(b3w), dim3(256), 0, h->stream, a);
-  if (grad_flag) {   // reference-FD tangent
-    if (h->dim == 2) hipLaunchKernelGGL(contact_residual_kernel<2>, dim3(b3), dim3(64), 0, h->stream, a, grad_flag);
-    else hipLaunchKernelGGL(contact_residual_kernel<3>, dim3(b3), dim3(64), 0, h->stream, a, grad_flag);
-  }
-  if (wave_tangent) {
-    const unsigned b4 = (unsigned)((h->n_faces + 3) / 4);
-    if (h->dim == 2) hipLaunchKernelGGL(contact_tangent_kernel<2>, dim3(b4), dim3(256), 0, h->stream, a);
-    else hipLaunchKernelGGL(contact_tangent_kernel<3>, dim3(b4), dim3(256), 0, h->stream, a);
-  }
-  if (h->mu > 0.0) {
-    if (h->mode == MIMI_HIP_TANGENT_REFERENCE_FD) fail("friction has no reference-FD tangent");   // (refused where either is set)
-    const FrictionArgs fa = friction_args(h, a);
-    if (h->dim == 2) hipLaunchKernelGGL(contact_friction_kernel<2>, dim3(b3w), dim3(256), 0, h->stream, fa);
-    else hipLaunchKernelGGL(contact_friction_kernel<3>, dim3(b3w), dim3(256), 0, h->stream, fa);
-    if (with_grad) {
-      if (h->dim == 2) hipLaunchKernelGGL(contact_friction_tangent_kernel<2>, dim3(b3w), dim3(256), 0, h->stream, fa);
-      else hipLaunchKernelGGL(contact_friction_tangent_kernel<3>, dim3(b3w), dim3(256), 0, h->stream, fa);
+  const ContactArgs a = contact_args(h, u_dev);
+  contact_pressure(h);
+  // analytic tangent: one wave per face; reference-FD tangent: the face-per-thread kernel
+  const bool fd_tangent = with_grad && h->mode == MIMI_HIP_TANGENT_REFERENCE_FD;
+  const dim3 waves = face_wave_grid(h->n_faces), wave_threads(kFaceWaveThreads);
+  face_dispatch_dim(h->dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    launch(contact_residual_wave_kernel<DIM>, waves, wave_threads, 0, h->stream, a);
+    if (fd_tangent) launch(contact_residual_kernel<DIM>, dim3((unsigned)((h->n_faces + 63) / 64)), dim3(64), 0, h->stream, a, 1);
+    else if (with_grad) launch(contact_tangent_kernel<DIM>, waves, wave_threads, 0, h->stream, a);
+    if (h->mu > 0.0) {
+      if (h->mode == MIMI_HIP_TANGENT_REFERENCE_FD) fail("friction has no reference-FD tangent");   // (refused where either is set)
+      const FrictionArgs fa = friction_args(h, a);
+      launch(contact_friction_kernel<DIM>, waves, wave_threads, 0, h->stream, fa);
+      if (with_grad) launch(contact_friction_tangent_kernel<DIM>, waves, wave_threads, 0, h->stream, fa);
     }
-    hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, kFrictionScalars, kFrictionScalars,
-                       h->fr_face.ptr, (const unsigned char*)nullptr, h->fr_scalars.ptr);
+  });
+  if (h->mu > 0.0) {
+    launch(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, kFrictionScalars, kFrictionScalars, h->fr_face.ptr,
+           (const unsigned char*)nullptr, h->fr_scalars.ptr);
     h->fr_trial = true;
   }
   // pressure integral and force of the active faces (last_pressure_ / last_force_), in a fixed order
-  hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, 1 + h->dim, 1 + h->dim,
-                     h->face_scal.ptr, h->face_active.ptr, h->scalars.ptr + 1);
-  if (!r_dev) return;
-  if (h->dim == 2) h->gather<2>(r_dev, A_dev, gf, with_grad);
-  else h->gather<3>(r_dev, A_dev, gf, with_grad);
+  launch(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, 1 + h->dim, 1 + h->dim, h->face_scal.ptr,
+         (const unsigned char*)h->face_active.ptr, h->scalars.ptr + 1);
+  if (r_dev) h->gather(r_dev, A_dev, gf, with_grad);
 }
 
 // which: 1 = pass 1 only (u), 2 = pass 2 only (u, r, A), 3 = both (the single-process call)
@@ -882,17 +785,8 @@ int mimi_hip_contact_gap_norm(mimi_hip_contact_t h, const double* u, double* out
     if (!h || !out) fail("null argument");
     MH_HIP(hipSetDevice(h->device));
     Mirror<double> mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
-    ContactArgs a = contact_args(h, mu.dev);
-    const int threads = 128;
-    const int64_t npts = (int64_t)h->n_faces * h->n_q;
-    const unsigned b1 = (unsigned)((npts + threads - 1) / threads);
-    if (h->dim == 2)
-      hipLaunchKernelGGL(contact_gap_area_kernel<2>, dim3(b1), dim3(threads), 0, h->stream, a, 1);
-    else
-      hipLaunchKernelGGL(contact_gap_area_kernel<3>, dim3(b1), dim3(threads), 0, h->stream, a, 1);
-    hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, npts, 1, 1, h->pt_scal.ptr,
-                       (const unsigned char*)nullptr, h->scalars.ptr + 5);
-    MH_HIP(hipGetLastError());
+    contact_pass1_kernels(h, contact_args(h, mu.dev), 1);
+    contact_sum_points(h, 5);
     double g2 = 0;
     MH_HIP(hipMemcpyAsync(&g2, h->scalars.ptr + 5, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     MH_HIP(hipStreamSynchronize(h->stream));

@@ -1,8 +1,8 @@
 // What the boundary-face integrators share -- contact.hip (integrators::MortarContact), pressure.hip (integrators::
 // FollowerPressure) and surface.hip (integrators::CouplingSurface):
-//   device   the size limits of a face, the wave-wide lane read, the non-normalised outward normal of a face point, the
-//            one-workgroup fixed-order sum, the pair positions of the face blocks in the CSR rows, and the row gather of
-//            the dense face residual vectors and tangent blocks through an LDS image of the row;
+//   device   the size limits of a face, the one-workgroup fixed-order sum, the pair positions of the face blocks in the CSR
+//            rows, and the row gather of the dense face residual vectors and tangent blocks through an LDS image of the row
+//            (the wave-per-face stages of the face kernels themselves are face_wave.hpp's);
 //   host     FaceSet (a handle's face tables on the device and the face-node incidence lists that give every node gather
 //            its fixed summation order; surface.hip stops here) and FaceAssembly (a FaceSet attached to a CSR pattern,
 //            with the dense face stores, their gather and the u / r / A mirroring of an assembly call).
@@ -12,13 +12,11 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "common.hpp"
-
-#ifndef MH_DEV
-#define MH_DEV __device__ __forceinline__
-#endif
+#include "face_wave.hpp"
 
 namespace mimi_hip {
 
@@ -27,24 +25,12 @@ constexpr int kFaceMaxQuad = 25;   // points of a face: (p + 2)^2 at degree 3 (r
 constexpr int kFaceGatherWaves = 4;
 constexpr int kFaceMaxRow = 1056;  // (2 p + 1)^3 neighbours x 3 at p = 3 is 1029
 
-MH_DEV double face_lane_read(double v, int l) {   // the value lane l holds, in every lane (l wave-uniform)
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)u, l), hi = __builtin_amdgcn_readlane((unsigned)(u >> 32), l);
-  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
+static_assert(kFaceMaxQuad <= 64, "face_wave.hpp: a lane holds one point of the face");
 
-// the non-normalised outward normal from the surface tangents t = [a_1 | a_2] (contact.hip surface_normal; the orientation
-// is the one splines.face_tables builds the face parametrisation for)
-template<int DIM>
-MH_DEV void face_normal(const double* t /*[DIM-1][DIM]*/, double* m) {
-  if constexpr (DIM == 2) {
-    m[0] = t[1];
-    m[1] = -t[0];
-  } else {
-    m[0] = t[1] * t[5] - t[2] * t[4];
-    m[1] = t[2] * t[3] - t[0] * t[5];
-    m[2] = t[0] * t[4] - t[1] * t[3];
-  }
+// calls f(integral_constant DIM): the one dimension switch of the face files
+template<class F>
+void face_dispatch_dim(int dim, F&& f) {
+  if (dim == 2) f(std::integral_constant<int, 2>{}); else f(std::integral_constant<int, 3>{});
 }
 
 // Kernels and the host code that launches them: each translation unit that includes this header has its own copy (its
@@ -216,7 +202,7 @@ struct FaceSet : StreamHandle {
     if (t.n_dof < 1 || t.n_dof > kFaceMaxDof) fail("face n_dof %d out of range [1,%d]", t.n_dof, kFaceMaxDof);
     if (t.n_faces < 1) fail("no %s faces", what);
     if (t.n_faces >= (1 << 25)) fail("too many %s faces for the incidence encoding", what);
-    if (t.n_quad < 1 || t.n_quad > max_quad) fail("face quadrature points %d out of range [1,%d]", t.n_quad, max_quad);   // (a lane per point)
+    if (t.n_quad < 1 || t.n_quad > max_quad) fail("face quadrature points %d out of range [1,%d]", t.n_quad, max_quad);   // (max_quad <= 64: face_wave.hpp rests on a lane per point)
     if (!t.dofs || !t.N || !t.dN_dxi || !t.weight || !t.x_ref) fail("null table");
     open(device);
     dim = t.dim;
@@ -242,6 +228,8 @@ struct FaceSet : StreamHandle {
     fnodes_dev.assign(inc.fnodes.data(), inc.fnodes.size(), stream);
     fnodes = std::move(inc.fnodes);
   }
+
+  FaceView view() const { return {n_faces, n_dof, n_q, dofs.ptr, local.ptr, N.ptr, dN.ptr, weight.ptr, x_ref.ptr}; }
 
   // the C entries that list the face nodes (out == NULL: count only)
   void copy_fnodes(int32_t* out, int64_t capacity, int64_t* n) const {
@@ -297,9 +285,8 @@ struct FaceAssembly : FaceSet {
     MH_HIP(hipMemsetAsync(status.ptr, 0, sizeof(int), stream));
     const int64_t total = (int64_t)n_faces * n_dof * n_dof;
     pair_pos.resize(total);
-    hipLaunchKernelGGL(face_pair_pos_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, n_faces, n_dof, dim,
-                       dofs.ptr, rowptr, col_dev, pair_pos.ptr, status.ptr);
-    MH_HIP(hipGetLastError());
+    launch(face_pair_pos_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, n_faces, n_dof, dim, dofs.ptr, rowptr,
+           col_dev, pair_pos.ptr, status.ptr);
     int st = 0;
     MH_HIP(hipMemcpyAsync(&st, status.ptr, sizeof(int), hipMemcpyDeviceToHost, stream));
     MH_HIP(hipStreamSynchronize(stream));
@@ -315,27 +302,33 @@ struct FaceAssembly : FaceSet {
     if (!face_k.ptr) face_k.resize((size_t)n_faces * nt * nt);
   }
 
-  // r (and, with_grad, A) += the rows of the face nodes, from face_r / face_k of the active faces
-  template<int DIM>
+  // r (and, with_grad, A) += the rows of the face nodes, from face_r / face_k of the active faces.  (The two gathers are
+  // templates so that a source that gathers nothing -- surface.hip -- holds no gather kernel.)
+  template<int = 0>
   void gather(double* r, double* A, double grad_factor, bool with_grad) {
     const FaceGatherArgs a{n_dof, rowptr, pair_pos.ptr, face_active.ptr, face_r.ptr, face_k.ptr, r, A, grad_factor};
-    const unsigned blocks = (unsigned)(((int64_t)n_fnodes * DIM + kFaceGatherWaves - 1) / kFaceGatherWaves);
-    if (with_grad)
-      hipLaunchKernelGGL((face_row_gather_kernel<DIM, 1>), dim3(blocks), dim3(64 * kFaceGatherWaves),
-                         kFaceGatherWaves * row_cap * sizeof(double), stream, a, n_fnodes, fnodes_dev.ptr, adj_ptr.ptr, adj.ptr, row_cap);
-    else
-      hipLaunchKernelGGL((face_row_gather_kernel<DIM, 0>), dim3(blocks), dim3(64 * kFaceGatherWaves), 0, stream, a, n_fnodes,
-                         fnodes_dev.ptr, adj_ptr.ptr, adj.ptr, 0);
+    face_dispatch_dim(dim, [&](auto D) {
+      constexpr int DIM = decltype(D)::value;
+      const dim3 grid((unsigned)(((int64_t)n_fnodes * DIM + kFaceGatherWaves - 1) / kFaceGatherWaves)), block(64 * kFaceGatherWaves);
+      if (with_grad)
+        launch(face_row_gather_kernel<DIM, 1>, grid, block, kFaceGatherWaves * row_cap * sizeof(double), stream, a, n_fnodes,
+               fnodes_dev.ptr, adj_ptr.ptr, adj.ptr, row_cap);
+      else
+        launch(face_row_gather_kernel<DIM, 0>, grid, block, 0, stream, a, n_fnodes, fnodes_dev.ptr, adj_ptr.ptr, adj.ptr, 0);
+    });
   }
 
   // y += the node sums of a dense face vector [n_faces][dim][n_dof] over the faces flagged in `active`, on stream s: the
   // gather above without K, for callers that keep flags and vectors of their own (kernels_face_action.hpp)
-  template<int DIM>
+  template<int = 0>
   void gather_vector(const unsigned char* active, const double* face_vec, double* y, hipStream_t s) {
     const FaceGatherArgs a{n_dof, rowptr, pair_pos.ptr, active, face_vec, nullptr, y, nullptr, 0.0};
-    const unsigned blocks = (unsigned)(((int64_t)n_fnodes * DIM + kFaceGatherWaves - 1) / kFaceGatherWaves);
-    hipLaunchKernelGGL((face_row_gather_kernel<DIM, 0>), dim3(blocks), dim3(64 * kFaceGatherWaves), 0, s, a, n_fnodes,
-                       fnodes_dev.ptr, adj_ptr.ptr, adj.ptr, 0);
+    face_dispatch_dim(dim, [&](auto D) {
+      constexpr int DIM = decltype(D)::value;
+      const dim3 grid((unsigned)(((int64_t)n_fnodes * DIM + kFaceGatherWaves - 1) / kFaceGatherWaves));
+      launch(face_row_gather_kernel<DIM, 0>, grid, dim3(64 * kFaceGatherWaves), 0, s, a, n_fnodes, fnodes_dev.ptr, adj_ptr.ptr,
+             adj.ptr, 0);
+    });
   }
 
   // One assembly call: u mirrored in, r (when given) and, with_grad, A mirrored in and out around

@@ -7,9 +7,11 @@
 //   linearize  one wave per face: per point c_q and the surface tangents t at u, per face the active flag -- the record
 //              (n_faces n_q (1 + (dim - 1) dim) doubles + n_faces bytes); nothing of u is kept
 //   action     one wave per face, four per workgroup.  Lane c holds node c's x, handed round by face_lane_read.  Stage 1,
-//              lane = point (trips of 64): dt, dm, g = c_q dm.  Stage 2, lane = (i, a): y_f(a, i) += g_i(q) N_q[a] over the
-//              trip's points in ascending order, so the bytes do not depend on the launch.  face_y [n_faces][dim][n_dof] is
-//              a buffer of the record's owner, not the assembly's face_r.
+//              lane = point: dt, dm, g = c_q dm.  Stage 2, lane = (i, a): y_f(a, i) += g_i(q) N_q[a] over the points in
+//              ascending order, so the bytes do not depend on the launch.  face_y [n_faces][dim][n_dof] is a buffer of the
+//              record's owner, not the assembly's face_r.
+// The stages -- wave index, node load, point stage, normal rate, point scatter -- are face_wave.hpp's, shared with every
+// other face kernel: the action forms the tangents' rate with the text that formed the recorded tangents.
 //   node sum   face_row_gather_kernel<DIM, 0> over the RECORDED flags, in the order of the incidences.  No atomics.
 // Registers only: the kernels are latency-bound like the face gather (face_common.hpp) and spend no LDS.
 #pragma once
@@ -20,13 +22,7 @@ namespace mimi_hip {
 namespace {
 
 struct BoundaryLinearizeArgs {
-  int n_faces, n_dof, n_q;
-  const int32_t* dofs;       // [n_faces][n_dof] global node ids
-  const int32_t* local;      // [n_faces][n_dof] index into `nodal`
-  const double* N;           // [n_faces][n_q][n_dof]
-  const double* dN;          // [n_faces][n_q][dim-1][n_dof]
-  const double* weight;      // [n_faces][n_q]
-  const double* x_ref;       // [n_nodes][dim]
+  FaceView v;
   const double* u;
   const double* nodal;       // values at the face nodes, or nullptr: `value` everywhere
   double value;
@@ -37,54 +33,27 @@ struct BoundaryLinearizeArgs {
 };
 
 template<int DIM>
-__global__ __launch_bounds__(256) void boundary_linearize_kernel(BoundaryLinearizeArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;
-  const int n_dof = p.n_dof, n_q = p.n_q;
-  double pc = 0.0, xc[DIM];
-#pragma unroll
-  for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
-  if (lane < n_dof) {
-    pc = p.nodal ? p.nodal[p.local[(int64_t)f * n_dof + lane]] : p.value;
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = p.u[node * DIM + i] + p.x_ref[node * DIM + i];
-  }
+__global__ __launch_bounds__(kFaceWaveThreads) void boundary_linearize_kernel(BoundaryLinearizeArgs p) {
+  int lane, f;
+  if (!face_wave_index(p.v, lane, f)) return;
+  double xc[DIM];
+  const double pc = face_load_nodes<DIM, true, kNodalOrValue>(p.v, f, lane, p.u, xc, p.nodal, p.value);
   const bool any = __ballot(pc != 0.0) != 0;
   if (lane == 0) p.active[f] = any ? 1 : 0;
   if (!any) return;
-  for (int q0 = 0; q0 < n_q; q0 += 64) {
-    const bool on = q0 + lane < n_q;
-    const int64_t pt = (int64_t)f * n_q + (on ? q0 + lane : 0);
-    const double* N = p.N + pt * n_dof;
-    const double* dN = p.dN + pt * n_dof * (DIM - 1);
-    double pq = 0.0, t[(DIM - 1) * DIM];
+  const int64_t pt = face_lane_point(p.v, f, lane);
+  double pq, t[(DIM - 1) * DIM];
+  face_point_stage<DIM, true, false, true>(p.v, pt, pc, xc, &pq, nullptr, t);
+  if (!p.nodal) pq = p.value;
+  if (lane < p.v.n_q) {
+    p.coef[pt] = p.sign * (p.v.weight[pt] * pq);
 #pragma unroll
-    for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = 0.0;
-    for (int c = 0; c < n_dof; ++c) {
-      pq = __builtin_fma(N[c], face_lane_read(pc, c), pq);
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) {
-        const double x = face_lane_read(xc[i], c);
-#pragma unroll
-        for (int k = 0; k < DIM - 1; ++k) t[k * DIM + i] = __builtin_fma(x, dN[k * n_dof + c], t[k * DIM + i]);
-      }
-    }
-    if (!p.nodal) pq = p.value;
-    if (on) {
-      p.coef[pt] = p.sign * (p.weight[pt] * pq);
-#pragma unroll
-      for (int k = 0; k < (DIM - 1) * DIM; ++k) p.tang[pt * ((DIM - 1) * DIM) + k] = t[k];
-    }
+    for (int k = 0; k < (DIM - 1) * DIM; ++k) p.tang[pt * ((DIM - 1) * DIM) + k] = t[k];
   }
 }
 
 struct BoundaryActionArgs {
-  int n_faces, n_dof, n_q;
-  const int32_t* dofs;
-  const double* N;
-  const double* dN;
+  FaceView v;
   const double* coef;
   const double* tang;
   const unsigned char* active;
@@ -93,70 +62,33 @@ struct BoundaryActionArgs {
   double* face_y;            // [n_faces][dim][n_dof]
 };
 
+// the recorded tangents of the lane's point
 template<int DIM>
-__global__ __launch_bounds__(256) void boundary_action_kernel(BoundaryActionArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;
+MH_WAVE void face_recorded_tangents(const double* tang, int64_t pt, double* t) {
+#pragma unroll
+  for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = tang[pt * ((DIM - 1) * DIM) + k];
+}
+
+template<int DIM>
+__global__ __launch_bounds__(kFaceWaveThreads) void boundary_action_kernel(BoundaryActionArgs p) {
+  int lane, f;
+  if (!face_wave_index(p.v, lane, f)) return;
   if (!p.active[f]) return;   // (wave-uniform; the node sum skips the face)
-  const int n_dof = p.n_dof, n_q = p.n_q, NT = n_dof * DIM;
   double xc[DIM];
+  face_load_nodes<DIM, false>(p.v, f, lane, p.x, xc);
+  const FaceEntry e = face_lane_entry<DIM>(p.v, lane);
+  // stage 1, lane = point: g = c_q dm
+  const int64_t pt = face_lane_point(p.v, f, lane);
+  double g[DIM], t[(DIM - 1) * DIM], dt[(DIM - 1) * DIM], m[DIM], dm[DIM];
+  face_recorded_tangents<DIM>(p.tang, pt, t);
+  face_point_stage<DIM, false, false, true>(p.v, pt, 0.0, xc, nullptr, nullptr, dt);
+  face_normal_rate<DIM>(t, dt, m, dm);
+  const double cq = lane < p.v.n_q ? p.coef[pt] : 0.0;
 #pragma unroll
-  for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
-  if (lane < n_dof) {
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = p.x[node * DIM + i];
-  }
-  const int k = lane < NT ? lane : 0, ki = k / n_dof, ka = k % n_dof;
-  double Y = 0.0;
-  for (int q0 = 0; q0 < n_q; q0 += 64) {
-    // stage 1, lane = point q0 + lane: g = c_q dm
-    double g[DIM];
-    {
-      const bool on = q0 + lane < n_q;
-      const int64_t pt = (int64_t)f * n_q + (on ? q0 + lane : 0);
-      const double* dN = p.dN + pt * n_dof * (DIM - 1);
-      double dt[(DIM - 1) * DIM];
-#pragma unroll
-      for (int kk = 0; kk < (DIM - 1) * DIM; ++kk) dt[kk] = 0.0;
-      for (int c = 0; c < n_dof; ++c) {
-#pragma unroll
-        for (int i = 0; i < DIM; ++i) {
-          const double x = face_lane_read(xc[i], c);
-#pragma unroll
-          for (int kk = 0; kk < DIM - 1; ++kk) dt[kk * DIM + i] = __builtin_fma(x, dN[kk * n_dof + c], dt[kk * DIM + i]);
-        }
-      }
-      const double cq = on ? p.coef[pt] : 0.0;
-      double dm[DIM];
-      if constexpr (DIM == 2) {
-        dm[0] = dt[1];
-        dm[1] = -dt[0];
-      } else {
-        double t[6];
-#pragma unroll
-        for (int kk = 0; kk < 6; ++kk) t[kk] = p.tang[pt * 6 + kk];
-        const double *t1 = t, *t2 = t + 3, *d1 = dt, *d2 = dt + 3;
-        dm[0] = (d1[1] * t2[2] - d1[2] * t2[1]) + (t1[1] * d2[2] - t1[2] * d2[1]);
-        dm[1] = (d1[2] * t2[0] - d1[0] * t2[2]) + (t1[2] * d2[0] - t1[0] * d2[2]);
-        dm[2] = (d1[0] * t2[1] - d1[1] * t2[0]) + (t1[0] * d2[1] - t1[1] * d2[0]);
-      }
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) g[i] = cq * dm[i];
-    }
-    // stage 2, lane = (i, a): the trip's points in ascending order
-    const int n_trip = n_q - q0 < 64 ? n_q - q0 : 64;
-    for (int q = 0; q < n_trip; ++q) {
-      double gi = face_lane_read(g[0], q);
-#pragma unroll
-      for (int ii = 1; ii < DIM; ++ii) {
-        const double v = face_lane_read(g[ii], q);
-        gi = ki == ii ? v : gi;
-      }
-      Y = __builtin_fma(gi, p.N[((int64_t)f * n_q + q0 + q) * n_dof + ka], Y);
-    }
-  }
+  for (int i = 0; i < DIM; ++i) g[i] = cq * dm[i];
+  // stage 2, lane = (i, a)
+  const double Y = face_scatter_points<DIM, true>(p.v, f, e, g);
+  const int NT = p.v.n_dof * DIM;
   if (lane < NT) p.face_y[(int64_t)f * NT + lane] = p.factor * Y;   // [i][a]
 }
 
@@ -186,11 +118,10 @@ struct BoundaryAction {
     coef.resize(npts);
     tang.resize(npts * (h.dim - 1) * h.dim);
     active.resize((size_t)h.n_faces);
-    const BoundaryLinearizeArgs a{h.n_faces, h.n_dof, h.n_q, h.dofs.ptr, h.local.ptr, h.N.ptr, h.dN.ptr, h.weight.ptr, h.x_ref.ptr,
-                                  u_dev,     nodal,   value, sign,       coef.ptr,    tang.ptr, active.ptr};
-    const dim3 grid((unsigned)((h.n_faces + 3) / 4));
-    if (h.dim == 2) launch(boundary_linearize_kernel<2>, grid, dim3(256), 0, h.stream, a);
-    else launch(boundary_linearize_kernel<3>, grid, dim3(256), 0, h.stream, a);
+    const BoundaryLinearizeArgs a{h.view(), u_dev, nodal, value, sign, coef.ptr, tang.ptr, active.ptr};
+    face_dispatch_dim(h.dim, [&](auto D) {
+      launch(boundary_linearize_kernel<decltype(D)::value>, face_wave_grid(h.n_faces), dim3(kFaceWaveThreads), 0, h.stream, a);
+    });
     if (!lin_event) MH_HIP(hipEventCreateWithFlags(&lin_event, hipEventDisableTiming));
     MH_HIP(hipEventRecord(lin_event, h.stream));
     lin_stream = h.stream;
@@ -209,13 +140,11 @@ struct BoundaryAction {
 
   // y += factor K_face x over the recorded active faces; x, y on the device, everything on s
   void add(FaceAssembly& h, double factor, const double* x, double* y, hipStream_t s) {
-    const BoundaryActionArgs a{h.n_faces, h.n_dof, h.n_q, h.dofs.ptr, h.N.ptr, h.dN.ptr, coef.ptr, tang.ptr, active.ptr, factor, x, face_y.ptr};
-    const dim3 grid((unsigned)((h.n_faces + 3) / 4));
-    if (h.dim == 2) launch(boundary_action_kernel<2>, grid, dim3(256), 0, s, a);
-    else launch(boundary_action_kernel<3>, grid, dim3(256), 0, s, a);
-    if (h.dim == 2) h.template gather_vector<2>(active.ptr, face_y.ptr, y, s);
-    else h.template gather_vector<3>(active.ptr, face_y.ptr, y, s);
-    MH_HIP(hipGetLastError());
+    const BoundaryActionArgs a{h.view(), coef.ptr, tang.ptr, active.ptr, factor, x, face_y.ptr};
+    face_dispatch_dim(h.dim, [&](auto D) {
+      launch(boundary_action_kernel<decltype(D)::value>, face_wave_grid(h.n_faces), dim3(kFaceWaveThreads), 0, s, a);
+    });
+    h.gather_vector(active.ptr, face_y.ptr, y, s);
   }
 };
 

@@ -13,7 +13,7 @@
 // p_i = 0, so the recorded flags of the frozen record decide which faces run here as well.
 //   record   on top of coef / tang / active (written by boundary_linearize_kernel as ever): per point g_q and chi_q nu_q,
 //            per marked node A_i and p_i (copies: later evaluations overwrite the handle's), the penalty of that moment
-//   action   face rates   one wave per face.  Lane = point (trips of 64): dx_q, dt, dm, n.dm, a_q = w (n.dm),
+//   action   face rates   one wave per face.  Lane = point: dx_q, dt, dm, n.dm, a_q = w (n.dm),
 //                         b_q = w ((n.dm) g_q + |m| chi nu.dx_q); lane = local node c: face_dA[f][c] = sum_q a_q N_q[c],
 //                         face_dG[f][c] = sum_q b_q N_q[c] over the points in ascending order
 //            nodal        one thread per marked node: the sums over its incidences in the order of adj, dp_l
@@ -21,6 +21,7 @@
 //            node sum     face_row_gather_kernel<DIM, 0> over the recorded flags
 // One wave per face, four faces per workgroup, no LDS, no atomics: equal inputs give equal bytes.  The action's kernels run in
 // registers only; the record kernel keeps the private arrays of the spline search in scratch, as pass 1 does.
+// The stages of the face kernels (wave index, node load, point stage, normal rate, point scatter) are face_wave.hpp's.
 // Only contact.hip includes this header.
 #pragma once
 
@@ -30,11 +31,7 @@ namespace mimi_hip {
 namespace {
 
 struct ConsistentRecordArgs {
-  int n_faces, n_dof, n_q;
-  const int32_t* dofs;
-  const int32_t* local;
-  const double* N;
-  const double* x_ref;
+  FaceView v;
   const double* u;
   const double* pressure;    // [n_marked] of the linearisation
   double* gq;                // [n_faces][n_q]        g_q
@@ -45,38 +42,22 @@ struct ConsistentRecordArgs {
 // waves per SIMD asked for: left to a whole SIMD's registers the compiler keeps the spline search's arrays in 255 vector and
 // 202 accumulator registers at one wave per SIMD; so they sit in scratch as in contact_gap_area_kernel, at 63 registers.)
 template<int DIM, class Body>
-__global__ __launch_bounds__(256, 4) void contact_consistent_record_kernel(ConsistentRecordArgs p, Body body) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;
-  const int n_dof = p.n_dof, n_q = p.n_q;
-  double pc = 0.0, xc[DIM];
-#pragma unroll
-  for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
-  if (lane < n_dof) {
-    pc = p.pressure[p.local[(int64_t)f * n_dof + lane]];
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = p.u[node * DIM + i] + p.x_ref[node * DIM + i];
-  }
+__global__ __launch_bounds__(kFaceWaveThreads, 4) void contact_consistent_record_kernel(ConsistentRecordArgs p, Body body) {
+  int lane, f;
+  if (!face_wave_index(p.v, lane, f)) return;
+  double xc[DIM];
+  const double pc = face_load_nodes<DIM, true, kNodal>(p.v, f, lane, p.u, xc, p.pressure);
   if (__ballot(pc != 0.0) == 0) return;   // IsPressureZero: the flag boundary_linearize_kernel records
-  // lane = point (a contact face holds at most a wave's 64: checked at create)
-  const bool on = lane < n_q;
-  const int64_t pt = (int64_t)f * n_q + (on ? lane : 0);
-  const double* N = p.N + pt * n_dof;
+  // lane = point: x_q in the accumulation order of contact_gap_area_kernel (face_wave.hpp's contract), hence the same g_q
+  const int64_t pt = face_lane_point(p.v, f, lane);
   double xq[DIM];
-#pragma unroll
-  for (int i = 0; i < DIM; ++i) xq[i] = 0.0;
-  for (int c = 0; c < n_dof; ++c) {     // (the order of contact_gap_area_kernel: the same x_q, hence the same g_q)
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) xq[i] = __builtin_fma(face_lane_read(xc[i], c), N[c], xq[i]);
-  }
+  face_point_stage<DIM, false, true, false>(p.v, pt, 0.0, xc, nullptr, xq, nullptr);
   double true_g, distance, nu[DIM];
   body.template nearest<DIM>(xq, true_g, distance, nu);
   double g = true_g < 0. ? true_g : 0.;
   const double ratio = fabs(true_g) / distance;
   if (acos(ratio < 1. ? ratio : 1.) > 1.e-5) g = 0.0;   // angle tolerance, mortar_contact.cpp:172-181
-  if (on) {
+  if (lane < p.v.n_q) {
     p.gq[pt] = g;
 #pragma unroll
     for (int i = 0; i < DIM; ++i) p.chinu[pt * DIM + i] = g != 0.0 ? nu[i] : 0.0;
@@ -84,11 +65,7 @@ __global__ __launch_bounds__(256, 4) void contact_consistent_record_kernel(Consi
 }
 
 struct ConsistentRatesArgs {
-  int n_faces, n_dof, n_q;
-  const int32_t* dofs;
-  const double* N;
-  const double* dN;
-  const double* weight;
+  FaceView v;
   const double* tang;
   const double* gq;
   const double* chinu;
@@ -98,83 +75,37 @@ struct ConsistentRatesArgs {
   double* face_dG;           // [n_faces][n_dof]
 };
 
-// dm of the direction's tangents dt at the recorded tangents t, and m itself
 template<int DIM>
-MH_DEV void consistent_normal_rate(const double* t, const double* dt, double* m, double* dm) {
-  face_normal<DIM>(t, m);
-  if constexpr (DIM == 2) {
-    dm[0] = dt[1];
-    dm[1] = -dt[0];
-  } else {
-    const double *t1 = t, *t2 = t + 3, *d1 = dt, *d2 = dt + 3;
-    dm[0] = (d1[1] * t2[2] - d1[2] * t2[1]) + (t1[1] * d2[2] - t1[2] * d2[1]);
-    dm[1] = (d1[2] * t2[0] - d1[0] * t2[2]) + (t1[2] * d2[0] - t1[0] * d2[2]);
-    dm[2] = (d1[0] * t2[1] - d1[1] * t2[0]) + (t1[0] * d2[1] - t1[1] * d2[0]);
-  }
-}
-
-template<int DIM>
-__global__ __launch_bounds__(256) void contact_consistent_rates_kernel(ConsistentRatesArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;
+__global__ __launch_bounds__(kFaceWaveThreads) void contact_consistent_rates_kernel(ConsistentRatesArgs p) {
+  int lane, f;
+  if (!face_wave_index(p.v, lane, f)) return;
   if (!p.active[f]) return;   // (wave-uniform; the nodal sum skips the face)
-  const int n_dof = p.n_dof, n_q = p.n_q;
+  const int n_dof = p.v.n_dof, n_q = p.v.n_q;
   double xc[DIM];
-#pragma unroll
-  for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
-  if (lane < n_dof) {
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = p.x[node * DIM + i];
-  }
+  face_load_nodes<DIM, false>(p.v, f, lane, p.x, xc);
   const int kc = lane < n_dof ? lane : 0;
+  // stage 1, lane = point: a_q, b_q
+  const bool on = lane < n_q;
+  const int64_t pt = face_lane_point(p.v, f, lane);
+  double dx[DIM], dt[(DIM - 1) * DIM], t[(DIM - 1) * DIM], m[DIM], dm[DIM];
+  face_recorded_tangents<DIM>(p.tang, pt, t);
+  face_point_stage<DIM, false, true, true>(p.v, pt, 0.0, xc, nullptr, dx, dt);
+  face_normal_rate<DIM>(t, dt, m, dm);
+  double mm = 0.0, mdm = 0.0, nudx = 0.0;
+#pragma unroll
+  for (int i = 0; i < DIM; ++i) {
+    mm += m[i] * m[i];
+    mdm += m[i] * dm[i];
+    nudx += p.chinu[pt * DIM + i] * dx[i];
+  }
+  const double len = sqrt(mm), ndm = mdm / len, w = p.v.weight[pt];
+  const double aq = on ? w * ndm : 0.0, bq = on ? w * (ndm * p.gq[pt] + len * nudx) : 0.0;
+  // stage 2, lane = local node: the points in ascending order
   double dA = 0.0, dG = 0.0;
-  for (int q0 = 0; q0 < n_q; q0 += 64) {
-    // stage 1, lane = point q0 + lane: a_q, b_q
-    double aq, bq;
-    {
-      const bool on = q0 + lane < n_q;
-      const int64_t pt = (int64_t)f * n_q + (on ? q0 + lane : 0);
-      const double* N = p.N + pt * n_dof;
-      const double* dN = p.dN + pt * n_dof * (DIM - 1);
-      double dx[DIM], dt[(DIM - 1) * DIM], t[(DIM - 1) * DIM];
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) dx[i] = 0.0;
-#pragma unroll
-      for (int kk = 0; kk < (DIM - 1) * DIM; ++kk) {
-        dt[kk] = 0.0;
-        t[kk] = p.tang[pt * ((DIM - 1) * DIM) + kk];
-      }
-      for (int c = 0; c < n_dof; ++c) {
-#pragma unroll
-        for (int i = 0; i < DIM; ++i) {
-          const double x = face_lane_read(xc[i], c);
-          dx[i] = __builtin_fma(x, N[c], dx[i]);
-#pragma unroll
-          for (int kk = 0; kk < DIM - 1; ++kk) dt[kk * DIM + i] = __builtin_fma(x, dN[kk * n_dof + c], dt[kk * DIM + i]);
-        }
-      }
-      double m[DIM], dm[DIM];
-      consistent_normal_rate<DIM>(t, dt, m, dm);
-      double mm = 0.0, mdm = 0.0, nudx = 0.0;
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) {
-        mm += m[i] * m[i];
-        mdm += m[i] * dm[i];
-        nudx += p.chinu[pt * DIM + i] * dx[i];
-      }
-      const double len = sqrt(mm), ndm = mdm / len, w = p.weight[pt];
-      aq = on ? w * ndm : 0.0;
-      bq = on ? w * (ndm * p.gq[pt] + len * nudx) : 0.0;
-    }
-    // stage 2, lane = local node: the trip's points in ascending order
-    const int n_trip = n_q - q0 < 64 ? n_q - q0 : 64;
-    for (int q = 0; q < n_trip; ++q) {
-      const double Nc = p.N[((int64_t)f * n_q + q0 + q) * n_dof + kc];
-      dA = __builtin_fma(face_lane_read(aq, q), Nc, dA);
-      dG = __builtin_fma(face_lane_read(bq, q), Nc, dG);
-    }
+  for (int q = 0; q < n_q; ++q) {
+    const double Nc = p.v.N[((int64_t)f * n_q + q) * n_dof + kc];
+    dA = __builtin_fma(face_lane_read(aq, q), Nc, dA);
+    dG = __builtin_fma(face_lane_read(bq, q), Nc, dG);
   }
   if (lane < n_dof) {
     p.face_dA[(int64_t)f * n_dof + lane] = dA;
@@ -206,12 +137,7 @@ __global__ __launch_bounds__(256) void contact_consistent_nodal_kernel(int n_mar
 }
 
 struct ConsistentActionArgs {
-  int n_faces, n_dof, n_q;
-  const int32_t* dofs;
-  const int32_t* local;
-  const double* N;
-  const double* dN;
-  const double* weight;
+  FaceView v;
   const double* coef;
   const double* tang;
   const unsigned char* active;
@@ -222,64 +148,26 @@ struct ConsistentActionArgs {
 };
 
 template<int DIM>
-__global__ __launch_bounds__(256) void contact_consistent_action_kernel(ConsistentActionArgs p) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;
+__global__ __launch_bounds__(kFaceWaveThreads) void contact_consistent_action_kernel(ConsistentActionArgs p) {
+  int lane, f;
+  if (!face_wave_index(p.v, lane, f)) return;
   if (!p.active[f]) return;   // (wave-uniform; the node sum skips the face)
-  const int n_dof = p.n_dof, n_q = p.n_q, NT = n_dof * DIM;
-  double dpc = 0.0, xc[DIM];
+  double xc[DIM];
+  const double dpc = face_load_nodes<DIM, false, kNodal>(p.v, f, lane, p.x, xc, p.dp);
+  const FaceEntry e = face_lane_entry<DIM>(p.v, lane);
+  // stage 1, lane = point: g = c_q dm - w dp_q m
+  const bool on = lane < p.v.n_q;
+  const int64_t pt = face_lane_point(p.v, f, lane);
+  double g[DIM], dpq, dt[(DIM - 1) * DIM], t[(DIM - 1) * DIM], m[DIM], dm[DIM];
+  face_recorded_tangents<DIM>(p.tang, pt, t);
+  face_point_stage<DIM, true, false, true>(p.v, pt, dpc, xc, &dpq, nullptr, dt);
+  face_normal_rate<DIM>(t, dt, m, dm);
+  const double cq = on ? p.coef[pt] : 0.0, wdp = on ? p.v.weight[pt] * dpq : 0.0;
 #pragma unroll
-  for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
-  if (lane < n_dof) {
-    dpc = p.dp[p.local[(int64_t)f * n_dof + lane]];
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = p.x[node * DIM + i];
-  }
-  const int k = lane < NT ? lane : 0, ki = k / n_dof, ka = k % n_dof;
-  double Y = 0.0;
-  for (int q0 = 0; q0 < n_q; q0 += 64) {
-    // stage 1, lane = point q0 + lane: g = c_q dm - w dp_q m
-    double g[DIM];
-    {
-      const bool on = q0 + lane < n_q;
-      const int64_t pt = (int64_t)f * n_q + (on ? q0 + lane : 0);
-      const double* N = p.N + pt * n_dof;
-      const double* dN = p.dN + pt * n_dof * (DIM - 1);
-      double dpq = 0.0, dt[(DIM - 1) * DIM], t[(DIM - 1) * DIM];
-#pragma unroll
-      for (int kk = 0; kk < (DIM - 1) * DIM; ++kk) {
-        dt[kk] = 0.0;
-        t[kk] = p.tang[pt * ((DIM - 1) * DIM) + kk];
-      }
-      for (int c = 0; c < n_dof; ++c) {
-        dpq = __builtin_fma(N[c], face_lane_read(dpc, c), dpq);
-#pragma unroll
-        for (int i = 0; i < DIM; ++i) {
-          const double x = face_lane_read(xc[i], c);
-#pragma unroll
-          for (int kk = 0; kk < DIM - 1; ++kk) dt[kk * DIM + i] = __builtin_fma(x, dN[kk * n_dof + c], dt[kk * DIM + i]);
-        }
-      }
-      double m[DIM], dm[DIM];
-      consistent_normal_rate<DIM>(t, dt, m, dm);
-      const double cq = on ? p.coef[pt] : 0.0, wdp = on ? p.weight[pt] * dpq : 0.0;
-#pragma unroll
-      for (int i = 0; i < DIM; ++i) g[i] = cq * dm[i] - wdp * m[i];
-    }
-    // stage 2, lane = (i, a): the trip's points in ascending order
-    const int n_trip = n_q - q0 < 64 ? n_q - q0 : 64;
-    for (int q = 0; q < n_trip; ++q) {
-      double gi = face_lane_read(g[0], q);
-#pragma unroll
-      for (int ii = 1; ii < DIM; ++ii) {
-        const double v = face_lane_read(g[ii], q);
-        gi = ki == ii ? v : gi;
-      }
-      Y = __builtin_fma(gi, p.N[((int64_t)f * n_q + q0 + q) * n_dof + ka], Y);
-    }
-  }
+  for (int i = 0; i < DIM; ++i) g[i] = cq * dm[i] - wdp * m[i];
+  // stage 2, lane = (i, a)
+  const double Y = face_scatter_points<DIM, true>(p.v, f, e, g);
+  const int NT = p.v.n_dof * DIM;
   if (lane < NT) p.face_y[(int64_t)f * NT + lane] = p.factor * Y;   // [i][a]
 }
 
@@ -311,10 +199,11 @@ struct ContactAction : BoundaryAction {
       pressure.resize((size_t)h.n_fnodes);
       MH_HIP(hipMemcpyAsync(area.ptr, area_now, nb, hipMemcpyDeviceToDevice, h.stream));
       MH_HIP(hipMemcpyAsync(pressure.ptr, pressure_now, nb, hipMemcpyDeviceToDevice, h.stream));
-      const ConsistentRecordArgs a{h.n_faces, h.n_dof, h.n_q, h.dofs.ptr, h.local.ptr, h.N.ptr, h.x_ref.ptr, u_dev, pressure_now, gq.ptr, chinu.ptr};
-      const dim3 grid((unsigned)((h.n_faces + 3) / 4));
-      if (h.dim == 2) launch(contact_consistent_record_kernel<2, Body>, grid, dim3(256), 0, h.stream, a, body);
-      else launch(contact_consistent_record_kernel<3, Body>, grid, dim3(256), 0, h.stream, a, body);
+      const ConsistentRecordArgs a{h.view(), u_dev, pressure_now, gq.ptr, chinu.ptr};
+      face_dispatch_dim(h.dim, [&](auto D) {
+        launch(contact_consistent_record_kernel<decltype(D)::value, Body>, face_wave_grid(h.n_faces), dim3(kFaceWaveThreads), 0,
+               h.stream, a, body);
+      });
       penalty = penalty_now;
     }
     consistent = on;
@@ -331,11 +220,10 @@ struct ContactAction : BoundaryAction {
 
   // dp [n_marked] of the direction x: the face rates and the nodal sums (a consistent record)
   void nodal_rates(FaceAssembly& h, const double* x, hipStream_t s) {
-    const dim3 grid((unsigned)((h.n_faces + 3) / 4));
-    const ConsistentRatesArgs r{h.n_faces, h.n_dof,   h.n_q,      h.dofs.ptr, h.N.ptr, h.dN.ptr,    h.weight.ptr,
-                                tang.ptr,  gq.ptr,    chinu.ptr,  active.ptr, x,       face_dA.ptr, face_dG.ptr};
-    if (h.dim == 2) launch(contact_consistent_rates_kernel<2>, grid, dim3(256), 0, s, r);
-    else launch(contact_consistent_rates_kernel<3>, grid, dim3(256), 0, s, r);
+    const ConsistentRatesArgs r{h.view(), tang.ptr, gq.ptr, chinu.ptr, active.ptr, x, face_dA.ptr, face_dG.ptr};
+    face_dispatch_dim(h.dim, [&](auto D) {
+      launch(contact_consistent_rates_kernel<decltype(D)::value>, face_wave_grid(h.n_faces), dim3(kFaceWaveThreads), 0, s, r);
+    });
     launch(contact_consistent_nodal_kernel, dim3((unsigned)((h.n_fnodes + 255) / 256)), dim3(256), 0, s, h.n_fnodes, h.n_dof,
            h.adj_ptr.ptr, h.adj.ptr, active.ptr, face_dA.ptr, face_dG.ptr, area.ptr, pressure.ptr, penalty, dp.ptr);
   }
@@ -347,14 +235,11 @@ struct ContactAction : BoundaryAction {
       return;
     }
     nodal_rates(h, x, s);
-    const dim3 grid((unsigned)((h.n_faces + 3) / 4));
-    const ConsistentActionArgs a{h.n_faces, h.n_dof,  h.n_q,      h.dofs.ptr, h.local.ptr, h.N.ptr, h.dN.ptr,   h.weight.ptr,
-                                 coef.ptr,  tang.ptr, active.ptr, dp.ptr,     factor,      x,       face_y.ptr};
-    if (h.dim == 2) launch(contact_consistent_action_kernel<2>, grid, dim3(256), 0, s, a);
-    else launch(contact_consistent_action_kernel<3>, grid, dim3(256), 0, s, a);
-    if (h.dim == 2) h.template gather_vector<2>(active.ptr, face_y.ptr, y, s);
-    else h.template gather_vector<3>(active.ptr, face_y.ptr, y, s);
-    MH_HIP(hipGetLastError());
+    const ConsistentActionArgs a{h.view(), coef.ptr, tang.ptr, active.ptr, dp.ptr, factor, x, face_y.ptr};
+    face_dispatch_dim(h.dim, [&](auto D) {
+      launch(contact_consistent_action_kernel<decltype(D)::value>, face_wave_grid(h.n_faces), dim3(kFaceWaveThreads), 0, s, a);
+    });
+    h.gather_vector(active.ptr, face_y.ptr, y, s);
   }
 };
 

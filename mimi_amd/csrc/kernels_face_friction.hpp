@@ -11,6 +11,7 @@
 //   K(ai,bj) = sum_q w N_a (t_i n_k D_kbj + |m| dt_i / dx_bj), D = dm / dx, with p_A, xi, xbar, d, c and the branch frozen.
 // State arrays are [n_faces][DIM][n_q] (c: [n_faces][n_q]): the lanes of a wave, one per point, read and write neighbours.
 // An evaluation writes the TRIAL arrays only; contact_friction_commit_kernel copies them over the committed ones.
+// Wave index, node load, point stage, normal column, point scatter and the node-pair loop are face_wave.hpp's.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -23,13 +24,7 @@ constexpr int kFrictionScalars = 6;   // per face and in total: force[3] = sum d
 
 struct FrictionArgs {
   // the face tables and stores of the contact handle (ContactArgs of contact.hip)
-  int n_faces, n_dof, n_q;
-  const int32_t* dofs;       // [n_faces][n_dof] global node ids
-  const int32_t* local;      // [n_faces][n_dof] index into the nodal arrays
-  const double* N;           // [n_faces][n_q][n_dof]
-  const double* dN;          // [n_faces][n_q][dim-1][n_dof]
-  const double* weight;      // [n_faces][n_q]
-  const double* x_ref;       // [n_nodes][dim]
+  FaceView v;
   const double* u;
   const double* pressure;    // [n_marked] nodal pressures of this evaluation
   double* face_r;            // [n_faces][dim][n_dof]  written by contact_residual_wave_kernel before
@@ -57,36 +52,20 @@ struct FrictionPoint {
 // lane c < n_dof holds node c of face f (pressure pc, position xc); lane q < n_q evaluates point q (the other lanes return
 // br = 0) and, with `store`, writes the trial state of its point
 template<int DIM>
-MH_DEV FrictionPoint<DIM> friction_point(const FrictionArgs& fr, int f, int lane, double pc, const double* xc,
+MH_WAVE FrictionPoint<DIM> friction_point(const FrictionArgs& fr, int f, int lane, double pc, const double* xc,
                                          bool store) {
   FrictionPoint<DIM> P;
-  const int n_dof = fr.n_dof, n_q = fr.n_q;
+  const int n_q = fr.v.n_q;
   const bool on = lane < n_q;
   const int q = on ? lane : 0;
-  const int64_t pt = (int64_t)f * n_q + q;
-  const double* N = fr.N + pt * n_dof;
-  const double* dN = fr.dN + pt * n_dof * (DIM - 1);
-  double pq = 0.0, xq[DIM];
-#pragma unroll
-  for (int i = 0; i < DIM; ++i) xq[i] = 0.0;
-#pragma unroll
-  for (int k = 0; k < (DIM - 1) * DIM; ++k) P.tq[k] = 0.0;
-  for (int c = 0; c < n_dof; ++c) {
-    pq = __builtin_fma(N[c], face_lane_read(pc, c), pq);
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) {
-      const double x = face_lane_read(xc[i], c);
-      xq[i] = __builtin_fma(x, N[c], xq[i]);
-#pragma unroll
-      for (int k = 0; k < DIM - 1; ++k) P.tq[k * DIM + i] = __builtin_fma(x, dN[k * n_dof + c], P.tq[k * DIM + i]);
-    }
-  }
-  double m[DIM], mm = 0.0;
+  const int64_t pt = face_lane_point(fr.v, f, lane);
+  double pq, xq[DIM], m[DIM], mm = 0.0;
+  face_point_stage<DIM, true, true, true>(fr.v, pt, pc, xc, &pq, xq, P.tq);
   face_normal<DIM>(P.tq, m);
 #pragma unroll
   for (int i = 0; i < DIM; ++i) mm += m[i] * m[i];
   P.detJ = sqrt(mm);
-  P.w = fr.weight[pt];
+  P.w = fr.v.weight[pt];
 #pragma unroll
   for (int i = 0; i < DIM; ++i) P.n[i] = m[i] / P.detJ;
   const double pn = -pq;
@@ -145,26 +124,17 @@ MH_DEV FrictionPoint<DIM> friction_point(const FrictionArgs& fr, int f, int lane
 
 // lane c < n_dof: the pressure and the position of node c of face f
 template<int DIM>
-MH_DEV void friction_face_nodes(const FrictionArgs& fr, int f, int lane, double& pc, double* xc) {
-  pc = 0.0;
-#pragma unroll
-  for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
-  if (lane < fr.n_dof) {
-    pc = fr.pressure[fr.local[(int64_t)f * fr.n_dof + lane]];
-    const int64_t node = fr.dofs[(int64_t)f * fr.n_dof + lane];
-#pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = fr.u[node * DIM + i] + fr.x_ref[node * DIM + i];
-  }
+MH_WAVE void friction_face_nodes(const FrictionArgs& fr, int f, int lane, double& pc, double* xc) {
+  pc = face_load_nodes<DIM, true, kNodal>(fr.v, f, lane, fr.u, xc, fr.pressure);
 }
 
 // point evaluation, trial-state store, face residual and history scalars of the face.  A face none of whose points carries
 // a traction leaves face_r alone (it may be an inactive face, whose face_r nobody wrote).
 template<int DIM>
-__global__ __launch_bounds__(256) void contact_friction_kernel(FrictionArgs fr) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= fr.n_faces) return;
-  const int n_dof = fr.n_dof, n_q = fr.n_q, NT = n_dof * DIM;
+__global__ __launch_bounds__(kFaceWaveThreads) void contact_friction_kernel(FrictionArgs fr) {
+  int lane, f;
+  if (!face_wave_index(fr.v, lane, f)) return;
+  const int n_q = fr.v.n_q, NT = fr.v.n_dof * DIM;
   double pc, xc[DIM];
   friction_face_nodes<DIM>(fr, f, lane, pc, xc);
   const FrictionPoint<DIM> P = friction_point<DIM>(fr, f, lane, pc, xc, true);
@@ -183,20 +153,8 @@ __global__ __launch_bounds__(256) void contact_friction_kernel(FrictionArgs fr) 
   }
   const double datn = da * sqrt(tt);
   // lane k = i n_dof + a: R(a, i) = sum_q (da t_i)_q N_q[a], over the points in order
-  {
-    const int k = lane < NT ? lane : 0, i = k / n_dof, a = k % n_dof;
-    double R = 0.0;
-    for (int q = 0; q < n_q; ++q) {
-      double v = face_lane_read(dat[0], q);
-#pragma unroll
-      for (int ii = 1; ii < DIM; ++ii) {
-        const double vi = face_lane_read(dat[ii], q);
-        v = i == ii ? vi : v;
-      }
-      R += v * fr.N[((int64_t)f * n_q + q) * n_dof + a];
-    }
-    if (lane < NT) fr.face_r[(int64_t)f * NT + lane] += R;      // [i][a]
-  }
+  const double R = face_scatter_points<DIM, false>(fr.v, f, face_lane_entry<DIM>(fr.v, lane), dat);
+  if (lane < NT) fr.face_r[(int64_t)f * NT + lane] += R;      // [i][a]
   // history of the face, in the order of the points (every lane the same sums; lane 0 stores)
   {
     double force[3] = {0.0, 0.0, 0.0}, trac = 0.0, n_stick = 0.0, n_slip = 0.0;
@@ -222,11 +180,10 @@ __global__ __launch_bounds__(256) void contact_friction_kernel(FrictionArgs fr) 
 // the friction tangent of the face added to its block of face_k (which contact_tangent_kernel wrote before): stage 1 as
 // above without the store, stage 2 lane = node pair (a, b), the point's numbers read from the lane that computed them
 template<int DIM>
-__global__ __launch_bounds__(256) void contact_friction_tangent_kernel(FrictionArgs fr) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= fr.n_faces) return;
-  const int n_dof = fr.n_dof, n_q = fr.n_q;
+__global__ __launch_bounds__(kFaceWaveThreads) void contact_friction_tangent_kernel(FrictionArgs fr) {
+  int lane, f;
+  if (!face_wave_index(fr.v, lane, f)) return;
+  const int n_dof = fr.v.n_dof, n_q = fr.v.n_q;
   double pc, xc[DIM];
   friction_face_nodes<DIM>(fr, f, lane, pc, xc);
   const FrictionPoint<DIM> P = friction_point<DIM>(fr, f, lane, pc, xc, false);
@@ -234,22 +191,14 @@ __global__ __launch_bounds__(256) void contact_friction_tangent_kernel(FrictionA
   double naq = 0.0;
 #pragma unroll
   for (int i = 0; i < DIM; ++i) naq += P.n[i] * P.a[i];
-  const int n_pairs = n_dof * n_dof, NT = n_dof * DIM;
-  double* Kf = fr.face_k + (int64_t)f * NT * NT;
-  for (int pair0 = 0; pair0 < n_pairs; pair0 += 64) {
-    const int pair = pair0 + lane;
-    const bool on = pair < n_pairs;
-    const int a = on ? pair / n_dof : 0, b = on ? pair % n_dof : 0;
-    double acc[DIM * DIM];
-#pragma unroll
-    for (int k = 0; k < DIM * DIM; ++k) acc[k] = 0.0;
+  face_pair_loop<DIM, true>(n_dof, lane, fr.face_k + (int64_t)f * (n_dof * DIM) * (n_dof * DIM), [&](int a, int b, double* acc) {
     for (int q = 0; q < n_q; ++q) {
       const int br = __builtin_amdgcn_readlane(P.br, q);
       if (br == 0) continue;   // (wave-uniform)
       const int64_t pt = (int64_t)f * n_q + q;
-      const double* dN = fr.dN + pt * n_dof * (DIM - 1);
-      const double Nb = fr.N[pt * n_dof + b];
-      const double wN = face_lane_read(P.w, q) * fr.N[pt * n_dof + a];
+      const double* dN = fr.v.dN + pt * n_dof * (DIM - 1);
+      const double Nb = fr.v.N[pt * n_dof + b];
+      const double wN = face_lane_read(P.w, q) * fr.v.N[pt * n_dof + a];
       const double detJ = face_lane_read(P.detJ, q), na = face_lane_read(naq, q), coef = face_lane_read(P.coef, q);
       double n[DIM], av[DIM], tv[DIM], sh[DIM], t[(DIM - 1) * DIM];
 #pragma unroll
@@ -259,26 +208,12 @@ __global__ __launch_bounds__(256) void contact_friction_tangent_kernel(FrictionA
         tv[i] = face_lane_read(P.t[i], q);
         sh[i] = face_lane_read(P.sh[i], q);
       }
-      if constexpr (DIM == 3) {
 #pragma unroll
-        for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = face_lane_read(P.tq[k], q);
-      }
+      for (int k = 0; k < (DIM - 1) * DIM; ++k) t[k] = face_lane_read(P.tq[k], q);
 #pragma unroll
       for (int j = 0; j < DIM; ++j) {
         double dm[DIM];   // d m / d x_bj
-        if constexpr (DIM == 2) {
-          dm[0] = (j == 1) ? dN[b] : 0.0;
-          dm[1] = (j == 0) ? -dN[b] : 0.0;
-        } else {
-          double e[3] = {0, 0, 0};
-          e[j] = 1.0;
-          const double* t1 = t;
-          const double* t2 = t + 3;
-          const double d1 = dN[b], d2 = dN[n_dof + b];
-          dm[0] = d1 * (e[1] * t2[2] - e[2] * t2[1]) + d2 * (t1[1] * e[2] - t1[2] * e[1]);
-          dm[1] = d1 * (e[2] * t2[0] - e[0] * t2[2]) + d2 * (t1[2] * e[0] - t1[0] * e[2]);
-          dm[2] = d1 * (e[0] * t2[1] - e[1] * t2[0]) + d2 * (t1[0] * e[1] - t1[1] * e[0]);
-        }
+        face_normal_column<DIM>(t, dN, n_dof, b, j, dm);
         double nD = 0.0;   // d |m|
 #pragma unroll
         for (int k = 0; k < DIM; ++k) nD += n[k] * dm[k];
@@ -302,13 +237,7 @@ __global__ __launch_bounds__(256) void contact_friction_tangent_kernel(FrictionA
         }
       }
     }
-    if (on) {
-#pragma unroll
-      for (int i = 0; i < DIM; ++i)
-#pragma unroll
-        for (int j = 0; j < DIM; ++j) Kf[(a * DIM + i) * NT + j * n_dof + b] += acc[i * DIM + j];
-    }
-  }
+  });
 }
 
 // commit: the trial state over the committed one (n_state = n_points * dim doubles each, n_points flags)

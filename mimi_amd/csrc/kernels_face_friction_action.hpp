@@ -22,6 +22,8 @@
 //            adds nothing.
 // One wave per face, four faces per workgroup, registers only: no LDS, no atomics, a fixed summation order -- equal inputs
 // give equal bytes.  A record without friction (the action off, or mu = 0 at the linearize) launches what it always did.
+// The record kernel stands on face_wave.hpp's stages; the action kernel has them in its own text (see there) and shares
+// face_normal_rate.
 // Only contact.hip includes this header.
 #pragma once
 
@@ -39,15 +41,14 @@ struct FrictionRecordArgs {
 
 // every face, active or not: a face without pressure gets branch 0 at all its points
 template<int DIM>
-__global__ __launch_bounds__(256) void contact_friction_record_kernel(FrictionArgs fr, FrictionRecordArgs rec) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= fr.n_faces) return;
+__global__ __launch_bounds__(kFaceWaveThreads) void contact_friction_record_kernel(FrictionArgs fr, FrictionRecordArgs rec) {
+  int lane, f;
+  if (!face_wave_index(fr.v, lane, f)) return;
   double pc, xc[DIM];
   friction_face_nodes<DIM>(fr, f, lane, pc, xc);
   const FrictionPoint<DIM> P = friction_point<DIM>(fr, f, lane, pc, xc, false);
-  if (lane < fr.n_q) {   // (a contact face holds at most a wave's 64 points: checked at create)
-    const int64_t pt = (int64_t)f * fr.n_q + lane;
+  if (lane < fr.v.n_q) {   // (a contact face holds at most a wave's 64 points: checked at create)
+    const int64_t pt = (int64_t)f * fr.v.n_q + lane;
 #pragma unroll
     for (int i = 0; i < DIM; ++i) rec.a[pt * DIM + i] = P.a[i];
     rec.coef[pt] = P.coef;
@@ -56,12 +57,7 @@ __global__ __launch_bounds__(256) void contact_friction_record_kernel(FrictionAr
 }
 
 struct FrictionActionArgs {
-  int n_faces, n_dof, n_q;
-  const int32_t* dofs;
-  const int32_t* local;
-  const double* N;
-  const double* dN;
-  const double* weight;
+  FaceView v;
   const double* coef;        // the frozen record
   const double* tang;
   const unsigned char* active;
@@ -75,19 +71,22 @@ struct FrictionActionArgs {
   double* face_y;            // [n_faces][dim][n_dof]
 };
 
+// (The kernel keeps its own stage text, the trips over the points included, although a face holds at most 64: written on
+// face_wave.hpp's stages without the loop it was 9 .. 14 % faster where few faces are active and 0.3 % slower, in every set of
+// runs, where all are -- profiles/face_wave_refactor.txt, section 6 -- and its times are to stay the parent's.)
 template<int DIM, bool CONSISTENT>
-__global__ __launch_bounds__(256) void contact_friction_action_kernel(FrictionActionArgs p) {
+__global__ __launch_bounds__(kFaceWaveThreads) void contact_friction_action_kernel(FrictionActionArgs p) {
   const int lane = threadIdx.x & 63;
   const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;
+  if (f >= p.v.n_faces) return;
   if (!p.active[f]) return;   // (wave-uniform; the node sum skips the face, and a face without pressure has no friction point)
-  const int n_dof = p.n_dof, n_q = p.n_q, NT = n_dof * DIM;
+  const int n_dof = p.v.n_dof, n_q = p.v.n_q, NT = n_dof * DIM;
   double dpc = 0.0, xc[DIM];
 #pragma unroll
   for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
   if (lane < n_dof) {
-    if constexpr (CONSISTENT) dpc = p.dp[p.local[(int64_t)f * n_dof + lane]];
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
+    if constexpr (CONSISTENT) dpc = p.dp[p.v.local[(int64_t)f * n_dof + lane]];
+    const int64_t node = p.v.dofs[(int64_t)f * n_dof + lane];
 #pragma unroll
     for (int i = 0; i < DIM; ++i) xc[i] = p.x[node * DIM + i];
   }
@@ -99,8 +98,8 @@ __global__ __launch_bounds__(256) void contact_friction_action_kernel(FrictionAc
     {
       const bool on = q0 + lane < n_q;
       const int64_t pt = (int64_t)f * n_q + (on ? q0 + lane : 0);
-      const double* N = p.N + pt * n_dof;
-      const double* dN = p.dN + pt * n_dof * (DIM - 1);
+      const double* N = p.v.N + pt * n_dof;
+      const double* dN = p.v.dN + pt * n_dof * (DIM - 1);
       double dpq = 0.0, dx[DIM], dt[(DIM - 1) * DIM], t[(DIM - 1) * DIM];
 #pragma unroll
       for (int i = 0; i < DIM; ++i) dx[i] = 0.0;
@@ -120,8 +119,8 @@ __global__ __launch_bounds__(256) void contact_friction_action_kernel(FrictionAc
         }
       }
       double m[DIM], dm[DIM];
-      consistent_normal_rate<DIM>(t, dt, m, dm);
-      const double cq = on ? p.coef[pt] : 0.0, w = on ? p.weight[pt] : 0.0;
+      face_normal_rate<DIM>(t, dt, m, dm);
+      const double cq = on ? p.coef[pt] : 0.0, w = on ? p.v.weight[pt] : 0.0;
       if constexpr (CONSISTENT) {
         const double wdp = w * dpq;
 #pragma unroll
@@ -180,7 +179,7 @@ __global__ __launch_bounds__(256) void contact_friction_action_kernel(FrictionAc
         const double v = face_lane_read(g[ii], q);
         gi = ki == ii ? v : gi;
       }
-      Y = __builtin_fma(gi, p.N[((int64_t)f * n_q + q0 + q) * n_dof + ka], Y);
+      Y = __builtin_fma(gi, p.v.N[((int64_t)f * n_q + q0 + q) * n_dof + ka], Y);
     }
   }
   if (lane < NT) p.face_y[(int64_t)f * NT + lane] = p.factor * Y;   // [i][a]
@@ -212,9 +211,9 @@ struct FrictionContactAction : ContactAction {
       fcoef.resize(npts);
       fbr.resize(npts);
       const FrictionRecordArgs rec{fa.ptr, fcoef.ptr, fbr.ptr};
-      const dim3 grid((unsigned)((h.n_faces + 3) / 4));
-      if (h.dim == 2) launch(contact_friction_record_kernel<2>, grid, dim3(256), 0, h.stream, *fr, rec);
-      else launch(contact_friction_record_kernel<3>, grid, dim3(256), 0, h.stream, *fr, rec);
+      face_dispatch_dim(h.dim, [&](auto D) {
+        launch(contact_friction_record_kernel<decltype(D)::value>, face_wave_grid(h.n_faces), dim3(kFaceWaveThreads), 0, h.stream, *fr, rec);
+      });
       mu = fr->mu;
     }
     friction = fr != nullptr;
@@ -227,19 +226,13 @@ struct FrictionContactAction : ContactAction {
       return;
     }
     if (consistent) nodal_rates(h, x, s);
-    const FrictionActionArgs a{h.n_faces, h.n_dof, h.n_q,    h.dofs.ptr, h.local.ptr, h.N.ptr, h.dN.ptr, h.weight.ptr, coef.ptr, tang.ptr,
-                               active.ptr, fa.ptr, fcoef.ptr, fbr.ptr,   mu,          dp.ptr,  factor,   x,            face_y.ptr};
-    const dim3 grid((unsigned)((h.n_faces + 3) / 4));
-    if (h.dim == 2) {
-      if (consistent) launch(contact_friction_action_kernel<2, true>, grid, dim3(256), 0, s, a);
-      else launch(contact_friction_action_kernel<2, false>, grid, dim3(256), 0, s, a);
-      h.template gather_vector<2>(active.ptr, face_y.ptr, y, s);
-    } else {
-      if (consistent) launch(contact_friction_action_kernel<3, true>, grid, dim3(256), 0, s, a);
-      else launch(contact_friction_action_kernel<3, false>, grid, dim3(256), 0, s, a);
-      h.template gather_vector<3>(active.ptr, face_y.ptr, y, s);
-    }
-    MH_HIP(hipGetLastError());
+    const FrictionActionArgs a{h.view(), coef.ptr, tang.ptr, active.ptr, fa.ptr, fcoef.ptr, fbr.ptr, mu, dp.ptr, factor, x, face_y.ptr};
+    face_dispatch_dim(h.dim, [&](auto D) {
+      constexpr int DIM = decltype(D)::value;
+      launch(consistent ? contact_friction_action_kernel<DIM, true> : contact_friction_action_kernel<DIM, false>,
+             face_wave_grid(h.n_faces), dim3(kFaceWaveThreads), 0, s, a);
+    });
+    h.gather_vector(active.ptr, face_y.ptr, y, s);
   }
 };
 

@@ -13,7 +13,9 @@
 // The pipeline is contact pass 2 (contact.hip) with a prescribed pressure: one wave per face stores the face residual
 // vector and tangent block densely (pressure_face_kernel), then the row gather both share (face_common.hpp: one wave per
 // CSR row of a face node walks the node's (face, local node) incidences in a fixed order into an LDS image of the row).
-// No atomics on the assembly path: the same bits every run.
+// No atomics on the assembly path: the same bits every run.  pressure_face_kernel has the stages of face_wave.hpp (wave index,
+// node load, point stage, point scatter, node-pair loop) in its own text, see there; the face tables reach it as a FaceView and
+// the matrix-free action shares the layer.
 // The matrix-free action of the tangent (mimi_hip_follower_linearize / _apply_tangent, and the Krylov solvers' boundary
 // terms through apply_seam.hpp) is kernels_face_action.hpp, shared with contact.hip: c_q = w p_q, no face tangent block.
 #include <hip/hip_runtime.h>
@@ -31,13 +33,7 @@
 namespace mimi_hip {
 
 struct PressureArgs {
-  int dim, n_faces, n_dof, n_q;
-  const int32_t* dofs;       // [n_faces][n_dof] global node ids
-  const int32_t* local;      // [n_faces][n_dof] index into the face nodes (nodal pressure)
-  const double* N;           // [n_faces][n_q][n_dof]
-  const double* dN;          // [n_faces][n_q][dim-1][n_dof]
-  const double* weight;      // [n_faces][n_q]
-  const double* x_ref;       // [n_nodes][dim]
+  FaceView v;
   const double* nodal;       // [n_face_nodes] or nullptr: uniform
   double value;              // uniform pressure
   const double* u;
@@ -50,20 +46,24 @@ struct PressureArgs {
 // One WAVE per face.  Lane c < n_dof holds node c (position, nodal pressure); lane q < n_q forms the point's pressure,
 // tangents and normal from them by lane reads; lane k = i n_dof + a sums the residual entry over the points; lane 0 sums the
 // face's area and force; with WITH_K, lane = node pair (a, b) accumulates its DIM x DIM tangent block over the points.
+// (The kernel keeps its own stage text: written on face_wave.hpp's helpers it computed the same bytes with the same arithmetic
+// instructions, but 4 to 23 instructions more of index arithmetic and branches, and no helper variant gave the old stream back.  Its
+// tangent block is the expanded [a]x form with wpn folded into d1 and d2: another association, another rounding, than
+// face_normal_column's.)
 template<int DIM, int WITH_K>
-__global__ __launch_bounds__(256) void pressure_face_kernel(PressureArgs p) {
+__global__ __launch_bounds__(kFaceWaveThreads) void pressure_face_kernel(PressureArgs p) {
   const int lane = threadIdx.x & 63;
   const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;
-  const int n_dof = p.n_dof, n_q = p.n_q, NT = n_dof * DIM;
+  if (f >= p.v.n_faces) return;
+  const int n_dof = p.v.n_dof, n_q = p.v.n_q, NT = n_dof * DIM;
   double pc = 0.0, xc[DIM];
 #pragma unroll
   for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
   if (lane < n_dof) {
-    pc = p.nodal ? p.nodal[p.local[(int64_t)f * n_dof + lane]] : p.value;
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
+    pc = p.nodal ? p.nodal[p.v.local[(int64_t)f * n_dof + lane]] : p.value;
+    const int64_t node = p.v.dofs[(int64_t)f * n_dof + lane];
 #pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = p.u[node * DIM + i] + p.x_ref[node * DIM + i];
+    for (int i = 0; i < DIM; ++i) xc[i] = p.u[node * DIM + i] + p.v.x_ref[node * DIM + i];
   }
   const bool active = __ballot(pc != 0.0) != 0;
   // stage 1, lane q: wq = w p(q), the tangents and the normal m
@@ -73,8 +73,8 @@ __global__ __launch_bounds__(256) void pressure_face_kernel(PressureArgs p) {
   {
     const int q = lane < n_q ? lane : 0;
     const int64_t pt = (int64_t)f * n_q + q;
-    const double* N = p.N + pt * n_dof;
-    const double* dN = p.dN + pt * n_dof * (DIM - 1);
+    const double* N = p.v.N + pt * n_dof;
+    const double* dN = p.v.dN + pt * n_dof * (DIM - 1);
     double pq = 0.0;
     for (int c = 0; c < n_dof; ++c) {
       pq = __builtin_fma(N[c], face_lane_read(pc, c), pq);
@@ -90,8 +90,8 @@ __global__ __launch_bounds__(256) void pressure_face_kernel(PressureArgs p) {
     double mm = 0.0;
 #pragma unroll
     for (int i = 0; i < DIM; ++i) mm += mq[i] * mq[i];
-    wq = p.weight[pt] * pq;
-    dA = p.weight[pt] * sqrt(mm);
+    wq = p.v.weight[pt] * pq;
+    dA = p.v.weight[pt] * sqrt(mm);
   }
   // area and external force of the face, lane 0, in the order of the points
   {
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void pressure_face_kernel(PressureArgs p) {
         const double v = face_lane_read(mq[ii], q) * wpq;
         aw = i == ii ? v : aw;
       }
-      R = __builtin_fma(aw, p.N[((int64_t)f * n_q + q) * n_dof + a], R);
+      R = __builtin_fma(aw, p.v.N[((int64_t)f * n_q + q) * n_dof + a], R);
     }
     if (lane < NT) p.face_r[(int64_t)f * NT + lane] = R;      // [i][a]
   }
@@ -140,8 +140,8 @@ __global__ __launch_bounds__(256) void pressure_face_kernel(PressureArgs p) {
       for (int k = 0; k < DIM * DIM; ++k) acc[k] = 0.0;
       for (int q = 0; q < n_q; ++q) {
         const int64_t pt = (int64_t)f * n_q + q;
-        const double wpn = face_lane_read(wq, q) * p.N[pt * n_dof + a];
-        const double* dN = p.dN + pt * n_dof * (DIM - 1);
+        const double wpn = face_lane_read(wq, q) * p.v.N[pt * n_dof + a];
+        const double* dN = p.v.dN + pt * n_dof * (DIM - 1);
         if constexpr (DIM == 2) {
           // dm_0 / dx_b1 = N_b,xi, dm_1 / dx_b0 = -N_b,xi
           const double d = wpn * dN[b];
@@ -198,46 +198,21 @@ void operator_add_action(mimi_hip_pressure_s* h, double factor, const double* x,
 }
 }  // namespace mimi_hip
 
-static PressureArgs pressure_args(mimi_hip_pressure_s* h, const double* u) {
-  PressureArgs a{};
-  a.dim = h->dim;
-  a.n_faces = h->n_faces;
-  a.n_dof = h->n_dof;
-  a.n_q = h->n_q;
-  a.dofs = h->dofs.ptr;
-  a.local = h->local.ptr;
-  a.N = h->N.ptr;
-  a.dN = h->dN.ptr;
-  a.weight = h->weight.ptr;
-  a.x_ref = h->x_ref.ptr;
-  a.nodal = h->use_nodal ? h->nodal.ptr : nullptr;
-  a.value = h->value;
-  a.u = u;
-  a.face_r = h->face_r.ptr;
-  a.face_k = h->face_k.ptr;
-  a.face_scal = h->face_scal.ptr;
-  a.face_active = h->face_active.ptr;
-  return a;
-}
-
-template<int DIM>
-static void launch_pressure(mimi_hip_pressure_s* h, const PressureArgs& a, double* r, double* A, double gf, bool with_grad) {
-  const unsigned bf = (unsigned)((h->n_faces + 3) / 4);
-  if (with_grad) hipLaunchKernelGGL((pressure_face_kernel<DIM, 1>), dim3(bf), dim3(256), 0, h->stream, a);
-  else hipLaunchKernelGGL((pressure_face_kernel<DIM, 0>), dim3(bf), dim3(256), 0, h->stream, a);
-  // area and force of the faces (last_area_ / last_force_), in a fixed order
-  hipLaunchKernelGGL(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, 1 + DIM, 1 + DIM,
-                     h->face_scal.ptr, (const unsigned char*)nullptr, h->scalars.ptr);
-  h->gather<DIM>(r, A, gf, with_grad);
-}
-
 static void run_pressure(mimi_hip_pressure_s* h, const double* u, double* r, double* A, double gf, bool with_grad) {
   if (!r) fail("null vector argument");
   h->run(u, r, A, with_grad, [&](const double* u_dev, double* r_dev, double* A_dev) {
     if (with_grad) h->reserve_face_k();
-    const PressureArgs a = pressure_args(h, u_dev);
-    if (h->dim == 2) launch_pressure<2>(h, a, r_dev, A_dev, gf, with_grad);
-    else launch_pressure<3>(h, a, r_dev, A_dev, gf, with_grad);
+    const PressureArgs a{h->view(), h->use_nodal ? h->nodal.ptr : nullptr, h->value, u_dev, h->face_r.ptr, h->face_k.ptr,
+                         h->face_scal.ptr, h->face_active.ptr};
+    face_dispatch_dim(h->dim, [&](auto D) {
+      constexpr int DIM = decltype(D)::value;
+      launch(with_grad ? pressure_face_kernel<DIM, 1> : pressure_face_kernel<DIM, 0>, face_wave_grid(h->n_faces), dim3(kFaceWaveThreads),
+             0, h->stream, a);
+    });
+    // area and force of the faces (last_area_ / last_force_), in a fixed order
+    launch(face_sum_kernel, dim3(1), dim3(1024), 0, h->stream, (int64_t)h->n_faces, 1 + h->dim, 1 + h->dim, h->face_scal.ptr,
+           (const unsigned char*)nullptr, h->scalars.ptr);
+    h->gather(r_dev, A_dev, gf, with_grad);
   });
 }
 

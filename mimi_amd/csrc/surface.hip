@@ -9,7 +9,8 @@
 // Points are face-major, point-minor.  Face pass: one WAVE per face, laid out as pressure_face_kernel -- lane c < n_dof holds
 // node c, lane q < n_q forms its point from lane reads; the points mode writes the face's [n_q][dim] outputs as consecutive
 // addresses of consecutive lanes, the load mode reads t the same way and sums lane k = (a, i) over the points in a fixed
-// order into a dense face vector [n_faces][n_dof][dim].  Node gather: one lane per (face node, component) walks the node's
+// order into a dense face vector [n_faces][n_dof][dim] (the stages of face_wave.hpp, here in the kernel's own text).
+// Node gather: one lane per (face node, component) walks the node's
 // (face, local node) incidences in ascending face order.  No atomics: the same bits every run.
 #include <hip/hip_runtime.h>
 
@@ -23,12 +24,7 @@
 namespace mimi_hip {
 
 struct SurfaceArgs {
-  int n_faces, n_dof, n_q;
-  const int32_t* dofs;     // [n_faces][n_dof] global node ids
-  const double* N;         // [n_faces][n_q][n_dof]
-  const double* dN;        // [n_faces][n_q][dim-1][n_dof]
-  const double* weight;    // [n_faces][n_q]
-  const double* x_ref;     // [n_nodes][dim]
+  FaceView v;
   const double* u;         // [n_nodes][dim], nullptr: the reference configuration
   const double* t;         // [n_points][dim] (load mode)
   double* x_out;           // [n_points][dim] or nullptr (points mode)
@@ -60,19 +56,21 @@ MH_DEV void surface_write_points(double* out, int64_t base, int count, const dou
   }
 }
 
+// (The kernel keeps its own stage text, for the reason pressure_face_kernel does: on face_wave.hpp's helpers the same arithmetic
+// came with 4 to 14 instructions more, and u may be null inside the node load.)
 template<int DIM, int LOAD>
-__global__ __launch_bounds__(256) void surface_face_kernel(SurfaceArgs p) {
+__global__ __launch_bounds__(kFaceWaveThreads) void surface_face_kernel(SurfaceArgs p) {
   const int lane = threadIdx.x & 63;
   const int f = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (f >= p.n_faces) return;   // the whole wave
-  const int n_dof = p.n_dof, n_q = p.n_q;
+  if (f >= p.v.n_faces) return;   // the whole wave
+  const int n_dof = p.v.n_dof, n_q = p.v.n_q;
   double xc[DIM];
 #pragma unroll
   for (int i = 0; i < DIM; ++i) xc[i] = 0.0;
   if (lane < n_dof) {
-    const int64_t node = p.dofs[(int64_t)f * n_dof + lane];
+    const int64_t node = p.v.dofs[(int64_t)f * n_dof + lane];
 #pragma unroll
-    for (int i = 0; i < DIM; ++i) xc[i] = p.u ? p.u[node * DIM + i] + p.x_ref[node * DIM + i] : p.x_ref[node * DIM + i];
+    for (int i = 0; i < DIM; ++i) xc[i] = p.u ? p.u[node * DIM + i] + p.v.x_ref[node * DIM + i] : p.v.x_ref[node * DIM + i];
   }
   // lane q: the position, the tangents (in pressure_face_kernel's order), the normal m and the area weight w |m|
   const int q = lane < n_q ? lane : 0;
@@ -83,8 +81,8 @@ __global__ __launch_bounds__(256) void surface_face_kernel(SurfaceArgs p) {
 #pragma unroll
   for (int k = 0; k < (DIM - 1) * DIM; ++k) tq[k] = 0.0;
   {
-    const double* N = p.N + pt * n_dof;
-    const double* dN = p.dN + pt * n_dof * (DIM - 1);
+    const double* N = p.v.N + pt * n_dof;
+    const double* dN = p.v.dN + pt * n_dof * (DIM - 1);
     for (int c = 0; c < n_dof; ++c) {
       const double Nc = N[c];
 #pragma unroll
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(256) void surface_face_kernel(SurfaceArgs p) {
   double mm = 0.0;
 #pragma unroll
   for (int i = 0; i < DIM; ++i) mm += mq[i] * mq[i];
-  const double len = sqrt(mm), dA = p.weight[pt] * len;
+  const double len = sqrt(mm), dA = p.v.weight[pt] * len;
   const int count = n_q * DIM;
   const int64_t base = (int64_t)f * count;
   if constexpr (!LOAD) {
@@ -134,7 +132,7 @@ __global__ __launch_bounds__(256) void surface_face_kernel(SurfaceArgs p) {
         const double w = face_lane_read(wt[ii], qq);
         v = i == ii ? w : v;
       }
-      F = __builtin_fma(v, p.N[((int64_t)f * n_q + qq) * n_dof + a], F);
+      F = __builtin_fma(v, p.v.N[((int64_t)f * n_q + qq) * n_dof + a], F);
     }
     if (lane < NT) p.face_f[(int64_t)f * NT + lane] = F;
   }
@@ -166,23 +164,12 @@ struct mimi_hip_surface_s : FaceSet {
   DeviceBuffer<double> stage_t, stage_f, stage_x, stage_n, stage_w;
 };
 
-static SurfaceArgs surface_args(const mimi_hip_surface_s* h, const double* u) {
-  SurfaceArgs a{};
-  a.n_faces = h->n_faces;
-  a.n_dof = h->n_dof;
-  a.n_q = h->n_q;
-  a.dofs = h->dofs.ptr;
-  a.N = h->N.ptr;
-  a.dN = h->dN.ptr;
-  a.weight = h->weight.ptr;
-  a.x_ref = h->x_ref.ptr;
-  a.u = u;
-  return a;
-}
-
-template<int DIM, int LOAD>
-static void launch_surface_face(const mimi_hip_surface_s* h, const SurfaceArgs& a) {
-  hipLaunchKernelGGL((surface_face_kernel<DIM, LOAD>), dim3((unsigned)((h->n_faces + 3) / 4)), dim3(256), 0, h->stream, a);
+static void launch_surface_face(const mimi_hip_surface_s* h, const SurfaceArgs& a, bool load) {
+  face_dispatch_dim(h->dim, [&](auto D) {
+    constexpr int DIM = decltype(D)::value;
+    launch(load ? surface_face_kernel<DIM, 1> : surface_face_kernel<DIM, 0>, face_wave_grid(h->n_faces), dim3(kFaceWaveThreads), 0,
+           h->stream, a);
+  });
 }
 
 extern "C" {
@@ -215,13 +202,7 @@ int mimi_hip_surface_points(mimi_hip_surface_t h, const double* u, double* x, do
     if (x) mx = Mirror<double>::inout(x, nv, h->stage_x, h->stream);
     if (normal) mn = Mirror<double>::inout(normal, nv, h->stage_n, h->stream);
     if (weight) mw = Mirror<double>::inout(weight, h->n_points, h->stage_w, h->stream);
-    SurfaceArgs a = surface_args(h, mu.dev);
-    a.x_out = mx.dev;
-    a.n_out = mn.dev;
-    a.w_out = mw.dev;
-    if (h->dim == 2) launch_surface_face<2, 0>(h, a);
-    else launch_surface_face<3, 0>(h, a);
-    MH_HIP(hipGetLastError());
+    launch_surface_face(h, SurfaceArgs{h->view(), mu.dev, nullptr, mx.dev, mn.dev, mw.dev, nullptr}, false);
     mx.finish(h->stream);
     mn.finish(h->stream);
     mw.finish(h->stream);
@@ -238,15 +219,10 @@ int mimi_hip_surface_add_load(mimi_hip_surface_t h, const double* u, const doubl
     if (u) mu = Mirror<double>::in(u, h->n_vdofs, h->stage_u, h->stream);
     Mirror<double> mt = Mirror<double>::in(t, (size_t)h->n_points * h->dim, h->stage_t, h->stream);
     Mirror<double> mf = Mirror<double>::inout(f, h->n_vdofs, h->stage_f, h->stream);
-    SurfaceArgs a = surface_args(h, mu.dev);
-    a.t = mt.dev;
-    a.face_f = h->face_f.ptr;
-    if (h->dim == 2) launch_surface_face<2, 1>(h, a);
-    else launch_surface_face<3, 1>(h, a);
+    launch_surface_face(h, SurfaceArgs{h->view(), mu.dev, mt.dev, nullptr, nullptr, nullptr, h->face_f.ptr}, true);
     const int64_t rows = (int64_t)h->n_fnodes * h->dim;
-    hipLaunchKernelGGL(surface_gather_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, h->dim, h->n_dof,
-                       rows, h->fnodes_dev.ptr, h->adj_ptr.ptr, h->adj.ptr, h->face_f.ptr, mf.dev);
-    MH_HIP(hipGetLastError());
+    launch(surface_gather_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, h->dim, h->n_dof, rows,
+           h->fnodes_dev.ptr, h->adj_ptr.ptr, h->adj.ptr, h->face_f.ptr, mf.dev);
     mf.finish(h->stream);
     if (mu.host || mt.host || mf.host) MH_HIP(hipStreamSynchronize(h->stream));
   });

@@ -5,6 +5,7 @@ The punch is handed over as any object with `degrees`, `knot_vectors`, `control_
 a SimpleNamespace is enough.
 
     python examples/nl_contact.py [--steps 30] [--friction MU] [--matrix-free] [--consistent-tangent]
+                                  [--augmented N [--gap-tolerance T]]
 
 --friction MU puts Coulomb friction on the punch (the reference has none): the tangential penalty is the scene's
 coefficient, and the punch's displacement of the step is handed over as step_displacement, so that only the relative slip
@@ -17,6 +18,11 @@ freezes: rc.set_int("contact_consistent_tangent", 1).  With --friction it needs 
 --matrix-free solves the Newton steps matrix-free with the frozen-pressure contact action; with --friction the friction
 tangent joins that action, rc.set_int("friction_matrix_free", 1), and --consistent-tangent may stand beside it: in slip
 the traction is mu p_N s / |s|, so the consistent action then carries the pressure's derivative of the friction residual too.
+
+--augmented N switches the contact to the augmented-Lagrangian law, rc.set_int("contact_augmented_lagrange", 1): a multiplier
+per marked node, and up to N multiplier updates per step (each followed by a Newton solve) until the largest violation of the
+constraint, a length, is at most --gap-tolerance (default 0: always N).  The loop contracts like k / (k + eps), k the stiffness
+under the contact: worth its solves at a penalty of the order of the body's stiffness, as here; use --consistent-tangent with it.
 """
 import argparse
 import os
@@ -60,6 +66,10 @@ def main():
                     help="matrix-free Newton solves with the consistent contact tangent (with --friction: needs --matrix-free)")
     ap.add_argument("--matrix-free", action="store_true",
                     help="matrix-free Newton solves; with --friction the friction tangent as a part of the contact action")
+    ap.add_argument("--augmented", type=int, default=0, metavar="N",
+                    help="augmented-Lagrangian contact with up to N multiplier updates per step (default 0: the penalty law)")
+    ap.add_argument("--gap-tolerance", type=float, default=0.0, metavar="T",
+                    help="stop updating once the largest violation of the constraint is at most T (with --augmented)")
     args = ap.parse_args()
     if args.consistent_tangent and args.friction > 0.0 and not args.matrix_free:
         ap.error("--consistent-tangent cannot be combined with --friction: the friction tangent is assembled only "
@@ -75,10 +85,15 @@ def main():
     conditions.initial.dirichlet(0, 0).dirichlet(0, 1)       # bottom edge clamped
     conditions.current.contact(1, rigid_scene)               # top edge may touch the punch
     block.boundary_condition = conditions
-    if args.consistent_tangent or args.matrix_free:
+    if args.consistent_tangent or args.matrix_free or args.augmented > 0:
         flags = mimi.RuntimeCommunication()
+        if args.augmented > 0:
+            flags.set_int("contact_augmented_lagrange", 1)
+            flags.set_int("contact_augmentations", args.augmented)
+            flags.set_real("contact_gap_tolerance", args.gap_tolerance)
         for key in ("use_iterative_solver", "use_kronecker_preconditioner", "matrix_free", "matrix_free_boundary"):
-            flags.set_int(key, 1)
+            if args.consistent_tangent or args.matrix_free:
+                flags.set_int(key, 1)
         if args.consistent_tangent:
             flags.set_int("contact_consistent_tangent", 1)
         if args.matrix_free and args.friction > 0.0:
@@ -102,6 +117,9 @@ def main():
         rubbing = ""
         if args.friction > 0.0:
             rubbing = f"  friction force {contact.last_friction_force_}  stick {contact.n_stick_} slip {contact.n_slip_}"
+        if args.augmented > 0 and block.augmentation_loops:
+            loop = block.augmentation_loops[-1]
+            rubbing += f"  augmentations {loop['augmentations']}  violation {loop['violations'][0]:.2e} -> {loop['violations'][-1]:.2e}"
         print(f"step {k:3d}  Newton iterations {info['iterations']:2d}  converged {info['converged']}  "
               f"|u|max = {np.abs(disp).max():.3e}  contact force {contact.last_force_}{rubbing}")
 

@@ -492,6 +492,32 @@ int mimi_hip_contact_friction_state(mimi_hip_contact_t h, double* xi, double* xb
  * ones. */
 int mimi_hip_contact_set_friction_action(mimi_hip_contact_t h, int on);
 
+/* Augmented-Lagrangian contact (the reference has none; law, rate and limits: DESIGN.md "Augmented-Lagrangian contact").
+ * Per marked node a multiplier lambda_i <= 0 (the sign of p_i: compressive is negative).  In the mode
+ *   pass 1    the point gap enters the nodal sum unclamped: g_q = true_g, 0 where the angle rule rejects the point;
+ *             Gt_i = sum_q w |J| g_q N_i, gt_i = Gt_i / A_i (what mimi_hip_contact_nodal then reads as the gap)
+ *   pressure  p_i = min(0, lambda_i + eps gt_i)
+ * and everything that reads p_i (pass 2, the assembled frozen tangent, the frozen action, friction) is unchanged.  A
+ * consistent record of the mode holds the unclamped g_q, chi_q = "the angle rule accepted the point" and G_l, and
+ *   dp_l = eps (dGt_l - gt_l dA_l) / A_l on the nodes with p_l < 0, 0 on the others.
+ *   set_augmented    on != 0: the mode; the first switch-on allocates lambda, every switch from off to on zeroes it.  Off
+ *                    (the default): launches and bytes of every entry are those of a handle that never saw this call.
+ *                    Refused in the reference-FD tangent mode, and set_tangent_mode(REFERENCE_FD) is refused in the mode.
+ *   lagrange         get (set == 0) / set the multipliers at the marked nodes, in the order of
+ *                    mimi_hip_contact_marked_nodes; host or device pointer; set values are projected onto lambda <= 0 on
+ *                    the device.  Refused on a handle that never was in the mode.
+ *   update_lagrange  the Uzawa step: pass 1 at u (the handle's nodal area / gap are overwritten, the history scalars of
+ *                    the last Add* call are not), dlambda_i = p_i - lambda_i = min(-lambda_i, eps gt_i), and with
+ *                    apply != 0 lambda_i <- p_i (exactly 0.0 on a released node).  out4 (host): max_i |dlambda_i| / eps (a
+ *                    length: the violation of the constraint), sqrt(sum_i A_i dlambda_i^2), the number of nodes with
+ *                    p_i < 0, max_i |lambda_i| after the call.  Fixed-shape reductions, no atomics: equal inputs give equal
+ *                    bytes.  u host or device.
+ * mimi_hip_contact_action_info(h, 4): whether the current record was made in the mode (a consistent one then holds
+ * n_marked doubles more). */
+int mimi_hip_contact_set_augmented(mimi_hip_contact_t h, int on);
+int mimi_hip_contact_lagrange(mimi_hip_contact_t h, int set, double* lambda);
+int mimi_hip_contact_update_lagrange(mimi_hip_contact_t h, const double* u, int apply, double* out4);
+
 /* ---- follower-pressure boundary integrator (integrators::FollowerPressure) ---------------------------------------
  * The reference stores BCMarker::Pressure(bid, value) (utils/boundary_conditions.cpp:43-50) and never applies it; here it
  * is the follower load t = -p n da on the CURRENT surface x = X + u of a set of faces of one patch:

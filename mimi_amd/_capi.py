@@ -112,6 +112,7 @@ EXPORTS = [
     "mimi_hip_contact_reset_friction", "mimi_hip_contact_friction_history", "mimi_hip_contact_friction_state",
     "mimi_hip_contact_set_consistent_tangent", "mimi_hip_contact_set_friction_action",
     "mimi_hip_domain_tangent_diagonal", "mimi_hip_linear_set_node_block", "mimi_hip_linear_set_operator_diagonal",
+    "mimi_hip_contact_set_augmented", "mimi_hip_contact_lagrange", "mimi_hip_contact_update_lagrange",
 ]
 
 
@@ -280,7 +281,10 @@ def lib():
         getattr(L, f"mimi_hip_{kind}_action_info").restype = C.c_int64
     L.mimi_hip_contact_set_consistent_tangent.argtypes = [C.c_void_p, C.c_int]
     L.mimi_hip_contact_set_friction_action.argtypes = [C.c_void_p, C.c_int]
-    L.mimi_hip_linear_add_boundary_operator.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_double]
+    L.mimi_hip_contact_set_augmented.argtypes = [C.c_void_p, C.c_int]
+    L.mimi_hip_contact_lagrange.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.mimi_hip_contact_update_lagrange.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.mimi_hip_linear_add_boundary_operator.argtypes =[C.c_void_p, C.c_int, C.c_void_p, C.c_double]
     L.mimi_hip_linear_set_operator_fold.argtypes = [C.c_void_p, C.c_void_p]
     L.mimi_hip_linear_operator_mult.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.mimi_hip_domain_tangent_diagonal.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_void_p]

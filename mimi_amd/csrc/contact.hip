@@ -24,7 +24,9 @@
 // no face tangent block.  The consistent tangent -- the frozen one plus the derivative of the nodal pressure, which leaves the
 // CSR pattern -- exists as such an action only (mimi_hip_contact_set_consistent_tangent, kernels_face_consistent.hpp).
 // Friction joins either action when the handle is set to it (mimi_hip_contact_set_friction_action,
-// kernels_face_friction_action.hpp).
+// kernels_face_friction_action.hpp).  In the mode "augmented" (mimi_hip_contact_set_augmented, kernels_face_augmented.hpp) the
+// nodal pressure is p_i = min(0, lambda_i + eps G_i / A_i) with a multiplier per marked node and the unclamped point gap in
+// G_i; a handle that never switches the mode on runs the kernels of the penalty law on its bytes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,6 +37,7 @@
 #include "common.hpp"
 #include "face_common.hpp"
 #include "kernels_face_action.hpp"
+#include "kernels_face_augmented.hpp"
 #include "kernels_face_consistent.hpp"
 #include "kernels_face_friction.hpp"
 #include "kernels_face_friction_action.hpp"
@@ -168,8 +171,9 @@ MH_DEV void gather_x(const ContactArgs& p, int f, double* x_e) {
   }
 }
 
-// pass 1: one thread per (face, quadrature point)
-template<int DIM>
+// pass 1: one thread per (face, quadrature point).  AUG (the augmented mode): the gap enters the nodal sum unclamped, the
+// clamp sits at the node (contact_pressure_kernel<true>); the gap norm and pt_scal are the same in both
+template<int DIM, bool AUG>
 __global__ void contact_gap_area_kernel(ContactArgs p, int gap_norm_only) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)p.v.n_faces * p.v.n_q) return;
@@ -201,7 +205,7 @@ __global__ void contact_gap_area_kernel(ContactArgs p, int gap_norm_only) {
     p.pt_scal[pt] = true_g < 0.0 ? true_g * true_g : 0.0;
     return;
   }
-  double g = true_g < 0. ? true_g : 0.;
+  double g = (AUG || true_g < 0.) ? true_g : 0.;
   // |J| (DenseMatrix::Weight) from the non-normalised normal (integrator_utils.hpp:216-251); this kernel keeps its own text
   double detJ;
   if constexpr (DIM == 2) {
@@ -250,9 +254,19 @@ __global__ __launch_bounds__(256) void contact_nodal_kernel(int n_marked, int n_
   }
 }
 
-__global__ void contact_pressure_kernel(int n, const double* area, const double* gap, double penalty, double* pressure) {
+// (AUG: p_i = min(0, lambda_i + eps G_i / A_i), +0.0 on a released node)
+template<bool AUG>
+__global__ void contact_pressure_kernel(int n, const double* area, const double* gap, double penalty, const double* lambda,
+                                        double* pressure) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) pressure[i] = gap[i] / area[i] * penalty;  // mortar_contact.cpp:253-257
+  if constexpr (AUG) {
+    if (i < n) {
+      const double v = lambda[i] + gap[i] / area[i] * penalty;
+      pressure[i] = v < 0.0 ? v : 0.0;
+    }
+  } else {
+    if (i < n) pressure[i] = gap[i] / area[i] * penalty;  // mortar_contact.cpp:253-257
+  }
 }
 
 // element residual at given x_e (used by the FD mode too)
@@ -469,6 +483,8 @@ struct mimi_hip_contact_s : FaceAssembly {
   DeviceBuffer<double> fr_xi, fr_xbar, fr_xi_t, fr_xbar_t, fr_face, fr_scalars;
   DeviceBuffer<unsigned char> fr_c, fr_c_t;
   bool fr_trial = false;   // an evaluation has written the trial state since create / reset
+  // the multipliers of the augmented mode (kernels_face_augmented.hpp); never switched on: none of it is allocated
+  AugmentedState aug;
 };
 
 // the friction state of a handle: allocated and zeroed by the first set_friction with mu > 0
@@ -602,7 +618,9 @@ static void contact_pass1_kernels(mimi_hip_contact_s* h, const ContactArgs& a, i
   const int64_t npts = (int64_t)h->n_faces * h->n_q;
   const dim3 grid((unsigned)((npts + kContactThreads - 1) / kContactThreads));
   face_dispatch_dim(h->dim, [&](auto D) {
-    launch(contact_gap_area_kernel<decltype(D)::value>, grid, dim3(kContactThreads), 0, h->stream, a, gap_norm_only);
+    constexpr int DIM = decltype(D)::value;
+    launch(h->aug.on ? contact_gap_area_kernel<DIM, true> : contact_gap_area_kernel<DIM, false>, grid, dim3(kContactThreads), 0,
+           h->stream, a, gap_norm_only);
   });
   if (!gap_norm_only)
     launch(contact_nodal_kernel, dim3((unsigned)((h->n_fnodes + 3) / 4)), dim3(256), 0, h->stream, h->n_fnodes, h->n_q, h->n_dof,
@@ -616,8 +634,9 @@ static void contact_sum_points(mimi_hip_contact_s* h, int slot) {
 }
 
 static void contact_pressure(mimi_hip_contact_s* h) {   // mortar_contact.cpp:253-257
-  launch(contact_pressure_kernel, dim3((unsigned)((h->n_fnodes + kContactThreads - 1) / kContactThreads)), dim3(kContactThreads), 0,
-         h->stream, h->n_fnodes, h->area.ptr, h->gap.ptr, h->penalty, h->pressure.ptr);
+  launch(h->aug.on ? contact_pressure_kernel<true> : contact_pressure_kernel<false>,
+         dim3((unsigned)((h->n_fnodes + kContactThreads - 1) / kContactThreads)), dim3(kContactThreads), 0, h->stream, h->n_fnodes,
+         h->area.ptr, h->gap.ptr, h->penalty, (const double*)h->aug.lambda.ptr, h->pressure.ptr);
 }
 
 // pass 1 (mortar_contact.cpp:148-193): nodal area / gap of this handle's faces; pressure not formed yet
@@ -640,7 +659,7 @@ static void contact_linearize(mimi_hip_contact_s* h, const double* u_dev) {
   const bool rough = h->friction_action && h->mu > 0.0;
   const FrictionArgs fa = rough ? friction_args(h, a) : FrictionArgs{};
   h->action.linearize(*h, u_dev, h->area.ptr, h->pressure.ptr, h->penalty, h->consistent_tangent, ContactBodyQuery{a},
-                      rough ? &fa : nullptr);
+                      rough ? &fa : nullptr, h->aug.on ? h->gap.ptr : nullptr);
 }
 
 // pressure from the nodal area / gap (mortar_contact.cpp:195-261), then pass 2: face residual vectors (+ tangent blocks)
@@ -722,6 +741,8 @@ int mimi_hip_contact_set_tangent_mode(mimi_hip_contact_t h, int mode) {
     if (!h) fail("null handle");
     if (mode != MIMI_HIP_TANGENT_ANALYTIC && mode != MIMI_HIP_TANGENT_REFERENCE_FD) fail("bad tangent mode %d", mode);
     if (mode == MIMI_HIP_TANGENT_REFERENCE_FD) refuse_friction(h, "the reference-FD tangent mode");
+    if (mode == MIMI_HIP_TANGENT_REFERENCE_FD && h->aug.on)
+      fail("the reference-FD tangent mode is not available on an augmented contact handle: its tangent is the analytic one");
     h->mode = mode;
   });
 }
@@ -762,6 +783,7 @@ int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const do
 int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what) {
   if (h && what == 2) return h->action.linearized && h->action.consistent ? 1 : 0;
   if (h && what == 3) return h->action.linearized && h->action.friction ? 1 : 0;
+  if (h && what == 4) return h->action.linearized && h->action.augmented ? 1 : 0;
   return boundary_action_info(h, what);
 }
 
@@ -951,6 +973,47 @@ int mimi_hip_contact_friction_state(mimi_hip_contact_t h, double* xi, double* xb
           if (xi) xi[(f * n_q + q) * dim + i] = a[(f * dim + i) * n_q + q];
           if (xbar) xbar[(f * n_q + q) * dim + i] = b[(f * dim + i) * n_q + q];
         }
+  });
+}
+
+// ---- augmented-Lagrangian mode (kernels_face_augmented.hpp) ---------------------------------------------------------------
+int mimi_hip_contact_set_augmented(mimi_hip_contact_t h, int on) {
+  return guarded([&] {
+    if (!h) fail("null handle");
+    if (on && h->mode == MIMI_HIP_TANGENT_REFERENCE_FD)
+      fail("the augmented mode is not available in the reference-FD tangent mode: its tangent is the analytic one");
+    MH_HIP(hipSetDevice(h->device));
+    h->aug.set(*h, on != 0);
+  });
+}
+
+int mimi_hip_contact_lagrange(mimi_hip_contact_t h, int set, double* lambda) {
+  return guarded([&] {
+    if (!h || !lambda) fail("null argument");
+    if (!h->aug.lambda.ptr) fail("mimi_hip_contact_lagrange: the handle was never set to the augmented mode (set_augmented first)");
+    MH_HIP(hipSetDevice(h->device));
+    const size_t bytes = (size_t)h->n_fnodes * sizeof(double);
+    if (set) {
+      MH_HIP(hipMemcpyAsync(h->aug.lambda.ptr, lambda, bytes, hipMemcpyDefault, h->stream));
+      h->aug.project(*h);
+    } else {
+      MH_HIP(hipMemcpyAsync(lambda, h->aug.lambda.ptr, bytes, hipMemcpyDefault, h->stream));
+    }
+    if (!is_device_pointer(lambda)) MH_HIP(hipStreamSynchronize(h->stream));
+  });
+}
+
+int mimi_hip_contact_update_lagrange(mimi_hip_contact_t h, const double* u, int apply, double* out4) {
+  return guarded([&] {
+    if (!h || !out4) fail("null argument");
+    if (!h->aug.on) fail("mimi_hip_contact_update_lagrange: the handle is not in the augmented mode (set_augmented first)");
+    h->run(u, nullptr, nullptr, false, [&](const double* u_dev, double*, double*) {
+      // pass 1 as contact_linearize runs it: the history scalars of the last Add* call are left alone
+      contact_pass1_kernels(h, contact_args(h, u_dev), 0);
+      h->aug.update(*h, h->area.ptr, h->gap.ptr, h->penalty, apply != 0);
+    });
+    MH_HIP(hipMemcpyAsync(out4, h->aug.out4.ptr, kAugmentedNodeScalars * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    MH_HIP(hipStreamSynchronize(h->stream));
   });
 }
 

@@ -22,6 +22,11 @@
 // One wave per face, four faces per workgroup, no LDS, no atomics: equal inputs give equal bytes.  The action's kernels run in
 // registers only; the record kernel keeps the private arrays of the spline search in scratch, as pass 1 does.
 // The stages of the face kernels (wave index, node load, point stage, normal rate, point scatter) are face_wave.hpp's.
+// A handle in the mode "augmented" (kernels_face_augmented.hpp) records with the launch flag `augmented`: g_q is the unclamped
+// gap, chi_q = "the angle rule accepted the point", and dp_l = eps (dG_l - gt_l dA_l) / A_l, gt_l = G_l / A_l, on the nodes with
+// p_l < 0 and 0 on the others -- the derivative of p_l = min(0, lambda_l + eps gt_l).  The record keeps G_l for it (the nodal
+// kernel's `gap`, null in penalty mode); lambda_l is not needed.  Both flags are uniform over a launch, and their off-branches
+// are the penalty law's text.
 // Only contact.hip includes this header.
 #pragma once
 
@@ -36,6 +41,7 @@ struct ConsistentRecordArgs {
   const double* pressure;    // [n_marked] of the linearisation
   double* gq;                // [n_faces][n_q]        g_q
   double* chinu;             // [n_faces][n_q][dim]   chi_q nu_q
+  int augmented;             // the unclamped gap, chi_q = accepted by the angle rule
 };
 
 // Body: nearest<DIM>(xq, true_g, distance, nu) -- the closest-point query of pass 1 with the body's unit normal.  (Four
@@ -54,13 +60,16 @@ __global__ __launch_bounds__(kFaceWaveThreads, 4) void contact_consistent_record
   face_point_stage<DIM, false, true, false>(p.v, pt, 0.0, xc, nullptr, xq, nullptr);
   double true_g, distance, nu[DIM];
   body.template nearest<DIM>(xq, true_g, distance, nu);
-  double g = true_g < 0. ? true_g : 0.;
+  const bool aug = p.augmented != 0;
+  double g = (aug || true_g < 0.) ? true_g : 0.;
   const double ratio = fabs(true_g) / distance;
-  if (acos(ratio < 1. ? ratio : 1.) > 1.e-5) g = 0.0;   // angle tolerance, mortar_contact.cpp:172-181
+  const bool rejected = acos(ratio < 1. ? ratio : 1.) > 1.e-5;   // angle tolerance, mortar_contact.cpp:172-181
+  if (rejected) g = 0.0;
   if (lane < p.v.n_q) {
     p.gq[pt] = g;
+    const bool chi = aug ? !rejected : g != 0.0;
 #pragma unroll
-    for (int i = 0; i < DIM; ++i) p.chinu[pt * DIM + i] = g != 0.0 ? nu[i] : 0.0;
+    for (int i = 0; i < DIM; ++i) p.chinu[pt * DIM + i] = chi ? nu[i] : 0.0;
   }
 }
 
@@ -115,13 +124,15 @@ __global__ __launch_bounds__(kFaceWaveThreads) void contact_consistent_rates_ker
 
 // dp_l = (eps dG_l - p_l dA_l) / A_l, one thread per marked node: its incidences in the order of adj, as contact_nodal_kernel
 // and the row gather walk them; the faces the record holds inactive wrote nothing and add nothing
+// (gap != nullptr, a record of the augmented mode: `pressure` decides the node's branch and `gap` is the recorded G_l)
 __global__ __launch_bounds__(256) void contact_consistent_nodal_kernel(int n_marked, int n_dof, const int32_t* __restrict__ adj_ptr,
                                                                        const int32_t* __restrict__ adj,
                                                                        const unsigned char* __restrict__ active,
                                                                        const double* __restrict__ face_dA,
                                                                        const double* __restrict__ face_dG,
                                                                        const double* __restrict__ area,
-                                                                       const double* __restrict__ pressure, double penalty,
+                                                                       const double* __restrict__ pressure,
+                                                                       const double* __restrict__ gap, double penalty,
                                                                        double* __restrict__ dp) {
   const int l = blockIdx.x * blockDim.x + threadIdx.x;
   if (l >= n_marked) return;
@@ -133,7 +144,11 @@ __global__ __launch_bounds__(256) void contact_consistent_nodal_kernel(int n_mar
     sA += face_dA[f * n_dof + (ea & 63)];
     sG += face_dG[f * n_dof + (ea & 63)];
   }
-  dp[l] = (penalty * sG - pressure[l] * sA) / area[l];
+  if (gap) {
+    dp[l] = pressure[l] < 0.0 ? (penalty * sG - gap[l] / area[l] * penalty * sA) / area[l] : 0.0;
+  } else {
+    dp[l] = (penalty * sG - pressure[l] * sA) / area[l];
+  }
 }
 
 struct ConsistentActionArgs {
@@ -176,21 +191,26 @@ __global__ __launch_bounds__(kFaceWaveThreads) void contact_consistent_action_ke
 // linearize only.  With the flag off none of the buffers below exists and begin / add are BoundaryAction's.
 struct ContactAction : BoundaryAction {
   bool consistent = false;
+  bool augmented = false;                          // the handle's mode at the linearisation
   double penalty = 0.0;                            // of the linearisation
   DeviceBuffer<double> gq, chinu, area, pressure;  // the record on top of coef / tang / active
+  DeviceBuffer<double> gap;                        // G_l (a consistent record of the augmented mode)
   DeviceBuffer<double> face_dA, face_dG, dp;       // what the action builds on first use, like face_y
 
   int64_t bytes(const FaceSet& h) const {
     int64_t n = BoundaryAction::bytes(h);
     if (linearized && consistent) n += (int64_t)h.n_faces * h.n_q * (1 + h.dim) * (int64_t)sizeof(double) + 16 * (int64_t)h.n_fnodes;
+    if (linearized && consistent && augmented) n += 8 * (int64_t)h.n_fnodes;
     return n;
   }
 
   // the snapshot at u_dev on the handle's stream: the consistent part first (on), then BoundaryAction::linearize, whose
-  // event then stands behind both.  area_now / pressure_now [n_marked]: the handle's nodal values at u_dev
+  // event then stands behind both.  area_now / pressure_now [n_marked]: the handle's nodal values at u_dev; gap_now: the
+  // nodal sums G_l of the augmented mode, or nullptr (the handle is in penalty mode)
   template<class Body>
   void linearize(FaceSet& h, const double* u_dev, const double* area_now, const double* pressure_now, double penalty_now, bool on,
-                 const Body& body) {
+                 const Body& body, const double* gap_now = nullptr) {
+    augmented = gap_now != nullptr;
     if (on) {
       const size_t npts = (size_t)h.n_faces * h.n_q, nb = (size_t)h.n_fnodes * sizeof(double);
       gq.resize(npts);
@@ -199,7 +219,11 @@ struct ContactAction : BoundaryAction {
       pressure.resize((size_t)h.n_fnodes);
       MH_HIP(hipMemcpyAsync(area.ptr, area_now, nb, hipMemcpyDeviceToDevice, h.stream));
       MH_HIP(hipMemcpyAsync(pressure.ptr, pressure_now, nb, hipMemcpyDeviceToDevice, h.stream));
-      const ConsistentRecordArgs a{h.view(), u_dev, pressure_now, gq.ptr, chinu.ptr};
+      if (augmented) {
+        gap.resize((size_t)h.n_fnodes);
+        MH_HIP(hipMemcpyAsync(gap.ptr, gap_now, nb, hipMemcpyDeviceToDevice, h.stream));
+      }
+      const ConsistentRecordArgs a{h.view(), u_dev, pressure_now, gq.ptr, chinu.ptr, augmented ? 1 : 0};
       face_dispatch_dim(h.dim, [&](auto D) {
         launch(contact_consistent_record_kernel<decltype(D)::value, Body>, face_wave_grid(h.n_faces), dim3(kFaceWaveThreads), 0,
                h.stream, a, body);
@@ -225,7 +249,8 @@ struct ContactAction : BoundaryAction {
       launch(contact_consistent_rates_kernel<decltype(D)::value>, face_wave_grid(h.n_faces), dim3(kFaceWaveThreads), 0, s, r);
     });
     launch(contact_consistent_nodal_kernel, dim3((unsigned)((h.n_fnodes + 255) / 256)), dim3(256), 0, s, h.n_fnodes, h.n_dof,
-           h.adj_ptr.ptr, h.adj.ptr, active.ptr, face_dA.ptr, face_dG.ptr, area.ptr, pressure.ptr, penalty, dp.ptr);
+           h.adj_ptr.ptr, h.adj.ptr, active.ptr, face_dA.ptr, face_dG.ptr, area.ptr, pressure.ptr,
+           (const double*)(augmented ? gap.ptr : nullptr), penalty, dp.ptr);
   }
 
   // y += factor K x over the recorded active faces, K the frozen or the consistent tangent as the record says

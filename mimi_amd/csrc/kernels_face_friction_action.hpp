@@ -204,7 +204,7 @@ struct FrictionContactAction : ContactAction {
   // part goes first: ContactAction::linearize records the event that then stands behind everything
   template<class Body>
   void linearize(FaceSet& h, const double* u_dev, const double* area_now, const double* pressure_now, double penalty_now,
-                 bool consistent_on, const Body& body, const FrictionArgs* fr) {
+                 bool consistent_on, const Body& body, const FrictionArgs* fr, const double* gap_now = nullptr) {
     if (fr) {
       const size_t npts = (size_t)h.n_faces * h.n_q;
       fa.resize(npts * h.dim);
@@ -217,7 +217,7 @@ struct FrictionContactAction : ContactAction {
       mu = fr->mu;
     }
     friction = fr != nullptr;
-    ContactAction::linearize(h, u_dev, area_now, pressure_now, penalty_now, consistent_on, body);
+    ContactAction::linearize(h, u_dev, area_now, pressure_now, penalty_now, consistent_on, body, gap_now);
   }
 
   void add(FaceAssembly& h, double factor, const double* x, double* y, hipStream_t s) {

@@ -587,6 +587,7 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
         self.friction_, self._has_increment = 0.0, False
         self.consistent_tangent_ = False
         self.friction_action_ = False
+        self.augmented_ = False
         self.last_friction_force_ = np.zeros(patch.dim)
         self.last_friction_traction_ = 0.0
         self.n_stick_ = self.n_slip_ = 0
@@ -715,6 +716,52 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
     def HoldsConsistentRecord(self):
         """whether the record of the last Linearize is a consistent one"""
         return bool(self._action_fn("action_info")(self._handle(), 2))
+
+    # -- augmented-Lagrangian mode (include/mimi_hip.h: mimi_hip_contact_set_augmented ...) ---------------------------
+    def SetAugmented(self, on=True):
+        """The augmented-Lagrangian law: a multiplier lambda_i <= 0 per marked node, the point gap unclamped in the nodal
+        sum, p_i = min(0, lambda_i + eps G_i / A_i).  Switching from off to on zeroes the multipliers.  Off (the default):
+        the penalty law on its launches and bytes.  It earns its place at a penalty of the order of the body's stiffness
+        (the Uzawa loop contracts like k / (k + eps): DESIGN.md).  Refused on the handles of a ShardedContact (the nodal
+        sums of a handle run over its own faces) and in the reference-FD tangent mode."""
+        if on and getattr(self, "sharded_", False):
+            raise RuntimeError("the augmented mode on a ShardedContact is not supported: the multipliers of a handle belong "
+                               "to its own faces' nodal sums")
+        check(_capi.lib().mimi_hip_contact_set_augmented(self._handle(), 1 if on else 0))
+        self.augmented_ = bool(on)
+
+    def Lagrange(self):
+        """the multipliers at MarkedNodes(), a host array"""
+        out = np.zeros(self.MarkedNodes().size)
+        check(_capi.lib().mimi_hip_contact_lagrange(self._handle(), 0, ptr(out)))
+        return out
+
+    def SetLagrange(self, values):
+        """multipliers at MarkedNodes() (host array or device tensor); projected onto lambda <= 0 on the device"""
+        if isinstance(values, np.ndarray) or not hasattr(values, "data_ptr"):
+            values = np.ascontiguousarray(values, dtype=np.float64)
+        else:
+            self._follow_torch(values)
+        n = self.MarkedNodes().size
+        if values.ndim != 1 or values.shape[0] != n:
+            raise ValueError(f"expected {n} multipliers (one per marked node), got shape {tuple(values.shape)}")
+        check(_capi.lib().mimi_hip_contact_lagrange(self._handle(), 1, fptr(values)))
+
+    def FillLagrange(self, value=0.0):
+        self.SetLagrange(np.full(self.MarkedNodes().size, float(value)))
+
+    def UpdateLagrange(self, u, apply=True):
+        """The Uzawa step at u: dlambda_i = p_i - lambda_i, and with `apply` lambda_i <- p_i.  Returns a dict:
+        violation = max |dlambda_i| / eps (a length), norm = sqrt(sum A_i dlambda_i^2), n_active = nodes with p_i < 0,
+        max_lagrange = max |lambda_i| after the call.  The history of the last Add* call is left alone."""
+        self._follow_torch(u)
+        out = np.zeros(4)
+        check(_capi.lib().mimi_hip_contact_update_lagrange(self._handle(), fptr(u), 1 if apply else 0, ptr(out)))
+        return {"violation": float(out[0]), "norm": float(out[1]), "n_active": int(out[2]), "max_lagrange": float(out[3])}
+
+    def HoldsAugmentedRecord(self):
+        """whether the record of the last Linearize was made in the augmented mode"""
+        return bool(self._action_fn("action_info")(self._handle(), 4))
 
     def UpdateBody(self, spline=False, penalty=-1.0):
         """the rigid body moved (spline=True: re-read it from nearest_distance_coeff_) and / or the penalty changed"""

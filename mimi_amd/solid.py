@@ -350,6 +350,7 @@ class Route(typing.NamedTuple):
     friction_actions: bool = False      # ... and Coulomb friction, which is assembled only without it
     operator_jacobi: bool = False       # matrix-free: the reference's Jacobi from the diagonal of the operator itself
     block_jacobi: bool = False          # node-block (dim x dim per control point) Jacobi, assembled or matrix-free
+    augmented_contact: bool = False     # the contacts carry nodal multipliers (MortarContact.SetAugmented)
 
 
 def resolve_route(rc, bc, axes):
@@ -404,6 +405,12 @@ def resolve_route(rc, bc, axes):
     if friction_actions and not boundary_actions:
         raise RuntimeError("friction_matrix_free needs matrix_free_boundary: it adds the friction tangent to the contact "
                            "action of the matrix-free product")
+    # "contact_augmented_lagrange": nodal multipliers on every contact, on every implicit route (assembled or matrix-free,
+    # frozen or consistent, with or without friction): whatever reads the nodal pressure reads the augmented one
+    augmented_contact = flag("contact_augmented_lagrange")
+    if augmented_contact and explicit:
+        raise RuntimeError("contact_augmented_lagrange cannot be combined with explicit_dynamics: an explicit step has no "
+                           "solve to repeat after a multiplier update -- unset one of the two")
     if explicit:
         for other, on in (("matrix_free", matrix_free), ("use_iterative_solver", iterative)):
             if on:
@@ -440,7 +447,7 @@ def resolve_route(rc, bc, axes):
     if explicit and host_setup:
         raise RuntimeError("explicit_dynamics cannot be combined with the host set-up: the lumped mass is assembled on the device")
     return Route(explicit, consistent, iterative, iterative and kronecker, matrix_free, boundary_actions, periodic_iterative, host_setup,
-                 consistent_contact, friction_actions, operator_jacobi, block_jacobi)
+                 consistent_contact, friction_actions, operator_jacobi, block_jacobi, augmented_contact)
 
 
 class NonlinearSolid(Solid, ExplicitDynamics):
@@ -454,6 +461,8 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         self._newton = dict(rel_tol=1e-8, abs_tol=1e-12, max_iter=None, iterative_mode=False)
         self.tangent_mode = 0
         self.newton_history = []
+        self.augmentation_history = []      # one entry per update_contact_lagrange
+        self.augmentation_loops = []        # one entry per step of the automatic loop (contact_augmentations > 0)
 
     def set_material(self, material):
         self.material = material
@@ -671,6 +680,11 @@ class NonlinearSolid(Solid, ExplicitDynamics):
                 self.contacts_[-1].SetFrictionAction(True)
             if self.route_.consistent_contact:
                 self.contacts_[-1].SetConsistentTangent(True)
+            if self.route_.augmented_contact:
+                self.contacts_[-1].SetAugmented(True)
+        # the automatic augmentation loop of step_time2 (off without the mode or with contact_augmentations = 0)
+        self._augmentations = max(rc.get_int("contact_augmentations", 0), 0) if self.route_.augmented_contact else 0
+        self._gap_tolerance = rc.get_real("contact_gap_tolerance", 0.0)
         # follower pressure (the reference stores BCMarker::pressure_ and never applies it): one device integrator per bid
         self.pressures_, self._pressure_by_bid = [], {}
         for bid, value in bc.initial.pressure_.items():
@@ -1130,7 +1144,53 @@ class NonlinearSolid(Solid, ExplicitDynamics):
             raise RuntimeError("step_time2() while a fixed-point step is open: finish it with advance_time2() first")
         self._predict()
         self._aa = self._newton_solve(self._aa)
+        self._augment()
         self._commit()
+
+    # -- augmented-Lagrangian contact (rc.set_int("contact_augmented_lagrange", 1)) ---------------------------------------
+    def _require_augmented(self, what):
+        if not getattr(self, "route_", None) or not self.route_.augmented_contact:
+            raise RuntimeError(f"{what} needs contact_augmented_lagrange: the contacts carry no multipliers")
+
+    def update_contact_lagrange(self, apply=True):
+        """The Uzawa step of every contact at the configuration of the latest converged residual, x_a + fac0 aa:
+        dlambda_i = p_i - lambda_i and, with `apply`, lambda_i <- p_i.  Returns the largest violation max |dlambda_i| / eps (a
+        length) over the contacts and appends dict(time, apply, violation, contacts=[MortarContact.UpdateLagrange's dict per
+        contact]) to augmentation_history.  The multipliers are an iterate, not history: they survive the step as a warm
+        start and no trial copy is kept.  Expect the violation to shrink like k / (k + eps) per update, k the effective
+        stiffness under the contact: useful at a penalty of the order of the body's stiffness, not at a soft one."""
+        self._require_augmented("update_contact_lagrange()")
+        if getattr(self, "_xa", None) is None or getattr(self, "_aa", None) is None:
+            raise RuntimeError("update_contact_lagrange() before any solve: there is no converged configuration to measure")
+        xu = self._expand(self._xa + self._fac0 * self._aa)
+        per = [c.UpdateLagrange(xu, apply) for c in self.contacts_]
+        violation = max([d["violation"] for d in per], default=0.0)
+        self.augmentation_history.append(dict(time=self.current_time, apply=bool(apply), violation=violation, contacts=per))
+        return violation
+
+    def fill_contact_lagrange(self, value=0.0):
+        """every multiplier of every contact <- value (projected onto lambda <= 0); the way to drop multipliers a node kept
+        because all its points slid past the rim of a spline body"""
+        self._require_augmented("fill_contact_lagrange()")
+        for c in self.contacts_:
+            c.FillLagrange(value)
+
+    def _augment(self):
+        """the automatic loop behind the first Newton solve of step_time2: measure; stop at the tolerance or after
+        contact_augmentations updates (converged=False, nothing raised, as Newton's own limit); else update and solve again
+        from the current aa"""
+        if not self._augmentations or not self.contacts_:
+            return
+        applied, violations = 0, []
+        while True:
+            violations.append(self.update_contact_lagrange(apply=False))
+            if violations[-1] <= self._gap_tolerance or applied >= self._augmentations:
+                break
+            self.update_contact_lagrange(apply=True)
+            applied += 1
+            self._aa = self._newton_solve(self._aa)
+        self.augmentation_loops.append(dict(converged=violations[-1] <= self._gap_tolerance, augmentations=applied,
+                                            violations=violations))
 
     # -- partitioned coupling: PySolid::FixedPointSolve2 / FixedPointAdvance2 / AdvanceTime2 (py_solid.cpp:443-511) -----
     def fixed_point_solve2(self):

@@ -180,11 +180,14 @@ int mimi_hip_domain_add_residual_and_grad_from(mimi_hip_domain_t h, const double
 /* DomainPostTimeAdvance(converged_u): commit material state (nonlinear_solid.cpp:179-199) */
 int mimi_hip_domain_post_time_advance(mimi_hip_domain_t h, const double* u);
 
-/* material state access (MaterialState of materials.hpp:278-286), for tests / output:
- * what = 0 accumulated plastic strain [n_el][n_q]; 1 temperature [n_el][n_q];
- *        2 the material's first state matrix [n_el][n_q][dim*dim] (column-major per point): plastic strain (J2,
- *          J2Linear), be_old (J2Simo), Fp_inv (J2Log);
- *        3 its second one: beta (J2Linear, materials.hpp:158), F_old (J2Simo, materials.hpp:434) */
+/* material state access (MaterialState of materials.hpp:278-286), for tests / output: `what` is one of */
+enum mimi_hip_state {
+  MIMI_HIP_STATE_EQPS = 0,         /* accumulated plastic strain [n_el][n_q] */
+  MIMI_HIP_STATE_TEMPERATURE = 1,  /* temperature [n_el][n_q] */
+  MIMI_HIP_STATE_MATRIX_1 = 2,     /* the material's first state matrix [n_el][n_q][dim*dim] (column-major per point):
+                                      plastic strain (J2, J2Linear), be_old (J2Simo), Fp_inv (J2Log) */
+  MIMI_HIP_STATE_MATRIX_2 = 3      /* its second one: beta (J2Linear, materials.hpp:158), F_old (J2Simo, materials.hpp:434) */
+};
 int mimi_hip_domain_get_state(mimi_hip_domain_t h, int what, double* out, int64_t capacity);
 int mimi_hip_domain_reset_state(mimi_hip_domain_t h);
 
@@ -199,8 +202,8 @@ int mimi_hip_domain_reset_state(mimi_hip_domain_t h);
  *                own Dev does (material_utils.hpp:33,44): for J2 this is the q of its yield function, and in 3-D the usual
  *                von Mises stress; in 2-D it is NOT the plane-strain von Mises stress of the 3-D tensor.
  *   DET_F        det(I + grad u)
- *   EQPS         the committed accumulated plastic strain, the values of mimi_hip_domain_get_state(what = 0)
- *   TEMPERATURE  the committed temperature, the values of mimi_hip_domain_get_state(what = 1)
+ *   EQPS         the committed accumulated plastic strain, the values of mimi_hip_domain_get_state(MIMI_HIP_STATE_EQPS)
+ *   TEMPERATURE  the committed temperature, the values of mimi_hip_domain_get_state(MIMI_HIP_STATE_TEMPERATURE)
  * EQPS and TEMPERATURE need no u (NULL allowed) and, like mimi_hip_domain_get_state, fail for a material without state. */
 enum mimi_hip_field {
   MIMI_HIP_FIELD_CAUCHY = 0,
@@ -287,15 +290,35 @@ int mimi_hip_domain_phase_ms(mimi_hip_domain_t h, double* phase1_ms, double* pha
 /* the same with phase 1 split at the end of its material pre-pass (0 when the path has none): pre-pass, integration /
  * contraction kernel, row gather */
 int mimi_hip_domain_phase_ms_detail(mimi_hip_domain_t h, double* prepass_ms, double* integration_ms, double* gather_ms);
-/* sizes: what = 0 n_elements, 1 n_quad, 2 n_dof, 3 nnz, 4 n_vdofs, 5 path (0 general, 1 tensor), 6 CSR kind (0 any,
- * 1 structured lexicographic, 2 structured permuted), 7 kernel family of the last assembly on the handle (0 none yet,
- * 1 two-phase tensor degree 2, 2 two-phase tensor degree 3, 3 small-element tensor, 4 general), 8 whether the handle
- * currently holds per-point gradient tables dN_dX (flat-table handles always; patch handles once a general kernel ran),
- * 9 kernel family of the last tangent action on the handle (the codes of 7), 10 bytes of linearisation record the handle
- * holds (0 before a linearize and on neo-Hookean handles), 11 and 12 the launch geometry of the handle's last assembly on
- * the symmetric-half degree-2 kernel (neo-Hookean tangent, family 1; 0 before any): 11 elements per unit -- the box's
- * column length, or the segment length where the columns were cut -- 12 units a workgroup walks back to back (1..4).
- * Tests assert them; an unknown code returns -1 */
+/* what MIMI_HIP_DOMAIN_INFO_LAST_FAMILY and _APPLY_FAMILY report */
+enum mimi_hip_kernel_family {
+  MIMI_HIP_FAMILY_NONE = 0,                 /* none yet */
+  MIMI_HIP_FAMILY_TENSOR_P2_TWO_PHASE = 1,  /* two-phase tensor degree 2 */
+  MIMI_HIP_FAMILY_TENSOR_P3_TWO_PHASE = 2,  /* two-phase tensor degree 3 */
+  MIMI_HIP_FAMILY_TENSOR_SMALL = 3,         /* small-element tensor */
+  MIMI_HIP_FAMILY_GENERAL = 4
+};
+/* sizes and what the handle last did: `what` of mimi_hip_domain_info.  Tests assert them; an unknown code returns -1 */
+enum mimi_hip_domain_info_what {
+  MIMI_HIP_DOMAIN_INFO_N_ELEMENTS = 0,
+  MIMI_HIP_DOMAIN_INFO_N_QUAD = 1,
+  MIMI_HIP_DOMAIN_INFO_N_DOF = 2,
+  MIMI_HIP_DOMAIN_INFO_NNZ = 3,
+  MIMI_HIP_DOMAIN_INFO_N_VDOFS = 4,
+  MIMI_HIP_DOMAIN_INFO_PATH = 5,                  /* 0 general, 1 tensor */
+  MIMI_HIP_DOMAIN_INFO_CSR_KIND = 6,              /* 0 any, 1 structured lexicographic, 2 structured permuted */
+  MIMI_HIP_DOMAIN_INFO_LAST_FAMILY = 7,           /* mimi_hip_kernel_family of the last assembly on the handle */
+  MIMI_HIP_DOMAIN_INFO_HAS_GRADIENT_TABLES = 8,   /* whether the handle currently holds per-point gradient tables dN_dX
+                                                     (flat-table handles always; patch handles once a general kernel ran) */
+  MIMI_HIP_DOMAIN_INFO_APPLY_FAMILY = 9,          /* mimi_hip_kernel_family of the last tangent action on the handle */
+  MIMI_HIP_DOMAIN_INFO_LINEARIZATION_BYTES = 10,  /* bytes of linearisation record the handle holds (0 before a linearize
+                                                     and on neo-Hookean handles) */
+  /* the launch geometry of the handle's last assembly on the symmetric-half degree-2 kernel (neo-Hookean tangent,
+   * MIMI_HIP_FAMILY_TENSOR_P2_TWO_PHASE; 0 before any): */
+  MIMI_HIP_DOMAIN_INFO_SEGMENT_LENGTH = 11,       /* elements per unit -- the box's column length, or the segment length
+                                                     where the columns were cut */
+  MIMI_HIP_DOMAIN_INFO_UNITS_PER_WORKGROUP = 12   /* units a workgroup walks back to back (1..4) */
+};
 int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what);
 
 /* ---- structured sparsity: PrecomputedData::PrepareSparsity (precomputed.cpp:151-174) ----
@@ -428,11 +451,21 @@ int mimi_hip_contact_add_residual_from_nodal(mimi_hip_contact_t h, const double*
  * incidences (no atomics: equal inputs give equal bytes); refused before the first linearize.  u, x, y host or device. */
 int mimi_hip_contact_linearize(mimi_hip_contact_t h, const double* u);
 int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const double* x, double* y);
-/* what: 0 bytes of the record (n_faces n_quad (1 + (dim - 1) dim) doubles + n_faces flags; 0 before the first linearize; a
- * consistent record: n_faces n_quad (2 + dim + (dim - 1) dim) doubles + 2 n_marked doubles + n_faces flags),
- * 1 whether the face tangent blocks of an assembly are allocated, 2 whether the current record is a consistent one
- * (mimi_hip_contact_set_consistent_tangent), 3 whether it carries friction (mimi_hip_contact_set_friction_action; what 0
- * then includes n_faces n_quad (8 (dim + 1) + 1) + 8 bytes more).  -1: bad argument. */
+/* `what` of mimi_hip_contact_action_info and mimi_hip_follower_action_info (the latter knows _BYTES and _FACE_BLOCKS) */
+enum mimi_hip_action_info_what {
+  MIMI_HIP_ACTION_INFO_BYTES = 0,        /* bytes of the record (n_faces n_quad (1 + (dim - 1) dim) doubles + n_faces flags;
+                                            0 before the first linearize; a consistent record: n_faces n_quad
+                                            (2 + dim + (dim - 1) dim) doubles + 2 n_marked doubles + n_faces flags) */
+  MIMI_HIP_ACTION_INFO_FACE_BLOCKS = 1,  /* whether the face tangent blocks of an assembly are allocated */
+  MIMI_HIP_ACTION_INFO_CONSISTENT = 2,   /* whether the current record is a consistent one
+                                            (mimi_hip_contact_set_consistent_tangent) */
+  MIMI_HIP_ACTION_INFO_FRICTION = 3,     /* whether it carries friction (mimi_hip_contact_set_friction_action; _BYTES then
+                                            includes n_faces n_quad (8 (dim + 1) + 1) + 8 bytes more) */
+  MIMI_HIP_ACTION_INFO_AUGMENTED = 4     /* whether the current record was made in the augmented-Lagrangian mode
+                                            (mimi_hip_contact_set_augmented; a consistent one then holds n_marked doubles
+                                            more) */
+};
+/* -1: bad argument */
 int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what);
 
 /* The consistent contact tangent as an action (the reference has none: its Jacobian freezes the nodal pressure,
@@ -512,8 +545,7 @@ int mimi_hip_contact_set_friction_action(mimi_hip_contact_t h, int on);
  *                    length: the violation of the constraint), sqrt(sum_i A_i dlambda_i^2), the number of nodes with
  *                    p_i < 0, max_i |lambda_i| after the call.  Fixed-shape reductions, no atomics: equal inputs give equal
  *                    bytes.  u host or device.
- * mimi_hip_contact_action_info(h, 4): whether the current record was made in the mode (a consistent one then holds
- * n_marked doubles more). */
+ * mimi_hip_contact_action_info(h, MIMI_HIP_ACTION_INFO_AUGMENTED) tells whether the current record was made in the mode. */
 int mimi_hip_contact_set_augmented(mimi_hip_contact_t h, int on);
 int mimi_hip_contact_lagrange(mimi_hip_contact_t h, int set, double* lambda);
 int mimi_hip_contact_update_lagrange(mimi_hip_contact_t h, const double* u, int apply, double* out4);
@@ -603,8 +635,14 @@ typedef struct mimi_hip_fold_s* mimi_hip_fold_t;
 int mimi_hip_fold_create(int32_t dim, int64_t n_nodes_u, const int64_t* node_map, const int64_t* rowptr_u,
                          const int32_t* col_u, int device, mimi_hip_fold_t* out);
 int mimi_hip_fold_destroy(mimi_hip_fold_t h);
-/* what: 0 n_nodes_f, 1 nnz_f, 2 nnz_u, 3 longest folded row (rounded up to 8), 4 folded rows added by one lane (a source
- * row whose window wraps onto itself).  -1: bad argument. */
+enum mimi_hip_fold_info_what {
+  MIMI_HIP_FOLD_INFO_N_NODES_F = 0,
+  MIMI_HIP_FOLD_INFO_NNZ_F = 1,
+  MIMI_HIP_FOLD_INFO_NNZ_U = 2,
+  MIMI_HIP_FOLD_INFO_ROW_CAPACITY = 3,  /* longest folded row (rounded up to 8) */
+  MIMI_HIP_FOLD_INFO_SERIAL_ROWS = 4    /* folded rows added by one lane (a source row whose window wraps onto itself) */
+};
+/* -1: bad argument */
 int64_t mimi_hip_fold_info(mimi_hip_fold_t h, int what);
 /* the folded pattern: rowptr_f[n_nodes_f dim + 1], col_f[nnz_f] (col_f NULL: rowptr only) */
 int mimi_hip_fold_pattern(mimi_hip_fold_t h, int64_t* rowptr_f, int32_t* col_f);
@@ -627,10 +665,16 @@ int mimi_hip_linear_create(int64_t n, const int64_t* csr_rowptr, const int32_t* 
 int mimi_hip_linear_destroy(mimi_hip_linear_t h);
 /* NULL = the handle's own stream */
 int mimi_hip_linear_set_stream(mimi_hip_linear_t h, void* hip_stream);
-/* what: 0 rows, 1 stored entries, 2 consecutive rows that share one column list (3 or 2: the dofs of a node in the byVDIM
- * numbering of py_nonlinear_solid.cpp:63 -- the products read the list once per group; 1: any other pattern), 3 whether
- * that shared list is made of node triples 3 c, 3 c + 1, 3 c + 2 (1: the products read one index per node, a ninth of the
- * index bytes).  -1: bad argument. */
+enum mimi_hip_linear_info_what {
+  MIMI_HIP_LINEAR_INFO_ROWS = 0,
+  MIMI_HIP_LINEAR_INFO_NNZ = 1,           /* stored entries */
+  MIMI_HIP_LINEAR_INFO_ROW_GROUP = 2,     /* consecutive rows that share one column list (3 or 2: the dofs of a node in the
+                                             byVDIM numbering of py_nonlinear_solid.cpp:63 -- the products read the list once
+                                             per group; 1: any other pattern) */
+  MIMI_HIP_LINEAR_INFO_NODE_COLUMNS = 3   /* whether that shared list is made of node triples 3 c, 3 c + 1, 3 c + 2 (1: the
+                                             products read one index per node, a ninth of the index bytes) */
+};
+/* -1: bad argument */
 int64_t mimi_hip_linear_info(mimi_hip_linear_t h, int what);
 /* forms::Nonlinear::AddMult / AddMultGrad tail (forms/nonlinear.hpp:76-80,112-115): r[ess] = 0 (r may be NULL);
  * A.EliminateRowCol(ess, DIAG_ONE) on the CSR values (A_values may be NULL).  Host or device pointers. */
@@ -638,11 +682,17 @@ int mimi_hip_linear_eliminate(mimi_hip_linear_t h, double* r, double* A_values);
 /* y += alpha A x on the handle's pattern (mfem::SparseMatrix::AddMult: `mass_->Mult(a, y)`, `viscosity_->AddMult(v, y)` of
  * operators::NonlinearSolid::Mult / ResidualAndGrad, operators/nonlinear_solid.cpp:172-205,240-283).  Host or device. */
 int mimi_hip_linear_add_mult(mimi_hip_linear_t h, const double* A_values, const double* x, double alpha, double* y);
+/* the `preconditioner` of mimi_hip_linear_gmres / _cg and the `kind` of mimi_hip_linear_apply_preconditioner */
+enum mimi_hip_preconditioner {
+  MIMI_HIP_PRECOND_NONE = 0,
+  MIMI_HIP_PRECOND_JACOBI = 1,       /* the reference's (mfem::DSmoother) */
+  MIMI_HIP_PRECOND_KRONECKER = 2,    /* the Kronecker operator below (needs set_kronecker and set_kronecker_coefficients
+                                        first; an error otherwise) */
+  MIMI_HIP_PRECOND_BLOCK_JACOBI = 3  /* the node-block Jacobi below (needs set_node_block first) */
+};
 /* The reference's iterative linear solver (py/py_nonlinear_solid.cpp:329-339: mfem::GMRESSolver + mfem::DSmoother,
  * rel 1e-8, abs 1e-12, 300 iterations; kdim <= 0 = mfem's default 50): x = 0 start, left-preconditioned restarted
  * GMRES, modified Gram-Schmidt, stops when the preconditioned residual estimate <= max(rel_tol * ||M b||, abs_tol).
- * preconditioner: 1 = the reference's Jacobi, 0 = none, 2 = the Kronecker operator below (needs set_kronecker and
- * set_kronecker_coefficients first; an error otherwise), 3 = the node-block Jacobi below (needs set_node_block first).
  * A_values / b / x host or device. */
 int mimi_hip_linear_gmres(mimi_hip_linear_t h, const double* A_values, const double* b, double* x, double rel_tol,
                           double abs_tol, int max_iter, int kdim, int preconditioner, int32_t* iterations,
@@ -667,8 +717,8 @@ int mimi_hip_linear_set_kronecker(mimi_hip_linear_t h, int32_t dim, const int32_
                                   const double* lambda);
 /* mass and stiff[c * dim + d] (host) of the operator above; the scaling array is rebuilt on the device */
 int mimi_hip_linear_set_kronecker_coefficients(mimi_hip_linear_t h, double mass_coef, const double* stiff_coef);
-/* z = M r with the preconditioner the solvers apply: kind 1 Jacobi (z = r / diag(A); needs A_values, or NULL with
- * set_operator_diagonal armed and an operator set), 2 Kronecker (A_values may be NULL), 3 node-block Jacobi (A_values, or
+/* z = M r with the preconditioner the solvers apply: kind _JACOBI (z = r / diag(A); needs A_values, or NULL with
+ * set_operator_diagonal armed and an operator set), _KRONECKER (A_values may be NULL), _BLOCK_JACOBI (A_values, or
  * NULL: the blocks of the operator).  Host or device arrays; z == r is allowed. */
 int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const double* A_values, const double* r, double* z);
 /* A domain handle in place of the matrix: with an operator set, A_values == NULL in mimi_hip_linear_gmres / _cg means
@@ -679,8 +729,11 @@ int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const do
  * waits once on the event behind the domain's last linearize.  The domain must be on the solver's device and have its n;
  * it must outlive the setting.  domain == NULL clears it. */
 int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, double density, double stiffness, double viscosity);
-/* A face tangent beside the domain operator: kind 0 = a mimi_hip_contact_t, 1 = a mimi_hip_pressure_t (`handle` must be of
- * that kind).  With A_values == NULL the product becomes
+enum mimi_hip_boundary_operator_kind {
+  MIMI_HIP_BOUNDARY_CONTACT = 0,  /* `handle` is a mimi_hip_contact_t */
+  MIMI_HIP_BOUNDARY_PRESSURE = 1  /* a mimi_hip_pressure_t */
+};
+/* A face tangent beside the domain operator (`handle` must be of the `kind` given).  With A_values == NULL the product becomes
  *   y = mask((density M + stiffness K + viscosity C + sum_k factor_k K_face,k) mask x) + x[ess],
  * the terms added in the order they were set (mimi_hip_contact_apply_tangent / mimi_hip_follower_apply_tangent: stands in
  * for SparseMatrix::Mult on the matrix MortarContact::AddBoundaryResidualAndGrad, mortar_contact.cpp:353-421, added to).
@@ -749,10 +802,20 @@ int mimi_hip_explicit_set_stream(mimi_hip_explicit_t h, void* stream);
 /* waits for the handle's stream and reads its status word: an error when set_mass saw a non-positive mass on a free or
  * prescribed dof */
 int mimi_hip_explicit_synchronize(mimi_hip_explicit_t h);
-/* what: 0 n, 1 / 2 the address of the internal / damping force vector of the previous step (the handle keeps the caller's
- * buffer by pointer: no copy), 3 corrects since start, 8 workgroups of a launch; the shape of the ledger's sums, valid
- * with h == NULL: 4 threads of a workgroup, 5 most workgroups of a launch, 6 partials a thread of the last workgroup adds,
- * 7 levels of the two trees.  -1: bad argument. */
+enum mimi_hip_explicit_info_what {
+  MIMI_HIP_EXPLICIT_INFO_N = 0,
+  MIMI_HIP_EXPLICIT_INFO_R_PREV = 1,   /* the address of the internal force vector of the previous step (the handle keeps
+                                          the caller's buffer by pointer: no copy) */
+  MIMI_HIP_EXPLICIT_INFO_D_PREV = 2,   /* the same of the damping force vector */
+  MIMI_HIP_EXPLICIT_INFO_STEPS = 3,    /* corrects since start */
+  /* the shape of the ledger's sums, valid with h == NULL: */
+  MIMI_HIP_EXPLICIT_INFO_SUM_BLOCK = 4,       /* threads of a workgroup */
+  MIMI_HIP_EXPLICIT_INFO_SUM_GRID_CAP = 5,    /* most workgroups of a launch */
+  MIMI_HIP_EXPLICIT_INFO_SUM_FINAL_RUN = 6,   /* partials a thread of the last workgroup adds */
+  MIMI_HIP_EXPLICIT_INFO_SUM_TREE_DEPTH = 7,  /* levels of the two trees */
+  MIMI_HIP_EXPLICIT_INFO_GRID = 8      /* workgroups of a launch on this handle */
+};
+/* -1: bad argument */
 int64_t mimi_hip_explicit_info(mimi_hip_explicit_t h, int what);
 /* the lumped mass (the M of ode.cpp:229-250 as a vector), copied; positive on every free and every prescribed dof (the
  * latter's enters KE), checked on the device; a fixed dof's is not read */

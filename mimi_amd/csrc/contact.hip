@@ -781,9 +781,9 @@ int mimi_hip_contact_apply_tangent(mimi_hip_contact_t h, double factor, const do
 }
 
 int64_t mimi_hip_contact_action_info(mimi_hip_contact_t h, int what) {
-  if (h && what == 2) return h->action.linearized && h->action.consistent ? 1 : 0;
-  if (h && what == 3) return h->action.linearized && h->action.friction ? 1 : 0;
-  if (h && what == 4) return h->action.linearized && h->action.augmented ? 1 : 0;
+  if (h && what == MIMI_HIP_ACTION_INFO_CONSISTENT) return h->action.linearized && h->action.consistent ? 1 : 0;
+  if (h && what == MIMI_HIP_ACTION_INFO_FRICTION) return h->action.linearized && h->action.friction ? 1 : 0;
+  if (h && what == MIMI_HIP_ACTION_INFO_AUGMENTED) return h->action.linearized && h->action.augmented ? 1 : 0;
   return boundary_action_info(h, what);
 }
 

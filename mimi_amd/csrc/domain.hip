@@ -253,17 +253,18 @@ int mimi_hip_domain_get_state(mimi_hip_domain_t h, int what, double* out, int64_
     MH_HIP(hipSetDevice(h->device));
     if (!material_has_state(h->mat.m.kind)) fail("material has no state");
     const int dd = h->dim * h->dim;
-    const int64_t need = (what == 2 || what == 3) ? h->n_pts * dd : h->n_pts;
+    const bool matrix = what == MIMI_HIP_STATE_MATRIX_1 || what == MIMI_HIP_STATE_MATRIX_2;
+    const int64_t need = matrix ? h->n_pts * dd : h->n_pts;
     if (capacity < need) fail("state buffer too small (%lld < %lld)", (long long)capacity, (long long)need);
     MH_HIP(hipStreamSynchronize(h->stream));
-    if (what == 0) {
+    if (what == MIMI_HIP_STATE_EQPS) {
       MH_HIP(hipMemcpy(out, h->eqps.ptr, need * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (what == 1) {
+    } else if (what == MIMI_HIP_STATE_TEMPERATURE) {
       MH_HIP(hipMemcpy(out, h->temperature.ptr, need * sizeof(double), hipMemcpyDeviceToHost));
-    } else if (what == 2 || what == 3) {
-      if (what == 3 && !h->state2.ptr) fail("material has no second state matrix");
+    } else if (matrix) {
+      if (what == MIMI_HIP_STATE_MATRIX_2 && !h->state2.ptr) fail("material has no second state matrix");
       std::vector<double> soa(need);
-      MH_HIP(hipMemcpy(soa.data(), what == 2 ? h->plastic_strain.ptr : h->state2.ptr, need * sizeof(double), hipMemcpyDeviceToHost));
+      MH_HIP(hipMemcpy(soa.data(), what == MIMI_HIP_STATE_MATRIX_1 ? h->plastic_strain.ptr : h->state2.ptr, need * sizeof(double), hipMemcpyDeviceToHost));
       for (int64_t pt = 0; pt < h->n_pts; ++pt)
         for (int c = 0; c < dd; ++c) out[pt * dd + c] = soa[(int64_t)c * h->n_pts + pt];
     } else {
@@ -396,19 +397,20 @@ int mimi_hip_domain_reset_state(mimi_hip_domain_t h) {
 int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what) {
   if (!h) return -1;
   switch (what) {
-  case 0: return h->n_el;
-  case 1: return h->n_q;
-  case 2: return h->n_dof;
-  case 3: return h->nnz;
-  case 4: return h->n_vdofs;
-  case 5: return h->path;
-  case 6: return h->structured_csr ? 1 : (h->structured_perm ? 2 : 0);
-  case 7: return h->last_family;
-  case 8: return h->dN_dX.ptr ? 1 : 0;
-  case 9: return h->apply_family;
-  case 10: return (h->linearized && h->lin_rec.ptr) ? h->n_pts * (int64_t)(h->dim * h->dim * h->dim * h->dim) * (int64_t)sizeof(double) : 0;
-  case 11: return h->last_seg_len;
-  case 12: return h->last_cols_per_wg;
+  case MIMI_HIP_DOMAIN_INFO_N_ELEMENTS: return h->n_el;
+  case MIMI_HIP_DOMAIN_INFO_N_QUAD: return h->n_q;
+  case MIMI_HIP_DOMAIN_INFO_N_DOF: return h->n_dof;
+  case MIMI_HIP_DOMAIN_INFO_NNZ: return h->nnz;
+  case MIMI_HIP_DOMAIN_INFO_N_VDOFS: return h->n_vdofs;
+  case MIMI_HIP_DOMAIN_INFO_PATH: return h->path;
+  case MIMI_HIP_DOMAIN_INFO_CSR_KIND: return h->structured_csr ? 1 : (h->structured_perm ? 2 : 0);
+  case MIMI_HIP_DOMAIN_INFO_LAST_FAMILY: return h->last_family;
+  case MIMI_HIP_DOMAIN_INFO_HAS_GRADIENT_TABLES: return h->dN_dX.ptr ? 1 : 0;
+  case MIMI_HIP_DOMAIN_INFO_APPLY_FAMILY: return h->apply_family;
+  case MIMI_HIP_DOMAIN_INFO_LINEARIZATION_BYTES:
+    return (h->linearized && h->lin_rec.ptr) ? h->n_pts * (int64_t)(h->dim * h->dim * h->dim * h->dim) * (int64_t)sizeof(double) : 0;
+  case MIMI_HIP_DOMAIN_INFO_SEGMENT_LENGTH: return h->last_seg_len;
+  case MIMI_HIP_DOMAIN_INFO_UNITS_PER_WORKGROUP: return h->last_cols_per_wg;
   default: return -1;
   }
 }

@@ -59,7 +59,7 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   bool integrated = false;
   // kernel family of the last assembly / state commit on this handle (mimi_hip_domain_info(h, 7)): 0 none yet,
   // 1 two-phase tensor degree 2, 2 two-phase tensor degree 3, 3 small-element tensor kernel, 4 general kernels
-  int last_family = 0;
+  int last_family = MIMI_HIP_FAMILY_NONE;
   // symmetric-half degree-2 kernel (wgsym_geometry.hpp): MIMI_HIP_WGSYM_MIN_WGS as read at create (0: unset, the shipped
   // WGSYM_MIN_WGS), and the geometry of the handle's last launch of it (mimi_hip_domain_info(h, 11) and (h, 12); 0: none yet)
   int wgsym_min_wgs = 0;
@@ -83,7 +83,7 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   mimi_hip::DeviceBuffer<double> lin_u, lin_rec, stage_x;
   bool linearized = false;
   hipEvent_t lin_event = nullptr;
-  int apply_family = 0;
+  int apply_family = MIMI_HIP_FAMILY_NONE;
 
   ~mimi_hip_domain_s();
 };

@@ -284,11 +284,11 @@ inline void run_domain(mimi_hip_domain_s* h, DomainCall c) {
   // (a 3-D degree-2 / 3 patch whose CSR is not the structured pattern is not tensor_usable: the general kernels take it)
   if (tensor_small(h) && c.grad != 2 && launch_tensor_small(h, c)) {
     // (2-D, degree 1: element kernel from the 1-D tables + the general gather)
-    h->last_family = 3;
+    h->last_family = MIMI_HIP_FAMILY_TENSOR_SMALL;
   } else if (tensor_usable(h) && !tensor_small(h) && c.grad != 2) {
     h->last_family = launch_tensor(h, c);
   } else {
-    h->last_family = 4;
+    h->last_family = MIMI_HIP_FAMILY_GENERAL;
     launch_general(h, c);
   }
   mr.finish(h->stream);

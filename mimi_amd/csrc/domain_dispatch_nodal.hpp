@@ -210,9 +210,9 @@ inline void run_body_force(mimi_hip_domain_s* h, const double* b, double* r) {
 
 // the kernel family an action runs on, with the codes of last_family: the tensor route for every tensor_usable handle
 inline int apply_family_of(const mimi_hip_domain_s* h) {
-  if (tensor_small(h)) return 3;
-  if (tensor_usable(h)) return h->degree[0] == 3 ? 2 : 1;
-  return 4;
+  if (tensor_small(h)) return MIMI_HIP_FAMILY_TENSOR_SMALL;
+  if (tensor_usable(h)) return h->degree[0] == 3 ? MIMI_HIP_FAMILY_TENSOR_P3_TWO_PHASE : MIMI_HIP_FAMILY_TENSOR_P2_TWO_PHASE;
+  return MIMI_HIP_FAMILY_GENERAL;
 }
 
 // the one switch over what a linearisation leaves: the neo-Hookean action recomputes, every other material has the record

@@ -305,19 +305,19 @@ int mimi_hip_explicit_create(int64_t n, const unsigned char* fixed, const unsign
 
 int64_t mimi_hip_explicit_info(mimi_hip_explicit_t h, int what) {
   switch (what) {          // the shape of the sums: no handle needed
-    case 4: return EXPLICIT_BLOCK;
-    case 5: return EXPLICIT_GRID_CAP;
-    case 6: return EXPLICIT_FINAL_RUN;
-    case 7: return EXPLICIT_TREE_DEPTH;
+    case MIMI_HIP_EXPLICIT_INFO_SUM_BLOCK: return EXPLICIT_BLOCK;
+    case MIMI_HIP_EXPLICIT_INFO_SUM_GRID_CAP: return EXPLICIT_GRID_CAP;
+    case MIMI_HIP_EXPLICIT_INFO_SUM_FINAL_RUN: return EXPLICIT_FINAL_RUN;
+    case MIMI_HIP_EXPLICIT_INFO_SUM_TREE_DEPTH: return EXPLICIT_TREE_DEPTH;
     default: break;
   }
   if (!h) return -1;
   switch (what) {
-    case 0: return h->n;
-    case 1: return (int64_t)(intptr_t)h->r_prev;
-    case 2: return (int64_t)(intptr_t)h->d_prev;
-    case 3: return h->steps;
-    case 8: return explicit_grid(h->n);
+    case MIMI_HIP_EXPLICIT_INFO_N: return h->n;
+    case MIMI_HIP_EXPLICIT_INFO_R_PREV: return (int64_t)(intptr_t)h->r_prev;
+    case MIMI_HIP_EXPLICIT_INFO_D_PREV: return (int64_t)(intptr_t)h->d_prev;
+    case MIMI_HIP_EXPLICIT_INFO_STEPS: return h->steps;
+    case MIMI_HIP_EXPLICIT_INFO_GRID: return explicit_grid(h->n);
     default: return -1;
   }
 }

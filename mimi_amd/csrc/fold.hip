@@ -344,11 +344,11 @@ int mimi_hip_fold_create(int32_t dim, int64_t n_nodes_u, const int64_t* node_map
 int64_t mimi_hip_fold_info(mimi_hip_fold_t h, int what) {
   if (!h) return -1;
   switch (what) {
-    case 0: return h->n_nodes_f;
-    case 1: return h->nnz_f;
-    case 2: return h->nnz_u;
-    case 3: return h->row_cap;
-    case 4: return h->n_serial;
+    case MIMI_HIP_FOLD_INFO_N_NODES_F: return h->n_nodes_f;
+    case MIMI_HIP_FOLD_INFO_NNZ_F: return h->nnz_f;
+    case MIMI_HIP_FOLD_INFO_NNZ_U: return h->nnz_u;
+    case MIMI_HIP_FOLD_INFO_ROW_CAPACITY: return h->row_cap;
+    case MIMI_HIP_FOLD_INFO_SERIAL_ROWS: return h->n_serial;
     default: return -1;
   }
 }

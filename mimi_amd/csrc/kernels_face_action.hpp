@@ -167,8 +167,8 @@ void boundary_apply_entry(H* h, const char* who, double factor, const double* x,
 template<typename H>
 int64_t boundary_action_info(const H* h, int what) {
   if (!h) return -1;
-  if (what == 0) return h->action.bytes(*h);
-  if (what == 1) return h->face_k.ptr ? 1 : 0;
+  if (what == MIMI_HIP_ACTION_INFO_BYTES) return h->action.bytes(*h);
+  if (what == MIMI_HIP_ACTION_INFO_FACE_BLOCKS) return h->face_k.ptr ? 1 : 0;
   return -1;
 }
 

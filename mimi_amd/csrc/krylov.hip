@@ -560,7 +560,7 @@ struct mimi_hip_linear_s : StreamHandle {
   DeviceBuffer<double> op_x;   // the masked input of the action
   // mimi_hip_linear_add_boundary_operator: face tangents added to the domain's action, in the order they were set
   struct BoundaryTerm {
-    int kind;        // 0 contact, 1 pressure
+    int kind;        // mimi_hip_boundary_operator_kind
     void* handle;
     double factor;
   };
@@ -626,7 +626,7 @@ void by_product_form(const mimi_hip_linear_s* h, F&& f) {
 // the handle of a boundary term by its kind: the one switch over it.  f(handle)
 template<class F>
 void by_boundary_kind(const mimi_hip_linear_s::BoundaryTerm& t, F&& f) {
-  if (t.kind == 0) f(static_cast<mimi_hip_contact_s*>(t.handle));
+  if (t.kind == MIMI_HIP_BOUNDARY_CONTACT) f(static_cast<mimi_hip_contact_s*>(t.handle));
   else f(static_cast<mimi_hip_pressure_s*>(t.handle));
 }
 
@@ -692,9 +692,6 @@ double total_to_host(mimi_hip_linear_s* h) {
   return t;
 }
 
-// the preconditioner ids of mimi_hip_linear_gmres / _cg / _apply_preconditioner
-enum { PRECOND_NONE = 0, PRECOND_JACOBI = 1, PRECOND_KRONECKER = 2, PRECOND_BLOCK_JACOBI = 3 };
-
 // d = the diagonal (block == 0: n doubles) or the node blocks (block != 0: n dim doubles) of the handle's operator in the
 // solver's numbering, on the solver's stream; solve_matrix has run.  The boundary terms contribute nothing (header comment).
 void operator_diagonal(mimi_hip_linear_s* h, int block, double* d) {
@@ -727,12 +724,12 @@ struct Preconditioner {
   const double* dinv = nullptr;   // Jacobi; fused into the kernels that take it
 
   Preconditioner(mimi_hip_linear_s* h_, int id_, const double* val) : h(h_), id(id_) {
-    if (id < PRECOND_NONE || id > PRECOND_BLOCK_JACOBI)
+    if (id < MIMI_HIP_PRECOND_NONE || id > MIMI_HIP_PRECOND_BLOCK_JACOBI)
       fail("unknown preconditioner id %d (0 none, 1 Jacobi, 2 Kronecker, 3 node-block Jacobi)", id);
-    if (id == PRECOND_KRONECKER) {
+    if (id == MIMI_HIP_PRECOND_KRONECKER) {
       if (!h->kron.set) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker first");
       if (!h->kron.have_coefficients) fail("preconditioner id 2 (Kronecker) needs mimi_hip_linear_set_kronecker_coefficients first");
-    } else if (id == PRECOND_JACOBI) {
+    } else if (id == MIMI_HIP_PRECOND_JACOBI) {
       if (!val && !(h->op_diagonal && h->op_domain)) fail("the Jacobi preconditioner needs the matrix values");
       h->dinv.resize((size_t)h->n);
       const dim3 grid((unsigned)((h->n + 255) / 256));
@@ -748,7 +745,7 @@ struct Preconditioner {
           fail("Jacobi from the operator's diagonal: the diagonal entry of dof %llu is zero or not finite", bad);
       }
       dinv = h->dinv.ptr;
-    } else if (id == PRECOND_BLOCK_JACOBI) {
+    } else if (id == MIMI_HIP_PRECOND_BLOCK_JACOBI) {
       build_blocks(val);
     }
   }
@@ -811,18 +808,18 @@ struct Preconditioner {
   // behind a plain one
   void product(const double* val, const double* x, const double* b, double* y) const {
     spmv(h, val, x, b, dinv, y);
-    if (id == PRECOND_KRONECKER) kronecker(y, y);
-    else if (id == PRECOND_BLOCK_JACOBI) blocks(y, y, nullptr);
+    if (id == MIMI_HIP_PRECOND_KRONECKER) kronecker(y, y);
+    else if (id == MIMI_HIP_PRECOND_BLOCK_JACOBI) blocks(y, y, nullptr);
   }
 
   // z = M r, and the partial sums of r . z into partial_rz when the caller wants them
   void apply(const double* r, double* z, double* partial_rz) const {
-    if (id == PRECOND_KRONECKER) {
+    if (id == MIMI_HIP_PRECOND_KRONECKER) {
       kronecker(r, z);
       if (partial_rz) dot(h, z, r, partial_rz);
       return;
     }
-    if (id == PRECOND_BLOCK_JACOBI) {
+    if (id == MIMI_HIP_PRECOND_BLOCK_JACOBI) {
       blocks(r, z, partial_rz);
       return;
     }
@@ -838,7 +835,7 @@ struct Preconditioner {
 Mirror<double> solve_matrix(mimi_hip_linear_s* h, const double* A_values, int preconditioner) {
   if (A_values) return Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, h->stream);
   if (!h->op_domain) fail("null argument (no matrix values, and no operator is set: mimi_hip_linear_set_operator)");
-  if (preconditioner == PRECOND_JACOBI && !h->op_diagonal) fail("the Jacobi preconditioner needs the matrix values");
+  if (preconditioner == MIMI_HIP_PRECOND_JACOBI && !h->op_diagonal) fail("the Jacobi preconditioner needs the matrix values");
   if (h->op_fold) {
     // (set_operator_fold and set_operator checked these against what was set then; either may have changed since)
     const OperatorFold f = operator_fold(h->op_fold);
@@ -954,10 +951,10 @@ int mimi_hip_linear_set_stream(mimi_hip_linear_t h, void* stream) { return handl
 int64_t mimi_hip_linear_info(mimi_hip_linear_t h, int what) {
   if (!h) return -1;
   switch (what) {
-    case 0: return h->n;
-    case 1: return h->nnz;
-    case 2: return h->group;
-    case 3: return h->nodecol ? 1 : 0;
+    case MIMI_HIP_LINEAR_INFO_ROWS: return h->n;
+    case MIMI_HIP_LINEAR_INFO_NNZ: return h->nnz;
+    case MIMI_HIP_LINEAR_INFO_ROW_GROUP: return h->group;
+    case MIMI_HIP_LINEAR_INFO_NODE_COLUMNS: return h->nodecol ? 1 : 0;
     default: return -1;
   }
 }
@@ -1213,7 +1210,7 @@ int mimi_hip_linear_set_operator(mimi_hip_linear_t h, mimi_hip_domain_t domain, 
 int mimi_hip_linear_add_boundary_operator(mimi_hip_linear_t h, int kind, void* handle, double factor) {
   return guarded([&] {
     if (!h || !handle) fail("null argument");
-    if (kind != 0 && kind != 1) fail("boundary operator kind %d (0 contact, 1 pressure)", kind);
+    if (kind != MIMI_HIP_BOUNDARY_CONTACT && kind != MIMI_HIP_BOUNDARY_PRESSURE) fail("boundary operator kind %d (0 contact, 1 pressure)", kind);
     if (!h->op_domain) fail("boundary operator: no domain operator is set (mimi_hip_linear_set_operator comes first)");
     if (h->n_op_terms >= mimi_hip_linear_s::kMaxBoundaryTerms)
       fail("boundary operator: at most %d terms", mimi_hip_linear_s::kMaxBoundaryTerms);
@@ -1267,7 +1264,7 @@ int mimi_hip_linear_operator_mult(mimi_hip_linear_t h, const double* x, double* 
     if (x == y) fail("operator product: x and y must be different vectors");
     MH_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    solve_matrix(h, nullptr, PRECOND_NONE);
+    solve_matrix(h, nullptr, MIMI_HIP_PRECOND_NONE);
     Mirror<double> mx = Mirror<double>::in(x, (size_t)h->n, h->stage_x, s);
     Mirror<double> my;   // written whole: a host y has nothing to upload
     my.count = (size_t)h->n;
@@ -1287,15 +1284,15 @@ int mimi_hip_linear_operator_mult(mimi_hip_linear_t h, const double* x, double* 
 int mimi_hip_linear_apply_preconditioner(mimi_hip_linear_t h, int kind, const double* A_values, const double* r, double* z) {
   return guarded([&] {
     if (!h || !r || !z) fail("null argument");
-    if (kind < PRECOND_JACOBI || kind > PRECOND_BLOCK_JACOBI) fail("preconditioner kind %d (1 Jacobi, 2 Kronecker, 3 node-block Jacobi)", kind);
+    if (kind < MIMI_HIP_PRECOND_JACOBI || kind > MIMI_HIP_PRECOND_BLOCK_JACOBI) fail("preconditioner kind %d (1 Jacobi, 2 Kronecker, 3 node-block Jacobi)", kind);
     MH_HIP(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     Mirror<double> mr = Mirror<double>::in(r, (size_t)h->n, h->stage_b, s);
     Mirror<double> mz = Mirror<double>::inout(z, (size_t)h->n, h->stage_x, s);
     Mirror<double> mA;   // the values: the two Jacobis alone read them; without them theirs is the operator's diagonal
-    if (kind != PRECOND_KRONECKER) {
+    if (kind != MIMI_HIP_PRECOND_KRONECKER) {
       if (A_values) mA = Mirror<double>::in(A_values, (size_t)h->nnz, h->stage_val, s);
-      else if (h->op_domain && (kind == PRECOND_BLOCK_JACOBI || h->op_diagonal)) solve_matrix(h, nullptr, kind);
+      else if (h->op_domain && (kind == MIMI_HIP_PRECOND_BLOCK_JACOBI || h->op_diagonal)) solve_matrix(h, nullptr, kind);
     }
     const Preconditioner M(h, kind, mA.dev);
     M.apply(mr.dev, mz.dev, nullptr);

@@ -21,13 +21,13 @@ inline int launch_tensor(mimi_hip_domain_s* h, const DomainCall& c) {
   TensorArgs a = tensor_args(h, c);
   if (h->degree[0] == 3) {
     launch_tensor_p3(h, c, a);
-    return 2;
+    return MIMI_HIP_FAMILY_TENSOR_P3_TWO_PHASE;
   }
   // the symmetric-half kernel for the hyperelastic law, the nine-block kernel behind the material pre-pass for the others
   if (!c.grad) launch_tensor_residual(h, a);
   else if (h->mat.m.kind == MIMI_HIP_MAT_NEOHOOKEAN) launch_tensor_wgsym(h, c, a);
   else launch_tensor_wgs(h, c, a);
-  return 1;
+  return MIMI_HIP_FAMILY_TENSOR_P2_TWO_PHASE;
 }
 
 inline void launch_tensor_post(mimi_hip_domain_s* h, const DomainCall& c) {

@@ -15,9 +15,10 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import check, fptr
+from ._capi import ABI, check, fptr
 
-# The shape of the ledger's sums (mimi_amd/csrc/explicit.hip; mimi_hip_explicit_info(NULL, 4..7) returns the same numbers):
+# The shape of the ledger's sums (mimi_amd/csrc/explicit.hip; mimi_hip_explicit_info(NULL, MIMI_HIP_EXPLICIT_INFO_SUM_*) returns the
+# same numbers):
 # a launch has min(ceil(n / SUM_BLOCK), SUM_GRID_CAP) workgroups of SUM_BLOCK threads; a thread adds its dofs i, i + stride,
 # ... in ascending order, the workgroup adds by a tree of log2(SUM_BLOCK) levels, and the last workgroup adds the partials,
 # SUM_FINAL_RUN consecutive ones per thread and the same tree again.
@@ -69,7 +70,7 @@ class ExplicitStepper(_capi.Handle):
 
     def PreviousForcePointers(self):
         """(r, d) addresses of the force vectors of the previous step the handle keeps (by pointer: no copy)"""
-        return self.Info(1), self.Info(2)
+        return self.Info(ABI.EXPLICIT_INFO_R_PREV), self.Info(ABI.EXPLICIT_INFO_D_PREV)
 
     def SetMass(self, m):
         self._follow_torch(m)

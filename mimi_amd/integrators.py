@@ -13,10 +13,10 @@ import weakref
 import numpy as np
 
 from . import _capi
-from ._capi import check, fptr, ptr
+from ._capi import ABI, check, fptr, ptr
 
-TANGENT_ANALYTIC = 0
-TANGENT_REFERENCE_FD = 1
+TANGENT_ANALYTIC = ABI.TANGENT_ANALYTIC
+TANGENT_REFERENCE_FD = ABI.TANGENT_REFERENCE_FD
 
 
 class CSRPattern:
@@ -145,14 +145,17 @@ class NonlinearSolid(NonlinearBase):
         self._h = h
         if self.patch_ is None and self.tables_.get("N") is not None:
             self.SetShapeValues(self.tables_["N"])
-        self.n_elements_ = int(L.mimi_hip_domain_info(h, 0))
-        self.n_quad_ = int(L.mimi_hip_domain_info(h, 1))
-        self.n_dof_ = int(L.mimi_hip_domain_info(h, 2))
-        self.nnz_ = int(L.mimi_hip_domain_info(h, 3))
-        self.n_vdofs_ = int(L.mimi_hip_domain_info(h, 4))
-        self.path_ = int(L.mimi_hip_domain_info(h, 5))
-        self.has_states_ = self.material_._kind == 1
+        self.n_elements_ = self._info(ABI.DOMAIN_INFO_N_ELEMENTS)
+        self.n_quad_ = self._info(ABI.DOMAIN_INFO_N_QUAD)
+        self.n_dof_ = self._info(ABI.DOMAIN_INFO_N_DOF)
+        self.nnz_ = self._info(ABI.DOMAIN_INFO_NNZ)
+        self.n_vdofs_ = self._info(ABI.DOMAIN_INFO_N_VDOFS)
+        self.path_ = self._info(ABI.DOMAIN_INFO_PATH)
+        self.has_states_ = self.material_._kind == ABI.MAT_J2
         return self
+
+    def _info(self, what):
+        return int(_capi.lib().mimi_hip_domain_info(self._handle(), what))
 
     def _push_dt(self):
         # forms::Nonlinear pushes these public members before each call (forms/nonlinear.hpp:63-65)
@@ -210,32 +213,35 @@ class NonlinearSolid(NonlinearBase):
         raise RuntimeError("Currently not implemented, use AddDomainResidualAndGrad")  # nonlinear_solid.hpp:108-113
 
     # -- material state (MaterialState, materials.hpp:278-286) --------------------------
-    KERNEL_FAMILIES = {0: "none", 1: "tensor_p2_two_phase", 2: "tensor_p3_two_phase", 3: "tensor_small", 4: "general"}
+    # mimi_hip_kernel_family by value: "none", "tensor_p2_two_phase", "tensor_p3_two_phase", "tensor_small", "general"
+    KERNEL_FAMILIES = {v: k[len("FAMILY_"):].lower() for k, v in vars(ABI).items() if k.startswith("FAMILY_")}
 
     def LastKernelFamily(self):
         """which kernel family the last assembly on this handle ran on (tests assert it; see mimi_hip_domain_info)"""
-        return self.KERNEL_FAMILIES[int(_capi.lib().mimi_hip_domain_info(self._handle(), 7))]
+        return self.KERNEL_FAMILIES[self._info(ABI.DOMAIN_INFO_LAST_FAMILY)]
 
     def LastWalkGeometry(self):
         """(seg_len, cols_per_wg) of the last launch of the symmetric-half degree-2 kernel on this handle: elements per unit
-        (column or column segment) and units a workgroup walks back to back; (0, 0) before any (mimi_hip_domain_info(h, 11)
-        and (h, 12); tests assert the walk they were written to reach)"""
-        L = _capi.lib()
-        return int(L.mimi_hip_domain_info(self._handle(), 11)), int(L.mimi_hip_domain_info(self._handle(), 12))
+        (column or column segment) and units a workgroup walks back to back; (0, 0) before any (MIMI_HIP_DOMAIN_INFO_SEGMENT_LENGTH
+        and _UNITS_PER_WORKGROUP; tests assert the walk they were written to reach)"""
+        return self._info(ABI.DOMAIN_INFO_SEGMENT_LENGTH), self._info(ABI.DOMAIN_INFO_UNITS_PER_WORKGROUP)
 
     def State(self, what):
         # "plastic_strain" = the material's first state matrix (J2 / J2Linear: plastic strain, J2Simo: be_old, J2Log:
         # Fp_inv); "state2" = its second one (J2Linear: beta, J2Simo: F_old)
-        ids = {"accumulated_plastic_strain": 0, "temperature": 1, "plastic_strain": 2, "state2": 3}
+        ids = {"accumulated_plastic_strain": ABI.STATE_EQPS, "temperature": ABI.STATE_TEMPERATURE,
+               "plastic_strain": ABI.STATE_MATRIX_1, "state2": ABI.STATE_MATRIX_2}
         n = self.n_elements_ * self.n_quad_
         dim = self.patch_.dim if self.patch_ is not None else self.tables_["dim"]
-        shape = (self.n_elements_, self.n_quad_, dim * dim) if ids[what] >= 2 else (self.n_elements_, self.n_quad_)
+        matrix = what in ("plastic_strain", "state2")
+        shape = (self.n_elements_, self.n_quad_, dim * dim) if matrix else (self.n_elements_, self.n_quad_)
         out = np.empty(shape)
         check(_capi.lib().mimi_hip_domain_get_state(self._handle(), ids[what], ptr(out), out.size))
         return out
 
     # -- field output (mimi_hip.h: "field output") ---------------------------------------------------
-    FIELDS = {"cauchy_stress": 0, "von_mises_stress": 1, "det_F": 2, "accumulated_plastic_strain": 3, "temperature": 4}
+    FIELDS = {"cauchy_stress": ABI.FIELD_CAUCHY, "von_mises_stress": ABI.FIELD_VON_MISES, "det_F": ABI.FIELD_DET_F,
+              "accumulated_plastic_strain": ABI.FIELD_EQPS, "temperature": ABI.FIELD_TEMPERATURE}
 
     def _dim(self):
         return self.patch_.dim if self.patch_ is not None else self.tables_["dim"]
@@ -255,12 +261,10 @@ class NonlinearSolid(NonlinearBase):
         N = np.ascontiguousarray(N, dtype=np.float64)
         if N.ndim != 3:
             raise ValueError(f"shape values must be [n_elements, n_quad, n_dof], got {N.shape}")
-        L = _capi.lib()
-        want = (int(L.mimi_hip_domain_info(self._handle(), 0)), int(L.mimi_hip_domain_info(self._handle(), 1)),
-                int(L.mimi_hip_domain_info(self._handle(), 2)))
+        want = (self._info(ABI.DOMAIN_INFO_N_ELEMENTS), self._info(ABI.DOMAIN_INFO_N_QUAD), self._info(ABI.DOMAIN_INFO_N_DOF))
         if N.shape != want:
             raise ValueError(f"shape values must be {want}, got {N.shape}")
-        check(L.mimi_hip_domain_set_shape_values(self._handle(), ptr(N)))
+        check(_capi.lib().mimi_hip_domain_set_shape_values(self._handle(), ptr(N)))
 
     def PointField(self, name, u, out=None):
         """the field at the quadrature points, [n_el, n_q, ncomp] (overwritten; allocated on the host when out is None).
@@ -340,16 +344,16 @@ class NonlinearSolid(NonlinearBase):
         return out
 
     def LastActionFamily(self):
-        """which kernel family the last ApplyTangent on this handle ran on (mimi_hip_domain_info(h, 9))"""
-        return self.KERNEL_FAMILIES[int(_capi.lib().mimi_hip_domain_info(self._handle(), 9))]
+        """which kernel family the last ApplyTangent on this handle ran on (MIMI_HIP_DOMAIN_INFO_APPLY_FAMILY)"""
+        return self.KERNEL_FAMILIES[self._info(ABI.DOMAIN_INFO_APPLY_FAMILY)]
 
     def LinearizationBytes(self):
-        """bytes of linearisation record the handle holds (mimi_hip_domain_info(h, 10)): 0 on neo-Hookean handles"""
-        return int(_capi.lib().mimi_hip_domain_info(self._handle(), 10))
+        """bytes of linearisation record the handle holds (MIMI_HIP_DOMAIN_INFO_LINEARIZATION_BYTES): 0 on neo-Hookean handles"""
+        return self._info(ABI.DOMAIN_INFO_LINEARIZATION_BYTES)
 
     def HoldsGradientTables(self):
-        """whether the handle holds per-point gradient tables (mimi_hip_domain_info(h, 8))"""
-        return bool(_capi.lib().mimi_hip_domain_info(self._handle(), 8))
+        """whether the handle holds per-point gradient tables (MIMI_HIP_DOMAIN_INFO_HAS_GRADIENT_TABLES)"""
+        return bool(self._info(ABI.DOMAIN_INFO_HAS_GRADIENT_TABLES))
 
     def SetPhaseTiming(self, on=True):
         check(_capi.lib().mimi_hip_domain_set_phase_timing(self._handle(), 1 if on else 0))
@@ -423,7 +427,7 @@ class _Frictional:
 class RigidSphere(_Frictional):
     """Analytic rigid body standing in for NearestDistanceToSplines
     (coefficients/nearest_distance.hpp:215-288; splinepy's proximity query is not available)."""
-    kind = 0
+    kind = ABI.BODY_SPHERE
 
     def __init__(self, center, radius, coefficient=1.0e4, friction=0.0, tangential_coefficient=None, step_displacement=None):
         self.center, self.radius = [float(c) for c in center], float(radius)
@@ -435,7 +439,7 @@ class RigidSphere(_Frictional):
 
 
 class RigidPlane(_Frictional):
-    kind = 1
+    kind = ABI.BODY_PLANE
 
     def __init__(self, point, normal, coefficient=1.0e4, friction=0.0, tangential_coefficient=None, step_displacement=None):
         n = np.asarray(normal, dtype=np.float64)
@@ -451,7 +455,7 @@ class RigidSpline(_Frictional):
     """One rigid boundary spline (curve in 2-D, surface in 3-D): what NearestDistanceToSplines holds
     (coefficients/nearest_distance.hpp:215-288).  Orientation: the normal (t_y, -t_x) / S_u x S_v must point out of the
     rigid body (nearest_distance.hpp:139-184)."""
-    kind = 2
+    kind = ABI.BODY_SPLINE
 
     def __init__(self, degrees, knots, control_points, weights=None, resolution=100, coefficient=1.0e4, max_iterations=-1,
                  friction=0.0, tangential_coefficient=None, step_displacement=None):
@@ -483,7 +487,7 @@ class NearestDistanceToSplines(_Frictional):
     """coefficients::NearestDistanceToSplines as bound in py/py_nearest_distance.cpp: add_spline / plant_kd_tree /
     coefficient.  `spline` is anything with the attributes degrees, knot_vectors, control_points and (optionally)
     weights -- a splinepy spline has them."""
-    kind = 2
+    kind = ABI.BODY_SPLINE
 
     def __init__(self):
         self._coefficient = 1.0e4       # nearest_distance.hpp:18
@@ -560,18 +564,18 @@ class _FaceTangentAction:
 
     def LinearizationBytes(self):
         """bytes of linearisation record the handle holds (0 before the first Linearize)"""
-        return int(self._action_fn("action_info")(self._handle(), 0))
+        return int(self._action_fn("action_info")(self._handle(), ABI.ACTION_INFO_BYTES))
 
     def HoldsTangentBlocks(self):
         """whether the per-face tangent blocks of an assembly are allocated"""
-        return bool(self._action_fn("action_info")(self._handle(), 1))
+        return bool(self._action_fn("action_info")(self._handle(), ABI.ACTION_INFO_FACE_BLOCKS))
 
 
 class MortarContact(_FaceTangentAction, NonlinearBase):
     """integrators::MortarContact (integrators/mortar_contact.hpp:23-172) against an analytic
     rigid body, on one face of a B-spline patch."""
     _prefix = "contact"
-    _action_prefix, _operator_kind = "contact", 0
+    _action_prefix, _operator_kind = "contact", ABI.BOUNDARY_CONTACT
 
     def __init__(self, nearest_distance_coeff, name, pattern, patch, axis, side, device=0, quadrature_order=-1,
                  element_box=None):
@@ -603,7 +607,7 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
         for i, v in enumerate(body.params(p.dim)):
             t.body[i] = v
         t.penalty = body.coefficient
-        if body.kind == 2:
+        if body.kind == ABI.BODY_SPLINE:
             self._spline_struct = body.c_struct()
             self._keep.append(body)
             t.spline = C.cast(C.pointer(self._spline_struct), C.c_void_p)
@@ -689,7 +693,7 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
 
     def HoldsFrictionRecord(self):
         """whether the record of the last Linearize carries friction"""
-        return bool(self._action_fn("action_info")(self._handle(), 3))
+        return bool(self._action_fn("action_info")(self._handle(), ABI.ACTION_INFO_FRICTION))
 
     def Linearize(self, u):
         self._refuse_friction("the matrix-free tangent action (Linearize)", self.friction_action_)
@@ -715,7 +719,7 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
 
     def HoldsConsistentRecord(self):
         """whether the record of the last Linearize is a consistent one"""
-        return bool(self._action_fn("action_info")(self._handle(), 2))
+        return bool(self._action_fn("action_info")(self._handle(), ABI.ACTION_INFO_CONSISTENT))
 
     # -- augmented-Lagrangian mode (include/mimi_hip.h: mimi_hip_contact_set_augmented ...) ---------------------------
     def SetAugmented(self, on=True):
@@ -761,7 +765,7 @@ class MortarContact(_FaceTangentAction, NonlinearBase):
 
     def HoldsAugmentedRecord(self):
         """whether the record of the last Linearize was made in the augmented mode"""
-        return bool(self._action_fn("action_info")(self._handle(), 4))
+        return bool(self._action_fn("action_info")(self._handle(), ABI.ACTION_INFO_AUGMENTED))
 
     def UpdateBody(self, spline=False, penalty=-1.0):
         """the rigid body moved (spline=True: re-read it from nearest_distance_coeff_) and / or the penalty changed"""
@@ -852,7 +856,7 @@ class FollowerPressure(_FaceTangentAction, NonlinearBase):
     dm/dx -- exact, not symmetric.  element_box = (begin, end): only the faces of the elements in that box (element slabs:
     every contribution lands in rows of the slab's own elements, no exchange of nodal values is needed)."""
     _prefix = "pressure"
-    _action_prefix, _operator_kind = "follower", 1
+    _action_prefix, _operator_kind = "follower", ABI.BOUNDARY_PRESSURE
 
     def __init__(self, name, pattern, patch, axis, side, device=0, quadrature_order=-1, element_box=None):
         super().__init__(name)
@@ -1059,9 +1063,9 @@ class PeriodicFold(_capi.Handle):
                                      ptr(self.pattern_u_.rowptr, "int64"), ptr(self.pattern_u_.col, "int32"), self.device_,
                                      C.byref(h)))
         self._h = h
-        self.n_nodes_f_ = int(L.mimi_hip_fold_info(h, 0))
-        self.nnz_f_ = int(L.mimi_hip_fold_info(h, 1))
-        self.nnz_u_ = int(L.mimi_hip_fold_info(h, 2))
+        self.n_nodes_f_ = int(L.mimi_hip_fold_info(h, ABI.FOLD_INFO_N_NODES_F))
+        self.nnz_f_ = int(L.mimi_hip_fold_info(h, ABI.FOLD_INFO_NNZ_F))
+        self.nnz_u_ = int(L.mimi_hip_fold_info(h, ABI.FOLD_INFO_NNZ_U))
         self.n_f_ = self.n_nodes_f_ * self.dim_
         self.n_u_ = len(self.node_map_) * self.dim_
         return self

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import check, fptr, ptr
+from ._capi import ABI, check, fptr, ptr
 
 
 class LinearSolver(_capi.Handle):
@@ -22,7 +22,8 @@ class LinearSolver(_capi.Handle):
     # "jacobi": mfem::DSmoother, the reference's; "kronecker": the fast-diagonalisation operator of SetKronecker;
     # "block_jacobi": the inverted dim x dim node blocks (SetNodeBlock); "none"
     preconditioner = "jacobi"
-    _PRECONDITIONER_IDS = {"none": 0, "jacobi": 1, "kronecker": 2, "block_jacobi": 3}
+    _PRECONDITIONER_IDS = {"none": ABI.PRECOND_NONE, "jacobi": ABI.PRECOND_JACOBI, "kronecker": ABI.PRECOND_KRONECKER,
+                           "block_jacobi": ABI.PRECOND_BLOCK_JACOBI}
 
     @property
     def use_jacobi(self):
@@ -53,11 +54,11 @@ class LinearSolver(_capi.Handle):
 
     def RowGroup(self):
         """consecutive rows sharing one column list that the products read once (3, 2 or 1)"""
-        return int(_capi.lib().mimi_hip_linear_info(self._h, 2))
+        return int(_capi.lib().mimi_hip_linear_info(self._h, ABI.LINEAR_INFO_ROW_GROUP))
 
     def NodeColumns(self):
         """True when the shared column list of a node's rows is made of node triples and is read as one index per node"""
-        return bool(_capi.lib().mimi_hip_linear_info(self._h, 3))
+        return bool(_capi.lib().mimi_hip_linear_info(self._h, ABI.LINEAR_INFO_NODE_COLUMNS))
 
     def Eliminate(self, r=None, A_values=None):
         """r[ess] = 0; A.EliminateRowCol(ess, DIAG_ONE)"""

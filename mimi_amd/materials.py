@@ -18,21 +18,21 @@ class HardeningBase:
 
 
 class PowerLawHardening(HardeningBase):
-    _kind = 0
+    _kind = _capi.ABI.HARD_POWERLAW
     sigma_y = 0.0
     n = 1.0
     eps0 = 1.0
 
 
 class VoceHardening(HardeningBase):
-    _kind = 1
+    _kind = _capi.ABI.HARD_VOCE
     sigma_y = 0.0
     sigma_sat = 0.0
     strain_constant = 1.0
 
 
 class JohnsonCookHardening(HardeningBase):
-    _kind = 2
+    _kind = _capi.ABI.HARD_JC
     A = 0.0
     B = 0.0
     n = 1.0
@@ -42,7 +42,7 @@ class JohnsonCookHardening(HardeningBase):
 
 
 class JohnsonCookRateDependentHardening(JohnsonCookHardening):
-    _kind = 3
+    _kind = _capi.ABI.HARD_JC_RATE
     # the reference leaves C_ uninitialised unless set (material_hardening.hpp:156); its
     # golden data correspond to 0
     C = 0.0
@@ -53,13 +53,13 @@ class JohnsonCookRateDependentHardening(JohnsonCookHardening):
 
 
 class JohnsonCookTemperatureAndRateDependentHardening(JohnsonCookRateDependentHardening):
-    _kind = 4
+    _kind = _capi.ABI.HARD_JC_TEMP_RATE
     reference_temperature = 0.0
     m = 1.0
 
 
 class JohnsonCookConstantTemperatureHardening(JohnsonCookTemperatureAndRateDependentHardening):
-    _kind = 5
+    _kind = _capi.ABI.HARD_JC_CONST_TEMP
 
 
 class Material:
@@ -96,11 +96,11 @@ class Material:
 
 
 class CompressibleOgdenNeoHookean(Material):
-    _kind = 0
+    _kind = _capi.ABI.MAT_NEOHOOKEAN
 
 
 class J2(Material):
-    _kind = 1
+    _kind = _capi.ABI.MAT_J2
     hardening = None
     heat_fraction = 0.9
     specific_heat = 0.0
@@ -126,12 +126,12 @@ class J2(Material):
 
 class StVenantKirchhoff(Material):
     """materials/materials.hpp:88-111"""
-    _kind = 2
+    _kind = _capi.ABI.MAT_STVK
 
 
 class J2Linear(Material):
     """materials/materials.hpp:142-249 (attribute names of py/py_material.cpp:47-53)"""
-    _kind = 3
+    _kind = _capi.ABI.MAT_J2LINEAR
     isotropic_hardening = 0.0
     kinematic_hardening = 0.0
     sigma_y = 0.0
@@ -146,9 +146,9 @@ class J2Linear(Material):
 
 class J2Simo(J2):
     """materials/materials.hpp:406-557"""
-    _kind = 4
+    _kind = _capi.ABI.MAT_J2SIMO
 
 
 class J2Log(J2):
     """materials/materials.hpp:559-753"""
-    _kind = 5
+    _kind = _capi.ABI.MAT_J2LOG

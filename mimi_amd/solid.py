@@ -33,7 +33,7 @@ import scipy.sparse.linalg as spla
 from . import nurbs_mesh, splines
 from .explicit import ExplicitDynamics
 from .integrators import (CouplingSurface, CSRPattern, FollowerPressure, MortarContact,
-                          NonlinearSolid as NonlinearSolidIntegrator, PeriodicFold, periodic_node_map)
+                          NonlinearSolid as NonlinearSolidIntegrator, PeriodicFold, TANGENT_ANALYTIC, periodic_node_map)
 from .kronecker import KroneckerOperator, stiffness_coefficients
 from .linear import LinearSolver
 from .splines import BSplinePatch
@@ -459,7 +459,7 @@ class NonlinearSolid(Solid, ExplicitDynamics):
         self.material = None
         self.device = device
         self._newton = dict(rel_tol=1e-8, abs_tol=1e-12, max_iter=None, iterative_mode=False)
-        self.tangent_mode = 0
+        self.tangent_mode = TANGENT_ANALYTIC
         self.newton_history = []
         self.augmentation_history = []      # one entry per update_contact_lagrange
         self.augmentation_loops = []        # one entry per step of the automatic loop (contact_augmentations > 0)

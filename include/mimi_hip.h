@@ -298,6 +298,15 @@ enum mimi_hip_kernel_family {
   MIMI_HIP_FAMILY_TENSOR_SMALL = 3,         /* small-element tensor */
   MIMI_HIP_FAMILY_GENERAL = 4
 };
+/* what MIMI_HIP_DOMAIN_INFO_GENERAL_ROUTE reports: how the element pieces of the last assembly reached r and A_values */
+enum mimi_hip_general_route {
+  MIMI_HIP_GENERAL_ROUTE_NONE = 0,     /* none yet, or a two-phase tensor family (its own row gather) */
+  MIMI_HIP_GENERAL_ROUTE_GATHER = 1,   /* element pieces stored, then the general row gather: MIMI_HIP_FAMILY_GENERAL and
+                                          MIMI_HIP_FAMILY_TENSOR_SMALL */
+  MIMI_HIP_GENERAL_ROUTE_ATOMICS = 2   /* MIMI_HIP_FAMILY_GENERAL adding into r and A_values with atomics: a CSR row longer
+                                          than the gather's row image, no room for the element blocks, or
+                                          MIMI_HIP_GENERAL_NO_TWO_PHASE=1 at create */
+};
 /* sizes and what the handle last did: `what` of mimi_hip_domain_info.  Tests assert them; an unknown code returns -1 */
 enum mimi_hip_domain_info_what {
   MIMI_HIP_DOMAIN_INFO_N_ELEMENTS = 0,
@@ -317,7 +326,8 @@ enum mimi_hip_domain_info_what {
    * MIMI_HIP_FAMILY_TENSOR_P2_TWO_PHASE; 0 before any): */
   MIMI_HIP_DOMAIN_INFO_SEGMENT_LENGTH = 11,       /* elements per unit -- the box's column length, or the segment length
                                                      where the columns were cut */
-  MIMI_HIP_DOMAIN_INFO_UNITS_PER_WORKGROUP = 12   /* units a workgroup walks back to back (1..4) */
+  MIMI_HIP_DOMAIN_INFO_UNITS_PER_WORKGROUP = 12,  /* units a workgroup walks back to back (1..4) */
+  MIMI_HIP_DOMAIN_INFO_GENERAL_ROUTE = 13         /* mimi_hip_general_route of the last assembly on the handle */
 };
 int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what);
 

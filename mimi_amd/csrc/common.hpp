@@ -77,13 +77,14 @@ inline bool env_starts(const char* name, char c) {
   return v && v[0] == c;
 }
 // once per process, at first use
-inline bool env_general_no_two_phase() { static const bool on = env_starts("MIMI_HIP_GENERAL_NO_TWO_PHASE", '1'); return on; }
 inline bool env_general_no_wpe() { static const bool on = env_starts("MIMI_HIP_GENERAL_NO_WPE", '1'); return on; }
 inline bool env_general_no_mfma() { static const bool on = env_starts("MIMI_HIP_GENERAL_NO_MFMA", '1'); return on; }
 // at every create
 inline bool env_force_general() { return env_starts("MIMI_HIP_FORCE_GENERAL", '1'); }
 inline bool env_keep_general() { return env_starts("MIMI_HIP_KEEP_GENERAL", '1'); }
 inline bool env_no_structured() { return env_starts("MIMI_HIP_NO_STRUCTURED", '1'); }
+// what the handle's general_two_phase_failed starts from (domain_dispatch.hpp: the atomics instead of store + row gather)
+inline bool env_general_no_two_phase() { return env_starts("MIMI_HIP_GENERAL_NO_TWO_PHASE", '1'); }
 // a test seam: what stands in for WGSYM_MIN_WGS on the handle (wgsym_geometry.hpp); 0 when unset
 inline int env_wgsym_min_wgs() {
   const char* v = env_text("MIMI_HIP_WGSYM_MIN_WGS");

@@ -411,6 +411,7 @@ int64_t mimi_hip_domain_info(mimi_hip_domain_t h, int what) {
     return (h->linearized && h->lin_rec.ptr) ? h->n_pts * (int64_t)(h->dim * h->dim * h->dim * h->dim) * (int64_t)sizeof(double) : 0;
   case MIMI_HIP_DOMAIN_INFO_SEGMENT_LENGTH: return h->last_seg_len;
   case MIMI_HIP_DOMAIN_INFO_UNITS_PER_WORKGROUP: return h->last_cols_per_wg;
+  case MIMI_HIP_DOMAIN_INFO_GENERAL_ROUTE: return h->last_general_route;
   default: return -1;
   }
 }

@@ -22,6 +22,8 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   mimi_hip::DeviceBuffer<int64_t> rowptr_own;
   mimi_hip::DeviceBuffer<int64_t> adj_ptr;   // node -> incident (element << 6 | local node) list, built at first use (node_adjacency):
   mimi_hip::DeviceBuffer<int32_t> adj;       // the general row gather, the form kernels, the node gather of fields and actions
+  // the general path scatters with atomics instead of store + row gather: MIMI_HIP_GENERAL_NO_TWO_PHASE as read at create,
+  // or what ensure_general_two_phase found (a CSR row longer than the gather's image, no room for the element blocks)
   bool general_two_phase_failed = false;
   const int64_t* rowptr = nullptr;           // device
 
@@ -60,6 +62,9 @@ struct mimi_hip_domain_s : mimi_hip::StreamHandle {
   // kernel family of the last assembly / state commit on this handle (mimi_hip_domain_info(h, 7)): 0 none yet,
   // 1 two-phase tensor degree 2, 2 two-phase tensor degree 3, 3 small-element tensor kernel, 4 general kernels
   int last_family = MIMI_HIP_FAMILY_NONE;
+  // scatter route of the last assembly (mimi_hip_domain_info(h, 13)): 0 none yet or a two-phase tensor family, 1 store +
+  // general row gather, 2 atomics
+  int last_general_route = MIMI_HIP_GENERAL_ROUTE_NONE;
   // symmetric-half degree-2 kernel (wgsym_geometry.hpp): MIMI_HIP_WGSYM_MIN_WGS as read at create (0: unset, the shipped
   // WGSYM_MIN_WGS), and the geometry of the handle's last launch of it (mimi_hip_domain_info(h, 11) and (h, 12); 0: none yet)
   int wgsym_min_wgs = 0;

@@ -26,6 +26,7 @@ inline void check_status(mimi_hip_domain_s* h) {
 inline void init_common(mimi_hip_domain_s* h, int device, const mimi_hip_material* material) {
   h->open(device);
   h->mat = make_material_dev(*material);
+  h->general_two_phase_failed = env_general_no_two_phase();
   MH_HIP(hipMalloc(reinterpret_cast<void**>(&h->status_dev), sizeof(int)));
   MH_HIP(hipMemsetAsync(h->status_dev, 0, sizeof(int), h->stream));
   MH_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->status_host), sizeof(int), hipHostMallocDefault));

@@ -97,13 +97,15 @@ inline int64_t longest_row(mimi_hip_domain_s* h) {
 
 // two-phase general path: element blocks / residual vectors densely into scratch_k / scratch_r, then
 // general_gather_kernel.  Needs n_el * n_tdof^2 doubles (77 GB at 128 x 128 x 16 p = 3) and the node -> element adjacency;
-// falls back to the atomics when the scratch does not fit (MIMI_HIP_GENERAL_NO_TWO_PHASE=1 forces that).  What it decides
-// depends on the CSR rows, the element size and the memory alone, never on what ran on the handle before
+// falls back to the atomics when the scratch does not fit (MIMI_HIP_GENERAL_NO_TWO_PHASE=1 at create forces that: the
+// handle's flag starts from it).  What it decides depends on the CSR rows, the element size and the memory alone, never on
+// what ran on the handle before
 inline bool ensure_general_two_phase(mimi_hip_domain_s* h, bool with_k) {
-  if (env_general_no_two_phase() || h->general_two_phase_failed) return false;
+  if (h->general_two_phase_failed) return false;
   const size_t n_tdof = (size_t)h->n_dof * h->dim;
-  // what rules the path out is checked BEFORE anything is allocated (3-D degree >= 4 would be 1.1 MB per element).
-  // The gather kernel keeps one CSR row in LDS: rows longer than its image -> atomics
+  // what rules the path out is checked BEFORE anything is allocated.  The gather kernel keeps one CSR row in LDS: rows
+  // longer than its image -> atomics.  n_dof > 64 is a guard, not a route: both creators refuse such a handle (the
+  // adjacency packs the local node into 6 bits)
   if (longest_row(h) > GG_MAX_ROW || h->n_dof > 64) {
     h->general_two_phase_failed = true;
     return false;
@@ -150,6 +152,7 @@ void launch_general_dim(mimi_hip_domain_s* h, const DomainCall& c) {
   // node-pair phase also for 64-node elements (A/B comparisons)
   const bool no_wpe = env_general_no_wpe(), no_mfma = env_general_no_mfma();
   const bool two_phase = ensure_general_two_phase(h, grad != 0);
+  h->last_general_route = two_phase ? MIMI_HIP_GENERAL_ROUTE_GATHER : MIMI_HIP_GENERAL_ROUTE_ATOMICS;
   // the atomics add into the values in place: A <- A_base first, on the stream, then "+="
   if (!two_phase && grad && c.A_base && c.A_base != c.A)
     MH_HIP(hipMemcpyAsync(c.A, c.A_base, (size_t)h->nnz * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -236,6 +239,7 @@ inline bool launch_tensor_small(mimi_hip_domain_s* h, const DomainCall& c, bool 
     if (!ensure_general_two_phase(h, mode == 1)) return false;
     a.scratch_k = h->scratch_k.ptr;
     a.scratch_r = h->scratch_r.ptr;
+    h->last_general_route = MIMI_HIP_GENERAL_ROUTE_GATHER;
   }
   by_dim_degree(h, [&](auto D, auto Pd) {
     constexpr int DIM = decltype(D)::value, P = decltype(Pd)::value;
@@ -287,6 +291,7 @@ inline void run_domain(mimi_hip_domain_s* h, DomainCall c) {
     h->last_family = MIMI_HIP_FAMILY_TENSOR_SMALL;
   } else if (tensor_usable(h) && !tensor_small(h) && c.grad != 2) {
     h->last_family = launch_tensor(h, c);
+    h->last_general_route = MIMI_HIP_GENERAL_ROUTE_NONE;
   } else {
     h->last_family = MIMI_HIP_FAMILY_GENERAL;
     launch_general(h, c);

@@ -220,6 +220,15 @@ class NonlinearSolid(NonlinearBase):
         """which kernel family the last assembly on this handle ran on (tests assert it; see mimi_hip_domain_info)"""
         return self.KERNEL_FAMILIES[self._info(ABI.DOMAIN_INFO_LAST_FAMILY)]
 
+    # mimi_hip_general_route by value: "none", "gather", "atomics"
+    GENERAL_ROUTES = {v: k[len("GENERAL_ROUTE_"):].lower() for k, v in vars(ABI).items() if k.startswith("GENERAL_ROUTE_")}
+
+    def LastGeneralRoute(self):
+        """how the element pieces of the last assembly on this handle reached r and A (MIMI_HIP_DOMAIN_INFO_GENERAL_ROUTE):
+        "gather" = stored, then the general row gather (families "general" and "tensor_small"); "atomics" = the general
+        kernels adding in place; "none" = no assembly yet, or a two-phase tensor family"""
+        return self.GENERAL_ROUTES[self._info(ABI.DOMAIN_INFO_GENERAL_ROUTE)]
+
     def LastWalkGeometry(self):
         """(seg_len, cols_per_wg) of the last launch of the symmetric-half degree-2 kernel on this handle: elements per unit
         (column or column segment) and units a workgroup walks back to back; (0, 0) before any (MIMI_HIP_DOMAIN_INFO_SEGMENT_LENGTH

@@ -26,7 +26,7 @@ MIMI_HIP_P3_CONTRACT flipped between two calls, MIMI_HIP_NO_STRUCTURED set betwe
 fixed order, so every hash must agree.  The linear-solver section (csrc/krylov.hip; it closes every run): GMRES and CG with
 preconditioner ids 0, 1, 2, every product form, a restarting and a cut solve, add_mult, eliminate, apply_preconditioner kinds
 1 and 2, arrays on the host and in HBM -- SHA-256 of x, the iterations, the final norm in hex.  --atomics runs the general path's atomics route
-(MIMI_HIP_GENERAL_NO_TWO_PHASE=1, read once per process) instead, whose sums do not: trace it, do not compare its hashes."""
+(MIMI_HIP_GENERAL_NO_TWO_PHASE=1, read at every create and kept on the handle) instead, whose sums do not: trace it, do not compare its hashes."""
 import csv
 import glob
 import hashlib

@@ -19,6 +19,8 @@ above 3100 points); the family is asserted after every call:
                        and ::test_rational_weights_general_path
   walks                WALK_CASES, apart from the above and neo-Hookean only: the multi-unit walks of the symmetric-half degree-2
                        kernel (tests/test_wgsym_walk_gpu.py), described where they are defined
+  atomics              ATOMICS_CASES and SEAM_PAIRS, apart from the above: the atomics fallback of the general path
+                       (tests/test_general_atomics_gpu.py), described where they are defined
 Flat tables (dofs, dN/dX, w det) are the reference's own, rounded to double; CSR patterns are the union of the element blocks
 found from the reference's values.
 
@@ -123,6 +125,33 @@ WALKS = [
 # the walk) with MIMI_HIP_WGSYM_MIN_WGS = 1: (box, cols_per_wg): 3 units in one workgroup; 6 units, 4 and a tail of 2
 WALK_BOXES = [(([0, 0, 0], [1, 3, 5]), 3), (([1, 0, 0], [3, 3, 5]), 4)]
 WALK_BOX_CASE = "walk335_p2"
+
+# The atomics fallback of the general path (tests/test_general_atomics_{cpu,gpu}.py; csrc/domain_dispatch.hpp,
+# ensure_general_two_phase), apart from CASES so that PAIRS does not grow.
+#   long2d_p1_o3   the natural trigger: 22 x 22 bilinear elements at quadrature order 3 (4 points per element, 1936 points;
+#                  23^2 nodes x 2 = 1058 dofs) with the CSR of `atomics_pattern`: the support pattern made a superset in which
+#                  the two rows of the interior node LONG_NODE hold every column 0 .. 1057, longer than the row image of the
+#                  general gather (GG_MAX_ROW = 1056, csrc/kernels_general.hpp).  No environment variable is set.
+#   SEAM_PAIRS     cases of CASES (their references are the session's) whose handles are created under
+#                  MIMI_HIP_GENERAL_NO_TWO_PHASE=1, one per scatter site of csrc/kernels_general.hpp:
+#                    rep2d_p3, rep3d_p1   launch_tensor_small hands over -> one wave per element, 2-D 16 nodes / 3-D 8 nodes
+#                    mix3d_231            256-thread node-pair kernel, 24 nodes
+#                    mix3d_322            512-thread vector-pipe kernel, 36 nodes (j2simo: the material pre-pass in front of it)
+#                    rep3d_p3             matrix-instruction kernel, 64 nodes
+#                    flat2d_p4            flat tables, 25 nodes;  nurbs_flat_p2: rational weights through flat tables
+ATOMICS_CASES = {"long2d_p1_o3": _uniform_case((1, 1), (22, 22), "general", order=3)}
+LONG_CASE = "long2d_p1_o3"
+LONG_NODE = (11, 11)                       # grid position of the node whose rows are full
+LONG_MATERIALS = ("neohook", "stvk")       # stateless laws: no seed scan
+LONG_PAIRS = [(LONG_CASE, m) for m in LONG_MATERIALS]
+SEAM_SITES = {"rep2d_p3": "wave per element 2-D", "rep3d_p1": "wave per element 3-D", "mix3d_231": "256-thread node pairs",
+              "mix3d_322": "512-thread vector pipe", "rep3d_p3": "matrix instruction", "flat2d_p4": "flat tables",
+              "nurbs_flat_p2": "rational flat tables"}
+SEAM_PAIRS = ([(c, m) for c in SEAM_SITES for m in ("neohook", "j2")] + [("mix3d_322", "j2simo"), ("rep3d_p3", "stvk")])
+SEAM_FD_PAIRS = [(c, m) for c in ("rep2d_p3", "mix3d_231", "rep3d_p3") for m in ("neohook", "j2")]
+SEAM_BOX_CASE = "mix3d_231"                # 3 x 2 x 4 spans, two complementary boxes cut in the third direction
+SEAM_BOXES = [([0, 0, 0], [3, 2, 1]), ([0, 0, 1], [3, 2, 4])]
+SEAM_ENV = "MIMI_HIP_GENERAL_NO_TWO_PHASE"
 
 # the element boxes of col8_p2: complementary, cutting every column
 BOXES = [([0, 0, 0], [2, 2, 3]), ([0, 0, 3], [2, 2, 8])]
@@ -251,7 +280,7 @@ def product_material(matname):
 @functools.lru_cache(maxsize=None)
 def arrays(case):
     """the plain arrays of a case; shared, never modified"""
-    c = CASES[case] if case in CASES else WALK_CASES[case]
+    c = next(d[case] for d in (CASES, WALK_CASES, ATOMICS_CASES) if case in d)
     degrees = tuple(c["degrees"])
     knots = [_patches.open_knots(p, k) for p, k in zip(degrees, c["inner"])]
     ctrl = _jittered(degrees, knots, c.get("jitter", 0.04), c.get("seed", 1))
@@ -332,6 +361,29 @@ def geometry(case):
 def pattern(case):
     """(rowptr, col, conn) of the union of the element blocks, from the reference's values"""
     out = dr.support_pattern(geometry(case).sp)
+    for x in out:
+        x.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def atomics_pattern(case):
+    """(rowptr, col, padded) of the CSR a handle of the atomics tests is created with.  LONG_CASE: `pattern` with the dim rows
+    of the node at grid position LONG_NODE replaced by the full row 0 .. n_vdofs - 1 (columns ascending, every node's dim
+    columns adjacent), padded[k] true where entry k is not an entry of `pattern`.  Every other case: `pattern`, nothing padded"""
+    rowptr, col, _ = pattern(case)
+    if case != LONG_CASE:
+        return rowptr, col, np.zeros(len(col), dtype=bool)
+    a = arrays(case)
+    node = LONG_NODE[0] + a.n_ctrl[0] * LONG_NODE[1]
+    full = np.arange(a.n_vdofs, dtype=np.int32)
+    rows, pad = [], []
+    for v in range(a.n_vdofs):
+        own = col[rowptr[v]:rowptr[v + 1]]
+        rows.append(full if v // a.dim == node else own)
+        pad.append(~np.isin(rows[-1], own))
+    out = (np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64), np.concatenate(rows).astype(np.int32),
+           np.concatenate(pad))
     for x in out:
         x.setflags(write=False)
     return out
